@@ -1,7 +1,7 @@
 """
 bench.py -- images/sec of Faster R-CNN VGG-16 inference (600x1000, 300 proposals) on N x MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,7 @@ A "step" is one `predict()` of one synthetic, already-preprocessed float32 3x600
 resident in HBM when the timed region starts: VGG-16 backbone, RPN (6000 pre- / 300 post-NMS),
 RoI pooling, FC head, on-device float64 decode + per-class NMS, one D2H copy of the detections.
 Every image is an independent batch-1 forward (BASELINE.json configs[1]); `--inflight` of them (default 4)
-are in flight on separate HIP streams (GPU_MAX_HW_QUEUES=16 unless the environment says otherwise).  float32 tensors end to end (the
+are in flight on separate HIP streams (with as many HIP hardware queues as the environment gives the process).  float32 tensors end to end (the
 reference's dtype).  WHICH matrix instructions every GEMM-shaped layer runs on is part of the JSON line (`dtype`, `layer_arithmetic`,
 `fc_math`, `winograd_x6_layers`, `winograd_x3_layers`, `f32_pipe_tflops` / `bf16_pipe_tflops` / `f16_pipe_tflops`): the 3x3 convolutions
 up to conv3_3 on the exact-f32 MFMA pipe as one-launch Winograd F(2x2,3x3) layers (`math`); the 512-channel layers (conv4_1 ... conv5_3,
@@ -25,6 +25,13 @@ Multi-GPU: image-parallel, rank r owns its own images, no data-path collective; 
 (K steps per rank).  The mAP@0.5 bookkeeping runs after the timed region on a small labelled
 subset and is merged across ranks with the single all-gather of fasterrcnn_amd/evaluate.py.
 
+The headline is ONE timed burst of exactly K steps (`--min-timed-seconds S` repeats it until S seconds are timed and reports
+the median burst); `ms_per_step` is that burst's milliseconds per step.  `--dump-outputs DIR` writes what the last timed step
+returned -- predict()'s per-class (n, 5) float64 detections -- as DIR/detections.npy, (N, 6) rows of (class, y1, x1, y2, x2,
+score) in class order, plus DIR/detections_per_class.npy, the row count of each class (rank 0; the inputs are seeded, so the
+same flags give the same inputs on every run and two builds can be compared output for output).  `config.hip_hw_queues` is the
+GPU_MAX_HW_QUEUES the environment sets, or null when it is unset (the HIP runtime's own default applies; bench.py sets none).
+
 Prints ONE JSON line on rank 0 (see DESIGN.md section "Measurement" for every field).
 """
 import argparse
@@ -36,11 +43,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-
-# One HIP hardware queue per two in-flight streams: the ROCm default of 4 queues serialises 8+ streams pairwise
-# (measured: 271 img/s with 4 queues / 8 images in flight, 288 with 16 / 24; more than 16 queues is slower).
-# Read by the HIP runtime at initialisation, so it must be set before torch creates the device context.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np   # noqa: E402
 import torch         # noqa: E402
@@ -641,11 +643,26 @@ def planted_ground_truth(seed, det, num_classes=21):
     return boxes
 
 
+def pack_detections(det):
+    """predict()'s dict {class: (n, 5) rows of (y1, x1, y2, x2, score)} as the two float64 arrays --dump-outputs writes: (N, 6) rows of
+    (class, y1, x1, y2, x2, score) in class order -- a class with no detection contributes no row -- and the row count of each class, in
+    the same order, which rebuilds the dict from the rows."""
+    det = sorted(det.items())
+    rows = [np.concatenate([np.full((len(r), 1), c, dtype=np.float64), np.asarray(r, dtype=np.float64).reshape(-1, 5)], axis=1) for c, r in det]
+    return (np.concatenate(rows, axis=0) if rows else np.zeros((0, 6))), np.array([len(r) for _, r in det], dtype=np.float64)
+
+
+def hw_queues(environ=None):
+    """GPU_MAX_HW_QUEUES as the environment sets it (int), or None when unset: the HIP runtime then uses its own default."""
+    v = (os.environ if environ is None else environ).get("GPU_MAX_HW_QUEUES")
+    return int(v) if v else None
+
+
 def launcher_command(gpus, argv, environ=None):
     """(command, environment) that re-runs this file as `gpus` ranks of ONE node under torch.distributed.run -- exactly the form the
     driver uses for N > 1 (docstring above): rendezvous on 127.0.0.1 (the container hostname may not resolve), a free port, the
     caller's flags passed through.  The environment adds what a multi-process GPU job needs on this stack: dmabuf IPC for RCCL
-    (HSA_ENABLE_IPC_MODE_LEGACY=0) and the HIP hardware-queue count of the in-flight streams."""
+    (HSA_ENABLE_IPC_MODE_LEGACY=0); the HIP hardware-queue count is the caller's environment's."""
     import socket
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
@@ -654,7 +671,6 @@ def launcher_command(gpus, argv, environ=None):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ if environ is None else environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env.setdefault("GPU_MAX_HW_QUEUES", "16")
     return cmd, env
 
 
@@ -692,11 +708,16 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run every barrier / all-reduce / all-gather also with ONE rank "
                          "(so the multi-GPU code path can be exercised on a one-GPU box)")
-    ap.add_argument("--min-timed-seconds", type=float, default=1.0,
-                    help="the timed burst of --steps steps is repeated until this much has been timed; the MEDIAN burst is reported")
+    ap.add_argument("--min-timed-seconds", type=float, default=0.0,
+                    help="the timed burst of --steps steps is repeated until this much has been timed; the MEDIAN burst is reported "
+                         "(default 0: ONE burst, i.e. exactly --steps timed steps)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the single-stream / ResNet-50 / train-step legs")
     ap.add_argument("--backbone", type=str, default="vgg16", choices=["vgg16", "resnet50", "resnet101", "resnet152"],
                     help="vgg16 is the BASELINE.json metric; the ResNets are informational (configs[2])")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (predict()'s per-class (n, 5) float64 detections) "
+                         "as DIR/detections.npy, (N, 6) rows of (class, y1, x1, y2, x2, score) in class order, and "
+                         "DIR/detections_per_class.npy, the row count of each class 1..20; rank 0 only")
     args = ap.parse_args()
 
     rank, local_rank, world = rank_environment()
@@ -756,13 +777,15 @@ def main():
             last = pending.pop(0).result()
         return last
 
+    last_step = {}
+
     def timed_burst(fn, n_steps):
         """EXACTLY n_steps steps bracketed by barrier + synchronize on both sides; MAX over ranks."""
         torch.cuda.synchronize(dev)
         if use_dist:
             dist.barrier()
         ts = time.perf_counter()
-        fn(n_steps)
+        last_step["out"] = fn(n_steps)
         torch.cuda.synchronize(dev)
         if use_dist:
             dist.barrier()
@@ -789,6 +812,12 @@ def main():
     run(max(args.warmup, nslots))
     elapsed, bursts = timed_median(run, args.steps, args.min_timed_seconds)
     value = n_gpus * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # the last timed step: image pool[(steps - 1) % pool], seeded, so the same flags give the same input on every run
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rows, counts = pack_detections(last_step["out"])
+        np.save(os.path.join(args.dump_outputs, "detections.npy"), rows)
+        np.save(os.path.join(args.dump_outputs, "detections_per_class.npy"), counts)
     # per-rank view of the same timed region (each rank's own wall time of its median burst is not kept: the burst time is already the
     # max over ranks; what differs per rank is its LOCAL burst, measured here without the barrier), gathered for the JSON line
     torch.cuda.synchronize(dev)
@@ -1324,7 +1353,7 @@ def main():
             "vs_baseline": None, "dtype": dtype_str, "data": "synthetic",
             "config": {"workload": ("VGG-16" if not is_resnet else args.backbone) + " Faster R-CNN predict(), 3x600x1000 float32, batch=1 per forward, "
                                    "6000 pre-/300 post-NMS proposals, score_threshold 0.05",
-                       "images_in_flight_per_gpu": nslots, "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")), "parallelism": "image-parallel x%d" % n_gpus,
+                       "images_in_flight_per_gpu": nslots, "hip_hw_queues": hw_queues(), "parallelism": "image-parallel x%d" % n_gpus,
                        "flops_per_image": flops_img,
                        # the same workload, same run: every GEMM on the exact-f32 matrix instructions / fed from pinned host memory
                        "strict_f32_images_per_sec": strict_f32_value,
