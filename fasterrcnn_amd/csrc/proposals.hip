@@ -61,12 +61,17 @@ void rpn_decode_kernel(const float* __restrict__ head, int ld, const float* __re
     keys[n] = ok ? (((u64)ordered_bits(score) << 32) | (u64)(unsigned)(n + 1)) : 0ull;
 }
 
-// keys for the stand-alone NMS entry: stable descending (ties -> LOWER index first).
+// keys for the stand-alone NMS entry: stable descending (ties -> LOWER index first), the order of the oracle's stable
+// argsort(-scores): -0.0 ties with +0.0 (the score bits alone would put +0.0 above it), and every NaN gets the lowest score key, 0, so
+// NaNs sort after -inf, among themselves by index.  (No non-NaN float maps to 0: -inf is 0x007FFFFF.)
 __global__ __launch_bounds__(256)
 void nms_keys_kernel(const float* __restrict__ scores, int n, u64* __restrict__ keys)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) keys[i] = ((u64)ordered_bits(scores[i]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
+    if (i >= n) return;
+    const float f = scores[i];
+    const unsigned hi = f != f ? 0u : ordered_bits(f == 0.f ? 0.f : f);
+    keys[i] = ((u64)hi << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
 }
 
 // ---- register-resident bitonic sort (descending) of 1024*PER keys held PER-per-thread ---------------
@@ -554,10 +559,14 @@ __device__ __forceinline__ bool iou_gt(const f32x4 a, const f32x4 b, float thr)
     // The decision is torchvision's `inter / union > thr` to the last bit -- but the quotient (a ~10-instruction sequence, a third of this
     // function) is computed only for the pairs that need it: with t = fl(thr * union), inter > t (1 + 1e-6) implies
     // fl(inter / union) > thr and inter < t (1 - 1e-6) implies fl(inter / union) < thr (the two roundings involved are 6e-8 relative each);
-    // only a pair inside that band of 2e-6 -- or a degenerate one, union = 0: 0 / 0 is NaN, not greater -- takes the division.
+    // only a pair inside that band of 2e-6 takes the division.  The bounds hold for union > 0 only: every other union divides
+    // (0 / 0 is NaN, not greater; a box inverted along one axis has a negative area, and 0 / negative is -0.0, not greater either,
+    // where the shortcut's t < 0 would say "suppress").
     const float uni = sa + sb - inter, t = thr * uni;
-    if (inter > t * 1.000001f) return true;
-    if (inter < t * 0.999999f) return false;
+    if (uni > 0.f) {
+        if (inter > t * 1.000001f) return true;
+        if (inter < t * 0.999999f) return false;
+    }
     return (inter / uni) > thr;
 }
 

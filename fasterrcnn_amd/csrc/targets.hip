@@ -48,7 +48,9 @@ __device__ __forceinline__ double iou_f64(const AnchorBox& a, const f32x4 g)
     const double by = fmin(a.y2, gy2), bx = fmin(a.x2, gx2);
     const bool ok = (ty < by) && (tx < bx);
     const double inter = ok ? __dmul_rn(by - ty, bx - tx) : 0.0;
-    const double garea = __dmul_rn(gy2 - gy1, gx2 - gx1);
+    // the GT area is a float32 product: math_utils.py:34 takes np.prod of the float32 corner array (voc.py:297), and only the sum
+    // with the float64 anchor area widens it (:35).  (Widening first changes the IoU by ~1e-7 relative: enough to reorder two GT boxes.)
+    const double garea = (double)__fmul_rn(__fsub_rn(g[2], g[0]), __fsub_rn(g[3], g[1]));
     const double uni = __dadd_rn(__dadd_rn(a.area, garea), -inter);
     return inter / __dadd_rn(uni, 1e-7);
 }

@@ -394,7 +394,10 @@ int frcnn_rpn_proposals(frcnn_ctx* ctx, const float* d_head, int ld_head,
  * torchvision.ops.nms as called at models/rpn.py:147-151: scores are sorted stably descending,
  * box j is suppressed by an earlier kept box i iff inter/(area_i+area_j-inter) > threshold.
  * d_keep receives up to max_keep indices into the INPUT order (score-descending), d_n_keep the
- * count.  n <= 16384. */
+ * count.  0 <= n <= 16384 and 1 <= max_keep <= 2048, else FRCNN_EINVAL.  The order is that of a stable
+ * argsort(-scores): ties keep the input order, -0.0 ties with +0.0, NaN scores go last (in input order).
+ * Boxes of any sign: a box inverted along one axis has a negative area, and a pair whose union is not
+ * positive is decided by the division itself, as torchvision does (0 / negative = -0.0: not suppressed). */
 int frcnn_nms(frcnn_ctx* ctx, const float* d_boxes, const float* d_scores, int n, float threshold,
               int max_keep, int32_t* d_keep, int32_t* d_n_keep, void* stream);
 
