@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FRCNN_LIB_PATH") or os.path.join(_HERE, "csrc", "libfrcnn_hip.so")   # override: kernel experiments
 
 OK = 0
-ABI_VERSION = 16    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
+ABI_VERSION = 17    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
 ERRORS = {0: "FRCNN_OK", -1: "FRCNN_EINVAL", -2: "FRCNN_EHIP", -3: "FRCNN_ENOMEM",
           -4: "FRCNN_EUNSUPPORTED", -5: "FRCNN_ENODEVICE"}
 RELU = 1
@@ -54,7 +54,7 @@ SYMBOLS = (
     "frcnn_label_proposals", "frcnn_gather_rows", "frcnn_rpn_loss", "frcnn_detector_loss",
     "frcnn_gemm_tn_math", "frcnn_conv3x3_wgrad_math", "frcnn_conv_wgrad_math", "frcnn_bottleneck_backward_workspace_bytes", "frcnn_bottleneck_backward",
     "frcnn_gemm_tn_workspace_bytes", "frcnn_gemm_tn", "frcnn_conv3x3_wgrad_workspace_bytes", "frcnn_conv3x3_wgrad",
-    "frcnn_pack_conv3x3_dgrad", "frcnn_relu_backward", "frcnn_add_inplace", "frcnn_maxpool2x2_backward",
+    "frcnn_pack_conv3x3_dgrad", "frcnn_relu_backward", "frcnn_dropout", "frcnn_dropout_relu_backward", "frcnn_add_inplace", "frcnn_maxpool2x2_backward",
     "frcnn_roi_pool_backward_workspace_bytes", "frcnn_roi_pool_backward", "frcnn_transpose", "frcnn_sgd_step", "frcnn_sgd_step_fold",
     "frcnn_conv_wgrad_workspace_bytes", "frcnn_conv_wgrad", "frcnn_conv_dgrad_workspace_bytes", "frcnn_conv_dgrad", "frcnn_conv_dgrad_math",
     "frcnn_pack_conv_dgrad", "frcnn_scale_rows", "frcnn_bn_scale_shift", "frcnn_spatial_mean_backward",
@@ -339,6 +339,8 @@ _SIGNATURES = {
     "frcnn_bn_scale_shift": (C.c_int, [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "frcnn_spatial_mean_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_relu_backward": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "frcnn_dropout": (C.c_int, [_vp, _sz, _f, _f, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "frcnn_dropout_relu_backward": (C.c_int, [_vp, _vp, _sz, _f, _vp]),
     "frcnn_add_inplace": (C.c_int, [_vp, _vp, _sz, _vp]),
     "frcnn_maxpool2x2_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "frcnn_roi_pool_backward_workspace_bytes": (C.c_size_t, [_i, _i, _i]),

@@ -4,6 +4,7 @@
 // (reference: models/faster_rcnn.py:80-132) on one stream with no host round trip.
 #include "common.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -874,6 +875,22 @@ int frcnn_relu_backward(float* d_dy, const float* d_y, size_t n, void* stream)
 {
     if (n > 0 && (!d_dy || !d_y)) return FRCNN_EINVAL;
     return launch_relu_backward(d_dy, d_y, n, as_stream(stream));
+}
+
+int frcnn_dropout(float* d_x, size_t n, float p, float scale, const uint64_t* d_seed, uint32_t stream_id, uint32_t rank,
+                  uint8_t* d_keep_out, void* stream)
+{
+    if (!(p >= 0.f && p <= 1.f)) return FRCNN_EINVAL;                          // (NaN fails both)
+    if (p < 1.f && !(std::isfinite(scale) && scale >= 1.f)) return FRCNN_EINVAL;
+    if (n > 0 && (!d_x || !d_seed)) return FRCNN_EINVAL;
+    return launch_dropout(d_x, n, p, scale, d_seed, stream_id, rank, d_keep_out, as_stream(stream));
+}
+
+int frcnn_dropout_relu_backward(float* d_dy, const float* d_y, size_t n, float scale, void* stream)
+{
+    if (!(scale >= 1.f)) return FRCNN_EINVAL;
+    if (n > 0 && (!d_dy || !d_y)) return FRCNN_EINVAL;
+    return launch_dropout_relu_backward(d_dy, d_y, n, scale, as_stream(stream));
 }
 
 int frcnn_add_inplace(float* d_a, const float* d_b, size_t n, void* stream)

@@ -291,6 +291,9 @@ int launch_rpn_loss(const float* head, int ld, int cells, const int32_t* sample,
 int launch_detector_loss(const float* classes, const float* deltas, const float* gt_onehot, const float* gt_deltas,
                          int S, int ncls, float* losses, float* d_logits, int ld, hipStream_t s);
 int launch_relu_backward(float* dy, const float* y, size_t n, hipStream_t s);
+int launch_dropout(float* x, size_t n, float p, float scale, const uint64_t* seed, uint32_t stream_id, uint32_t rank,
+                   uint8_t* keep_out, hipStream_t s);
+int launch_dropout_relu_backward(float* dy, const float* y, size_t n, float scale, hipStream_t s);
 int launch_add_inplace(float* a, const float* b, size_t n, hipStream_t s);
 int launch_maxpool2x2_backward(const float* x, const float* dy, float* dx, int H, int W, int C, hipStream_t s);
 size_t roi_pool_backward_workspace_bytes(int n_rois, int pooled, int C);

@@ -209,7 +209,7 @@ class PoolToFeatureVector(nn.Module):
         super().__init__()
         self._fc1 = nn.Linear(in_features=512 * 7 * 7, out_features=4096)
         self._fc2 = nn.Linear(in_features=4096, out_features=4096)
-        # Dropout is identity at inference; kept so the module tree matches the reference
+        # Dropout is the identity at inference; in training mode (forward below, and the train step) csrc/dropout.hip applies it
         self._dropout1 = nn.Dropout(p=dropout_probability)
         self._dropout2 = nn.Dropout(p=dropout_probability)
         self._packed_key = None
@@ -249,21 +249,62 @@ class PoolToFeatureVector(nn.Module):
         return self._packed[mode]
 
     def forward(self, rois):
-        """rois (N, 512, 7, 7) -> (N, 4096): fc1+ReLU, fc2+ReLU (dropout = identity at inference)."""
-        if self.training and (self._dropout1.p > 0 or self._dropout2.p > 0):
-            raise NotImplementedError("training-mode dropout is outside the inference hot path")
+        """rois (N, 512, 7, 7) -> (N, 4096): fc1+ReLU(+dropout1), fc2+ReLU(+dropout2).  Dropout is the identity at inference; in training
+        mode with p > 0 both layers drop with masks keyed by one seed drawn from the device's torch generator (stream ids 1 and 2, rank 0)."""
         x = rt.as_f32_cuda(rois, "rois")
+        ps = dropout_probabilities(self) if self.training else (0.0, 0.0)
+        if ps[0] > 0 or ps[1] > 0:
+            seed = draw_dropout_seed(x.device)
+            drop = lambda h, i: dropout_(h, ps[i], seed, i + 1)      # noqa: E731  (in place on the ReLU output of fc i + 1)
+        else:
+            drop = lambda h, i: h                                     # noqa: E731
         n = int(x.shape[0])
         x = x.permute(0, 2, 3, 1).contiguous().reshape(n, 49 * 512)   # layout plumbing: (C,7,7) -> (7,7,C)
         mode = self.fc_math_mode
         w1p, b1, w2, b2 = self.packed(mode)
-        if mode == "f32x6":
-            h1 = linear_x6t(x, w1p, b1, 4096, relu=True)
-            return linear_x6t(h1, w2, b2, 4096, relu=True)
-        if mode == "f32x3":
-            h1 = linear_x3t(x, w1p, b1, 4096, relu=True)
-            return linear_x3t(h1, w2, b2, 4096, relu=True)
-        return linear(linear(x, w1p, b1, 4096, relu=True), w2, b2, 4096, relu=True)
+        fc = {"f32x6": linear_x6t, "f32x3": linear_x3t}.get(mode, linear)
+        h1 = drop(fc(x, w1p, b1, 4096, relu=True), 0)
+        return drop(fc(h1, w2, b2, 4096, relu=True), 1)
+
+
+def dropout_probabilities(pv):
+    """(p1, p2) of a PoolToFeatureVector's two nn.Dropout modules, checked to lie in [0, 1]."""
+    ps = (float(pv._dropout1.p), float(pv._dropout2.p))
+    if not all(0.0 <= p <= 1.0 for p in ps):
+        raise ValueError("dropout probabilities must lie in [0, 1], got %r" % (ps,))
+    return ps
+
+
+def dropout_scale(p):
+    """The kept elements' factor 1 / (1 - p), computed in double and rounded once to float32 by the call (inf for p == 1)."""
+    return float("inf") if p >= 1.0 else 1.0 / (1.0 - p)
+
+
+def draw_dropout_seed(device):
+    """One int64 seed on `device`, from that device's torch generator (torch.manual_seed reproduces it; no host synchronisation; the CPU
+    generator and python `random`, which the train step's samplers use, are not touched)."""
+    return t.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=t.int64, device=device)
+
+
+def dropout_(x, p, seed, stream_id, rank=0, keep_out=None):
+    """nn.Dropout(p) in training mode, in place on the float32 CUDA tensor x (frcnn_dropout: Philox4x32-10 keyed by the device int64 `seed`,
+    counter (element / 4, stream_id, rank)).  keep_out: None, or a uint8 tensor of x's size that receives the keep mask.  Returns x."""
+    assert x.is_contiguous() and x.dtype == t.float32
+    if keep_out is not None:
+        assert keep_out.dtype == t.uint8 and keep_out.numel() == x.numel() and keep_out.is_contiguous()
+    with t.cuda.device(x.device):
+        nv.check(nv.lib().frcnn_dropout(nv.ptr(x), x.numel(), p, dropout_scale(p), nv.ptr(seed), stream_id, rank, nv.ptr(keep_out),
+                                        nv.stream_ptr()), "frcnn_dropout")
+    return x
+
+
+def dropout_relu_backward_(dy, y, p):
+    """dy <- gradient of dropout(relu(z)) with respect to z, in place, from dy = gradient of its output y (frcnn_dropout_relu_backward)."""
+    assert dy.is_contiguous() and y.is_contiguous() and dy.numel() == y.numel()
+    with t.cuda.device(dy.device):
+        nv.check(nv.lib().frcnn_dropout_relu_backward(nv.ptr(dy), nv.ptr(y), dy.numel(), dropout_scale(p), nv.stream_ptr()),
+                 "frcnn_dropout_relu_backward")
+    return dy
 
 
 def split_rows_x6t(a, rows_padded):

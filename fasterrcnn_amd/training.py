@@ -20,6 +20,8 @@ kernel with a flipped/transposed weight pack.  Design points:
   * host-side randomness is drawn exactly as the reference draws it (python `random.sample` for the anchor
     mini-batch, `torch.randperm` on the CPU generator for the proposal batch), so a seeded run selects the
     same samples;
+  * training-mode dropout of the VGG-16 head (`--dropout p`, vgg16.py:129-133) draws its masks on the GPU (csrc/dropout.hip: Philox4x32-10
+    keyed by ONE int64 per step from the device's torch generator), so it neither synchronises the host nor moves those samplers' draws;
   * there are two host synchronisations per step, as in the reference: the count/labels of the labelled
     proposals (the reference's `len()` / `t.where` calls) and the final read of the loss values.
 """
@@ -295,8 +297,7 @@ class VGG16TrainState(TrainState):
         super().__init__(model)
         fe = model._stage1_feature_extractor
         pv = model._stage3_detector_network._pool_to_feature_vector
-        if pv._dropout1.p > 0 or pv._dropout2.p > 0:
-            raise NotImplementedError("dropout > 0 is not implemented in the train step (reference default: 0.0)")
+        vgg16.dropout_probabilities(pv)           # 0 <= p <= 1 (read again at every step: the nn.Dropout modules may change)
         # clones: the inference-side packed caches are rebuilt from the parameters, these are the training masters
         self.conv = fe.packed_direct()
         self._frozen_banks = {}                # one-launch Winograd banks of the frozen layers (their weights never change here)
@@ -365,31 +366,44 @@ class VGG16TrainState(TrainState):
                 g = maxpool2x2_backward(y_out[i - 1], gx) if (i - 1) in _POOL_AFTER else gx
         side.flush()
 
+    def dropout_step(self, rank, masks=False):
+        """The step's head dropout (vgg16.py:129-133 in training mode), or None when both probabilities are 0: ONE seed drawn on the device."""
+        ps = vgg16.dropout_probabilities(self.model._stage3_detector_network._pool_to_feature_vector)
+        if ps[0] == 0 and ps[1] == 0:
+            return None
+        return HeadDropout(ps, vgg16.draw_dropout_seed(self.device), rank, masks)
+
     # ---- RoI features -> feature vector (vgg16.py:129-133) ------------------------------------------------
-    def head_forward(self, roi_out, inject=None):
+    def head_forward(self, roi_out, inject=None, drop=None):
+        """h1 = dropout1(relu(fc1(roi_out))), h2 = dropout2(relu(fc2(h1))); `inject` "fc1" / "fc2" replace h1 / h2 (as they are after
+        dropout: an injected activation is not dropped)."""
         inject = inject or {}
         h1 = inject.get("fc1", None)
         if h1 is None:
             h1 = vgg16.linear(roi_out, self.fc1, self.fc1_b, 4096, relu=True)
+            if drop is not None:
+                drop.apply(h1, 0)
         h2 = inject.get("fc2", None)
         if h2 is None:
-            h2 = vgg16.linear(h1, self.fc2, self.fc2_b, 4096, relu=True)
-        return h2, (roi_out, h1, h2)
+            h2 = vgg16.linear(h1, self.fc2, self.fc2_b, 4096, relu=True)      # fc2 (and its weight gradient) read the DROPPED h1
+            if drop is not None:
+                drop.apply(h2, 1)
+        return h2, (roi_out, h1, h2, drop.p if drop is not None else (0.0, 0.0))
 
     def head_backward(self, dh2, saved, grads, detail=None):
-        roi_out, h1, h2 = saved
+        roi_out, h1, h2, ps = saved
         S = int(h2.shape[0])
         if detail is not None:
             detail["dh2"] = dh2.clone()
         side = _SideGrads(grads, self.device)          # fc2's and fc1's weight gradients on the second stream, under the chain dh2 -> dh1 -> d roi
-        relu_backward(dh2, h2)
+        _head_relu_backward(dh2, h2, ps[1])
         side.run("fc2", lambda: gemm_tn(dh2, 4096, h1, 4096, 4096, 4096, S), (dh2, h1))
         dh2_t, sp = transpose(dh2, S, 4096, 4096)
         dh1 = gemm_tn(dh2_t, sp, self.fc2, 4096, S, 4096, 4096)
         if detail is not None:
             detail["dh1"] = dh1.clone()
             detail.update(h1=h1, h2=h2)
-        relu_backward(dh1, h1)
+        _head_relu_backward(dh1, h1, ps[0])
         side.run("fc1", lambda: gemm_tn(dh1, 4096, roi_out, 49 * 512, 4096, 49 * 512, S), (dh1, roi_out))
         dh1_t, sp = transpose(dh1, S, 4096, 4096)
         droi = gemm_tn(dh1_t, sp, self.fc1, 49 * 512, S, 49 * 512, 4096)
@@ -399,6 +413,27 @@ class VGG16TrainState(TrainState):
     def zero_head_grads(self, grads):
         for name in ("fc2", "fc1"):
             grads[name] = t.zeros_like(self.trainable()[name])
+
+
+class HeadDropout:
+    """One train step's dropout of the two VGG-16 head activations: probabilities (p1, p2), the device int64 seed, the data-parallel rank
+    (part of the Philox counter, beside stream ids 1 and 2), and with `masks` the uint8 keep masks (tests: train_step's `detail`)."""
+    def __init__(self, p, seed, rank, masks=False):
+        self.p, self.seed, self.rank, self.masks = p, seed, int(rank), masks
+        self.keep = [None, None]
+
+    def apply(self, h, i):
+        if self.masks:
+            self.keep[i] = t.empty(h.shape, dtype=t.uint8, device=h.device)
+        vgg16.dropout_(h, self.p[i], self.seed, i + 1, self.rank, self.keep[i])
+
+
+def _head_relu_backward(dy, y, p):
+    """ReLU backward of a head activation, fused with its dropout's when p > 0 (y is the activation after dropout)."""
+    if p > 0:
+        vgg16.dropout_relu_backward_(dy, y, p)
+    else:
+        relu_backward(dy, y)
 
 
 _wgrad_streams = {}
@@ -913,6 +948,9 @@ def _train_step(model, optimizer, image_data, anchor_map, anchor_valid_map, gt_r
         losses = t.zeros((4,), dtype=t.float32, device=dev)
         sync = getattr(model, "_gradient_sync", None)
         grads = sync.track() if sync is not None else {}              # data parallel: every gradient is exchanged as soon as it exists
+        drop = None
+        if isinstance(st, VGG16TrainState):                          # head dropout: one device seed per step when p > 0
+            drop = st.dropout_step(sync.dist.get_rank(sync.group) if sync is not None else 0, masks=detail is not None)
         dfm = None
         if S > 0:
             idx_dev = sample_idx.to(t.int32).to(dev)
@@ -932,7 +970,7 @@ def _train_step(model, optimizer, image_data, anchor_map, anchor_valid_map, gt_r
                 nv.check(lib.frcnn_roi_pool(nv.ptr(fm), fh, fw, C, nv.ptr(s_props), nv.ptr(cnt), S, 7, 1.0 / 16.0,
                                             nv.ptr(roi_out), s), "frcnn_roi_pool")
             roi_out = inject.get("roi_out", roi_out)
-            vec, hsaved = st.head_forward(roi_out, inject) if inject else st.head_forward(roi_out)
+            vec, hsaved = st.head_forward(roi_out, inject, drop) if isinstance(st, VGG16TrainState) else st.head_forward(roi_out)
             logits = vgg16.linear(vec, st.head, st.head_b, ncls + nd, relu=False)
             classes = t.empty((S, ncls), dtype=t.float32, device=dev)
             nv.check(lib.frcnn_softmax_rows(nv.ptr(logits), ncls + nd, nv.ptr(classes), S, ncls, s), "frcnn_softmax_rows")
@@ -972,6 +1010,8 @@ def _train_step(model, optimizer, image_data, anchor_map, anchor_valid_map, gt_r
         g = conv3x3_dgrad(dtrunk, st.rpn_conv, C, C, st.zero_bias, st.winograd)
         if dfm is not None:
             nv.check(lib.frcnn_add_inplace(nv.ptr(g), nv.ptr(dfm), g.numel(), s), "frcnn_add_inplace")
+        if detail is not None and drop is not None:
+            detail.update(dropout_seed=int(drop.seed.item()), dropout_keep=tuple(drop.keep))
         if detail is not None:
             detail.update(dfm=g.clone(), dhead=dhead, head=head, trunk=trunk, fm=fm, rpn_sample=rpn_sample,
                           proposals=props, counts=counts, labelled=(lab_props[:K], lab_cls[:K], lab_onehot[:K], lab_deltas[:K]),

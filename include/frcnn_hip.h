@@ -37,7 +37,7 @@ extern "C" {
 #define FRCNN_EUNSUPPORTED -4   /* valid request outside what this build implements */
 #define FRCNN_ENODEVICE    -5   /* no gfx950 device visible */
 
-#define FRCNN_ABI_VERSION 16  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
+#define FRCNN_ABI_VERSION 17  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
                                  5: bf16 gradient GEMMs (the *_math entry points); 6: x6t GEMM, x6 Winograd layers, frcnn_forward_params.winograd_x6_mask,
                                  timing classes 8 / 9; 7: batched feature extractor (frcnn_resnet_backbone, frcnn_resnet_forward_features,
                                  frcnn_ctx_create_backbone, frcnn_conv3x3_nhwc_winograd_fused_maps); 8: the f32x3 arithmetic (frcnn_*_x3t, frcnn_*_winograd_x3,
@@ -48,7 +48,8 @@ extern "C" {
                                  (frcnn_pack_conv3x3_x6, frcnn_conv3x3_nhwc_x6, frcnn_split_rows_x6, frcnn_linear_x6(_workspace_bytes), math mode 1 =
                                  FRCNN_MATH_F32X6 and fc mode 1 = FRCNN_FC_F32X6 are FRCNN_EINVAL); the f32x6 arithmetic stays as gemm_x6t / wino_x6; 14: FRCNN_X3F_PAIR, frcnn_conv3x3_winograd_x3_pair_workspace_bytes, frcnn_forward_params.winograd_x3p_mask,
                                  frcnn_resnet_rpn_roipool / frcnn_ctx_create_head / frcnn_resnet_head; 15: frcnn_conv_nhwc_x3g_tickets (split reductions finished inside the kernel), frcnn_pack_conv_x3g_weights + FRCNN_X3G_WSPLIT + frcnn_bottleneck_weights.g3 == 2 (pre-split weight packs);
-                                 16: frcnn_train_conv, frcnn_bottleneck_backward(_workspace_bytes): the backward of one trainable bottleneck as ONE call, weight gradients on a second stream */
+                                 16: frcnn_train_conv, frcnn_bottleneck_backward(_workspace_bytes): the backward of one trainable bottleneck as ONE call, weight gradients on a second stream;
+                                 17: frcnn_dropout, frcnn_dropout_relu_backward (training-mode dropout of the VGG-16 head) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -820,6 +821,18 @@ int frcnn_spatial_mean_backward(const float* d_dy, float* d_dx, int N, int H, in
 /* dy[i] = y[i] > 0 ? dy[i] : 0 (ReLU backward, in place); a[i] += b[i]. */
 int frcnn_relu_backward(float* d_dy, const float* d_y, size_t n, void* stream);
 int frcnn_add_inplace(float* d_a, const float* d_b, size_t n, void* stream);
+/* ABI 17: nn.Dropout(p) in training mode (models/vgg16.py:129-133 with `--dropout p`), in place on n floats (d_x 16-byte aligned):
+ *   keep[i] = (w >> 8) * 2^-24 < 1 - p (float32), w = word (i & 3) of Philox4x32-10 with key (seed lo32, seed hi32) and counter
+ *             (i >> 2 lo32, i >> 2 hi32, stream_id, rank), seed = *d_seed (device memory: drawing it needs no host synchronisation);
+ *   x[i]    = keep[i] ? x[i] * scale : 0, scale = (float)(1.0 / (1.0 - p)) computed in double by the caller.
+ * p == 0 leaves x untouched, p == 1 zeroes it.  d_keep_out: NULL, or n bytes that receive keep[i] as 0 / 1 (tests).
+ * FRCNN_EINVAL: p outside [0, 1] or NaN, scale not finite or below 1 while p < 1, d_x / d_seed NULL while n > 0, d_x misaligned.
+ * frcnn_dropout_relu_backward: dy[i] = y[i] > 0 ? dy[i] * scale : 0 in place, y = the output of relu followed by frcnn_dropout: the
+ * gradient of dropout(relu(z)) with respect to z without a stored mask (y > 0 exactly on kept elements with relu(z) > 0).
+ * scale >= 1 (else FRCNN_EINVAL); d_dy, d_y 16-byte aligned. */
+int frcnn_dropout(float* d_x, size_t n, float p, float scale, const uint64_t* d_seed, uint32_t stream_id, uint32_t rank,
+                  uint8_t* d_keep_out, void* stream);
+int frcnn_dropout_relu_backward(float* d_dy, const float* d_y, size_t n, float scale, void* stream);
 /* MaxPool2d(2,2) backward: x [H][W][c] pool input, dy [H/2][W/2][c] -> dx [H][W][c] (first maximum wins). */
 int frcnn_maxpool2x2_backward(const float* d_x, const float* d_dy, float* d_dx, int H, int W, int c, void* stream);
 /* torchvision RoIPool backward (detector.py:72): dout [n][pooled][pooled][c] -> dfm [fh][fw][c] (gradient to

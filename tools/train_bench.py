@@ -36,11 +36,14 @@ def main():
     ap.add_argument("--grad-math", type=str, default="f32", choices=["f32", "bf16"],
                     help="arithmetic of the gradient GEMMs (FasterRCNNModel.grad_math); bf16 = BASELINE configs[4]'s reduced-precision step")
     ap.add_argument("--roi", type=str, default="pool", choices=["pool", "align"])
+    ap.add_argument("--dropout", type=float, default=0.0, help="VGG-16 head dropout probability (the reference's --dropout)")
     ap.add_argument("--host-clocks", action="store_true", help="also report what the host needs to ENQUEUE a step (training.HOST_CLOCKS)")
     args = ap.parse_args()
     h, w = args.height, args.width
+    if args.dropout and args.backbone != "vgg16":
+        ap.error("--dropout applies to the VGG-16 head (the ResNet head has no dropout)")
     if args.backbone == "vgg16":
-        model = FasterRCNNModel(num_classes=21, backbone=VGG16Backbone(dropout_probability=0.0), roi_pooling=args.roi)
+        model = FasterRCNNModel(num_classes=21, backbone=VGG16Backbone(dropout_probability=args.dropout), roi_pooling=args.roi)
         model.load_state_dict(synthetic.vgg16_state_dict(1234), strict=True)
         make_image = synthetic.image
     else:
@@ -87,6 +90,7 @@ def main():
                                      "wait_sync_2": round(1e3 * float(np.median(hc[:, 4] - hc[:, 3])), 3)}}
     print(json.dumps({**host, "metric": "train_step (%s Faster R-CNN, %dx%d, batch 1)" % (args.backbone, h, w), "ms_per_step": 1e3 * dt / args.steps,
                       "steps_per_sec": args.steps / dt, "steps": args.steps, "warmup": args.warmup, "dtype": "f32", "grad_math": model.grad_math, "roi": args.roi, "math": model.math_mode,
+                      "dropout": args.dropout,
                       "first_total_loss": losses[0], "last_total_loss": losses[-1], "data": "synthetic"}))
 
 
