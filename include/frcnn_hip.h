@@ -37,7 +37,7 @@ extern "C" {
 #define FRCNN_EUNSUPPORTED -4   /* valid request outside what this build implements */
 #define FRCNN_ENODEVICE    -5   /* no gfx950 device visible */
 
-#define FRCNN_ABI_VERSION 17  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
+#define FRCNN_ABI_VERSION 18  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
                                  5: bf16 gradient GEMMs (the *_math entry points); 6: x6t GEMM, x6 Winograd layers, frcnn_forward_params.winograd_x6_mask,
                                  timing classes 8 / 9; 7: batched feature extractor (frcnn_resnet_backbone, frcnn_resnet_forward_features,
                                  frcnn_ctx_create_backbone, frcnn_conv3x3_nhwc_winograd_fused_maps); 8: the f32x3 arithmetic (frcnn_*_x3t, frcnn_*_winograd_x3,
@@ -49,21 +49,15 @@ extern "C" {
                                  FRCNN_MATH_F32X6 and fc mode 1 = FRCNN_FC_F32X6 are FRCNN_EINVAL); the f32x6 arithmetic stays as gemm_x6t / wino_x6; 14: FRCNN_X3F_PAIR, frcnn_conv3x3_winograd_x3_pair_workspace_bytes, frcnn_forward_params.winograd_x3p_mask,
                                  frcnn_resnet_rpn_roipool / frcnn_ctx_create_head / frcnn_resnet_head; 15: frcnn_conv_nhwc_x3g_tickets (split reductions finished inside the kernel), frcnn_pack_conv_x3g_weights + FRCNN_X3G_WSPLIT + frcnn_bottleneck_weights.g3 == 2 (pre-split weight packs);
                                  16: frcnn_train_conv, frcnn_bottleneck_backward(_workspace_bytes): the backward of one trainable bottleneck as ONE call, weight gradients on a second stream;
-                                 17: frcnn_dropout, frcnn_dropout_relu_backward (training-mode dropout of the VGG-16 head) */
+                                 17: frcnn_dropout, frcnn_dropout_relu_backward (training-mode dropout of the VGG-16 head);
+                                 18: REMOVED the eight-wave (round 5) and two-pass (round 6) forms of the one-launch f32x3 layer that no table has used (FRCNN_X3F_WAVES4 /
+                                 FRCNN_X3F_WAVES8 / FRCNN_X3F_PAIR, frcnn_conv3x3_winograd_x3_pair_workspace_bytes, frcnn_forward_params.winograd_x3p_mask;
+                                 measured in DESIGN.md section 5) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
 #define FRCNN_POOL2  2u   /* fuse MaxPool2d(2, stride 2, floor) into the conv epilogue */
-/* ABI 12, frcnn_conv3x3_nhwc_winograd_x3_fused / _chain only: force one of the two forms of the one-launch f32x3 layer (both bits clear: the
- * launcher chooses by cin).  The forms give the same results bit for bit (tests/test_gemm_x3t_gpu.py); the bits exist for that test and for
- * tools/x3f_bench.py / tools/xd_clocks.py. */
-#define FRCNN_X3F_WAVES4 0x100u   /* wino_x3d_kernel: four waves, one per SIMD, 256 accumulator registers (csrc/wino_x3f.hip) */
-#define FRCNN_X3F_WAVES8 0x200u   /* wino_x3e_kernel: eight waves, two per SIMD, 128 accumulator registers (csrc/wino_x3e.hip) */
-/* ABI 14: the TWO-PASS form of the one-launch f32x3 layer, 128 output channels per block (wino_x3p_kernel, csrc/wino_x3p.hip): cin % 32 == 0,
- * cin >= 64, cout % 128 == 0; same results bit for bit; d_ws >= frcnn_conv3x3_winograd_x3_pair_workspace_bytes (channel maxima + the
- * block-private scratch the first pass's accumulators rest in). */
 #define FRCNN_X3G_WSPLIT 0x800u   /* frcnn_conv_nhwc_x3g(_tickets): d_w_packed is the PRE-SPLIT image of the float32 pack (frcnn_pack_conv_x3g_weights, round 6) */
-#define FRCNN_X3F_PAIR   0x400u
 
 int         frcnn_abi_version(void);
 const char* frcnn_error_string(int code);
@@ -279,9 +273,9 @@ int frcnn_conv3x3_nhwc_winograd_x3(const float* d_x, const void* d_blob, const f
  * of VGG-16; with several images in flight also the 512-channel layers).  The same operands, products and accumulation order as
  * frcnn_conv3x3_nhwc_winograd_x3 on the same blob; the output transform combines columns before rows, so the two forms differ by the
  * float32 rounding of that transform only (<= 2e-6 of max|y|, tests/test_gemm_x3t_gpu.py).  cin % 32 == 0, cout % 64 == 0;
- * d_ws >= frcnn_conv3x3_winograd_x3_fused_workspace_bytes (the channel maxima of the input). */
+ * d_ws >= frcnn_conv3x3_winograd_x3_fused_workspace_bytes (the channel maxima of the input).  Its eight-wave and two-pass forms were removed
+ * in ABI 18 (measurements: DESIGN.md section 5); flag bits other than FRCNN_RELU / FRCNN_POOL2 are ignored. */
 size_t frcnn_conv3x3_winograd_x3_fused_workspace_bytes(int n_maps, int H, int W);
-size_t frcnn_conv3x3_winograd_x3_pair_workspace_bytes(int n_maps, int H, int W, int cout);   /* with FRCNN_X3F_PAIR (0: shape not supported) */
 int frcnn_conv3x3_nhwc_winograd_x3_fused(const float* d_x, const void* d_blob, const float* d_bias, float* d_y, int n_maps, int H, int W,
                                          int cin, int cout, unsigned flags, void* d_ws, size_t ws_bytes, void* stream);
 /* The same two layers CHAINED (round 4): an f32x3 layer takes its scales from the per-pixel channel maximum of its INPUT.  d_cmax_in (optional):
@@ -523,9 +517,6 @@ typedef struct frcnn_forward_params {
                                    pointer is frcnn_pack_conv3x3_winograd_x3's blob.  For the layers whose V + M scratch does not fit the Infinity
                                    Cache (conv2_1 .. conv3_3) and, when several images are in flight and the chip is full anyway, for the 512-channel
                                    layers too (one launch instead of three, no scratch traffic).  cin % 32 == 0, cout % 64 == 0 */
-    int32_t winograd_x3p_mask;  /* round 6 (ABI 14): a subset of winograd_x3f_mask -- the one-launch f32x3 layers that run in the TWO-PASS form with 128 output
-                                   channels per block (FRCNN_X3F_PAIR, csrc/wino_x3p.hip; cin >= 64, cout % 128 == 0).  Same results bit for bit;
-                                   the ctx keeps the scratch the first pass's accumulators rest in (256 KB per block of the layer's grid) */
 } frcnn_forward_params;
 #define FRCNN_X6_RPN_TRUNK_BIT 13
 /* capacity of the detector heads: classifier (n) + regressor (4 n - 4) rows are stacked into one zero-padded GEMM operand of

@@ -1,6 +1,6 @@
 // tools/micro/mfma_fill2.hip -- development aid (round 5): what does a SIMD pay for NF "filler" instructions per v_mfma_f32_32x32x16_f16 gap
 // with ONE wave on it (256-thread block, 512 registers) and with TWO (512-thread block, 256 registers each)?  The question behind the
-// 8-wave form of the one-launch f32x3 Winograd kernel (csrc/wino_x3e.hip): the 4-wave kernel pays MFMA + fillers as a SUM.
+// 8-wave form of the one-launch f32x3 Winograd kernel (removed in ABI 18): the 4-wave kernel pays MFMA + fillers as a SUM.
 //   hipcc --offload-arch=gfx950 -O3 tools/micro/mfma_fill2.hip -o /tmp/mfma_fill2 && /tmp/mfma_fill2
 // Every instruction is `asm volatile` (program order = source order).  Filler kinds:
 //   0 v_fma_f32 on 16 independent chains          1 v_fma_mixlo_f16 / v_fma_mixhi_f16 pairs (the operand split of wino_x3d_kernel)

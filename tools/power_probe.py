@@ -67,7 +67,7 @@ def main():
     ws = t.empty((wsb,), dtype=t.uint8, device=dev)
     cm = t.empty((h, w), device=dev)
     nv.check(lib.frcnn_pixel_absmax(nv.ptr(x), nv.ptr(cm), h * w, cin, s), "absmax")
-    flags = nv.RELU | (nv.POOL2 if pool else 0) | nv.X3F_WAVES4
+    flags = nv.RELU | (nv.POOL2 if pool else 0)
 
     def launch(n):
         for _ in range(n):

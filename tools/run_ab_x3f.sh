@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for spec in "$@"; do
     name=${spec%%:*}; rest=${spec#*:}; lib=${rest%%:*}; clk=${rest#*:}
-    FRCNN_LIB_PATH=$lib timeout 300 python tools/x3f_bench.py 2>&1 | grep -v amdgpu.ids | sed -e 's/.*one-launch, channel maxima given: four//' -e 's/ (.*//' | tr '\n' ' ' > $OUT/x3f_${name}_$rep.txt
+    FRCNN_LIB_PATH=$lib timeout 300 python tools/x3f_bench.py 2>&1 | grep -v amdgpu.ids | sed -e 's/.*one-launch, channel maxima given: //' -e 's/ (.*//' | tr '\n' ' ' > $OUT/x3f_${name}_$rep.txt
     echo "x3f us $name #$rep: $(cat $OUT/x3f_${name}_$rep.txt)"
 done; done
 for spec in "$@"; do

@@ -25,7 +25,7 @@ def run(name, cin, cout, h, w, pool):
     y = t.zeros((oh * ow * cout + 16 * nblk,), device=dev)
     wsb = int(lib.frcnn_conv3x3_winograd_x3_fused_workspace_bytes(1, h, w))
     ws = t.empty((wsb,), dtype=t.uint8, device=dev)
-    flags = nv.RELU | (nv.POOL2 if pool else 0) | nv.X3F_WAVES4
+    flags = nv.RELU | (nv.POOL2 if pool else 0)
     for rep in range(5):
         nv.check(lib.frcnn_conv3x3_nhwc_winograd_x3_fused(nv.ptr(x), nv.ptr(u), nv.ptr(b), nv.ptr(y), 1, h, w, cin, cout, flags, nv.ptr(ws), wsb, s), "x3f")
     t.cuda.synchronize()
