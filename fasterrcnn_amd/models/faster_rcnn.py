@@ -90,9 +90,10 @@ class FasterRCNNModel(nn.Module):
 
         # Backbone
         self.backbone = backbone
+        # (vgg16_torch.VGG16Backbone is a vgg16.VGG16Backbone: the same network in torchvision's module layout)
         if not isinstance(backbone, (vgg16.VGG16Backbone, resnet.ResNetBackbone)):
-            raise NotImplementedError("this build accelerates the VGG-16 (models/vgg16.py) and ResNet (models/resnet.py) "
-                                      "backbones; got %s" % type(backbone).__name__)
+            raise NotImplementedError("this build accelerates the VGG-16 (models/vgg16.py, models/vgg16_torch.py) and ResNet "
+                                      "(models/resnet.py) backbones; got %s" % type(backbone).__name__)
         self._is_resnet = isinstance(backbone, resnet.ResNetBackbone)
 
         # Network stages

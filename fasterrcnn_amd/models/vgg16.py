@@ -136,12 +136,11 @@ def conv3x3(x_hwc, wp, b, cin, cout, relu=True, pool=False, one_launch=False):
 class FeatureExtractor(nn.Module):
     def __init__(self):
         super().__init__()
-        for name, cin, cout, _ in _LAYERS:
-            setattr(self, name, nn.Conv2d(in_channels=cin, out_channels=cout, kernel_size=(3, 3), stride=1, padding="same"))
+        self._make_layers()
         # Freeze first two convolutional blocks (vgg16.py:49-58) -- no effect on inference
-        for name in ("_block1_conv1", "_block1_conv2", "_block2_conv1", "_block2_conv2"):
-            getattr(self, name).weight.requires_grad = False
-            getattr(self, name).bias.requires_grad = False
+        for conv in self.convs()[:4]:
+            conv.weight.requires_grad = False
+            conv.bias.requires_grad = False
         self._packed_key = None
         self._packed = None
         self.math_mode = "f32"
@@ -162,7 +161,13 @@ class FeatureExtractor(nn.Module):
             return "f32_winograd_x3" if name in self.x3_layers else "f32_winograd_x6"
         return self.math_mode
 
+    def _make_layers(self):
+        """Registers the 13 nn.Conv2d parameter holders (a subclass with another module layout overrides this and convs())."""
+        for name, cin, cout, _ in _LAYERS:
+            setattr(self, name, nn.Conv2d(in_channels=cin, out_channels=cout, kernel_size=(3, 3), stride=1, padding="same"))
+
     def convs(self):
+        """The 13 nn.Conv2d in _LAYERS order: everything that packs, trains or writes back the weights reaches them through here."""
         return [getattr(self, name) for name, _, _, _ in _LAYERS]
 
     def packed(self):
@@ -207,14 +212,19 @@ class FeatureExtractor(nn.Module):
 class PoolToFeatureVector(nn.Module):
     def __init__(self, dropout_probability):
         super().__init__()
+        self._make_layers(dropout_probability)
+        self._packed_key = None
+        self._packed = None
+        self.fc_math_mode = "f32"
+
+    def _make_layers(self, dropout_probability):
+        """Registers _fc1, _fc2, _dropout1, _dropout2 (a subclass with another module layout overrides this and exposes the same four
+        names, which packing, dropout and the train step read)."""
         self._fc1 = nn.Linear(in_features=512 * 7 * 7, out_features=4096)
         self._fc2 = nn.Linear(in_features=4096, out_features=4096)
         # Dropout is the identity at inference; in training mode (forward below, and the train step) csrc/dropout.hip applies it
         self._dropout1 = nn.Dropout(p=dropout_probability)
         self._dropout2 = nn.Dropout(p=dropout_probability)
-        self._packed_key = None
-        self._packed = None
-        self.fc_math_mode = "f32"
 
     def packed_direct(self):
         """float32 packs whatever the inference arithmetic is (the train step's masters): fc1 with its input dimension permuted
@@ -386,6 +396,10 @@ def linear(x, w, b, n_out, relu):
 
 
 class VGG16Backbone(Backbone):
+    # the stage modules built below (models/vgg16_torch.py swaps in its torchvision-layout subclasses)
+    _feature_extractor_class = FeatureExtractor
+    _pool_to_feature_vector_class = PoolToFeatureVector
+
     def __init__(self, dropout_probability):
         super().__init__()
         self.feature_map_channels = 512
@@ -393,8 +407,8 @@ class VGG16Backbone(Backbone):
         self.feature_vector_size = 4096
         self.image_preprocessing_params = image.PreprocessingParams(
             channel_order=image.ChannelOrder.BGR, scaling=1.0, means=[103.939, 116.779, 123.680], stds=[1, 1, 1])
-        self.feature_extractor = FeatureExtractor()
-        self.pool_to_feature_vector = PoolToFeatureVector(dropout_probability=dropout_probability)
+        self.feature_extractor = self._feature_extractor_class()
+        self.pool_to_feature_vector = self._pool_to_feature_vector_class(dropout_probability=dropout_probability)
 
     def compute_feature_map_shape(self, image_shape):
         image_width = image_shape[-1]

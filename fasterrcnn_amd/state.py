@@ -7,6 +7,7 @@ trained weights into the HIP-backed FasterRCNNModel from the file formats the re
      load as-is (VGG-16 and ResNet alike);
   2. Caffe VGG-16 `.pth` files (torchvision-style keys features.N / classifier.N, state.py:178-219);
   3. the author's Keras VGG-16 `.h5` files (state.py:61-176) when h5py is installed.
+Formats 2 and 3 load into either VGG-16 backbone (models/vgg16.py, models/vgg16_torch.py: keys remapped).
 
 One deliberate difference: state.py:197-198 maps fc1/fc2 to `_stage3_detector_network._fc1/_fc2`,
 which are not the model's keys (the live ones are `..._pool_to_feature_vector._fc1/_fc2`), so the
@@ -15,6 +16,8 @@ reference's strict load raises after copying the conv layers and the FC weights 
 and the partial state is loaded non-strictly, with the untouched keys reported.
 """
 import torch as t
+
+from .models import vgg16_torch
 
 _CAFFE_VGG16 = {
     "features.0": "_stage1_feature_extractor._block1_conv1", "features.2": "_stage1_feature_extractor._block1_conv2",
@@ -86,6 +89,10 @@ def vgg16_state_from_keras(filepath):
     return state, missing
 
 
+def _is_vgg16_torch(model):
+    return isinstance(getattr(model, "backbone", None), vgg16_torch.VGG16Backbone)
+
+
 def load(model, filepath):
     """
     Loads weights from `filepath` into `model` (state.py:221-272).  Returns the list of model keys that
@@ -108,6 +115,8 @@ def load(model, filepath):
                 print("Loaded initial VGG-16 layer weights from Caffe model '%s'" % filepath)
             except ValueError:
                 state = None
+    if state is not None and _is_vgg16_torch(model):
+        state = vgg16_torch.from_vgg16_state_dict(state)        # the same tensors under the torchvision-layout backbone's keys
     if state is None:
         if not isinstance(blob, dict) or "model_state_dict" not in blob:
             raise KeyError("Model state file '%s' is missing top-level key 'model_state_dict'" % filepath)

@@ -9,6 +9,12 @@ scaled by fixed constants so the pipeline is exercised non-degenerately (feature
 objectness logits std ~1, RPN deltas std ~0.3, class logits std ~3, box deltas std ~1).  The
 constants were measured once with the imported reference (oracle/calibrate.py prints them) and
 are frozen here so no calibration forward is needed at run time.
+
+The torchvision-layout VGG-16 backbone (models/vgg16_torch.py) takes the same weights under its own keys
+(vgg16_torch_state_dict: the key remap of vgg16_torch.from_vgg16_state_dict) and RGB input scaled by 1/255
+with the ImageNet mean / std (image_rgb), about 59x smaller than the caffe-range BGR input the multipliers
+were measured with; the network is positively homogeneous (ReLU, max-pool, zero biases), so one extra
+multiplier on the last convolution (VGG16_TORCH_INPUT_GAIN) restores the calibrated statistics.
 """
 import math
 
@@ -53,6 +59,20 @@ def vgg16_state_dict(seed=1234, num_classes=21, calibration=None):
     he("_stage3_detector_network._pool_to_feature_vector._fc2", (4096, 4096), 4096)
     he("_stage3_detector_network._classifier", (num_classes, 4096), 4096)
     he("_stage3_detector_network._regressor", ((num_classes - 1) * 4, 4096), 4096)
+    return sd
+
+
+# feature-map std on image(0) / on image_rgb(0) with vgg16_state_dict(1234) (tools/make_vgg16_torch_golden.py --calibrate)
+VGG16_TORCH_INPUT_GAIN = 59.2677745
+
+
+def vgg16_torch_state_dict(seed=1234, num_classes=21, gain=VGG16_TORCH_INPUT_GAIN):
+    """state_dict (CPU float32) of FasterRCNNModel over vgg16_torch.VGG16Backbone (the reference's vgg16-torch keys): vgg16_state_dict's
+    tensors under the remapped keys, the last convolution multiplied by `gain` for ImageNet-normalised RGB input (image_rgb)."""
+    from .models import vgg16_torch
+    sd = vgg16_torch.from_vgg16_state_dict(vgg16_state_dict(seed, num_classes))
+    key = "_stage1_feature_extractor._layers.%d.weight" % vgg16_torch.CONV_INDICES[-1]
+    sd[key] = sd[key] * float(gain)
     return sd
 
 
