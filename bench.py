@@ -1,9 +1,14 @@
 """
 bench.py -- images/sec of Faster R-CNN VGG-16 inference (600x1000, 300 proposals) on N x MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline alone: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+Everything else this file measures or checks runs only with `--full`: the other arithmetic tables, the host-fed, single-stream,
+ResNet-50 and train-step legs, the per-rank burst, clocks under load, the parity block, the host CPU per image, mAP@0.5, the
+roofline block and the CPU baseline.  Their fields are null (or absent) in a plain run's line.
 
 A "step" is one `predict()` of one synthetic, already-preprocessed float32 3x600x1000 image that is
 resident in HBM when the timed region starts: VGG-16 backbone, RPN (6000 pre- / 300 post-NMS),
@@ -17,12 +22,12 @@ RPN trunk) as Winograd layers whose GEMMs run in the "f32x3" split-operand arith
 operand, three fp16 MFMAs per product, f32 accumulation: operands held to 22-23 bits of their row's / tile's largest element); the 1x1 /
 head GEMMs on the exact-f32 pipe.  The table is chosen by measurement against a float64 evaluation of the network on held-out images
 (the f32x3 layers are CLOSER to the float64 truth than the exact-f32 matrix instructions are).  Legs of the same
-workload in the same run: `config.strict_f32_images_per_sec` (EVERY GEMM on the exact-f32 pipe), `config.h2d_preprocess_images_per_sec`
+workload in the same run (--full): `config.strict_f32_images_per_sec` (EVERY GEMM on the exact-f32 pipe), `config.h2d_preprocess_images_per_sec`
 (fed from pinned host memory through H2D + GPU preprocessing inside the timed region), `fc_math_f32_images_per_sec`,
 `winograd_all_f32_pipe_images_per_sec`, `f32x6_only_images_per_sec`, `round3_table_images_per_sec`.
 
 Multi-GPU: image-parallel, rank r owns its own images, no data-path collective; weak scaling
-(K steps per rank).  The mAP@0.5 bookkeeping runs after the timed region on a small labelled
+(K steps per rank).  With --full, the mAP@0.5 bookkeeping runs after the timed region on a small labelled
 subset and is merged across ranks with the single all-gather of fasterrcnn_amd/evaluate.py.
 
 The headline is ONE timed burst of exactly K steps (`--min-timed-seconds S` repeats it until S seconds are timed and reports
@@ -718,6 +723,10 @@ def main():
                     help="after the timed steps, write what the last timed step returned (predict()'s per-class (n, 5) float64 detections) "
                          "as DIR/detections.npy, (N, 6) rows of (class, y1, x1, y2, x2, score) in class order, and "
                          "DIR/detections_per_class.npy, the row count of each class 1..20; rank 0 only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: the other arithmetic tables, host-fed, single-stream, ResNet-50 and "
+                         "train-step legs, per-rank burst, clocks under load, parity, host CPU per image, mAP@0.5, roofline, CPU baseline "
+                         "(the --no-* options and --map-images / --roofline-images / --cpu-images shape them); off by default")
     args = ap.parse_args()
 
     rank, local_rank, world = rank_environment()
@@ -818,28 +827,31 @@ def main():
         rows, counts = pack_detections(last_step["out"])
         np.save(os.path.join(args.dump_outputs, "detections.npy"), rows)
         np.save(os.path.join(args.dump_outputs, "detections_per_class.npy"), counts)
+    # ---- --full only from here on: every leg below is informational, outside the timed region, and not the headline value ----------
     # per-rank view of the same timed region (each rank's own wall time of its median burst is not kept: the burst time is already the
     # max over ranks; what differs per rank is its LOCAL burst, measured here without the barrier), gathered for the JSON line
-    torch.cuda.synchronize(dev)
-    t_loc = time.perf_counter()
-    run(args.steps)
-    torch.cuda.synchronize(dev)
-    local_ips = args.steps / (time.perf_counter() - t_loc)
-    per_rank = [round(local_ips, 3)]
-    if use_dist:
-        tt = torch.zeros(world, dtype=torch.float64, device=dev)
-        tt[rank] = local_ips
-        dist.all_reduce(tt, op=dist.ReduceOp.SUM)
-        per_rank = [round(float(v), 3) for v in tt.tolist()]
+    per_rank = None
+    if args.full:
+        torch.cuda.synchronize(dev)
+        t_loc = time.perf_counter()
+        run(args.steps)
+        torch.cuda.synchronize(dev)
+        local_ips = args.steps / (time.perf_counter() - t_loc)
+        per_rank = [round(local_ips, 3)]
+        if use_dist:
+            tt = torch.zeros(world, dtype=torch.float64, device=dev)
+            tt[rank] = local_ips
+            dist.all_reduce(tt, op=dist.ReduceOp.SUM)
+            per_rank = [round(float(v), 3) for v in tt.tolist()]
 
     # clocks / power under the headline load (rocm-smi sampled in the middle of one more, untimed, second of the same load)
     smi = None
-    if rank == 0:
+    if rank == 0 and args.full:
         smi = sample_rocm_smi(lambda: run(nslots), local_rank)
 
     # ---- informational: the same workload in the other math modes (not the headline value) -----------
     secondary = {}
-    if not is_resnet and not args.no_secondary:
+    if args.full and not is_resnet and not args.no_secondary:
         for mode in ("f32", "f32_winograd"):
             if mode == args.math:
                 continue
@@ -853,7 +865,7 @@ def main():
     x3 = tuple(getattr(model, "winograd_x3_layers", ())) if args.math == "f32_winograd" else ()
     x3f = tuple(n_ for n_ in getattr(model, "winograd_x3f_layers", ()) if n_ not in x6) if (args.math == "f32_winograd" and not is_resnet) else ()
     fc_f32_value = None
-    if not is_resnet and not args.no_secondary and fc_math != "f32":
+    if args.full and not is_resnet and not args.no_secondary and fc_math != "f32":
         # the same workload with fc1 / fc2 on the exact-f32 pipe too: every GEMM of the image on v_mfma_f32_*_f32
         model.fc_math_mode = "f32"
         run(max(args.warmup, nslots))
@@ -863,7 +875,7 @@ def main():
         run(nslots)
 
     wino_f32_value = None
-    if not is_resnet and not args.no_secondary and (x6 or x3f):
+    if args.full and not is_resnet and not args.no_secondary and (x6 or x3f):
         # the same workload with EVERY 3x3 layer on the exact-f32 pipe (rounds 1-2's default table: no x6 Winograd layer)
         model.winograd_x6_layers = ()
         model.winograd_x3f_layers = ()
@@ -876,7 +888,7 @@ def main():
         run(nslots)
 
     strict_f32_value = None
-    if not is_resnet and not args.no_secondary and (x6 or x3f or fc_math != "f32"):
+    if args.full and not is_resnet and not args.no_secondary and (x6 or x3f or fc_math != "f32"):
         # STRICT float32: every GEMM of the image on the exact-f32 matrix instructions (no split-operand layer anywhere)
         model.winograd_x6_layers = ()
         model.winograd_x3f_layers = ()
@@ -896,7 +908,7 @@ def main():
     # slot's feeder stream -> frcnn_preprocess (PIL-exact resize 375x625 -> 600x1000 + normalisation) -> predict_async; and the
     # reference's literal form, the preprocessed float32 tensor uploaded as is (7.2 MB per image).
     h2d = {}
-    if not is_resnet and not args.no_secondary:
+    if args.full and not is_resnet and not args.no_secondary:
         from fasterrcnn_amd.evaluate import HostFeeder
         feeder = HostFeeder(model, lookahead=2 * nslots)
         host_u8 = [synthetic.image_u8(s_).pin_memory() for s_ in seeds]
@@ -941,7 +953,7 @@ def main():
         run(nslots)
 
     x3_legs = {}
-    if not is_resnet and not args.no_secondary and x3f:
+    if args.full and not is_resnet and not args.no_secondary and x3f:
         # conv1_2 .. conv3_3 back on the float32 one-launch Winograd kernel and the 512-channel layers on their three launches in every slot
         # (round 3's pipeline for those layers)
         inflight_x3f = model.inflight_winograd_x3f_layers
@@ -953,7 +965,7 @@ def main():
         model.winograd_x3f_layers = x3f
         model.inflight_winograd_x3f_layers = inflight_x3f
         run(nslots)
-    if not is_resnet and not args.no_secondary and x6:
+    if args.full and not is_resnet and not args.no_secondary and x6:
         # the f32x3 arithmetic switched off (every split-operand GEMM in f32x6: the table before the f32x3 kernels existed), and round 3's
         # default table (conv5_1 kept in f32x6 because one box of one golden fixture then landed at 0.92e-3 instead of 1.04e-3 px; round 4
         # chooses the table against the float64 truth on held-out images instead: DESIGN.md section 4)
@@ -967,7 +979,7 @@ def main():
 
     # ---- driver-timed secondary legs (rank 0 of a one-GPU run; none of them is the headline value) -------------------
     extra = {}
-    if rank == 0 and n_gpus == 1 and not args.no_extra_legs and not is_resnet:
+    if rank == 0 and args.full and n_gpus == 1 and not args.no_extra_legs and not is_resnet:
         # (1) configs[1] taken literally: ONE image on the chip at a time (slot 0 = the latency configuration of predict())
         def run_single(n_steps):
             for i in range(n_steps):
@@ -1088,7 +1100,7 @@ def main():
     # ---- parity block and the host's cost per image (item 7), rank 0, outside the timed region -------------------
     parity = None
     host_us = None
-    if rank == 0 and not is_resnet:
+    if rank == 0 and args.full and not is_resnet:
         try:
             parity = parity_leg(model, 0 if nslots == 1 else 1, synthetic.image, dev)
         except Exception as e:
@@ -1115,15 +1127,18 @@ def main():
                            "one host need 8 x this per image-interval of CPU, against the wall time per image beside it"}
 
     # ---- mAP@0.5 leg (outside the timed region): labelled subset, merged across ranks -------------
-    records = ImageRecords()
-    for i in range(min(args.map_images, len(pool))):
-        det = model.predict(pool[i], score_threshold=0.05)
-        records.add(seeds[i], det, planted_ground_truth(seeds[i], det))
-    calc = merged_calculator(records, force_gather=use_dist)       # ONE all-gather over RCCL when a process group is up
-    mean_ap = float(calc.compute_mean_average_precision()) if calc._object_count_by_class_index else None
+    mean_ap = None
+    if args.full:
+        records = ImageRecords()
+        for i in range(min(args.map_images, len(pool))):
+            det = model.predict(pool[i], score_threshold=0.05)
+            records.add(seeds[i], det, planted_ground_truth(seeds[i], det))
+        calc = merged_calculator(records, force_gather=use_dist)       # ONE all-gather over RCCL when a process group is up
+        mean_ap = float(calc.compute_mean_average_precision()) if calc._object_count_by_class_index else None
 
     out = None
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: HIP events around every conv3x3 MFMA launch, one stream
         # Per image: read + reset the per-class event sums, then keep the MEDIAN image per class (times its launch count), so
         # that one image hit by a clock ramp after the idle gap of the previous leg does not skew the mean.
@@ -1282,9 +1297,13 @@ def main():
                 roofline["per_layer"] = winograd_layer_fracs(dev)
             except Exception as e:
                 roofline["per_layer"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        if is_resnet:
+            roofline = {"note": "roofline block is defined for the VGG-16 headline workload only",
+                        "per_class_ms_per_image": roofline["per_class_ms_per_image"]}
 
+    if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and n_gpus == 1 and not is_resnet:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1 and not is_resnet:
             from oracle import frcnn_oracle as O       # CPU baseline leg only (checker, never the product)
             img0 = synthetic.image(seeds[0]).unsqueeze(0)
             cores = cpu_threads_for_baseline(sd, img0, O)
@@ -1301,9 +1320,6 @@ def main():
         # algorithmic FLOP per image: VGG-16 from the layer shapes, ResNets from BASELINE.md section 3
         flops_img = {"vgg16": total_flops_per_image(), "resnet50": 2.7845e11, "resnet101": 3.6913e11,
                      "resnet152": 4.5937e11}[args.backbone]
-        if is_resnet:
-            roofline = {"note": "roofline block is defined for the VGG-16 headline workload only",
-                        "per_class_ms_per_image": roofline["per_class_ms_per_image"]}
         pipes = {}
         if not is_resnet:
             ips = value / n_gpus
@@ -1349,7 +1365,7 @@ def main():
             "ms_per_step": round(1e3 * elapsed / args.steps, 4),
             "timed_bursts": {"count": len(bursts), "reported": "median burst of `steps` steps", "min_ms": round(1e3 * min(bursts), 3),
                              "max_ms": round(1e3 * max(bursts), 3), "total_timed_s": round(sum(bursts), 3)},
-            "rocm_smi_under_load": smi, "process_group": ("nccl x%d" % world) if use_dist else None, "world_size": world, "higher_is_better": True, "scaling": "weak",
+            "full": args.full, "rocm_smi_under_load": smi, "process_group": ("nccl x%d" % world) if use_dist else None, "world_size": world, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": dtype_str, "data": "synthetic",
             "config": {"workload": ("VGG-16" if not is_resnet else args.backbone) + " Faster R-CNN predict(), 3x600x1000 float32, batch=1 per forward, "
                                    "6000 pre-/300 post-NMS proposals, score_threshold 0.05",
@@ -1367,10 +1383,10 @@ def main():
             "winograd_all_f32_pipe_images_per_sec": wino_f32_value, "strict_f32_images_per_sec": strict_f32_value,
             **h2d,
             **x3_legs,
-            "per_rank_images_per_sec": per_rank, "slowest_rank_images_per_sec": min(per_rank),
+            "per_rank_images_per_sec": per_rank, "slowest_rank_images_per_sec": min(per_rank) if per_rank else None,
             **pipes,
             **extra,
-            "map_at_0.5": mean_ap, "map_images": int(args.map_images * world),
+            "map_at_0.5": mean_ap, "map_images": int(args.map_images * world) if args.full else 0,
             "map_note": "plumbing check, not accuracy: random-init weights; the ground truth of each labelled image is seeded random boxes plus up "
                         "to 3 of the model's OWN top detections jittered by a few pixels, so the value only shows that predict -> per-image "
                         "records -> (all-gather) -> AP integration runs end to end and is reproducible; README.md:38's mAP needs trained weights",

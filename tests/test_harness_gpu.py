@@ -8,6 +8,7 @@ predict / predict_one) and the multi-GPU code path on ONE GPU:
   * the mAP gather over RCCL (backend "nccl") in a one-rank group: merged_calculator(force_gather=True);
   * bench.py under torch.distributed.run with --force-dist: init_process_group("nccl"), barriers, the max-over-ranks
     all-reduce of the burst time and the record all-gather all execute on RCCL;
+  * a plain bench.py run (no --full) runs the headline alone and still dumps its outputs;
   * predict_one on a PNG file == oracle preprocessing + oracle predict.
 """
 import json
@@ -216,11 +217,12 @@ print("RESULT " + json.dumps({"local": local, "merged": merged}), flush=True)
 
 def test_bench_multi_rank_branch_on_rccl():
     """bench.py launched exactly as the driver launches N > 1 (torch.distributed.run, one rank per GPU) with ONE rank and
-    --force-dist: process group on RCCL, barriers around the timed bursts, all-reduce(MAX) of the elapsed time, record gather."""
+    --force-dist: process group on RCCL, barriers around the timed bursts, all-reduce(MAX) of the elapsed time, record gather
+    (the mAP leg: --full)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
            "--force-dist", "--inflight", "4", "--no-cpu-baseline", "--no-secondary", "--no-extra-legs", "--ramp-seconds", "0.2",
-           "--min-timed-seconds", "0.05", "--roofline-images", "2", "--map-images", "2"]
+           "--min-timed-seconds", "0.05", "--roofline-images", "2", "--map-images", "2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -229,6 +231,28 @@ def test_bench_multi_rank_branch_on_rccl():
     assert r["process_group"] == "nccl x1" and r["n_gpus"] == 1 and r["steps"] == 4 and r["scaling"] == "weak"
     assert r["value"] > 0 and abs(r["value"] - 4 / (r["ms_per_step"] * 4 / 1e3)) <= 1e-2 * r["value"]
     assert r["map_at_0.5"] is not None and r["timed_bursts"]["count"] >= 1
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs no leg but the headline: the line carries the headline's fields, --full's
+    legs are null in it, and --dump-outputs still writes the last timed step's detections."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--ramp-seconds", "0.2",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["full"] is False and r["steps"] == 4 and r["warmup"] == 1 and r["timed_bursts"]["count"] == 1
+    assert r["unit"] == "images/sec" and r["higher_is_better"] is True and r["metric"].startswith("images/sec") and r["dtype"].startswith("f32")
+    assert r["value"] > 0 and abs(r["value"] - 4 / (r["ms_per_step"] * 4 / 1e3)) <= 1e-2 * r["value"]
+    for k in ("roofline", "cpu_baseline", "parity", "host_cpu_per_image", "map_at_0.5", "rocm_smi_under_load", "per_rank_images_per_sec",
+              "strict_f32_images_per_sec", "fc_math_f32_images_per_sec", "winograd_all_f32_pipe_images_per_sec"):
+        assert r[k] is None, k
+    assert r["other_math_modes_images_per_sec"] == {} and "single_stream_images_per_sec" not in r and "train_step_ms" not in r
+    assert "h2d_preprocess_images_per_sec" not in r and r["map_images"] == 0
+    rows, counts = np.load(str(tmp_path / "detections.npy")), np.load(str(tmp_path / "detections_per_class.npy"))
+    assert rows.shape == (int(counts.sum()), 6) and len(counts) == 20
 
 
 def test_predict_one_on_png_file(gpu_model, sd_cpu, tmp_path):

@@ -5,8 +5,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; grep -n "passed\|failed" $OUT/pytest_gpu.log | tail -2
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; echo "driver-form exit $?"
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default exit $?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; echo "driver-form exit $?"
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default exit $?"
 B="python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-secondary --no-extra-legs"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trace -o t -- $B > $OUT/trace.log 2>&1; echo "trace exit $?"
 cp $(ls /tmp/trace/*kernel_stats.csv /tmp/trace/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/kernel_stats.csv

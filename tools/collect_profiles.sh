@@ -8,10 +8,10 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 B="python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-secondary --no-extra-legs"
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"
 tail -c 2500 $OUT/bench_default.json
 # the driver's form of the same command (BENCH_rNN.json): --steps 20 --warmup 5
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; echo "driver-form bench exit $?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err; echo "driver-form bench exit $?"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $B > $OUT/trace.log 2>&1; echo "trace exit $?"
 P="python bench.py --steps 12 --warmup 4 --ramp-seconds 0 --no-cpu-baseline --no-secondary --no-extra-legs --inflight 1 --roofline-images 2 --map-images 0 --min-timed-seconds 0"
 # single-stream kernel durations (what bench.py's roofline block times with HIP events): kernel trace + stats, no counters

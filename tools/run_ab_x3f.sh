@@ -19,7 +19,7 @@ done
 for rep in 1 2; do
 for spec in "$@"; do
     name=${spec%%:*}; rest=${spec#*:}; lib=${rest%%:*}
-    FRCNN_LIB_PATH=$lib timeout 600 python bench.py --steps 20 --warmup 5 --no-secondary --no-extra-legs --no-cpu-baseline > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err
+    FRCNN_LIB_PATH=$lib timeout 600 python bench.py --steps 20 --warmup 5 --full --no-secondary --no-extra-legs --no-cpu-baseline > $OUT/bench_${name}_$rep.json 2> $OUT/bench_${name}_$rep.err
     python -c "
 import json;d=json.loads(open('$OUT/bench_${name}_$rep.json').read().strip().splitlines()[-1]);print('bench $name #$rep', d['value'],d['ms_per_step'],d['roofline']['frac'],d.get('parity',{}).get('golden_600x1000',{}).get('forward_rows_within_gate'))"
 done; done

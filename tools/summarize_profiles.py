@@ -23,7 +23,7 @@ def main(d):
     if os.path.exists(bench):
         lines = [l for l in open(bench).read().splitlines() if l.startswith("{")]
         if lines:
-            print("## bench.py (default flags)\n\n```json\n%s\n```\n" % lines[-1])
+            print("## bench.py --full (default flags otherwise)\n\n```json\n%s\n```\n" % lines[-1])
     stats = load(os.path.join(d, "trace", "*kernel_stats.csv"))
     if stats:
         print("## kernel trace + stats (bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-secondary, default images in flight)\n")
