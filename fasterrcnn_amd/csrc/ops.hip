@@ -1,0 +1,547 @@
+// ops.hip -- the kernels behind fasterrcnn_amd.ops: torchvision.ops-style roi_align, roi_pool, nms and batched_nms over N images,
+// with deterministic backward passes (the frcnn_ops_* entry points of include/frcnn_hip.h).
+//
+// Layouts: the feature map is NHWC [n][h][w][c] (a channels_last NCHW tensor), RoIs are torchvision's rows (b, x1, y1, x2, y2), the
+// pooled output is [k][out_h][out_w][c] (a channels_last [k][c][out_h][out_w] tensor).  c % 4 == 0: a pixel is float4 runs.
+// A RoI whose batch index b is outside (-1, n) -- truncated to an int as torchvision truncates it -- pools to zeros and gets no gradient.
+//
+// RoIAlign forward: the arithmetic of roi_align_kernel (csrc/roialign.hip), one block per (roi, ph), lanes over (pw, channel quad).
+// Backwards: no atomics.  One block per 2 x 2 cells of one image and 64 channel quads; its threads first cull the RoIs whose footprint
+// can touch the tile (in ascending order, up to OPS_LIST at a time), then each wave owns one cell and sums, RoI by RoI, the samples /
+// bins that hold it in a fixed order: bit-identical from run to run.  RoIAlign finds the samples of a cell analytically -- the sample rows within one
+// pixel of the cell, from the RoI's sample spacing, each then tested exactly -- so there is no cap on out_h / out_w or sampling_ratio.
+// RoIPool's backward sends each bin's gradient to the argmax cell its forward wrote (the first maximum in (h, w) scan order, -1 for an
+// empty bin), the design of roi_pool_argmax_kernel / roi_pool_scatter_kernel (csrc/train.hip).
+//
+// NMS: the caller sorts (torch.sort, stable) and passes the permutation; for batched NMS the permutation groups each category into
+// one contiguous segment.  ops_nms_mask_kernel writes 64 x 64 IoU bit tiles (only tiles on or above the diagonal whose rows and
+// columns can share a category), ops_nms_reduce_kernel runs the greedy pass of every segment in its own wave, in parallel, with the
+// segment's removed-bits in LDS.  float32 decides with iou_gt (csrc/geometry.h), float64 with the division in float64.
+#include "geometry.h"
+#include <cfloat>
+
+namespace frcnn {
+
+typedef unsigned long long u64;
+
+static constexpr int OPS_TILE = 2;           // backward tile: 2 x 2 cells, one per wave, 64 channel quads per block
+static constexpr int OPS_LIST = 1024;        // RoIs culled per pass of a tile
+static constexpr int OPS_MAX_OUT = 64;       // out_h, out_w <= 64
+static constexpr int OPS_MAX_SAMPLING = 16;  // sampling_ratio <= 16
+static constexpr int OPS_NMS_MAX_WORDS = 8192;   // removed-bits of one segment in 64 KB of LDS: n <= 524288
+
+// torchvision's `int roi_batch_ind = rois[0]` with the range check the op contract adds (NaN fails it)
+__device__ __forceinline__ bool roi_image(float v, int n_img, int& b)
+{
+    if (!(v > -1.0f && v < (float)n_img)) return false;
+    b = (int)v;
+    return true;
+}
+
+__device__ __forceinline__ RoiGeom ops_align_geom(const float* roi, float scale, int out_h, int out_w, int sampling_ratio, int aligned)
+{
+    return roi_align_geom(f32x4{roi[2], roi[1], roi[4], roi[3]}, scale, out_h, out_w, sampling_ratio, aligned);
+}
+
+// sample coordinate of bin p, sample i (roi_align_kernel's expression)
+__device__ __forceinline__ float sample_coord(float start, float bin, int grid, int p, int i)
+{
+    return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)grid;
+}
+
+__global__ __launch_bounds__(256)
+void ops_roi_align_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
+                          int out_w, float scale, int sampling_ratio, int aligned, float* __restrict__ out)
+{
+    const int r = blockIdx.x, ph = blockIdx.y;
+    const int C4 = C >> 2;
+    const float* roi = rois + (size_t)r * 5;
+    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * out_h + ph) * out_w * C);
+    int b;
+    if (!roi_image(roi[0], n_img, b)) {
+        for (int i = threadIdx.x; i < out_w * C4; i += 256) orow[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    const float* fm = x + (size_t)b * fh * fw * C;
+    const RoiGeom g = ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned);
+    for (int i = threadIdx.x; i < out_w * C4; i += 256) {
+        const int pw = i / C4, c4 = i - pw * C4;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int iy = 0; iy < g.grid_h; ++iy) {
+            const float y = sample_coord(g.start_h, g.bin_h, g.grid_h, ph, iy);
+            int yl, yh; float hy, ly;
+            const bool yok = axis_weights(y, fh, yl, yh, hy, ly);
+            for (int ix = 0; ix < g.grid_w; ++ix) {
+                const float xx = sample_coord(g.start_w, g.bin_w, g.grid_w, pw, ix);
+                int xl, xh; float hx, lx;
+                if (!yok || !axis_weights(xx, fw, xl, xh, hx, lx)) continue;
+                const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+                const f32x4 v1 = reinterpret_cast<const f32x4*>(fm + ((size_t)yl * fw + xl) * C)[c4];
+                const f32x4 v2 = reinterpret_cast<const f32x4*>(fm + ((size_t)yl * fw + xh) * C)[c4];
+                const f32x4 v3 = reinterpret_cast<const f32x4*>(fm + ((size_t)yh * fw + xl) * C)[c4];
+                const f32x4 v4 = reinterpret_cast<const f32x4*>(fm + ((size_t)yh * fw + xh) * C)[c4];
+                acc = acc + (((v1 * w1 + v2 * w2) + v3 * w3) + v4 * w4);
+            }
+        }
+        orow[i] = acc / g.count;
+    }
+}
+
+// The sample positions s = p * grid + i (0 <= s < n_out * grid) whose coordinate can lie within one pixel of `cell`: the linear model
+// of the positions, widened by one sample and a relative margin for rounding; every candidate is then evaluated exactly by the caller.
+__device__ __forceinline__ void sample_range(int cell, float start, float bin, int grid, int n_out, int& s_lo, int& s_hi)
+{
+    const long long last = min((long long)n_out * grid, (long long)INT32_MAX) - 1;      // grid >= 1 here
+    const float step = bin / (float)grid;
+    if (!(step > 0.f)) { s_lo = 0; s_hi = (int)last; return; }              // zero-size or inverted RoI (aligned): every sample
+    const float pad = 1.0f + 1e-4f * (fabsf(start) + fabsf(bin) * (float)n_out + 2.0f) / step;
+    const float a = ((float)cell - 1.0f - start) / step - 0.5f - pad;
+    const float e = ((float)cell + 1.0f - start) / step - 0.5f + pad;
+    // clamped in float first (the conversion of an out-of-range float is undefined), then exactly in integers
+    s_lo = (int)fminf(fmaxf(floorf(a), 0.f), 2.0e9f);
+    s_hi = (int)min((long long)fmaxf(fminf(ceilf(e), 2.0e9f), -1.0f), last);
+}
+
+// the weight of `cell` in a sample's bilinear footprint along one axis; false when the sample does not touch it
+__device__ __forceinline__ bool cell_weight(float v, int n, int cell, float& w)
+{
+    int lo, hi; float wl, wh;
+    if (!axis_weights(v, n, lo, hi, wl, wh)) return false;
+    bool hit = false;
+    if (lo == cell) { w = wl; hit = true; }
+    if (hi == cell) { w = hit ? w + wh : wh; hit = true; }
+    return hit;
+}
+
+// Ordered culling shared by the two backward kernels: appends to s_list, in ascending order, the RoIs r >= r_begin for which
+// touches(r) holds, until OPS_LIST are listed.  Returns the first RoI not examined (k when all were).  Block of 256 threads.
+template <typename Touches>
+__device__ int cull_rois(int r_begin, int k, Touches touches, int* s_list, int* s_cnt, int* s_n)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                     // the previous pass has finished reading s_list
+    if (tid == 0) *s_n = 0;
+    int r0 = r_begin;
+    for (; r0 < k; r0 += 256) {
+        const int r = r0 + tid;
+        const bool hit = r < k && touches(r);
+        const u64 m = __ballot(hit);
+        if (lane == 0) s_cnt[wave] = __popcll(m);
+        __syncthreads();
+        const int base = *s_n;
+        const int total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (base + total > OPS_LIST) break;              // uniform: the list is full; this group starts the next pass
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += s_cnt[w];
+        if (hit) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+        __syncthreads();
+        if (tid == 0) *s_n = base + total;
+    }
+    __syncthreads();
+    return r0 < k ? r0 : k;
+}
+
+__global__ __launch_bounds__(256)
+void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
+                                   float scale, int sampling_ratio, int aligned, const float* __restrict__ dout, float* __restrict__ dx)
+{
+    __shared__ int s_list[OPS_LIST];
+    __shared__ int s_cnt[4];
+    __shared__ int s_n;
+    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    const int img = blockIdx.z / n_chunks, chunk = blockIdx.z - img * n_chunks;
+    const int ty0 = blockIdx.y * OPS_TILE, tx0 = blockIdx.x * OPS_TILE;
+    const int ty1 = min(ty0 + OPS_TILE, fh) - 1, tx1 = min(tx0 + OPS_TILE, fw) - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c4 = chunk * 64 + lane;
+    const bool act = c4 < C4;
+    f32x4* const dimg = reinterpret_cast<f32x4*>(dx + (size_t)img * fh * fw * C);
+
+    auto touches = [&](int r) {
+        const float* roi = rois + (size_t)r * 5;
+        int b;
+        if (!roi_image(roi[0], n_img, b) || b != img) return false;
+        const RoiGeom g = ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned);
+        if (g.grid_h <= 0 || g.grid_w <= 0) return false;
+        // every sample lies between start and start + out * bin; its footprint within one cell of it (two: margin for rounding)
+        const float ey = g.start_h + g.bin_h * (float)out_h, ex = g.start_w + g.bin_w * (float)out_w;
+        return fmaxf(g.start_h, ey) + 2.f >= (float)ty0 && fminf(g.start_h, ey) - 2.f <= (float)ty1 &&
+               fmaxf(g.start_w, ex) + 2.f >= (float)tx0 && fminf(g.start_w, ex) - 2.f <= (float)tx1;
+    };
+
+    int r_next = 0;
+    bool first = true;
+    do {
+        r_next = cull_rois(r_next, k, touches, s_list, s_cnt, &s_n);
+        const int n_list = s_n;
+        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
+            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
+            if (cy > ty1 || cx > tx1) continue;
+            f32x4* const dcell = dimg + ((size_t)cy * fw + cx) * C4;
+            {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                if (!first && act) acc = dcell[c4];
+                for (int li = 0; li < n_list; ++li) {
+                    const int r = s_list[li];
+                    const RoiGeom g = ops_align_geom(rois + (size_t)r * 5, scale, out_h, out_w, sampling_ratio, aligned);
+                    int ys0, ys1, xs0, xs1;
+                    sample_range(cy, g.start_h, g.bin_h, g.grid_h, out_h, ys0, ys1);
+                    sample_range(cx, g.start_w, g.bin_w, g.grid_w, out_w, xs0, xs1);
+                    const f32x4* const dr = reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C);
+                    // a bin's samples form a grid_h x grid_w product, so the cell's weight in bin (ph, pw) is (sum of its row weights
+                    // in ph) x (sum of its column weights in pw): one term per bin, not per sample (256 float32 terms per bin at
+                    // sampling_ratio 16 drift ~4e-6 from the float64 sum)
+                    for (int sy = ys0; sy <= ys1; ) {
+                        const int ph = sy / g.grid_h, y_end = min(ys1, (ph + 1) * g.grid_h - 1);
+                        float wy_sum = 0.f;
+                        bool y_hit = false;
+                        for (; sy <= y_end; ++sy) {
+                            float wy;
+                            if (cell_weight(sample_coord(g.start_h, g.bin_h, g.grid_h, ph, sy - ph * g.grid_h), fh, cy, wy)) {
+                                wy_sum += wy;
+                                y_hit = true;
+                            }
+                        }
+                        if (!y_hit) continue;
+                        for (int sx = xs0; sx <= xs1; ) {
+                            const int pw = sx / g.grid_w, x_end = min(xs1, (pw + 1) * g.grid_w - 1);
+                            float wx_sum = 0.f;
+                            bool x_hit = false;
+                            for (; sx <= x_end; ++sx) {
+                                float wx;
+                                if (cell_weight(sample_coord(g.start_w, g.bin_w, g.grid_w, pw, sx - pw * g.grid_w), fw, cx, wx)) {
+                                    wx_sum += wx;
+                                    x_hit = true;
+                                }
+                            }
+                            if (x_hit && act) acc = acc + (dr[((size_t)ph * out_w + pw) * C4 + c4] * (wy_sum * wx_sum)) / g.count;
+                        }
+                    }
+                }
+                if (act) dcell[c4] = acc;
+            }
+        }
+        first = false;
+    } while (r_next < k);
+}
+
+// ---- RoIPool ------------------------------------------------------------------------------------------------------------------------
+// torchvision's roi_pool geometry (oracle/frcnn_oracle.py: roi_pool) for out_h x out_w bins
+struct PoolGeom { int rs_h, rs_w; float bin_h, bin_w; };
+
+__device__ __forceinline__ PoolGeom ops_pool_geom(const float* roi, float scale, int out_h, int out_w)
+{
+    PoolGeom g;
+    g.rs_w = (int)roundf(roi[1] * scale); g.rs_h = (int)roundf(roi[2] * scale);
+    const int re_w = (int)roundf(roi[3] * scale), re_h = (int)roundf(roi[4] * scale);
+    const int roi_w = max(re_w - g.rs_w + 1, 1), roi_h = max(re_h - g.rs_h + 1, 1);
+    g.bin_h = (float)roi_h / (float)out_h; g.bin_w = (float)roi_w / (float)out_w;
+    return g;
+}
+__device__ __forceinline__ void pool_bin(int p, float bin, int rs, int limit, int& s, int& e)
+{
+    const int a = (int)floorf((float)p * bin) + rs, b = (int)ceilf((float)(p + 1) * bin) + rs;
+    s = min(max(a, 0), limit); e = min(max(b, 0), limit);
+}
+
+// One block per bin (roi, ph, pw), one thread per channel quad: the max and the argmax cell (h * fw + w; -1 for an empty bin) per
+// channel, first maximum in (h, w) scan order with torchvision's strict '>' from -FLT_MAX.
+__global__ __launch_bounds__(128)
+void ops_roi_pool_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
+                         int out_w, float scale, float* __restrict__ out, int32_t* __restrict__ argmax)
+{
+    const int r = blockIdx.x, ph = blockIdx.y, pw = blockIdx.z;
+    const int C4 = C >> 2;
+    const float* roi = rois + (size_t)r * 5;
+    const size_t o = (((size_t)r * out_h + ph) * out_w + pw) * C4;
+    f32x4* const op = reinterpret_cast<f32x4*>(out) + o;
+    int4* const ap = reinterpret_cast<int4*>(argmax) + o;
+    int b, hs = 0, he = 0, ws = 0, we = 0;
+    if (roi_image(roi[0], n_img, b)) {
+        const PoolGeom g = ops_pool_geom(roi, scale, out_h, out_w);
+        pool_bin(ph, g.bin_h, g.rs_h, fh, hs, he);
+        pool_bin(pw, g.bin_w, g.rs_w, fw, ws, we);
+    } else {
+        b = 0;
+    }
+    const bool empty = he <= hs || we <= ws;
+    const f32x4* const fm = reinterpret_cast<const f32x4*>(x + (size_t)b * fh * fw * C);
+    for (int c4 = threadIdx.x; c4 < C4; c4 += 128) {
+        const float m0 = empty ? 0.f : -FLT_MAX;
+        f32x4 m = {m0, m0, m0, m0};
+        int4 am = make_int4(-1, -1, -1, -1);
+        for (int h = hs; h < he; ++h)
+            for (int w = ws; w < we; ++w) {
+                const int cell = h * fw + w;
+                const f32x4 v = fm[(size_t)cell * C4 + c4];
+                if (v[0] > m[0]) { m[0] = v[0]; am.x = cell; }
+                if (v[1] > m[1]) { m[1] = v[1]; am.y = cell; }
+                if (v[2] > m[2]) { m[2] = v[2]; am.z = cell; }
+                if (v[3] > m[3]) { m[3] = v[3]; am.w = cell; }
+            }
+        op[c4] = m;
+        ap[c4] = am;
+    }
+}
+
+__global__ __launch_bounds__(256)
+void ops_roi_pool_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
+                                  float scale, const int32_t* __restrict__ argmax, const float* __restrict__ dout, float* __restrict__ dx)
+{
+    __shared__ int s_list[OPS_LIST];
+    __shared__ int s_cnt[4];
+    __shared__ int s_n;
+    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    const int img = blockIdx.z / n_chunks, chunk = blockIdx.z - img * n_chunks;
+    const int ty0 = blockIdx.y * OPS_TILE, tx0 = blockIdx.x * OPS_TILE;
+    const int ty1 = min(ty0 + OPS_TILE, fh) - 1, tx1 = min(tx0 + OPS_TILE, fw) - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c4 = chunk * 64 + lane;
+    const bool act = c4 < C4;
+    f32x4* const dimg = reinterpret_cast<f32x4*>(dx + (size_t)img * fh * fw * C);
+
+    auto touches = [&](int r) {
+        const float* roi = rois + (size_t)r * 5;
+        int b;
+        if (!roi_image(roi[0], n_img, b) || b != img) return false;
+        const PoolGeom g = ops_pool_geom(roi, scale, out_h, out_w);
+        // the bins cover [rs, rs + ceil(out * bin)) along each axis, out * bin = the RoI's size
+        const float eh = (float)g.rs_h + g.bin_h * (float)out_h + 1.f, ew = (float)g.rs_w + g.bin_w * (float)out_w + 1.f;
+        return eh >= (float)ty0 && (float)g.rs_h <= (float)ty1 && ew >= (float)tx0 && (float)g.rs_w <= (float)tx1;
+    };
+
+    int r_next = 0;
+    bool first = true;
+    do {
+        r_next = cull_rois(r_next, k, touches, s_list, s_cnt, &s_n);
+        const int n_list = s_n;
+        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
+            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
+            if (cy > ty1 || cx > tx1) continue;
+            const int cell = cy * fw + cx;
+            f32x4* const dcell = dimg + (size_t)cell * C4;
+            {
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                if (!first && act) acc = dcell[c4];
+                for (int li = 0; li < n_list; ++li) {
+                    const int r = s_list[li];
+                    const PoolGeom g = ops_pool_geom(rois + (size_t)r * 5, scale, out_h, out_w);
+                    // bin p holds offset t iff floor(p bin) <= t < ceil((p + 1) bin): p in (t / bin - 1, (t + 1) / bin), widened by one
+                    const int th = cy - g.rs_h, tw = cx - g.rs_w;
+                    const int ph0 = max((int)floorf((float)th / g.bin_h) - 2, 0), ph1 = min((int)ceilf((float)(th + 1) / g.bin_h) + 1, out_h - 1);
+                    const int pw0 = max((int)floorf((float)tw / g.bin_w) - 2, 0), pw1 = min((int)ceilf((float)(tw + 1) / g.bin_w) + 1, out_w - 1);
+                    const size_t rb = (size_t)r * out_h * out_w * C4;
+                    for (int ph = ph0; ph <= ph1; ++ph) {
+                        int hs, he;
+                        pool_bin(ph, g.bin_h, g.rs_h, fh, hs, he);
+                        if (cy < hs || cy >= he) continue;
+                        for (int pw = pw0; pw <= pw1; ++pw) {
+                            int ws, we;
+                            pool_bin(pw, g.bin_w, g.rs_w, fw, ws, we);
+                            if (cx < ws || cx >= we || !act) continue;
+                            const size_t o = rb + ((size_t)ph * out_w + pw) * C4 + c4;
+                            const int4 am = reinterpret_cast<const int4*>(argmax)[o];
+                            const f32x4 gv = reinterpret_cast<const f32x4*>(dout)[o];
+                            if (am.x == cell) acc[0] += gv[0];
+                            if (am.y == cell) acc[1] += gv[1];
+                            if (am.z == cell) acc[2] += gv[2];
+                            if (am.w == cell) acc[3] += gv[3];
+                        }
+                    }
+                }
+                if (act) dcell[c4] = acc;
+            }
+        }
+        first = false;
+    } while (r_next < k);
+}
+
+// ---- NMS ----------------------------------------------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ bool ops_iou_gt(const T* a, const T* b, float thr);
+template <> __device__ __forceinline__ bool ops_iou_gt<float>(const float* a, const float* b, float thr)
+{
+    return iou_gt(f32x4{a[0], a[1], a[2], a[3]}, f32x4{b[0], b[1], b[2], b[3]}, thr);
+}
+// torchvision's devIoU for double: the whole decision in float64 against the float threshold
+template <> __device__ __forceinline__ bool ops_iou_gt<double>(const double* a, const double* b, float thr)
+{
+    const double l0 = fmax(a[0], b[0]), l1 = fmax(a[1], b[1]);
+    const double r0 = fmin(a[2], b[2]), r1 = fmin(a[3], b[3]);
+    const double d0 = fmax(r0 - l0, 0.0), d1 = fmax(r1 - l1, 0.0);
+    const double inter = d0 * d1;
+    const double sa = (a[2] - a[0]) * (a[3] - a[1]);
+    const double sb = (b[2] - b[0]) * (b[3] - b[1]);
+    return inter / (sa + sb - inter) > (double)thr;
+}
+
+// grid (nw, nw), one wave per 64 x 64 tile of the sorted order; bit j of word bx of row i: sorted box 64 bx + j (> i, same category)
+// is suppressed by sorted box i.  Tiles below the diagonal, and tiles whose rows and columns cannot share a category, are not written.
+template <typename T>
+__global__ __launch_bounds__(64)
+void ops_nms_mask_kernel(const T* __restrict__ boxes, const int64_t* __restrict__ order, const int64_t* __restrict__ cats, int n,
+                         int nw, float thr, u64* __restrict__ mask)
+{
+    const int by = blockIdx.y, bx = blockIdx.x;
+    if (bx < by) return;
+    if (cats && cats[order[bx * 64]] > cats[order[min(by * 64 + 63, n - 1)]]) return;
+    __shared__ T colb[64][4];
+    __shared__ int64_t colc[64];
+    const int t = threadIdx.x;
+    const int jn = bx * 64 + t;
+    if (jn < n) {
+        const T* p = boxes + (size_t)order[jn] * 4;
+        colb[t][0] = p[0]; colb[t][1] = p[1]; colb[t][2] = p[2]; colb[t][3] = p[3];
+        colc[t] = cats ? cats[order[jn]] : 0;
+    }
+    __syncthreads();
+    const int i = by * 64 + t;
+    if (i >= n) return;
+    const T* p = boxes + (size_t)order[i] * 4;
+    const T a[4] = {p[0], p[1], p[2], p[3]};
+    const int64_t ca = cats ? cats[order[i]] : 0;
+    u64 bits = 0ull;
+    const int jmax = min(n - bx * 64, 64);
+    for (int j = 0; j < jmax; ++j)
+        if (bx * 64 + j > i && colc[j] == ca && ops_iou_gt<T>(a, colb[j], thr)) bits |= 1ull << j;
+    mask[(size_t)i * nw + bx] = bits;
+}
+
+// One wave per segment of the sorted order (a category of batched NMS; the whole list otherwise): block s works iff sorted position s
+// starts a segment.  The segment's removed-bits live in LDS; per 64-box chunk the kept boxes are resolved serially on the chunk's
+// diagonal words, then their rows are OR-ed into the words of the chunks after it.  keep[s] = 1 iff sorted box s is kept.
+__global__ __launch_bounds__(64)
+void ops_nms_reduce_kernel(const u64* __restrict__ mask, const int64_t* __restrict__ order, const int64_t* __restrict__ cats, int n,
+                           int nw, uint8_t* __restrict__ keep)
+{
+    extern __shared__ __attribute__((aligned(16))) u64 ops_rem[];
+    const int s0 = blockIdx.x, lane = threadIdx.x;
+    int s1 = n;
+    if (cats) {
+        const int64_t cat = cats[order[s0]];
+        if (s0 > 0 && cats[order[s0 - 1]] == cat) return;
+        for (int base = s0 + 1; base < n; base += 64) {
+            const int j = base + lane;
+            const u64 m = __ballot(j < n && cats[order[j]] != cat);
+            if (m) { s1 = base + __ffsll((long long)m) - 1; break; }
+        }
+    }
+    const int w0 = s0 >> 6, w1 = (s1 - 1) >> 6;
+    for (int w = lane; w <= w1 - w0; w += 64) ops_rem[w] = 0ull;
+    __syncthreads();
+    for (int c = w0; c <= w1; ++c) {
+        const int row = c * 64 + lane;
+        const bool in = row >= s0 && row < s1;
+        const u64 diag = in ? mask[(size_t)row * nw + c] : 0ull;
+        u64 alive = __ballot(in) & ~ops_rem[c - w0];
+        u64 kept = 0ull;
+        while (alive) {
+            const int b = __ffsll((long long)alive) - 1;
+            kept |= 1ull << b;
+            alive &= ~(1ull << b);
+            alive &= ~__shfl(diag, b);
+        }
+        if (in) keep[row] = (uint8_t)((kept >> lane) & 1ull);
+        // the rows kept here remove from the later chunks of the segment: sixteen rows' loads in flight at a time
+        for (u64 kk = c < w1 ? kept : 0ull; kk; ) {
+            int rb[16];
+            int cnt = 0;
+            for (int q = 0; q < 16; ++q) {
+                rb[q] = kk ? __ffsll((long long)kk) - 1 : rb[0];
+                if (kk) { kk &= kk - 1ull; ++cnt; }
+            }
+            for (int w = c + 1 + lane; w <= w1; w += 64) {
+                u64 v = 0ull;
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if (q < cnt) v |= mask[(size_t)(c * 64 + rb[q]) * nw + w];
+                ops_rem[w - w0] |= v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w)
+{
+    return n_img >= 1 && fh >= 1 && fw >= 1 && c >= 4 && c % 4 == 0 && k >= 0 && out_h >= 1 && out_h <= OPS_MAX_OUT && out_w >= 1 &&
+           out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / 4, 64) <= 65535;   // backward grid z
+}
+
+}  // namespace frcnn
+
+using namespace frcnn;
+
+extern "C" {
+
+int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                        float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream)
+{
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
+    if (k == 0) return FRCNN_OK;
+    if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_roi_align_kernel, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, d_x, n_img, fh, fw, c, d_rois, out_h,
+                       out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0, d_out);
+    return check_launch();
+}
+
+int frcnn_ops_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                 int sampling_ratio, int aligned, const float* d_dout, float* d_dx, void* stream)
+{
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
+    if (!d_dx || (k > 0 && (!d_rois || !d_dout))) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_roi_align_backward_kernel, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / 4, 64)), dim3(256), 0,
+                       (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0,
+                       d_dout, d_dx);
+    return check_launch();
+}
+
+int frcnn_ops_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                       float spatial_scale, float* d_out, int32_t* d_argmax, void* stream)
+{
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w)) return FRCNN_EINVAL;
+    if (k == 0) return FRCNN_OK;
+    if (!d_x || !d_rois || !d_out || !d_argmax) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_roi_pool_kernel, dim3(k, out_h, out_w), dim3(128), 0, (hipStream_t)stream, d_x, n_img, fh, fw, c, d_rois,
+                       out_h, out_w, spatial_scale, d_out, d_argmax);
+    return check_launch();
+}
+
+int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                const int32_t* d_argmax, const float* d_dout, float* d_dx, void* stream)
+{
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w)) return FRCNN_EINVAL;
+    if (!d_dx || (k > 0 && (!d_rois || !d_argmax || !d_dout))) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_roi_pool_backward_kernel, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / 4, 64)), dim3(256), 0,
+                       (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax, d_dout, d_dx);
+    return check_launch();
+}
+
+size_t frcnn_ops_nms_workspace_bytes(int n)
+{
+    if (n <= 0 || n > 64 * OPS_NMS_MAX_WORDS) return 0;
+    return (size_t)n * (size_t)cdiv(n, 64) * sizeof(u64);
+}
+
+int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
+                  uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream)
+{
+    if (n < 0 || n > 64 * OPS_NMS_MAX_WORDS || (boxes_f64 != 0 && boxes_f64 != 1)) return FRCNN_EINVAL;
+    if (n == 0) return FRCNN_OK;
+    if (!d_boxes || !d_order || !d_keep || !d_ws || ws_bytes < frcnn_ops_nms_workspace_bytes(n)) return FRCNN_EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    const int nw = cdiv(n, 64);
+    u64* mask = static_cast<u64*>(d_ws);
+    if (boxes_f64)
+        hipLaunchKernelGGL(ops_nms_mask_kernel<double>, dim3(nw, nw), dim3(64), 0, s, static_cast<const double*>(d_boxes), d_order,
+                           d_categories, n, nw, iou_threshold, mask);
+    else
+        hipLaunchKernelGGL(ops_nms_mask_kernel<float>, dim3(nw, nw), dim3(64), 0, s, static_cast<const float*>(d_boxes), d_order,
+                           d_categories, n, nw, iou_threshold, mask);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(ops_nms_reduce_kernel, dim3(d_categories ? n : 1), dim3(64), (size_t)nw * sizeof(u64), s, mask, d_order,
+                       d_categories, n, nw, d_keep);
+    return check_launch();
+}
+
+}  // extern "C"

@@ -14,7 +14,7 @@
 //                                              nms_reduce_kernel (one wave: 64 boxes per step,
 //                                              readlane over the diagonal word, a band of
 //                                              look-ahead words per row, early exit)
-#include "common.h"
+#include "geometry.h"
 #include <type_traits>
 
 namespace frcnn {
@@ -544,30 +544,6 @@ void topk_emit_kernel(const f32x4* __restrict__ tmp_boxes, const float* __restri
     else if (per == 4) body(std::integral_constant<int, 4>());
     else if (per == 2) body(std::integral_constant<int, 2>());
     else body(std::integral_constant<int, 1>());
-}
-
-// IoU exactly as torchvision's nms kernels compute it (fp32, no +1, no epsilon):
-//   inter / (area_a + area_b - inter), suppression iff iou > thr.
-__device__ __forceinline__ bool iou_gt(const f32x4 a, const f32x4 b, float thr)
-{
-    const float l0 = fmaxf(a[0], b[0]), l1 = fmaxf(a[1], b[1]);
-    const float r0 = fminf(a[2], b[2]), r1 = fminf(a[3], b[3]);
-    const float d0 = fmaxf(r0 - l0, 0.f), d1 = fmaxf(r1 - l1, 0.f);
-    const float inter = d0 * d1;
-    const float sa = (a[2] - a[0]) * (a[3] - a[1]);
-    const float sb = (b[2] - b[0]) * (b[3] - b[1]);
-    // The decision is torchvision's `inter / union > thr` to the last bit -- but the quotient (a ~10-instruction sequence, a third of this
-    // function) is computed only for the pairs that need it: with t = fl(thr * union), inter > t (1 + 1e-6) implies
-    // fl(inter / union) > thr and inter < t (1 - 1e-6) implies fl(inter / union) < thr (the two roundings involved are 6e-8 relative each);
-    // only a pair inside that band of 2e-6 takes the division.  The bounds hold for union > 0 only: every other union divides
-    // (0 / 0 is NaN, not greater; a box inverted along one axis has a negative area, and 0 / negative is -0.0, not greater either,
-    // where the shortcut's t < 0 would say "suppress").
-    const float uni = sa + sb - inter, t = thr * uni;
-    if (uni > 0.f) {
-        if (inter > t * 1.000001f) return true;
-        if (inter < t * 0.999999f) return false;
-    }
-    return (inter / uni) > thr;
 }
 
 // grid (nw, nw), one wave per 64x64 tile; only tiles on or above the diagonal are written.

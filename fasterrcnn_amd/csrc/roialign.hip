@@ -18,42 +18,9 @@
 // feature-map cell: the block walks the RoIs in ascending order, finds the samples whose bilinear footprint contains its
 // cell from the RoI's geometry (uniform across the block: scalar work) and sums g * w / count in that fixed order --
 // deterministic, no atomics, no scratch.
-#include "common.h"
+#include "geometry.h"
 
 namespace frcnn {
-
-struct RoiGeom { float start_h, start_w, bin_h, bin_w; int grid_h, grid_w; float count; };
-
-__device__ __forceinline__ RoiGeom roi_geom(const f32x4 roi /* y1, x1, y2, x2 */, float scale, int pooled, int sampling_ratio, int aligned)
-{
-    RoiGeom g;
-    const float offset = aligned ? 0.5f : 0.0f;
-    g.start_w = roi[1] * scale - offset;
-    g.start_h = roi[0] * scale - offset;
-    const float end_w = roi[3] * scale - offset, end_h = roi[2] * scale - offset;
-    float roi_w = end_w - g.start_w, roi_h = end_h - g.start_h;
-    if (!aligned) { roi_w = fmaxf(roi_w, 1.0f); roi_h = fmaxf(roi_h, 1.0f); }
-    g.bin_h = roi_h / (float)pooled;
-    g.bin_w = roi_w / (float)pooled;
-    g.grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_h / (float)pooled);
-    g.grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(roi_w / (float)pooled);
-    const int cnt = g.grid_h * g.grid_w;
-    g.count = (float)(cnt > 1 ? cnt : 1);
-    return g;
-}
-
-// one coordinate of bilinear_interpolate: returns false when the sample contributes nothing
-__device__ __forceinline__ bool axis_weights(float v, int n, int& low, int& high, float& wl, float& wh)
-{
-    if (v < -1.0f || v > (float)n) return false;
-    if (v <= 0.f) v = 0.f;
-    low = (int)v;
-    if (low >= n - 1) { high = low = n - 1; v = (float)low; }
-    else high = low + 1;
-    wh = v - (float)low;
-    wl = 1.0f - wh;
-    return true;
-}
 
 // rois: [max_rois][4] (y1, x1, y2, x2) as `forward` produces them; rows >= *n_rois are written as zeros.  out: [max_rois][P][P][C].
 __global__ __launch_bounds__(256)
@@ -68,7 +35,7 @@ void roi_align_kernel(const float* __restrict__ fm, int fh, int fw, int C, const
         for (int i = threadIdx.x; i < pooled * C4; i += 256) orow[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         return;
     }
-    const RoiGeom g = roi_geom(reinterpret_cast<const f32x4*>(rois)[r], scale, pooled, sampling_ratio, aligned);
+    const RoiGeom g = roi_align_geom(reinterpret_cast<const f32x4*>(rois)[r], scale, pooled, pooled, sampling_ratio, aligned);
     for (int pw = 0; pw < pooled; ++pw) {
         for (int c4 = threadIdx.x; c4 < C4; c4 += 256) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -111,7 +78,7 @@ void roi_align_backward_kernel(const float* __restrict__ rois, int n_rois, int f
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if (accumulate && c4 < C4) acc = drow[c4];
         for (int r = 0; r < n_rois; ++r) {
-            const RoiGeom g = roi_geom(reinterpret_cast<const f32x4*>(rois)[r], scale, pooled, sampling_ratio, aligned);
+            const RoiGeom g = roi_align_geom(reinterpret_cast<const f32x4*>(rois)[r], scale, pooled, pooled, sampling_ratio, aligned);
             // quick reject: the footprints of all samples lie within [start - 1, start + size + 1]
             const float end_h = g.start_h + g.bin_h * (float)pooled, end_w = g.start_w + g.bin_w * (float)pooled;
             if ((float)cy < g.start_h - 2.f || (float)cy > end_h + 2.f || (float)cx < g.start_w - 2.f || (float)cx > end_w + 2.f) continue;

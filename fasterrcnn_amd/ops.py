@@ -1,0 +1,408 @@
+"""
+torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as torch custom ops with autograd.
+
+    from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign
+
+Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
+  nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
+                                                     the scores; box j goes iff inter / union > float32(iou_threshold), computed in the
+                                                     boxes' dtype.  Any n (up to 524288: the n x n / 64 bit mask), no cap on K.
+  batched_nms(boxes, scores, idxs, iou_threshold)   NMS within each category, one pass over all of them; kept indices by descending
+                                                     score, ties by ascending index (torchvision's per-category loop, no coordinate offset).
+  roi_pool(input, boxes, output_size, spatial_scale=1.0)
+  roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False)
+      input float32 [N, C, H, W]; boxes Tensor[K, 5] (batch index, x1, y1, x2, y2) or list[Tensor[L_i, 4]]; output_size int or
+      (oh, ow), each <= 64; sampling_ratio <= 16.  The result is [K, C, oh, ow] in channels_last memory ([K, oh, ow, C]).  A batch
+      index outside [0, N) pools to zeros and receives no gradient.  Backward passes are deterministic gathers (no atomics):
+      RoIPool sends each bin's gradient to its first maximum in scan order, an empty bin sends none.  Double backward raises.
+
+Inputs must be CUDA (HIP) tensors; there is no CPU implementation.  channels_last inputs go to the NHWC kernels as they are, contiguous
+NCHW inputs are converted once, a channel count that is not a multiple of 4 goes through a zero-padded copy; input gradients come back in
+the input's memory format.
+"""
+import torch
+from torch import Tensor
+
+from . import _native as nv
+
+__all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign"]
+
+_CL = torch.channels_last
+MAX_OUTPUT = 64
+MAX_SAMPLING_RATIO = 16
+MAX_NMS_BOXES = 524288
+
+
+# ---- argument checks (the public functions; the custom ops assume them) -----------------------------------------------------------
+def _check_tensor(name, t, dtypes, what):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in dtypes:
+        raise TypeError("%s must be %s, got %s" % (name, what, t.dtype))
+    if t.device.type not in ("cuda", "meta"):
+        raise ValueError("%s must be a tensor on the GPU, got device %s: fasterrcnn_amd.ops has no CPU implementation" % (name, t.device))
+
+
+def _check_same_device(a, b, na, nb):
+    if a.device != b.device:
+        raise ValueError("%s and %s must be on the same device, got %s and %s" % (na, nb, a.device, b.device))
+
+
+def _output_size(output_size):
+    if isinstance(output_size, int):
+        oh = ow = output_size
+    elif isinstance(output_size, (tuple, list)) and len(output_size) == 2 and all(isinstance(v, int) for v in output_size):
+        oh, ow = output_size
+    else:
+        raise TypeError("output_size must be an int or a pair of ints, got %r" % (output_size,))
+    if not (1 <= oh <= MAX_OUTPUT and 1 <= ow <= MAX_OUTPUT):
+        raise ValueError("output_size must lie in [1, %d], got (%d, %d)" % (MAX_OUTPUT, oh, ow))
+    return oh, ow
+
+
+def _roi_input(input, boxes):
+    """Checks the RoI ops' inputs; returns boxes as a Tensor[K, 5] (torchvision's convert_boxes_to_roi_format)."""
+    _check_tensor("input", input, (torch.float32,), "float32")
+    if input.dim() != 4:
+        raise ValueError("input must be [N, C, H, W], got shape %s" % (tuple(input.shape),))
+    if isinstance(boxes, (list, tuple)):
+        for i, b in enumerate(boxes):
+            _check_tensor("boxes[%d]" % i, b, (torch.float32,), "float32")
+            _check_same_device(input, b, "input", "boxes[%d]" % i)
+            if b.dim() != 2 or b.shape[1] != 4:
+                raise ValueError("boxes[%d] must be [L, 4], got shape %s" % (i, tuple(b.shape)))
+        if not boxes:
+            return input.new_zeros((0, 5))
+        return torch.cat([torch.cat([torch.full_like(b[:, :1], float(i)), b], dim=1) for i, b in enumerate(boxes)], dim=0)
+    _check_tensor("boxes", boxes, (torch.float32,), "float32")
+    _check_same_device(input, boxes, "input", "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise ValueError("boxes must be a Tensor[K, 5] (batch index, x1, y1, x2, y2) or a list of Tensor[L, 4], got shape %s"
+                         % (tuple(boxes.shape),))
+    return boxes
+
+
+def _input_is_channels_last(x):
+    return x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=_CL)
+
+
+# ---- layout helpers of the real implementations ------------------------------------------------------------------------------------
+def _padded_channels(c):
+    return (c + 3) // 4 * 4
+
+
+def _nhwc(x, fill=0):
+    """x [A, C, B, D] as a channels_last tensor with C padded to a multiple of 4 (no copy when x already is one)."""
+    c = x.shape[1]
+    cp = _padded_channels(c)
+    if cp == c:
+        return x.contiguous(memory_format=_CL)
+    xp = torch.full((x.shape[0], cp) + tuple(x.shape[2:]), fill, dtype=x.dtype, device=x.device).contiguous(memory_format=_CL)
+    xp[:, :c].copy_(x)
+    return xp
+
+
+def _empty_cl(shape, like, dtype=torch.float32):
+    return torch.empty(shape, dtype=dtype, device=like.device, memory_format=_CL)
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _grad_layout(dx, c, channels_last):
+    dx = dx[:, :c]
+    return dx.contiguous(memory_format=_CL if channels_last else torch.contiguous_format)
+
+
+def _grad_empty(shape, like, channels_last):
+    return torch.empty(shape, dtype=like.dtype, device=like.device, memory_format=_CL if channels_last else torch.contiguous_format)
+
+
+def _no_double_backward(name):
+    def backward(ctx, *grads):
+        raise RuntimeError("%s: double backward is not supported (the backward of %s is not differentiable)" % (name, name))
+    return backward
+
+
+# ---- frcnn::roi_align -------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("frcnn::roi_align", mutates_args=())
+def _roi_align(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
+               aligned: bool) -> Tensor:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        cp = x.shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
+        nv.check(nv.lib().frcnn_ops_roi_align(x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width,
+                                              spatial_scale, sampling_ratio, int(aligned), dst.data_ptr(), _stream(input)),
+                 "frcnn_ops_roi_align")
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_roi_align.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned):
+    return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
+
+
+@torch.library.custom_op("frcnn::roi_align_backward", mutates_args=())
+def _roi_align_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
+                        aligned: bool, batch_size: int, channels: int, height: int, width: int, channels_last: bool) -> Tensor:
+    cp = _padded_channels(channels)
+    k = rois.shape[0]
+    if channels == 0 or batch_size * height * width == 0:
+        return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
+    with torch.cuda.device(grad.device):
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        dx = _empty_cl((batch_size, cp, height, width), grad)
+        nv.check(nv.lib().frcnn_ops_roi_align_backward(r.data_ptr() if k else None, k, batch_size, height, width, cp,
+                                                       pooled_height, pooled_width, spatial_scale, sampling_ratio, int(aligned),
+                                                       g.data_ptr() if k else None, dx.data_ptr(), _stream(grad)),
+                 "frcnn_ops_roi_align_backward")
+        return _grad_layout(dx, channels, channels_last)
+
+
+@_roi_align_backward.register_fake
+def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned, batch_size, channels, height, width, channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+def _roi_align_setup(ctx, inputs, output):
+    input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned = inputs
+    ctx.save_for_backward(rois)
+    ctx.args = (spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned)
+    ctx.shape = tuple(input.shape)
+    ctx.channels_last = _input_is_channels_last(input)
+
+
+def _roi_align_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    n, c, h, w = ctx.shape
+    dx = _roi_align_backward(grad, rois, *ctx.args, n, c, h, w, ctx.channels_last)
+    return dx, None, None, None, None, None, None
+
+
+torch.library.register_autograd("frcnn::roi_align", _roi_align_bwd, setup_context=_roi_align_setup)
+torch.library.register_autograd("frcnn::roi_align_backward", _no_double_backward("frcnn::roi_align"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
+# ---- frcnn::roi_pool --------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("frcnn::roi_pool", mutates_args=())
+def _roi_pool(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int) -> tuple[Tensor, Tensor]:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    argmax = _empty_cl((k, c, pooled_height, pooled_width), input, torch.int32)
+    if k == 0 or c == 0:
+        return out, argmax
+    if n * h * w == 0:
+        return out.zero_(), argmax.fill_(-1)
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        cp = x.shape[1]
+        padded = cp != c
+        dst = _empty_cl((k, cp, pooled_height, pooled_width), input) if padded else out
+        am = _empty_cl((k, cp, pooled_height, pooled_width), input, torch.int32) if padded else argmax
+        nv.check(nv.lib().frcnn_ops_roi_pool(x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width,
+                                             spatial_scale, dst.data_ptr(), am.data_ptr(), _stream(input)), "frcnn_ops_roi_pool")
+        if padded:
+            out.copy_(dst[:, :c])
+            argmax.copy_(am[:, :c])
+    return out, argmax
+
+
+@_roi_pool.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width):
+    shape = (rois.shape[0], input.shape[1], pooled_height, pooled_width)
+    return _empty_cl(shape, input), _empty_cl(shape, input, torch.int32)
+
+
+@torch.library.custom_op("frcnn::roi_pool_backward", mutates_args=())
+def _roi_pool_backward(grad: Tensor, rois: Tensor, argmax: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int,
+                       batch_size: int, channels: int, height: int, width: int, channels_last: bool) -> Tensor:
+    cp = _padded_channels(channels)
+    k = rois.shape[0]
+    if channels == 0 or batch_size * height * width == 0:
+        return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
+    with torch.cuda.device(grad.device):
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        am = _nhwc(argmax, fill=-1)
+        dx = _empty_cl((batch_size, cp, height, width), grad)
+        nv.check(nv.lib().frcnn_ops_roi_pool_backward(r.data_ptr() if k else None, k, batch_size, height, width, cp,
+                                                      pooled_height, pooled_width, spatial_scale, am.data_ptr() if k else None,
+                                                      g.data_ptr() if k else None, dx.data_ptr(), _stream(grad)),
+                 "frcnn_ops_roi_pool_backward")
+        return _grad_layout(dx, channels, channels_last)
+
+
+@_roi_pool_backward.register_fake
+def _(grad, rois, argmax, spatial_scale, pooled_height, pooled_width, batch_size, channels, height, width, channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+def _roi_pool_setup(ctx, inputs, output):
+    input, rois, spatial_scale, pooled_height, pooled_width = inputs
+    ctx.save_for_backward(rois, output[1])
+    ctx.args = (spatial_scale, pooled_height, pooled_width)
+    ctx.shape = tuple(input.shape)
+    ctx.channels_last = _input_is_channels_last(input)
+
+
+def _roi_pool_bwd(ctx, grad, grad_argmax):
+    rois, argmax = ctx.saved_tensors
+    n, c, h, w = ctx.shape
+    dx = _roi_pool_backward(grad, rois, argmax, *ctx.args, n, c, h, w, ctx.channels_last)
+    return dx, None, None, None, None
+
+
+torch.library.register_autograd("frcnn::roi_pool", _roi_pool_bwd, setup_context=_roi_pool_setup)
+torch.library.register_autograd("frcnn::roi_pool_backward", _no_double_backward("frcnn::roi_pool"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
+# ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
+def _score_order(scores):
+    """The oracle's argsort(-scores, "stable"): descending score, ties in input order, NaN scores last in input order."""
+    nan = torch.isnan(scores)
+    order = torch.sort(torch.where(nan, 0.0, -scores), stable=True).indices
+    return order[torch.sort(nan[order].to(torch.uint8), stable=True).indices]
+
+
+def _nms(boxes, scores, idxs, iou_threshold):
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        order = _score_order(scores)
+        cats = None
+        if idxs is not None:
+            cats = idxs.to(torch.int64).contiguous()
+            order = order[torch.sort(cats[order], stable=True).indices]       # each category one run, by score inside it
+        lib = nv.lib()
+        ws = torch.empty((lib.frcnn_ops_nms_workspace_bytes(n),), dtype=torch.uint8, device=boxes.device)
+        keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
+        b = boxes.contiguous()
+        nv.check(lib.frcnn_ops_nms(b.data_ptr(), int(b.dtype == torch.float64), order.data_ptr(),
+                                   cats.data_ptr() if cats is not None else None, n, iou_threshold, keep.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), _stream(boxes)), "frcnn_ops_nms")
+        kept = order[keep.bool()]
+        if idxs is not None:                                                   # merge: descending score, ties by ascending index
+            kept = torch.sort(kept).values
+            kept = kept[_score_order(scores[kept])]
+        return kept
+
+
+def _nms_fake_result(boxes):
+    k = torch.library.get_ctx().new_dynamic_size()
+    return boxes.new_empty((k,), dtype=torch.int64)
+
+
+@torch.library.custom_op("frcnn::nms", mutates_args=())
+def _nms_op(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
+    return _nms(boxes, scores, None, iou_threshold)
+
+
+@_nms_op.register_fake
+def _(boxes, scores, iou_threshold):
+    return _nms_fake_result(boxes)
+
+
+@torch.library.custom_op("frcnn::batched_nms", mutates_args=())
+def _batched_nms_op(boxes: Tensor, scores: Tensor, idxs: Tensor, iou_threshold: float) -> Tensor:
+    return _nms(boxes, scores, idxs, iou_threshold)
+
+
+@_batched_nms_op.register_fake
+def _(boxes, scores, idxs, iou_threshold):
+    return _nms_fake_result(boxes)
+
+
+def _nms_input(boxes, scores):
+    _check_tensor("boxes", boxes, (torch.float32, torch.float64), "float32 or float64")
+    _check_tensor("scores", scores, (torch.float32, torch.float64), "float32 or float64")
+    _check_same_device(boxes, scores, "boxes", "scores")
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be [N, 4] (x1, y1, x2, y2), got shape %s" % (tuple(boxes.shape),))
+    if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise ValueError("scores must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(scores.shape)))
+    if boxes.shape[0] > MAX_NMS_BOXES:
+        raise ValueError("nms takes at most %d boxes, got %d" % (MAX_NMS_BOXES, boxes.shape[0]))
+
+
+# ---- public interface -------------------------------------------------------------------------------------------------------------
+def nms(boxes, scores, iou_threshold):
+    """torchvision.ops.nms: int64 indices of the kept boxes, by descending score."""
+    _nms_input(boxes, scores)
+    return _nms_op(boxes, scores, float(iou_threshold))
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold):
+    """torchvision.ops.batched_nms: NMS within each category of idxs; kept indices by descending score, ties by ascending index."""
+    _nms_input(boxes, scores)
+    _check_tensor("idxs", idxs, (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8), "an integer tensor")
+    _check_same_device(boxes, idxs, "boxes", "idxs")
+    if idxs.dim() != 1 or idxs.shape[0] != boxes.shape[0]:
+        raise ValueError("idxs must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(idxs.shape)))
+    return _batched_nms_op(boxes, scores, idxs, float(iou_threshold))
+
+
+def roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False):
+    """torchvision.ops.roi_align: [K, C, oh, ow] (channels_last memory)."""
+    rois = _roi_input(input, boxes)
+    oh, ow = _output_size(output_size)
+    if int(sampling_ratio) > MAX_SAMPLING_RATIO:
+        raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
+    return _roi_align(input, rois, float(spatial_scale), oh, ow, int(sampling_ratio), bool(aligned))
+
+
+def roi_pool(input, boxes, output_size, spatial_scale=1.0):
+    """torchvision.ops.roi_pool: [K, C, oh, ow] (channels_last memory)."""
+    rois = _roi_input(input, boxes)
+    oh, ow = _output_size(output_size)
+    return _roi_pool(input, rois, float(spatial_scale), oh, ow)[0]
+
+
+class RoIAlign(torch.nn.Module):
+    """torchvision.ops.RoIAlign."""
+
+    def __init__(self, output_size, spatial_scale, sampling_ratio, aligned=False):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+        self.sampling_ratio = sampling_ratio
+        self.aligned = aligned
+
+    def forward(self, input, rois):
+        return roi_align(input, rois, self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, aligned=%s" % (
+            self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned)
+
+
+class RoIPool(torch.nn.Module):
+    """torchvision.ops.RoIPool."""
+
+    def __init__(self, output_size, spatial_scale):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+
+    def forward(self, input, rois):
+        return roi_pool(input, rois, self.output_size, self.spatial_scale)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s" % (self.output_size, self.spatial_scale)

@@ -5,8 +5,8 @@
  * The reference (trzy/FasterRCNN, pytorch tree) has no FFI: its hot path is Python calling
  * torch / torchvision native kernels.  Each entry point below replaces one of those call sites;
  * the reference file:line it stands in for is cited per function (paths relative to
- * /root/reference/pytorch/FasterRCNN/).  INTEGRATION.md shows the ctypes stub a maintainer of
- * the reference would add to bind them.
+ * /root/reference/pytorch/FasterRCNN/).  INTEGRATION.md shows how a maintainer of the reference
+ * binds them (the torchvision.ops call sites through fasterrcnn_amd.ops, on the frcnn_ops_* entry points).
  *
  * Conventions (all functions):
  *   - return int: 0 = FRCNN_OK, negative = error code below; never throws, never aborts.
@@ -37,7 +37,7 @@ extern "C" {
 #define FRCNN_EUNSUPPORTED -4   /* valid request outside what this build implements */
 #define FRCNN_ENODEVICE    -5   /* no gfx950 device visible */
 
-#define FRCNN_ABI_VERSION 18  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
+#define FRCNN_ABI_VERSION 19  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
                                  5: bf16 gradient GEMMs (the *_math entry points); 6: x6t GEMM, x6 Winograd layers, frcnn_forward_params.winograd_x6_mask,
                                  timing classes 8 / 9; 7: batched feature extractor (frcnn_resnet_backbone, frcnn_resnet_forward_features,
                                  frcnn_ctx_create_backbone, frcnn_conv3x3_nhwc_winograd_fused_maps); 8: the f32x3 arithmetic (frcnn_*_x3t, frcnn_*_winograd_x3,
@@ -52,7 +52,8 @@ extern "C" {
                                  17: frcnn_dropout, frcnn_dropout_relu_backward (training-mode dropout of the VGG-16 head);
                                  18: REMOVED the eight-wave (round 5) and two-pass (round 6) forms of the one-launch f32x3 layer that no table has used (FRCNN_X3F_WAVES4 /
                                  FRCNN_X3F_WAVES8 / FRCNN_X3F_PAIR, frcnn_conv3x3_winograd_x3_pair_workspace_bytes, frcnn_forward_params.winograd_x3p_mask;
-                                 measured in DESIGN.md section 5) */
+                                 measured in DESIGN.md section 5);
+                                 19: frcnn_ops_* (torchvision.ops-style roi_align / roi_pool / nms over N images, no context: fasterrcnn_amd.ops) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -424,6 +425,38 @@ int frcnn_roi_align(const float* d_fm, int fh, int fw, int c, const float* d_roi
                     int pooled, float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream);
 int frcnn_roi_align_backward(const float* d_rois, int n_rois, int fh, int fw, int c, int pooled, float spatial_scale,
                              int sampling_ratio, int aligned, const float* d_dout, float* d_dfm, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * torchvision.ops-style operators (csrc/ops.hip; Python: fasterrcnn_amd.ops, torch custom ops frcnn::*).  No context; float32 maps.
+ *   d_x    : float32 NHWC [n_img][fh][fw][c] (a channels_last NCHW tensor), c % 4 == 0, c >= 4
+ *   d_rois : float32 [k][5] torchvision rows (batch index, x1, y1, x2, y2); a batch index outside (-1, n_img) pools to zeros and
+ *            receives no gradient (checked on the device: no host sync)
+ *   d_out  : float32 [k][out_h][out_w][c];  1 <= out_h, out_w <= 64;  k >= 0 (k == 0: nothing to do)
+ * frcnn_ops_roi_align: torchvision.ops.roi_align, the arithmetic of frcnn_roi_align; sampling_ratio <= 16 (<= 0: adaptive
+ *   ceil(roi_size / out)), aligned = the half-pixel shift.
+ * frcnn_ops_roi_align_backward: d_dx [n_img][fh][fw][c] = the gradient of d_dout (overwritten, every cell).  A gather per 2 x 2 tile of
+ *   cells over the RoIs culled for it, in a fixed order: no atomics, bit-identical from run to run; no cap on out or sampling_ratio.
+ * frcnn_ops_roi_pool: torchvision.ops.roi_pool; d_argmax int32 [k][out_h][out_w][c] receives each bin's first maximum in (h, w)
+ *   scan order as h * fw + w (-1: empty bin, output 0).
+ * frcnn_ops_roi_pool_backward: d_dx = each bin's gradient sent to its d_argmax cell (overwritten; deterministic gather).
+ * frcnn_ops_nms: greedy NMS on d_boxes [n][4] (x1, y1, x2, y2), float32 (boxes_f64 = 0) or float64 (1), visited in the order d_order
+ *   (int64 [n], a permutation: the stable score-descending sort).  Box j is suppressed by an earlier kept box i iff
+ *   inter / (area_i + area_j - inter) > threshold, computed in the boxes' dtype (the threshold a float, as in torchvision's kernel);
+ *   boxes of any sign are decided by the division itself (frcnn_nms).  d_categories (int64 [n], optional): batched NMS -- boxes
+ *   interact only within a category, and d_order must list each category as one contiguous run; every run is reduced in parallel.
+ *   d_keep uint8 [n]: d_keep[s] = 1 iff box d_order[s] is kept.  0 <= n <= 524288; d_ws of frcnn_ops_nms_workspace_bytes(n) bytes
+ *   (the n x n / 64 bit mask). */
+int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                        float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream);
+int frcnn_ops_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                 int sampling_ratio, int aligned, const float* d_dout, float* d_dx, void* stream);
+int frcnn_ops_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                       float spatial_scale, float* d_out, int32_t* d_argmax, void* stream);
+int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                const int32_t* d_argmax, const float* d_dout, float* d_dx, void* stream);
+size_t frcnn_ops_nms_workspace_bytes(int n);
+int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
+                  uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -1,0 +1,123 @@
+"""
+Times of fasterrcnn_amd.ops (torch custom ops over csrc/ops.hip) at the reference's shapes, beside the model's own kernels on the same
+input, and at an FPN-like shape.  Device events around `--reps` calls after `--warmup` calls; median of 5 windows, in microseconds.
+
+    python tools/ops_bench.py [--reps 50] [--warmup 10]
+
+  * one image, C = 512, 37 x 62 (VGG-16's map of a 600 x 1000 image), 128 and 300 RoIs, 7 x 7:
+      ops.roi_pool / ops.roi_align on an NCHW input (the layout conversion included) and on a channels_last input,
+      frcnn_roi_pool / frcnn_roi_align (sampling_ratio 2) on the NHWC map, and the backward passes (ops via autograd, with the
+      forward) beside frcnn_roi_pool_backward / frcnn_roi_align_backward;
+  * FPN-like: 2 images, 256 x 200 x 336, 1000 RoIs, 7 x 7, sampling_ratio 2: roi_align forward, forward + backward;
+  * nms on 12000 float32 boxes and 2000 float64 boxes (the sort included).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fasterrcnn_amd import _native as nv          # noqa: E402
+from fasterrcnn_amd import ops                    # noqa: E402
+
+DEV = "cuda:0"
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1000.0 / reps)
+    return float(np.median(ts))
+
+
+def proposals(rng, k, H, W):
+    y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
+    return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    a = ap.parse_args()
+    nv.require_gpu()
+    lib = nv.lib()
+    S = nv.stream_ptr
+    rng = np.random.RandomState(0)
+    res = {}
+    c, fh, fw = 512, 37, 62
+    x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
+    x_cl = x.contiguous(memory_format=torch.channels_last)
+    fm_hwc = x[0].permute(1, 2, 0).contiguous()
+    for k in (128, 300):
+        props = torch.from_numpy(proposals(rng, k, 600, 1000)).to(DEV)              # (y1, x1, y2, x2)
+        rois = torch.cat([torch.zeros((k, 1), device=DEV), props[:, [1, 0, 3, 2]]], 1)
+        cnt = torch.tensor([k], dtype=torch.int32, device=DEV)
+        out = torch.empty((k, 7, 7, c), device=DEV)
+        g = torch.randn((k, c, 7, 7), device=DEV)
+        g_hwc = g.permute(0, 2, 3, 1).contiguous()
+        dfm = torch.empty((fh, fw, c), device=DEV)
+        wsb = int(lib.frcnn_roi_pool_backward_workspace_bytes(k, 7, c))
+        ws = torch.empty((wsb // 4,), device=DEV)
+        r = {}
+        r["ops.roi_pool nchw"] = timed(lambda: ops.roi_pool(x, rois, 7, 1 / 16), a.reps, a.warmup)
+        r["ops.roi_pool channels_last"] = timed(lambda: ops.roi_pool(x_cl, rois, 7, 1 / 16), a.reps, a.warmup)
+        r["frcnn_roi_pool"] = timed(lambda: lib.frcnn_roi_pool(nv.ptr(fm_hwc), fh, fw, c, nv.ptr(props), nv.ptr(cnt), k, 7, 1 / 16,
+                                                               nv.ptr(out), S()), a.reps, a.warmup)
+        r["ops.roi_align nchw"] = timed(lambda: ops.roi_align(x, rois, 7, 1 / 16, 2), a.reps, a.warmup)
+        r["ops.roi_align channels_last"] = timed(lambda: ops.roi_align(x_cl, rois, 7, 1 / 16, 2), a.reps, a.warmup)
+        r["frcnn_roi_align"] = timed(lambda: lib.frcnn_roi_align(nv.ptr(fm_hwc), fh, fw, c, nv.ptr(props), nv.ptr(cnt), k, 7, 1 / 16, 2,
+                                                                 0, nv.ptr(out), S()), a.reps, a.warmup)
+        xg = x_cl.clone().requires_grad_(True)
+
+        def pool_fb():
+            ops.roi_pool(xg, rois, 7, 1 / 16).backward(g)
+
+        def align_fb():
+            ops.roi_align(xg, rois, 7, 1 / 16, 2).backward(g)
+        r["ops.roi_pool fwd+bwd channels_last"] = timed(pool_fb, a.reps, a.warmup)
+        r["frcnn_roi_pool_backward (argmax + gather)"] = timed(
+            lambda: lib.frcnn_roi_pool_backward(nv.ptr(fm_hwc), fh, fw, c, nv.ptr(props), k, 7, 1 / 16, nv.ptr(g_hwc), nv.ptr(dfm), 0,
+                                                nv.ptr(ws), wsb, S()), a.reps, a.warmup)
+        r["ops.roi_align fwd+bwd channels_last"] = timed(align_fb, a.reps, a.warmup)
+        r["frcnn_roi_align_backward"] = timed(
+            lambda: lib.frcnn_roi_align_backward(nv.ptr(props), k, fh, fw, c, 7, 1 / 16, 2, 0, nv.ptr(g_hwc), nv.ptr(dfm), 0, S()),
+            a.reps, a.warmup)
+        res["vgg16 map, %d RoIs" % k] = r
+    # FPN-like
+    n, c, h, w, k = 2, 256, 200, 336, 1000
+    xf = torch.randn((n, c, h, w), device=DEV).contiguous(memory_format=torch.channels_last)
+    bx = proposals(rng, k, h * 4, w * 4)
+    rois = torch.from_numpy(np.concatenate([rng.randint(0, n, (k, 1)).astype(np.float32), bx[:, [1, 0, 3, 2]]], 1)).to(DEV)
+    gf = torch.randn((k, c, 7, 7), device=DEV)
+    xfg = xf.clone().requires_grad_(True)
+    res["fpn-like 2x256x200x336, 1000 RoIs, sr 2"] = {
+        "ops.roi_align fwd": timed(lambda: ops.roi_align(xf, rois, 7, 0.25, 2), 10, 3),
+        "ops.roi_align fwd+bwd": timed(lambda: ops.roi_align(xfg, rois, 7, 0.25, 2).backward(gf), 10, 3),
+    }
+    # nms
+    r = {}
+    for dt, nb in ((torch.float32, 12000), (torch.float64, 2000)):
+        b = proposals(rng, nb, 600, 1000)
+        boxes = torch.from_numpy(b[:, [1, 0, 3, 2]]).to(DEV).to(dt)
+        scores = torch.rand((nb,), device=DEV, dtype=dt)
+        r["nms %d %s (0.7), %d kept" % (nb, str(dt).split(".")[-1], len(ops.nms(boxes, scores, 0.7)))] = timed(
+            lambda: ops.nms(boxes, scores, 0.7), 20, 3)
+    res["nms"] = r
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
