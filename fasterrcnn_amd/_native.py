@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FRCNN_LIB_PATH") or os.path.join(_HERE, "csrc", "libfrcnn_hip.so")   # override: kernel experiments
 
 OK = 0
-ABI_VERSION = 19    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
+ABI_VERSION = 20    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
 ERRORS = {0: "FRCNN_OK", -1: "FRCNN_EINVAL", -2: "FRCNN_EHIP", -3: "FRCNN_ENOMEM",
           -4: "FRCNN_EUNSUPPORTED", -5: "FRCNN_ENODEVICE"}
 RELU = 1
@@ -60,6 +60,7 @@ SYMBOLS = (
     # fasterrcnn_amd.ops
     "frcnn_ops_roi_align", "frcnn_ops_roi_align_backward", "frcnn_ops_roi_pool", "frcnn_ops_roi_pool_backward",
     "frcnn_ops_nms_workspace_bytes", "frcnn_ops_nms",
+    "frcnn_ops_ms_roi_align", "frcnn_ops_ms_roi_align_workspace_bytes", "frcnn_ops_ms_roi_align_backward",
 )
 
 
@@ -239,6 +240,10 @@ _SIGNATURES = {
     "frcnn_ops_roi_pool_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "frcnn_ops_nms_workspace_bytes": (C.c_size_t, [_i]),
     "frcnn_ops_nms": (C.c_int, [_vp, _i, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_ms_roi_align": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp]),
+    "frcnn_ops_ms_roi_align_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "frcnn_ops_ms_roi_align_backward": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _sz,
+                                                  _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

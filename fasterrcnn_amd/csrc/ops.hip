@@ -10,6 +10,8 @@
 // can touch the tile (in ascending order, up to OPS_LIST at a time), then each wave owns one cell and sums, RoI by RoI, the samples /
 // bins that hold it in a fixed order: bit-identical from run to run.  RoIAlign finds the samples of a cell analytically -- the sample rows within one
 // pixel of the cell, from the RoI's sample spacing, each then tested exactly -- so there is no cap on out_h / out_w or sampling_ratio.
+// Multi-scale RoIAlign (torchvision's MultiScaleRoIAlign): the RoIAlign forward with the level picked per RoI, and the RoIAlign backward
+// on a grid over the tiles of every level, each tile culling only the RoIs of its (level, image), listed once by a bucketing launch.
 // RoIPool's backward sends each bin's gradient to the argmax cell its forward wrote (the first maximum in (h, w) scan order, -1 for an
 // empty bin), the design of roi_pool_argmax_kernel / roi_pool_scatter_kernel (csrc/train.hip).
 //
@@ -29,6 +31,7 @@ static constexpr int OPS_LIST = 1024;        // RoIs culled per pass of a tile
 static constexpr int OPS_MAX_OUT = 64;       // out_h, out_w <= 64
 static constexpr int OPS_MAX_SAMPLING = 16;  // sampling_ratio <= 16
 static constexpr int OPS_NMS_MAX_WORDS = 8192;   // removed-bits of one segment in 64 KB of LDS: n <= 524288
+static constexpr int OPS_MS_MAX_LEVELS = 8;  // multi-scale RoIAlign: feature maps per call
 
 // torchvision's `int roi_batch_ind = rois[0]` with the range check the op contract adds (NaN fails it)
 __device__ __forceinline__ bool roi_image(float v, int n_img, int& b)
@@ -49,21 +52,17 @@ __device__ __forceinline__ float sample_coord(float start, float bin, int grid, 
     return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)grid;
 }
 
-__global__ __launch_bounds__(256)
-void ops_roi_align_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
-                          int out_w, float scale, int sampling_ratio, int aligned, float* __restrict__ out)
+__device__ __forceinline__ void zero_row(f32x4* orow, int n)
 {
-    const int r = blockIdx.x, ph = blockIdx.y;
+    for (int i = threadIdx.x; i < n; i += 256) orow[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Output row ph of one RoI (out_w x C4 quads at orow) pooled from the image map fm [fh][fw][C]: the loop body of ops_roi_align_kernel,
+// shared with ops_ms_roi_align_kernel so that the two stay bit-identical.  Block of 256 threads.
+__device__ __forceinline__ void align_row(const float* __restrict__ fm, int fh, int fw, int C, const RoiGeom& g, int ph, int out_w,
+                                          f32x4* __restrict__ orow)
+{
     const int C4 = C >> 2;
-    const float* roi = rois + (size_t)r * 5;
-    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * out_h + ph) * out_w * C);
-    int b;
-    if (!roi_image(roi[0], n_img, b)) {
-        for (int i = threadIdx.x; i < out_w * C4; i += 256) orow[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        return;
-    }
-    const float* fm = x + (size_t)b * fh * fw * C;
-    const RoiGeom g = ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned);
     for (int i = threadIdx.x; i < out_w * C4; i += 256) {
         const int pw = i / C4, c4 = i - pw * C4;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -85,6 +84,21 @@ void ops_roi_align_kernel(const float* __restrict__ x, int n_img, int fh, int fw
         }
         orow[i] = acc / g.count;
     }
+}
+
+__global__ __launch_bounds__(256)
+void ops_roi_align_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
+                          int out_w, float scale, int sampling_ratio, int aligned, float* __restrict__ out)
+{
+    const int r = blockIdx.x, ph = blockIdx.y;
+    const float* roi = rois + (size_t)r * 5;
+    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * out_h + ph) * out_w * C);
+    int b;
+    if (!roi_image(roi[0], n_img, b)) {
+        zero_row(orow, out_w * (C >> 2));
+        return;
+    }
+    align_row(x + (size_t)b * fh * fw * C, fh, fw, C, ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned), ph, out_w, orow);
 }
 
 // The sample positions s = p * grid + i (0 <= s < n_out * grid) whose coordinate can lie within one pixel of `cell`: the linear model
@@ -141,6 +155,55 @@ __device__ int cull_rois(int r_begin, int k, Touches touches, int* s_list, int* 
     return r0 < k ? r0 : k;
 }
 
+// whether a RoI's samples can touch the tile of cells [ty0, ty1] x [tx0, tx1]: conservative, the gather tests each sample exactly
+__device__ __forceinline__ bool align_touches_tile(const RoiGeom& g, int out_h, int out_w, int ty0, int ty1, int tx0, int tx1)
+{
+    if (g.grid_h <= 0 || g.grid_w <= 0) return false;
+    // every sample lies between start and start + out * bin; its footprint within one cell of it (two: margin for rounding)
+    const float ey = g.start_h + g.bin_h * (float)out_h, ex = g.start_w + g.bin_w * (float)out_w;
+    return fmaxf(g.start_h, ey) + 2.f >= (float)ty0 && fminf(g.start_h, ey) - 2.f <= (float)ty1 &&
+           fmaxf(g.start_w, ex) + 2.f >= (float)tx0 && fminf(g.start_w, ex) - 2.f <= (float)tx1;
+}
+
+// Adds to acc the gradient that one RoI (plan g, output gradient rows dr [out_h][out_w][C4]) sends to cell (cy, cx), channel quad c4
+// (act: c4 < C4): the per-RoI body of the gather, shared by ops_roi_align_backward_kernel and ops_ms_roi_align_backward_kernel.
+__device__ __forceinline__ void align_cell_grad(const RoiGeom& g, const f32x4* __restrict__ dr, int fh, int fw, int cy, int cx, int out_h,
+                                                int out_w, int C4, int c4, bool act, f32x4& acc)
+{
+    int ys0, ys1, xs0, xs1;
+    sample_range(cy, g.start_h, g.bin_h, g.grid_h, out_h, ys0, ys1);
+    sample_range(cx, g.start_w, g.bin_w, g.grid_w, out_w, xs0, xs1);
+    // a bin's samples form a grid_h x grid_w product, so the cell's weight in bin (ph, pw) is (sum of its row weights
+    // in ph) x (sum of its column weights in pw): one term per bin, not per sample (256 float32 terms per bin at
+    // sampling_ratio 16 drift ~4e-6 from the float64 sum)
+    for (int sy = ys0; sy <= ys1; ) {
+        const int ph = sy / g.grid_h, y_end = min(ys1, (ph + 1) * g.grid_h - 1);
+        float wy_sum = 0.f;
+        bool y_hit = false;
+        for (; sy <= y_end; ++sy) {
+            float wy;
+            if (cell_weight(sample_coord(g.start_h, g.bin_h, g.grid_h, ph, sy - ph * g.grid_h), fh, cy, wy)) {
+                wy_sum += wy;
+                y_hit = true;
+            }
+        }
+        if (!y_hit) continue;
+        for (int sx = xs0; sx <= xs1; ) {
+            const int pw = sx / g.grid_w, x_end = min(xs1, (pw + 1) * g.grid_w - 1);
+            float wx_sum = 0.f;
+            bool x_hit = false;
+            for (; sx <= x_end; ++sx) {
+                float wx;
+                if (cell_weight(sample_coord(g.start_w, g.bin_w, g.grid_w, pw, sx - pw * g.grid_w), fw, cx, wx)) {
+                    wx_sum += wx;
+                    x_hit = true;
+                }
+            }
+            if (x_hit && act) acc = acc + (dr[((size_t)ph * out_w + pw) * C4 + c4] * (wy_sum * wx_sum)) / g.count;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256)
 void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
                                    float scale, int sampling_ratio, int aligned, const float* __restrict__ dout, float* __restrict__ dx)
@@ -161,12 +224,7 @@ void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_
         const float* roi = rois + (size_t)r * 5;
         int b;
         if (!roi_image(roi[0], n_img, b) || b != img) return false;
-        const RoiGeom g = ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned);
-        if (g.grid_h <= 0 || g.grid_w <= 0) return false;
-        // every sample lies between start and start + out * bin; its footprint within one cell of it (two: margin for rounding)
-        const float ey = g.start_h + g.bin_h * (float)out_h, ex = g.start_w + g.bin_w * (float)out_w;
-        return fmaxf(g.start_h, ey) + 2.f >= (float)ty0 && fminf(g.start_h, ey) - 2.f <= (float)ty1 &&
-               fmaxf(g.start_w, ex) + 2.f >= (float)tx0 && fminf(g.start_w, ex) - 2.f <= (float)tx1;
+        return align_touches_tile(ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned), out_h, out_w, ty0, ty1, tx0, tx1);
     };
 
     int r_next = 0;
@@ -183,46 +241,198 @@ void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_
                 if (!first && act) acc = dcell[c4];
                 for (int li = 0; li < n_list; ++li) {
                     const int r = s_list[li];
-                    const RoiGeom g = ops_align_geom(rois + (size_t)r * 5, scale, out_h, out_w, sampling_ratio, aligned);
-                    int ys0, ys1, xs0, xs1;
-                    sample_range(cy, g.start_h, g.bin_h, g.grid_h, out_h, ys0, ys1);
-                    sample_range(cx, g.start_w, g.bin_w, g.grid_w, out_w, xs0, xs1);
-                    const f32x4* const dr = reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C);
-                    // a bin's samples form a grid_h x grid_w product, so the cell's weight in bin (ph, pw) is (sum of its row weights
-                    // in ph) x (sum of its column weights in pw): one term per bin, not per sample (256 float32 terms per bin at
-                    // sampling_ratio 16 drift ~4e-6 from the float64 sum)
-                    for (int sy = ys0; sy <= ys1; ) {
-                        const int ph = sy / g.grid_h, y_end = min(ys1, (ph + 1) * g.grid_h - 1);
-                        float wy_sum = 0.f;
-                        bool y_hit = false;
-                        for (; sy <= y_end; ++sy) {
-                            float wy;
-                            if (cell_weight(sample_coord(g.start_h, g.bin_h, g.grid_h, ph, sy - ph * g.grid_h), fh, cy, wy)) {
-                                wy_sum += wy;
-                                y_hit = true;
-                            }
-                        }
-                        if (!y_hit) continue;
-                        for (int sx = xs0; sx <= xs1; ) {
-                            const int pw = sx / g.grid_w, x_end = min(xs1, (pw + 1) * g.grid_w - 1);
-                            float wx_sum = 0.f;
-                            bool x_hit = false;
-                            for (; sx <= x_end; ++sx) {
-                                float wx;
-                                if (cell_weight(sample_coord(g.start_w, g.bin_w, g.grid_w, pw, sx - pw * g.grid_w), fw, cx, wx)) {
-                                    wx_sum += wx;
-                                    x_hit = true;
-                                }
-                            }
-                            if (x_hit && act) acc = acc + (dr[((size_t)ph * out_w + pw) * C4 + c4] * (wy_sum * wx_sum)) / g.count;
-                        }
-                    }
+                    align_cell_grad(ops_align_geom(rois + (size_t)r * 5, scale, out_h, out_w, sampling_ratio, aligned),
+                                    reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C), fh, fw, cy, cx, out_h, out_w,
+                                    C4, c4, act, acc);
                 }
                 if (act) dcell[c4] = acc;
             }
         }
         first = false;
     } while (r_next < k);
+}
+
+// ---- multi-scale RoIAlign (torchvision.ops.MultiScaleRoIAlign) ------------------------------------------------------------------
+// Every level's descriptor travels in one by-value argument.  block0: the level's first block in the backward grid, which is flattened
+// over (image, channel chunk, tile row, tile column) of every level in turn.
+struct OpsMsLevel {
+    const float* x;
+    float* dx;
+    int fh, fw, tiles_y, tiles_x, block0;
+    float scale;
+};
+struct OpsMsArgs {
+    OpsMsLevel lv[OPS_MS_MAX_LEVELS];
+    int n_levels, n_img, C, out_h, out_w, sampling_ratio, k_min, k_max;
+    float canonical_level, inv_canonical_scale;
+};
+
+template <typename T> __device__ __forceinline__ T uniform(T v) { return __builtin_amdgcn_readfirstlane(v); }
+template <typename T> __device__ __forceinline__ T* uniform(T* p)
+{
+    const u64 v = (u64)p;
+    return (T*)(((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v));
+}
+
+// a.lv[l] for a block-uniform l, as scalar selects: each field is read into a register first, else the compiler folds the selects
+// into a dynamic index over a private copy of the argument (scratch)
+__device__ __forceinline__ OpsMsLevel ms_level(const OpsMsArgs& a, int l)
+{
+    OpsMsLevel d = a.lv[0];
+#pragma unroll
+    for (int i = 1; i < OPS_MS_MAX_LEVELS; ++i) {
+        const OpsMsLevel& s = a.lv[i];
+        const float* x = uniform(s.x);
+        float* dx = uniform(s.dx);
+        const int fh = uniform(s.fh), fw = uniform(s.fw), ty = uniform(s.tiles_y), tx = uniform(s.tiles_x), b0 = uniform(s.block0);
+        const float sc = __int_as_float(uniform(__float_as_int(s.scale)));
+        if (l == i) d = OpsMsLevel{x, dx, fh, fw, ty, tx, b0, sc};
+    }
+    return d;
+}
+
+// torchvision's LevelMapper on one RoI row, in float32 and in its order of operations, on the GPU as torch evaluates it (s / s0 is
+// s * (1 / s0) there):  floor(canonical_level + log2(sqrt(area) / canonical_scale) + 1e-6), torch.clamp to [k_min, k_max] (k_max when
+// k_min > k_max), minus k_min.  -1 for a NaN level (negative or NaN area: no level, as on torchvision's CPU path) and for an index
+// outside [0, n_levels).  One level: every RoI is on it, as in torchvision's num_levels == 1 branch.
+__device__ __forceinline__ int ms_roi_level(const float* roi, const OpsMsArgs& a)
+{
+    if (a.n_levels == 1) return 0;
+    const float area = (roi[3] - roi[1]) * (roi[4] - roi[2]);
+    const float v = floorf((a.canonical_level + log2f(sqrtf(area) * a.inv_canonical_scale)) + 1e-6f);
+    if (v != v) return -1;
+    float t = v < (float)a.k_min ? (float)a.k_min : v;
+    t = t > (float)a.k_max ? (float)a.k_max : t;
+    const int l = (int)t - a.k_min;
+    return l >= 0 && l < a.n_levels ? l : -1;
+}
+
+// the (level, image) bucket of a RoI; -1: no level or an image outside [0, n_img)
+__device__ __forceinline__ int ms_bucket(const float* roi, const OpsMsArgs& a)
+{
+    int b;
+    if (!roi_image(roi[0], a.n_img, b)) return -1;
+    const int l = ms_roi_level(roi, a);
+    return l < 0 ? -1 : l * a.n_img + b;
+}
+
+// One block per (roi, ph), as ops_roi_align_kernel: the RoI's level (uniform over the block) picks the map and the scale.
+__global__ __launch_bounds__(256)
+void ops_ms_roi_align_kernel(const OpsMsArgs a, const float* __restrict__ rois, float* __restrict__ out)
+{
+    const int r = blockIdx.x, ph = blockIdx.y;
+    const float* roi = rois + (size_t)r * 5;
+    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * a.out_h + ph) * a.out_w * a.C);
+    const int l = __builtin_amdgcn_readfirstlane(ms_roi_level(roi, a));      // uniform: one RoI per block
+    const OpsMsLevel d = ms_level(a, l);
+    int b;
+    if (l < 0 || d.fh == 0 || d.fw == 0 || !roi_image(roi[0], a.n_img, b)) {
+        zero_row(orow, a.out_w * (a.C >> 2));
+        return;
+    }
+    align_row(d.x + (size_t)b * d.fh * d.fw * a.C, d.fh, d.fw, a.C,
+              ops_align_geom(roi, d.scale, a.out_h, a.out_w, a.sampling_ratio, 0), ph, a.out_w, orow);
+}
+
+// One block per (level, image) bucket: ids[span[2 q] .. span[2 q + 1]) = the RoIs of bucket q in ascending order; the buckets follow
+// one another in bucket order.  Two passes over the RoIs: count those of lower buckets and of this one, then list this one's.
+__global__ __launch_bounds__(256)
+void ops_ms_bucket_kernel(const OpsMsArgs a, const float* __restrict__ rois, int k, int* __restrict__ ids, int* __restrict__ span)
+{
+    __shared__ int s_lo[4], s_own[4];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int lo = 0, own = 0;
+    for (int r = tid; r < k; r += 256) {
+        const int qr = ms_bucket(rois + (size_t)r * 5, a);
+        lo += qr >= 0 && qr < q;
+        own += qr == q;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo += __shfl_xor(lo, o);
+        own += __shfl_xor(own, o);
+    }
+    if (lane == 0) { s_lo[wave] = lo; s_own[wave] = own; }
+    __syncthreads();
+    const int begin = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+    if (tid == 0) {
+        span[2 * q] = begin;
+        span[2 * q + 1] = begin + s_own[0] + s_own[1] + s_own[2] + s_own[3];
+    }
+    int base = begin;
+    for (int r0 = 0; r0 < k; r0 += 256) {
+        const int r = r0 + tid;
+        const bool hit = r < k && ms_bucket(rois + (size_t)r * 5, a) == q;
+        const u64 m = __ballot(hit);
+        __syncthreads();                                 // the previous group has read s_own
+        if (lane == 0) s_own[wave] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += s_own[w];
+        if (hit) ids[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
+        base += s_own[0] + s_own[1] + s_own[2] + s_own[3];
+    }
+}
+
+// The backward of ops_ms_roi_align_kernel: ops_roi_align_backward_kernel's gather on every level in one grid, each block culling only
+// the RoIs of its (level, image) bucket, in ascending order -- the RoIs, and the order, of that level's ops_roi_align_backward_kernel.
+__global__ __launch_bounds__(256)
+void ops_ms_roi_align_backward_kernel(const OpsMsArgs a, const float* __restrict__ rois, const int* __restrict__ ids,
+                                      const int* __restrict__ span, const float* __restrict__ dout)
+{
+    __shared__ int s_list[OPS_LIST];
+    __shared__ int s_cnt[4];
+    __shared__ int s_n;
+    const int bid = blockIdx.x;
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < OPS_MS_MAX_LEVELS; ++i)
+        if (i < a.n_levels && bid >= a.lv[i].block0) l = i;
+    const OpsMsLevel d = ms_level(a, l);
+    const int fh = d.fh, fw = d.fw, C = a.C, out_h = a.out_h, out_w = a.out_w;
+    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    int t = bid - d.block0;
+    const int tx = t % d.tiles_x;
+    t /= d.tiles_x;
+    const int ty = t % d.tiles_y;
+    t /= d.tiles_y;
+    const int img = t / n_chunks, chunk = t - img * n_chunks;
+    const int ty0 = ty * OPS_TILE, tx0 = tx * OPS_TILE;
+    const int ty1 = min(ty0 + OPS_TILE, fh) - 1, tx1 = min(tx0 + OPS_TILE, fw) - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c4 = chunk * 64 + lane;
+    const bool act = c4 < C4;
+    f32x4* const dimg = reinterpret_cast<f32x4*>(d.dx + (size_t)img * fh * fw * C);
+    const int q = l * a.n_img + img;
+    const int* const bucket = ids + span[2 * q];
+    const int n_bucket = span[2 * q + 1] - span[2 * q];
+
+    auto touches = [&](int i) {
+        return align_touches_tile(ops_align_geom(rois + (size_t)bucket[i] * 5, d.scale, out_h, out_w, a.sampling_ratio, 0), out_h, out_w,
+                                  ty0, ty1, tx0, tx1);
+    };
+
+    int i_next = 0;
+    bool first = true;
+    do {
+        i_next = cull_rois(i_next, n_bucket, touches, s_list, s_cnt, &s_n);
+        const int n_list = s_n;
+        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
+            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
+            if (cy > ty1 || cx > tx1) continue;
+            f32x4* const dcell = dimg + ((size_t)cy * fw + cx) * C4;
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if (!first && act) acc = dcell[c4];
+            for (int li = 0; li < n_list; ++li) {
+                const int r = bucket[s_list[li]];
+                align_cell_grad(ops_align_geom(rois + (size_t)r * 5, d.scale, out_h, out_w, a.sampling_ratio, 0),
+                                reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C), fh, fw, cy, cx, out_h, out_w, C4,
+                                c4, act, acc);
+            }
+            if (act) dcell[c4] = acc;
+        }
+        first = false;
+    } while (i_next < n_bucket);
 }
 
 // ---- RoIPool ------------------------------------------------------------------------------------------------------------------------
@@ -467,6 +677,30 @@ static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int 
            out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / 4, 64) <= 65535;   // backward grid z
 }
 
+// Fills the multi-scale argument (without map pointers) and the size of the backward grid; false on an invalid request.
+static bool ms_args_ok(OpsMsArgs& a, long long& blocks, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
+                       int k, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level, int k_min, int k_max)
+{
+    if (n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || !fh || !fw || !scales || n_img < 1 || c < 4 || c % 4 != 0 || k < 0 ||
+        out_h < 1 || out_h > OPS_MAX_OUT || out_w < 1 || out_w > OPS_MAX_OUT || sampling_ratio > OPS_MAX_SAMPLING ||
+        (long long)n_levels * n_img > INT32_MAX / 2)
+        return false;
+    a = OpsMsArgs{};
+    a.n_levels = n_levels; a.n_img = n_img; a.C = c; a.out_h = out_h; a.out_w = out_w; a.sampling_ratio = sampling_ratio;
+    a.k_min = k_min; a.k_max = k_max; a.canonical_level = canonical_level;
+    a.inv_canonical_scale = 1.0f / canonical_scale;              // torch's tensor / scalar on the GPU: a * (1 / b), 1 / b in float32
+    blocks = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        if (fh[l] < 0 || fw[l] < 0 || (long long)fh[l] * fw[l] > INT32_MAX) return false;
+        OpsMsLevel& d = a.lv[l];
+        d.fh = fh[l]; d.fw = fw[l]; d.scale = scales[l];
+        d.tiles_y = cdiv(fh[l], OPS_TILE); d.tiles_x = cdiv(fw[l], OPS_TILE);
+        d.block0 = (int)min(blocks, (long long)INT32_MAX);
+        blocks += (long long)d.tiles_y * d.tiles_x * n_img * cdiv(c / 4, 64);
+    }
+    return blocks <= INT32_MAX;
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -513,6 +747,58 @@ int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, i
     if (!d_dx || (k > 0 && (!d_rois || !d_argmax || !d_dout))) return FRCNN_EINVAL;
     hipLaunchKernelGGL(ops_roi_pool_backward_kernel, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / 4, 64)), dim3(256), 0,
                        (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax, d_dout, d_dx);
+    return check_launch();
+}
+
+int frcnn_ops_ms_roi_align(const float* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
+                           const float* d_rois, int k, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                           float canonical_level, int k_min, int k_max, float* d_out, void* stream)
+{
+    OpsMsArgs a;
+    long long blocks;
+    if (!ms_args_ok(a, blocks, fh, fw, scales, n_levels, n_img, c, k, out_h, out_w, sampling_ratio, canonical_scale, canonical_level,
+                    k_min, k_max))
+        return FRCNN_EINVAL;
+    if (k == 0) return FRCNN_OK;
+    if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
+    for (int l = 0; l < n_levels; ++l) {
+        if (!d_x[l] && fh[l] * fw[l] > 0) return FRCNN_EINVAL;
+        a.lv[l].x = d_x[l];
+    }
+    hipLaunchKernelGGL(ops_ms_roi_align_kernel, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, a, d_rois, d_out);
+    return check_launch();
+}
+
+size_t frcnn_ops_ms_roi_align_workspace_bytes(int k, int n_levels, int n_img)
+{
+    if (k < 0 || n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || n_img < 1 || (long long)n_levels * n_img > INT32_MAX / 2) return 0;
+    return ((size_t)k + 2 * (size_t)n_levels * n_img) * sizeof(int);
+}
+
+int frcnn_ops_ms_roi_align_backward(const float* d_rois, int k, const int* fh, const int* fw, const float* scales, int n_levels, int n_img,
+                                    int c, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level,
+                                    int k_min, int k_max, const float* d_dout, float* const* d_dx, void* d_ws, size_t ws_bytes,
+                                    void* stream)
+{
+    OpsMsArgs a;
+    long long blocks;
+    if (!ms_args_ok(a, blocks, fh, fw, scales, n_levels, n_img, c, k, out_h, out_w, sampling_ratio, canonical_scale, canonical_level,
+                    k_min, k_max))
+        return FRCNN_EINVAL;
+    if (!d_dx || !d_ws || ws_bytes < frcnn_ops_ms_roi_align_workspace_bytes(k, n_levels, n_img) || (k > 0 && (!d_rois || !d_dout)))
+        return FRCNN_EINVAL;
+    for (int l = 0; l < n_levels; ++l) {
+        if (!d_dx[l] && fh[l] * fw[l] > 0) return FRCNN_EINVAL;
+        a.lv[l].dx = d_dx[l];
+    }
+    if (blocks == 0) return FRCNN_OK;
+    int* const span = static_cast<int*>(d_ws);
+    int* const ids = span + 2 * n_levels * n_img;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ops_ms_bucket_kernel, dim3(n_levels * n_img), dim3(256), 0, s, a, d_rois, k, ids, span);
+    const int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(ops_ms_roi_align_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, d_rois, ids, span, d_dout);
     return check_launch();
 }
 

@@ -1,7 +1,7 @@
 """
 torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as torch custom ops with autograd.
 
-    from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign
+    from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign, multi_scale_roi_align, MultiScaleRoIAlign
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -15,22 +15,31 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       (oh, ow), each <= 64; sampling_ratio <= 16.  The result is [K, C, oh, ow] in channels_last memory ([K, oh, ow, C]).  A batch
       index outside [0, N) pools to zeros and receives no gradient.  Backward passes are deterministic gathers (no atomics):
       RoIPool sends each bin's gradient to its first maximum in scan order, an empty bin sends none.  Double backward raises.
+  MultiScaleRoIAlign(featmap_names, output_size, sampling_ratio, *, canonical_scale=224, canonical_level=4)(x, boxes, image_shapes)
+  multi_scale_roi_align(features, boxes, output_size, spatial_scales, sampling_ratio=-1, canonical_scale=224, canonical_level=4)
+      torchvision's FPN pooler (ops/poolers.py): 1 to 8 float32 maps of the same N and C; each RoI's level by LevelMapper in float32 as
+      torch computes it on the GPU, then roi_align(aligned=False) on that level, bit-identical to the per-level torch.where loop (forward
+      and backward) in one launch each way and without a host sync.  A RoI without a level (negative or NaN area) pools to zeros.
 
 Inputs must be CUDA (HIP) tensors; there is no CPU implementation.  channels_last inputs go to the NHWC kernels as they are, contiguous
 NCHW inputs are converted once, a channel count that is not a multiple of 4 goes through a zero-padded copy; input gradients come back in
 the input's memory format.
 """
+import ctypes as C
+from typing import List
+
 import torch
 from torch import Tensor
 
 from . import _native as nv
 
-__all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign"]
+__all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
+MAX_LEVELS = 8
 
 
 # ---- argument checks (the public functions; the custom ops assume them) -----------------------------------------------------------
@@ -194,6 +203,95 @@ def _roi_align_bwd(ctx, grad):
 
 torch.library.register_autograd("frcnn::roi_align", _roi_align_bwd, setup_context=_roi_align_setup)
 torch.library.register_autograd("frcnn::roi_align_backward", _no_double_backward("frcnn::roi_align"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
+# ---- frcnn::multi_scale_roi_align -------------------------------------------------------------------------------------------------
+def _ms_levels(heights, widths, scales):
+    n = len(scales)
+    return (C.c_int * n)(*heights), (C.c_int * n)(*widths), (C.c_float * n)(*scales)
+
+
+@torch.library.custom_op("frcnn::multi_scale_roi_align", mutates_args=())
+def _ms_roi_align(features: List[Tensor], rois: Tensor, scales: List[float], pooled_height: int, pooled_width: int, sampling_ratio: int,
+                  canonical_scale: float, canonical_level: float, k_min: int, k_max: int) -> Tensor:
+    x0 = features[0]
+    n, c = x0.shape[:2]
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), x0)
+    if k == 0 or c == 0:
+        return out
+    if n == 0:
+        return out.zero_()
+    with torch.cuda.device(x0.device):
+        xs = [_nhwc(f) for f in features]
+        r = rois.contiguous()
+        cp = xs[0].shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), x0)
+        hs, ws, sc = _ms_levels([f.shape[2] for f in features], [f.shape[3] for f in features], scales)
+        ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+        nv.check(nv.lib().frcnn_ops_ms_roi_align(ptrs, hs, ws, sc, len(xs), n, cp, r.data_ptr(), k, pooled_height, pooled_width,
+                                                 sampling_ratio, canonical_scale, canonical_level, k_min, k_max, dst.data_ptr(),
+                                                 _stream(x0)), "frcnn_ops_ms_roi_align")
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_ms_roi_align.register_fake
+def _(features, rois, scales, pooled_height, pooled_width, sampling_ratio, canonical_scale, canonical_level, k_min, k_max):
+    return _empty_cl((rois.shape[0], features[0].shape[1], pooled_height, pooled_width), features[0])
+
+
+@torch.library.custom_op("frcnn::multi_scale_roi_align_backward", mutates_args=())
+def _ms_roi_align_backward(grad: Tensor, rois: Tensor, scales: List[float], pooled_height: int, pooled_width: int, sampling_ratio: int,
+                           canonical_scale: float, canonical_level: float, k_min: int, k_max: int, batch_size: int, channels: int,
+                           heights: List[int], widths: List[int], channels_last: List[bool]) -> List[Tensor]:
+    if channels == 0 or batch_size == 0:
+        return [_grad_layout(grad.new_zeros((batch_size, channels, h, w)), channels, cl)
+                for h, w, cl in zip(heights, widths, channels_last)]
+    cp = _padded_channels(channels)
+    k = rois.shape[0]
+    with torch.cuda.device(grad.device):
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        dxs = [_empty_cl((batch_size, cp, h, w), grad) for h, w in zip(heights, widths)]
+        lib = nv.lib()
+        ws = torch.empty((lib.frcnn_ops_ms_roi_align_workspace_bytes(k, len(scales), batch_size),), dtype=torch.uint8, device=grad.device)
+        hs, wd, sc = _ms_levels(heights, widths, scales)
+        ptrs = (C.c_void_p * len(dxs))(*[d.data_ptr() for d in dxs])
+        nv.check(lib.frcnn_ops_ms_roi_align_backward(r.data_ptr() if k else None, k, hs, wd, sc, len(scales), batch_size, cp, pooled_height,
+                                                     pooled_width, sampling_ratio, canonical_scale, canonical_level, k_min, k_max,
+                                                     g.data_ptr() if k else None, ptrs, ws.data_ptr(), ws.numel(), _stream(grad)),
+                 "frcnn_ops_ms_roi_align_backward")
+        return [_grad_layout(d, channels, cl) for d, cl in zip(dxs, channels_last)]
+
+
+@_ms_roi_align_backward.register_fake
+def _(grad, rois, scales, pooled_height, pooled_width, sampling_ratio, canonical_scale, canonical_level, k_min, k_max, batch_size, channels,
+      heights, widths, channels_last):
+    return [_grad_empty((batch_size, channels, h, w), grad, cl) for h, w, cl in zip(heights, widths, channels_last)]
+
+
+def _ms_roi_align_setup(ctx, inputs, output):
+    features, rois = inputs[:2]
+    ctx.save_for_backward(rois)
+    ctx.args = tuple(inputs[2:])
+    ctx.shape = tuple(features[0].shape[:2])
+    ctx.heights = [f.shape[2] for f in features]
+    ctx.widths = [f.shape[3] for f in features]
+    ctx.channels_last = [_input_is_channels_last(f) for f in features]
+
+
+def _ms_roi_align_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    n, c = ctx.shape
+    dxs = _ms_roi_align_backward(grad, rois, *ctx.args, n, c, ctx.heights, ctx.widths, ctx.channels_last)
+    return (list(dxs),) + (None,) * 9
+
+
+torch.library.register_autograd("frcnn::multi_scale_roi_align", _ms_roi_align_bwd, setup_context=_ms_roi_align_setup)
+torch.library.register_autograd("frcnn::multi_scale_roi_align_backward", _no_double_backward("frcnn::multi_scale_roi_align"),
                                 setup_context=lambda ctx, inputs, output: None)
 
 
@@ -373,6 +471,92 @@ def roi_pool(input, boxes, output_size, spatial_scale=1.0):
     rois = _roi_input(input, boxes)
     oh, ow = _output_size(output_size)
     return _roi_pool(input, rois, float(spatial_scale), oh, ow)[0]
+
+
+def _ms_features(features):
+    if not isinstance(features, (list, tuple)):
+        raise TypeError("features must be a list of tensors, got %s" % type(features).__name__)
+    if not 1 <= len(features) <= MAX_LEVELS:
+        raise ValueError("features must hold 1 to %d feature maps, got %d" % (MAX_LEVELS, len(features)))
+    for i, f in enumerate(features):
+        _check_tensor("features[%d]" % i, f, (torch.float32,), "float32")
+        if f.dim() != 4:
+            raise ValueError("features[%d] must be [N, C, H, W], got shape %s" % (i, tuple(f.shape)))
+        _check_same_device(features[0], f, "features[0]", "features[%d]" % i)
+        if f.shape[:2] != features[0].shape[:2]:
+            raise ValueError("every feature map must have the same N and C: features[0] is %s, features[%d] is %s"
+                             % (tuple(features[0].shape), i, tuple(f.shape)))
+
+
+def _level_range(scales):
+    """torchvision's _setup_scales: k_min, k_max = int(-log2(scale)) of the first and the last level, log2 in float32."""
+    k_min = -torch.log2(torch.tensor(scales[0], dtype=torch.float32)).item()
+    k_max = -torch.log2(torch.tensor(scales[-1], dtype=torch.float32)).item()
+    return int(k_min), int(k_max)
+
+
+def _infer_scales(features, image_shapes):
+    """torchvision's _setup_scales / _infer_scale: per level 2 ** round(log2(H_l / max_h)) (float32 log2, round half to even), max_h the
+    largest image height; only H decides."""
+    if not image_shapes:
+        raise ValueError("image_shapes must not be empty")
+    max_h = max(int(s[0]) for s in image_shapes)
+    return [2 ** float(torch.tensor(float(f.shape[2]) / float(max_h)).log2().round()) for f in features]
+
+
+def _multi_scale_roi_align(features, boxes, output_size, scales, sampling_ratio, canonical_scale, canonical_level, k_range):
+    _ms_features(features)
+    rois = _roi_input(features[0], boxes)
+    oh, ow = _output_size(output_size)
+    if int(sampling_ratio) > MAX_SAMPLING_RATIO:
+        raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
+    if len(scales) != len(features):
+        raise ValueError("spatial_scales must hold one scale per feature map: %d scales, %d maps" % (len(scales), len(features)))
+    k_min, k_max = _level_range(scales) if k_range is None else k_range
+    return _ms_roi_align(list(features), rois, [float(s) for s in scales], oh, ow, int(sampling_ratio), float(canonical_scale),
+                         float(canonical_level), k_min, k_max)
+
+
+def multi_scale_roi_align(features, boxes, output_size, spatial_scales, sampling_ratio=-1, canonical_scale=224, canonical_level=4):
+    """torchvision.ops.MultiScaleRoIAlign's pooling on explicit levels: [K, C, oh, ow] (channels_last memory).  features: 1 to 8 float32
+    maps [N, C, H_l, W_l] (the same N and C), finest first; spatial_scales: one per map.  Each RoI goes to level
+    floor(canonical_level + log2(sqrt(area) / canonical_scale) + 1e-6), clamped to [k_min, k_max] = int(-log2) of the first and the last
+    scale, minus k_min, and is pooled there by roi_align(aligned=False); a RoI without a level (negative or NaN area, an index outside the
+    maps) pools to zeros.  One map: every RoI is pooled on it."""
+    return _multi_scale_roi_align(features, boxes, output_size, list(spatial_scales), sampling_ratio, canonical_scale, canonical_level,
+                                  None)
+
+
+class MultiScaleRoIAlign(torch.nn.Module):
+    """torchvision.ops.MultiScaleRoIAlign: forward(x, boxes, image_shapes) pools boxes (list[Tensor[L_i, 4]] or Tensor[K, 5]) from the
+    maps of the dict x named in featmap_names (in x's order).  The scales are inferred from the maps and image_shapes on the first call
+    and kept, as torchvision does."""
+
+    def __init__(self, featmap_names, output_size, sampling_ratio, *, canonical_scale=224, canonical_level=4):
+        super().__init__()
+        if isinstance(output_size, int):
+            output_size = (output_size, output_size)
+        self.featmap_names = featmap_names
+        self.sampling_ratio = sampling_ratio
+        self.output_size = tuple(output_size)
+        self.scales = None
+        self.canonical_scale = canonical_scale
+        self.canonical_level = canonical_level
+        self._k_range = None
+
+    def forward(self, x, boxes, image_shapes):
+        features = [v for k, v in x.items() if k in self.featmap_names]
+        if not features:
+            raise ValueError("none of featmap_names %r is a key of x" % (list(self.featmap_names),))
+        if self.scales is None or self._k_range is None:
+            scales = _infer_scales(features, image_shapes)
+            self._k_range = _level_range(scales)
+            self.scales = scales
+        return _multi_scale_roi_align(features, boxes, self.output_size, self.scales, self.sampling_ratio, self.canonical_scale,
+                                      self.canonical_level, self._k_range)
+
+    def extra_repr(self):
+        return "featmap_names=%s, output_size=%s, sampling_ratio=%s" % (self.featmap_names, self.output_size, self.sampling_ratio)
 
 
 class RoIAlign(torch.nn.Module):

@@ -37,7 +37,7 @@ extern "C" {
 #define FRCNN_EUNSUPPORTED -4   /* valid request outside what this build implements */
 #define FRCNN_ENODEVICE    -5   /* no gfx950 device visible */
 
-#define FRCNN_ABI_VERSION 19  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
+#define FRCNN_ABI_VERSION 20  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
                                  5: bf16 gradient GEMMs (the *_math entry points); 6: x6t GEMM, x6 Winograd layers, frcnn_forward_params.winograd_x6_mask,
                                  timing classes 8 / 9; 7: batched feature extractor (frcnn_resnet_backbone, frcnn_resnet_forward_features,
                                  frcnn_ctx_create_backbone, frcnn_conv3x3_nhwc_winograd_fused_maps); 8: the f32x3 arithmetic (frcnn_*_x3t, frcnn_*_winograd_x3,
@@ -53,7 +53,9 @@ extern "C" {
                                  18: REMOVED the eight-wave (round 5) and two-pass (round 6) forms of the one-launch f32x3 layer that no table has used (FRCNN_X3F_WAVES4 /
                                  FRCNN_X3F_WAVES8 / FRCNN_X3F_PAIR, frcnn_conv3x3_winograd_x3_pair_workspace_bytes, frcnn_forward_params.winograd_x3p_mask;
                                  measured in DESIGN.md section 5);
-                                 19: frcnn_ops_* (torchvision.ops-style roi_align / roi_pool / nms over N images, no context: fasterrcnn_amd.ops) */
+                                 19: frcnn_ops_* (torchvision.ops-style roi_align / roi_pool / nms over N images, no context: fasterrcnn_amd.ops);
+                                 20: frcnn_ops_ms_roi_align(_backward / _workspace_bytes): torchvision.ops.MultiScaleRoIAlign (FPN pooling) in one launch
+                                 per direction */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -450,6 +452,25 @@ int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, cons
                         float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream);
 int frcnn_ops_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
                                  int sampling_ratio, int aligned, const float* d_dout, float* d_dx, void* stream);
+/* frcnn_ops_ms_roi_align: torchvision.ops.MultiScaleRoIAlign's pooling (ops/poolers.py: LevelMapper + one roi_align per level,
+ *   aligned = False) over n_levels (1..8) maps in ONE launch.  Level l: d_x[l] NHWC [n_img][fh[l]][fw[l]][c] (device pointer in a HOST
+ *   array; fh[l] or fw[l] == 0: an empty map, its RoIs pool to zeros), spatial scale scales[l] (host arrays).  A RoI's level is
+ *   floor(canonical_level + log2(sqrt(area) * (1 / canonical_scale)) + 1e-6) in float32, clamped to [k_min, k_max] as torch.clamp does
+ *   (k_max when k_min > k_max), minus k_min; a NaN level (negative or NaN area) or one outside [0, n_levels) pools to zeros.
+ *   n_levels == 1: every RoI is pooled on level 0 and no level is computed.  Each RoI's values are bit-identical to frcnn_ops_roi_align
+ *   on its level.  d_out [k][out_h][out_w][c] as frcnn_ops_roi_align.
+ * frcnn_ops_ms_roi_align_backward: d_dx[l] (device pointers in a host array) [n_img][fh[l]][fw[l]][c] = level l's gradient (overwritten,
+ *   every cell: no zero fill), bit-identical to frcnn_ops_roi_align_backward over the RoIs of level l in ascending order.  Two launches:
+ *   one lists the RoIs of every (level, image) in ascending order in d_ws (frcnn_ops_ms_roi_align_workspace_bytes(k, n_levels, n_img)
+ *   bytes), then one grid over the 2 x 2 tiles of every level gathers, each tile culling only its (level, image) list.  No atomics. */
+int frcnn_ops_ms_roi_align(const float* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
+                           const float* d_rois, int k, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                           float canonical_level, int k_min, int k_max, float* d_out, void* stream);
+size_t frcnn_ops_ms_roi_align_workspace_bytes(int k, int n_levels, int n_img);
+int frcnn_ops_ms_roi_align_backward(const float* d_rois, int k, const int* fh, const int* fw, const float* scales, int n_levels, int n_img,
+                                    int c, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level,
+                                    int k_min, int k_max, const float* d_dout, float* const* d_dx, void* d_ws, size_t ws_bytes,
+                                    void* stream);
 int frcnn_ops_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
                        float spatial_scale, float* d_out, int32_t* d_argmax, void* stream);
 int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,

@@ -9,7 +9,13 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
       frcnn_roi_pool / frcnn_roi_align (sampling_ratio 2) on the NHWC map, and the backward passes (ops via autograd, with the
       forward) beside frcnn_roi_pool_backward / frcnn_roi_align_backward;
   * FPN-like: 2 images, 256 x 200 x 336, 1000 RoIs, 7 x 7, sampling_ratio 2: roi_align forward, forward + backward;
-  * nms on 12000 float32 boxes and 2000 float64 boxes (the sort included).
+  * nms on 12000 float32 boxes and 2000 float64 boxes (the sort included);
+  * multi-scale: torchvision's FPN pooler (2 images, 256 x {200 x 304, 100 x 152, 50 x 76, 25 x 38}, 7 x 7, sampling_ratio 2), 512 and
+    1000 RoIs per image with sizes log-uniform over 16 .. 800 px (every level gets RoIs): ops.multi_scale_roi_align beside torchvision's
+    composition (LevelMapper, then torch.where + ops.roi_align + index_put per level), forward and forward + backward, the two timed in
+    alternating windows of the same call.
+
+    python tools/ops_bench.py --only multiscale      # just the multi-scale leg
 """
 import argparse
 import json
@@ -42,6 +48,67 @@ def timed(fn, reps, warmup):
     return float(np.median(ts))
 
 
+def timed_pair(fa, fb, reps, warmup):
+    """timed() of two callables in alternating windows (a, b, a, b, ...): medians of 5 each"""
+    for _ in range(warmup):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    ts = ([], [])
+    for _ in range(5):
+        for fn, t in ((fa, ts[0]), (fb, ts[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            t.append(a.elapsed_time(b) * 1000.0 / reps)
+    return float(np.median(ts[0])), float(np.median(ts[1]))
+
+
+def tv_multiscale(features, rois, scales, k_min, k_max):
+    """torchvision's _multiscale_roi_align over ops.roi_align (7 x 7, sampling_ratio 2): LevelMapper, then per level torch.where (a host
+    sync each), roi_align and index_put"""
+    b = rois[:, 1:]
+    s = torch.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]))
+    levels = torch.clamp(torch.floor(4 + torch.log2(s / 224) + torch.tensor(1e-6, dtype=s.dtype)), min=k_min, max=k_max)
+    levels = levels.to(torch.int64) - k_min
+    result = torch.zeros((rois.shape[0], features[0].shape[1], 7, 7), device=rois.device)
+    for level, (f, sc) in enumerate(zip(features, scales)):
+        idx = torch.where(levels == level)[0]
+        result[idx] = ops.roi_align(f, rois[idx], 7, sc, 2)
+    return result
+
+
+def multiscale_leg(rng, reps, warmup):
+    n, c = 2, 256
+    shapes = [(200, 304), (100, 152), (50, 76), (25, 38)]
+    scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
+    feats = [torch.randn((n, c, h, w), device=DEV).contiguous(memory_format=torch.channels_last) for h, w in shapes]
+    feats_g = [f.clone().requires_grad_(True) for f in feats]
+    res = {}
+    for per_img in (512, 1000):
+        k = n * per_img
+        side = np.exp(rng.uniform(np.log(16), np.log(800), (k, 2)))
+        x1, y1 = rng.uniform(0, 1216 - 16, k), rng.uniform(0, 800 - 16, k)
+        rois = np.stack([np.repeat(np.arange(n), per_img), x1, y1, np.minimum(x1 + side[:, 0], 1216), np.minimum(y1 + side[:, 1], 800)], 1)
+        rois = torch.from_numpy(rois.astype(np.float32)).to(DEV)
+        g = torch.randn((k, c, 7, 7), device=DEV)
+        b = rois[:, 1:]
+        lv = (torch.clamp(torch.floor(4 + torch.log2(torch.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) / 224) + 1e-6), 2, 5) - 2).long()
+        r = {"rois per level": torch.bincount(lv, minlength=4).tolist()}
+        fwd = timed_pair(lambda: ops.multi_scale_roi_align(feats, rois, 7, scales, 2), lambda: tv_multiscale(feats, rois, scales, 2, 5),
+                         reps, warmup)
+        fb = timed_pair(lambda: ops.multi_scale_roi_align(feats_g, rois, 7, scales, 2).backward(g),
+                        lambda: tv_multiscale(feats_g, rois, scales, 2, 5).backward(g), reps, warmup)
+        r["ops.multi_scale_roi_align fwd"], r["composition fwd"] = fwd
+        r["ops.multi_scale_roi_align fwd+bwd"], r["composition fwd+bwd"] = fb
+        r["ops.roi_align fwd, all RoIs on level 0"] = timed(lambda: ops.roi_align(feats[0], rois, 7, 0.25, 2), reps, warmup)
+        res["multi-scale fpn 2 x 256 x 200 x 304 .. 25 x 38, %d RoIs per image, 7 x 7, sr 2" % per_img] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -51,12 +118,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--only", choices=["multiscale"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
     S = nv.stream_ptr
     rng = np.random.RandomState(0)
     res = {}
+    if a.only == "multiscale":
+        print(json.dumps(multiscale_leg(rng, 10, 3), indent=1))
+        return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
     x_cl = x.contiguous(memory_format=torch.channels_last)
@@ -116,6 +187,7 @@ def main():
         r["nms %d %s (0.7), %d kept" % (nb, str(dt).split(".")[-1], len(ops.nms(boxes, scores, 0.7)))] = timed(
             lambda: ops.nms(boxes, scores, 0.7), 20, 3)
     res["nms"] = r
+    res.update(multiscale_leg(rng, 10, 3))
     print(json.dumps(res, indent=1))
 
 
