@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FRCNN_LIB_PATH") or os.path.join(_HERE, "csrc", "libfrcnn_hip.so")   # override: kernel experiments
 
 OK = 0
-ABI_VERSION = 20    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
+ABI_VERSION = 21    # must equal FRCNN_ABI_VERSION of include/frcnn_hip.h
 ERRORS = {0: "FRCNN_OK", -1: "FRCNN_EINVAL", -2: "FRCNN_EHIP", -3: "FRCNN_ENOMEM",
           -4: "FRCNN_EUNSUPPORTED", -5: "FRCNN_ENODEVICE"}
 RELU = 1
@@ -61,6 +61,8 @@ SYMBOLS = (
     "frcnn_ops_roi_align", "frcnn_ops_roi_align_backward", "frcnn_ops_roi_pool", "frcnn_ops_roi_pool_backward",
     "frcnn_ops_nms_workspace_bytes", "frcnn_ops_nms",
     "frcnn_ops_ms_roi_align", "frcnn_ops_ms_roi_align_workspace_bytes", "frcnn_ops_ms_roi_align_backward",
+    "frcnn_ops_half_run", "frcnn_ops_roi_align_16", "frcnn_ops_roi_align_backward_16", "frcnn_ops_roi_pool_16",
+    "frcnn_ops_roi_pool_backward_16", "frcnn_ops_ms_roi_align_16", "frcnn_ops_ms_roi_align_backward_16",
 )
 
 
@@ -122,6 +124,7 @@ MAX_POST_NMS_DETECT = 512   # DET_MAX of csrc/detect.hip (per-class NMS bit matr
 MAX_POST_NMS_CTX = 512      # frcnn_ctx_create's max_rois bound (forward() without detections is limited by the ctx only)
 MAX_PRE_NMS = 16384         # frcnn_ctx pre_cap (csrc/api.hip): one-block radix select + sort
 
+OPS_F16, OPS_BF16 = 1, 2     # FRCNN_OPS_F16 / FRCNN_OPS_BF16: element type of the frcnn_ops_*_16 entry points
 MATH_F32 = 0      # exact f32 MFMA
 MATH_F32_WINOGRAD = 2   # exact f32 MFMA; 3x3 layers with uses_winograd(cin, cout) as Winograd F(2x2,3x3) in float32
 MATH_MODES = {"f32": MATH_F32, "f32_winograd": MATH_F32_WINOGRAD}     # (1 was the direct f32x6 convolution of round 2: removed, ABI 13)
@@ -244,6 +247,15 @@ _SIGNATURES = {
     "frcnn_ops_ms_roi_align_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
     "frcnn_ops_ms_roi_align_backward": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _sz,
                                                   _vp]),
+    # the same operators on float16 / bfloat16 maps (ABI 21): the element-type code first, then the float32 sibling's arguments
+    "frcnn_ops_half_run": (C.c_int, []),
+    "frcnn_ops_roi_align_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "frcnn_ops_roi_align_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_roi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "frcnn_ops_roi_pool_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_ms_roi_align_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp]),
+    "frcnn_ops_ms_roi_align_backward_16": (C.c_int, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp,
+                                                     _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

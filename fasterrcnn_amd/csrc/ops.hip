@@ -3,12 +3,17 @@
 //
 // Layouts: the feature map is NHWC [n][h][w][c] (a channels_last NCHW tensor), RoIs are torchvision's rows (b, x1, y1, x2, y2), the
 // pooled output is [k][out_h][out_w][c] (a channels_last [k][c][out_h][out_w] tensor).  c % 4 == 0: a pixel is float4 runs.
+// Element types: the RoI kernels are templates over the storage type E of maps, outputs and gradients -- float, or float16 / bfloat16
+// (the frcnn_ops_*_16 entry points).  A lane owns a Run<E> of V channels (4 floats; 8, or in a narrow backward 4, 16-bit values): widened exactly on load,
+// every sum, weight and coordinate in float32 in one shared body, rounded once (to nearest even, as Tensor.to() rounds) on store -- so
+// op(x_T) == op(x_T.float()).to(T) bit for bit, the definition of torchvision's autocast wrappers.  RoIs are always float32.
 // A RoI whose batch index b is outside (-1, n) -- truncated to an int as torchvision truncates it -- pools to zeros and gets no gradient.
 //
 // RoIAlign forward: the arithmetic of roi_align_kernel (csrc/roialign.hip), one block per (roi, ph), lanes over (pw, channel quad).
 // Backwards: no atomics.  One block per 2 x 2 cells of one image and 64 channel quads; its threads first cull the RoIs whose footprint
 // can touch the tile (in ascending order, up to OPS_LIST at a time), then each wave owns one cell and sums, RoI by RoI, the samples /
-// bins that hold it in a fixed order: bit-identical from run to run.  RoIAlign finds the samples of a cell analytically -- the sample rows within one
+// bins that hold it in a fixed order: bit-identical from run to run.  The sum stays in registers over every culling pass and is stored
+// once (a 16-bit dx never holds a partial sum).  RoIAlign finds the samples of a cell analytically -- the sample rows within one
 // pixel of the cell, from the RoI's sample spacing, each then tested exactly -- so there is no cap on out_h / out_w or sampling_ratio.
 // Multi-scale RoIAlign (torchvision's MultiScaleRoIAlign): the RoIAlign forward with the level picked per RoI, and the RoIAlign backward
 // on a grid over the tiles of every level, each tile culling only the RoIs of its (level, image), listed once by a bucketing launch.
@@ -26,7 +31,8 @@ namespace frcnn {
 
 typedef unsigned long long u64;
 
-static constexpr int OPS_TILE = 2;           // backward tile: 2 x 2 cells, one per wave, 64 channel quads per block
+static constexpr int OPS_TILE = 2;           // backward tile: 2 x 2 cells, one per wave, 64 channel runs per block
+static_assert(OPS_TILE * OPS_TILE == 4, "the backward kernels give each of a block's four waves one cell of the tile");
 static constexpr int OPS_LIST = 1024;        // RoIs culled per pass of a tile
 static constexpr int OPS_MAX_OUT = 64;       // out_h, out_w <= 64
 static constexpr int OPS_MAX_SAMPLING = 16;  // sampling_ratio <= 16
@@ -52,20 +58,84 @@ __device__ __forceinline__ float sample_coord(float start, float bin, int grid, 
     return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)grid;
 }
 
-__device__ __forceinline__ void zero_row(f32x4* orow, int n)
+// ---- storage types --------------------------------------------------------------------------------------------------------------
+// 16-bit elements carry the width N of a lane's run in their type, so that one tensor can be walked in runs of 8 or of 4 channels
+template <int N> struct f16_t { _Float16 v; };
+template <int N> struct bf16_t { unsigned short bits; };
+
+// 16-bit channels per lane.  8 = 16 B per load and store, as a float quad: measured faster than 4 in every forward kernel and in the
+// backward kernels once C / 8 fills a wave (C >= 512).  Below that a backward block, whose lanes are the channel runs of one cell,
+// would idle half of each wave: there the gather walks the same tensors in runs of 4 (C = 256: 7 % faster forward + backward).
+static constexpr int OPS_HALF_RUN = 8, OPS_HALF_RUN_NARROW = 4;
+
+// Run<E>: V consecutive channels of one pixel, in memory as E, in registers as float32 (vec).  load widens exactly; store rounds to
+// nearest even once, NaN and infinities as torch's Tensor.to(): float16 by the hardware conversion (v_cvt_f16_f32), bfloat16 by the
+// integer rounding of c10::BFloat16 (every NaN becomes 0x7FC0 there, which the packed hardware conversion would not give).
+template <typename E> struct Run;
+template <> struct Run<float> {
+    static constexpr int V = 4;
+    typedef f32x4 vec;
+    typedef int ivec __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ vec load(const float* p, size_t i) { return reinterpret_cast<const vec*>(p)[i]; }
+    static __device__ __forceinline__ void store(float* p, size_t i, vec v) { reinterpret_cast<vec*>(p)[i] = v; }
+};
+template <int N> struct Run<f16_t<N>> {
+    static constexpr int V = N;
+    typedef float vec __attribute__((ext_vector_type(N)));
+    typedef int ivec __attribute__((ext_vector_type(N)));
+    typedef _Float16 raw __attribute__((ext_vector_type(N)));
+    static __device__ __forceinline__ vec load(const f16_t<N>* p, size_t i)
+    {
+        return __builtin_convertvector(reinterpret_cast<const raw*>(p)[i], vec);
+    }
+    static __device__ __forceinline__ void store(f16_t<N>* p, size_t i, vec v)
+    {
+        reinterpret_cast<raw*>(p)[i] = __builtin_convertvector(v, raw);
+    }
+};
+template <int N> struct Run<bf16_t<N>> {
+    static constexpr int V = N;
+    typedef float vec __attribute__((ext_vector_type(N)));
+    typedef int ivec __attribute__((ext_vector_type(N)));
+    typedef unsigned short raw __attribute__((ext_vector_type(N)));
+    static __device__ __forceinline__ vec load(const bf16_t<N>* p, size_t i)
+    {
+        const raw u = reinterpret_cast<const raw*>(p)[i];
+        vec v;
+#pragma unroll
+        for (int j = 0; j < N; ++j) v[j] = __uint_as_float((unsigned)u[j] << 16);
+        return v;
+    }
+    static __device__ __forceinline__ void store(bf16_t<N>* p, size_t i, vec v)
+    {
+        raw u;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const unsigned b = __float_as_uint(v[j]);
+            u[j] = v[j] != v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+        }
+        reinterpret_cast<raw*>(p)[i] = u;
+    }
+};
+
+template <typename E> __device__ __forceinline__ void zero_row(E* orow, int n)
 {
-    for (int i = threadIdx.x; i < n; i += 256) orow[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const typename Run<E>::vec z = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) Run<E>::store(orow, i, z);
 }
 
-// Output row ph of one RoI (out_w x C4 quads at orow) pooled from the image map fm [fh][fw][C]: the loop body of ops_roi_align_kernel,
+// Output row ph of one RoI (out_w x C / V runs at orow) pooled from the image map fm [fh][fw][C]: the loop body of ops_roi_align_kernel,
 // shared with ops_ms_roi_align_kernel so that the two stay bit-identical.  Block of 256 threads.
-__device__ __forceinline__ void align_row(const float* __restrict__ fm, int fh, int fw, int C, const RoiGeom& g, int ph, int out_w,
-                                          f32x4* __restrict__ orow)
+template <typename E>
+__device__ __forceinline__ void align_row(const E* __restrict__ fm, int fh, int fw, int C, const RoiGeom& g, int ph, int out_w,
+                                          E* __restrict__ orow)
 {
-    const int C4 = C >> 2;
+    typedef Run<E> R;
+    typedef typename R::vec vec;
+    const int C4 = C / R::V;
     for (int i = threadIdx.x; i < out_w * C4; i += 256) {
         const int pw = i / C4, c4 = i - pw * C4;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        vec acc = 0.f;
         for (int iy = 0; iy < g.grid_h; ++iy) {
             const float y = sample_coord(g.start_h, g.bin_h, g.grid_h, ph, iy);
             int yl, yh; float hy, ly;
@@ -75,27 +145,28 @@ __device__ __forceinline__ void align_row(const float* __restrict__ fm, int fh, 
                 int xl, xh; float hx, lx;
                 if (!yok || !axis_weights(xx, fw, xl, xh, hx, lx)) continue;
                 const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-                const f32x4 v1 = reinterpret_cast<const f32x4*>(fm + ((size_t)yl * fw + xl) * C)[c4];
-                const f32x4 v2 = reinterpret_cast<const f32x4*>(fm + ((size_t)yl * fw + xh) * C)[c4];
-                const f32x4 v3 = reinterpret_cast<const f32x4*>(fm + ((size_t)yh * fw + xl) * C)[c4];
-                const f32x4 v4 = reinterpret_cast<const f32x4*>(fm + ((size_t)yh * fw + xh) * C)[c4];
+                const vec v1 = R::load(fm + ((size_t)yl * fw + xl) * C, c4);
+                const vec v2 = R::load(fm + ((size_t)yl * fw + xh) * C, c4);
+                const vec v3 = R::load(fm + ((size_t)yh * fw + xl) * C, c4);
+                const vec v4 = R::load(fm + ((size_t)yh * fw + xh) * C, c4);
                 acc = acc + (((v1 * w1 + v2 * w2) + v3 * w3) + v4 * w4);
             }
         }
-        orow[i] = acc / g.count;
+        R::store(orow, i, acc / g.count);
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(256)
-void ops_roi_align_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
-                          int out_w, float scale, int sampling_ratio, int aligned, float* __restrict__ out)
+void ops_roi_align_kernel(const E* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
+                          int out_w, float scale, int sampling_ratio, int aligned, E* __restrict__ out)
 {
     const int r = blockIdx.x, ph = blockIdx.y;
     const float* roi = rois + (size_t)r * 5;
-    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * out_h + ph) * out_w * C);
+    E* orow = out + ((size_t)r * out_h + ph) * out_w * C;
     int b;
     if (!roi_image(roi[0], n_img, b)) {
-        zero_row(orow, out_w * (C >> 2));
+        zero_row(orow, out_w * (C / Run<E>::V));
         return;
     }
     align_row(x + (size_t)b * fh * fw * C, fh, fw, C, ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned), ph, out_w, orow);
@@ -165,10 +236,11 @@ __device__ __forceinline__ bool align_touches_tile(const RoiGeom& g, int out_h, 
            fmaxf(g.start_w, ex) + 2.f >= (float)tx0 && fminf(g.start_w, ex) - 2.f <= (float)tx1;
 }
 
-// Adds to acc the gradient that one RoI (plan g, output gradient rows dr [out_h][out_w][C4]) sends to cell (cy, cx), channel quad c4
+// Adds to acc the gradient that one RoI (plan g, output gradient rows dr [out_h][out_w][C4] runs) sends to cell (cy, cx), channel run c4
 // (act: c4 < C4): the per-RoI body of the gather, shared by ops_roi_align_backward_kernel and ops_ms_roi_align_backward_kernel.
-__device__ __forceinline__ void align_cell_grad(const RoiGeom& g, const f32x4* __restrict__ dr, int fh, int fw, int cy, int cx, int out_h,
-                                                int out_w, int C4, int c4, bool act, f32x4& acc)
+template <typename E>
+__device__ __forceinline__ void align_cell_grad(const RoiGeom& g, const E* __restrict__ dr, int fh, int fw, int cy, int cx, int out_h,
+                                                int out_w, int C4, int c4, bool act, typename Run<E>::vec& acc)
 {
     int ys0, ys1, xs0, xs1;
     sample_range(cy, g.start_h, g.bin_h, g.grid_h, out_h, ys0, ys1);
@@ -199,26 +271,28 @@ __device__ __forceinline__ void align_cell_grad(const RoiGeom& g, const f32x4* _
                     x_hit = true;
                 }
             }
-            if (x_hit && act) acc = acc + (dr[((size_t)ph * out_w + pw) * C4 + c4] * (wy_sum * wx_sum)) / g.count;
+            if (x_hit && act) acc = acc + (Run<E>::load(dr, ((size_t)ph * out_w + pw) * C4 + c4) * (wy_sum * wx_sum)) / g.count;
         }
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(256)
 void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
-                                   float scale, int sampling_ratio, int aligned, const float* __restrict__ dout, float* __restrict__ dx)
+                                   float scale, int sampling_ratio, int aligned, const E* __restrict__ dout, E* __restrict__ dx)
 {
     __shared__ int s_list[OPS_LIST];
     __shared__ int s_cnt[4];
     __shared__ int s_n;
-    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    const int C4 = C / Run<E>::V, n_chunks = (C4 + 63) >> 6;
     const int img = blockIdx.z / n_chunks, chunk = blockIdx.z - img * n_chunks;
     const int ty0 = blockIdx.y * OPS_TILE, tx0 = blockIdx.x * OPS_TILE;
     const int ty1 = min(ty0 + OPS_TILE, fh) - 1, tx1 = min(tx0 + OPS_TILE, fw) - 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4 = chunk * 64 + lane;
     const bool act = c4 < C4;
-    f32x4* const dimg = reinterpret_cast<f32x4*>(dx + (size_t)img * fh * fw * C);
+    const int cy = ty0 + wave / OPS_TILE, cx = tx0 + wave % OPS_TILE;       // this wave's cell, for every pass
+    const bool cell_ok = cy <= ty1 && cx <= tx1;
 
     auto touches = [&](int r) {
         const float* roi = rois + (size_t)r * 5;
@@ -227,37 +301,27 @@ void ops_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_
         return align_touches_tile(ops_align_geom(roi, scale, out_h, out_w, sampling_ratio, aligned), out_h, out_w, ty0, ty1, tx0, tx1);
     };
 
+    typename Run<E>::vec acc = 0.f;
     int r_next = 0;
-    bool first = true;
     do {
         r_next = cull_rois(r_next, k, touches, s_list, s_cnt, &s_n);
         const int n_list = s_n;
-        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
-            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
-            if (cy > ty1 || cx > tx1) continue;
-            f32x4* const dcell = dimg + ((size_t)cy * fw + cx) * C4;
-            {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (!first && act) acc = dcell[c4];
-                for (int li = 0; li < n_list; ++li) {
-                    const int r = s_list[li];
-                    align_cell_grad(ops_align_geom(rois + (size_t)r * 5, scale, out_h, out_w, sampling_ratio, aligned),
-                                    reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C), fh, fw, cy, cx, out_h, out_w,
-                                    C4, c4, act, acc);
-                }
-                if (act) dcell[c4] = acc;
+        if (cell_ok)
+            for (int li = 0; li < n_list; ++li) {
+                const int r = s_list[li];
+                align_cell_grad<E>(ops_align_geom(rois + (size_t)r * 5, scale, out_h, out_w, sampling_ratio, aligned),
+                                   dout + (size_t)r * out_h * out_w * C, fh, fw, cy, cx, out_h, out_w, C4, c4, act, acc);
             }
-        }
-        first = false;
     } while (r_next < k);
+    if (cell_ok && act) Run<E>::store(dx + (size_t)img * fh * fw * C, ((size_t)cy * fw + cx) * C4 + c4, acc);
 }
 
 // ---- multi-scale RoIAlign (torchvision.ops.MultiScaleRoIAlign) ------------------------------------------------------------------
 // Every level's descriptor travels in one by-value argument.  block0: the level's first block in the backward grid, which is flattened
 // over (image, channel chunk, tile row, tile column) of every level in turn.
 struct OpsMsLevel {
-    const float* x;
-    float* dx;
+    const void* x;                            // maps and gradients of the launch's element type
+    void* dx;
     int fh, fw, tiles_y, tiles_x, block0;
     float scale;
 };
@@ -283,8 +347,8 @@ __device__ __forceinline__ OpsMsLevel ms_level(const OpsMsArgs& a, int l)
 #pragma unroll
     for (int i = 1; i < OPS_MS_MAX_LEVELS; ++i) {
         const OpsMsLevel& s = a.lv[i];
-        const float* x = uniform(s.x);
-        float* dx = uniform(s.dx);
+        const void* x = uniform(s.x);
+        void* dx = uniform(s.dx);
         const int fh = uniform(s.fh), fw = uniform(s.fw), ty = uniform(s.tiles_y), tx = uniform(s.tiles_x), b0 = uniform(s.block0);
         const float sc = __int_as_float(uniform(__float_as_int(s.scale)));
         if (l == i) d = OpsMsLevel{x, dx, fh, fw, ty, tx, b0, sc};
@@ -318,20 +382,21 @@ __device__ __forceinline__ int ms_bucket(const float* roi, const OpsMsArgs& a)
 }
 
 // One block per (roi, ph), as ops_roi_align_kernel: the RoI's level (uniform over the block) picks the map and the scale.
+template <typename E>
 __global__ __launch_bounds__(256)
-void ops_ms_roi_align_kernel(const OpsMsArgs a, const float* __restrict__ rois, float* __restrict__ out)
+void ops_ms_roi_align_kernel(const OpsMsArgs a, const float* __restrict__ rois, E* __restrict__ out)
 {
     const int r = blockIdx.x, ph = blockIdx.y;
     const float* roi = rois + (size_t)r * 5;
-    f32x4* orow = reinterpret_cast<f32x4*>(out + ((size_t)r * a.out_h + ph) * a.out_w * a.C);
+    E* orow = out + ((size_t)r * a.out_h + ph) * a.out_w * a.C;
     const int l = __builtin_amdgcn_readfirstlane(ms_roi_level(roi, a));      // uniform: one RoI per block
     const OpsMsLevel d = ms_level(a, l);
     int b;
     if (l < 0 || d.fh == 0 || d.fw == 0 || !roi_image(roi[0], a.n_img, b)) {
-        zero_row(orow, a.out_w * (a.C >> 2));
+        zero_row(orow, a.out_w * (a.C / Run<E>::V));
         return;
     }
-    align_row(d.x + (size_t)b * d.fh * d.fw * a.C, d.fh, d.fw, a.C,
+    align_row(static_cast<const E*>(d.x) + (size_t)b * d.fh * d.fw * a.C, d.fh, d.fw, a.C,
               ops_align_geom(roi, d.scale, a.out_h, a.out_w, a.sampling_ratio, 0), ph, a.out_w, orow);
 }
 
@@ -376,9 +441,10 @@ void ops_ms_bucket_kernel(const OpsMsArgs a, const float* __restrict__ rois, int
 
 // The backward of ops_ms_roi_align_kernel: ops_roi_align_backward_kernel's gather on every level in one grid, each block culling only
 // the RoIs of its (level, image) bucket, in ascending order -- the RoIs, and the order, of that level's ops_roi_align_backward_kernel.
+template <typename E>
 __global__ __launch_bounds__(256)
 void ops_ms_roi_align_backward_kernel(const OpsMsArgs a, const float* __restrict__ rois, const int* __restrict__ ids,
-                                      const int* __restrict__ span, const float* __restrict__ dout)
+                                      const int* __restrict__ span, const E* __restrict__ dout)
 {
     __shared__ int s_list[OPS_LIST];
     __shared__ int s_cnt[4];
@@ -390,7 +456,7 @@ void ops_ms_roi_align_backward_kernel(const OpsMsArgs a, const float* __restrict
         if (i < a.n_levels && bid >= a.lv[i].block0) l = i;
     const OpsMsLevel d = ms_level(a, l);
     const int fh = d.fh, fw = d.fw, C = a.C, out_h = a.out_h, out_w = a.out_w;
-    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    const int C4 = C / Run<E>::V, n_chunks = (C4 + 63) >> 6;
     int t = bid - d.block0;
     const int tx = t % d.tiles_x;
     t /= d.tiles_x;
@@ -402,7 +468,8 @@ void ops_ms_roi_align_backward_kernel(const OpsMsArgs a, const float* __restrict
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4 = chunk * 64 + lane;
     const bool act = c4 < C4;
-    f32x4* const dimg = reinterpret_cast<f32x4*>(d.dx + (size_t)img * fh * fw * C);
+    const int cy = ty0 + wave / OPS_TILE, cx = tx0 + wave % OPS_TILE;
+    const bool cell_ok = cy <= ty1 && cx <= tx1;
     const int q = l * a.n_img + img;
     const int* const bucket = ids + span[2 * q];
     const int n_bucket = span[2 * q + 1] - span[2 * q];
@@ -412,27 +479,19 @@ void ops_ms_roi_align_backward_kernel(const OpsMsArgs a, const float* __restrict
                                   ty0, ty1, tx0, tx1);
     };
 
+    typename Run<E>::vec acc = 0.f;
     int i_next = 0;
-    bool first = true;
     do {
         i_next = cull_rois(i_next, n_bucket, touches, s_list, s_cnt, &s_n);
         const int n_list = s_n;
-        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
-            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
-            if (cy > ty1 || cx > tx1) continue;
-            f32x4* const dcell = dimg + ((size_t)cy * fw + cx) * C4;
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if (!first && act) acc = dcell[c4];
+        if (cell_ok)
             for (int li = 0; li < n_list; ++li) {
                 const int r = bucket[s_list[li]];
-                align_cell_grad(ops_align_geom(rois + (size_t)r * 5, d.scale, out_h, out_w, a.sampling_ratio, 0),
-                                reinterpret_cast<const f32x4*>(dout + (size_t)r * out_h * out_w * C), fh, fw, cy, cx, out_h, out_w, C4,
-                                c4, act, acc);
+                align_cell_grad<E>(ops_align_geom(rois + (size_t)r * 5, d.scale, out_h, out_w, a.sampling_ratio, 0),
+                                   dout + (size_t)r * out_h * out_w * C, fh, fw, cy, cx, out_h, out_w, C4, c4, act, acc);
             }
-            if (act) dcell[c4] = acc;
-        }
-        first = false;
     } while (i_next < n_bucket);
+    if (cell_ok && act) Run<E>::store(static_cast<E*>(d.dx) + (size_t)img * fh * fw * C, ((size_t)cy * fw + cx) * C4 + c4, acc);
 }
 
 // ---- RoIPool ------------------------------------------------------------------------------------------------------------------------
@@ -454,18 +513,21 @@ __device__ __forceinline__ void pool_bin(int p, float bin, int rs, int limit, in
     s = min(max(a, 0), limit); e = min(max(b, 0), limit);
 }
 
-// One block per bin (roi, ph, pw), one thread per channel quad: the max and the argmax cell (h * fw + w; -1 for an empty bin) per
+// One block per bin (roi, ph, pw), one thread per channel run: the max and the argmax cell (h * fw + w; -1 for an empty bin) per
 // channel, first maximum in (h, w) scan order with torchvision's strict '>' from -FLT_MAX.
+template <typename E>
 __global__ __launch_bounds__(128)
-void ops_roi_pool_kernel(const float* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
-                         int out_w, float scale, float* __restrict__ out, int32_t* __restrict__ argmax)
+void ops_roi_pool_kernel(const E* __restrict__ x, int n_img, int fh, int fw, int C, const float* __restrict__ rois, int out_h,
+                         int out_w, float scale, E* __restrict__ out, int32_t* __restrict__ argmax)
 {
+    typedef Run<E> R;
+    typedef typename R::vec vec;
+    typedef typename R::ivec ivec;
     const int r = blockIdx.x, ph = blockIdx.y, pw = blockIdx.z;
-    const int C4 = C >> 2;
+    const int C4 = C / R::V;
     const float* roi = rois + (size_t)r * 5;
     const size_t o = (((size_t)r * out_h + ph) * out_w + pw) * C4;
-    f32x4* const op = reinterpret_cast<f32x4*>(out) + o;
-    int4* const ap = reinterpret_cast<int4*>(argmax) + o;
+    ivec* const ap = reinterpret_cast<ivec*>(argmax) + o;
     int b, hs = 0, he = 0, ws = 0, we = 0;
     if (roi_image(roi[0], n_img, b)) {
         const PoolGeom g = ops_pool_geom(roi, scale, out_h, out_w);
@@ -475,40 +537,44 @@ void ops_roi_pool_kernel(const float* __restrict__ x, int n_img, int fh, int fw,
         b = 0;
     }
     const bool empty = he <= hs || we <= ws;
-    const f32x4* const fm = reinterpret_cast<const f32x4*>(x + (size_t)b * fh * fw * C);
+    const E* const fm = x + (size_t)b * fh * fw * C;
     for (int c4 = threadIdx.x; c4 < C4; c4 += 128) {
-        const float m0 = empty ? 0.f : -FLT_MAX;
-        f32x4 m = {m0, m0, m0, m0};
-        int4 am = make_int4(-1, -1, -1, -1);
+        vec m = empty ? 0.f : -FLT_MAX;
+        ivec am = -1;
         for (int h = hs; h < he; ++h)
             for (int w = ws; w < we; ++w) {
                 const int cell = h * fw + w;
-                const f32x4 v = fm[(size_t)cell * C4 + c4];
-                if (v[0] > m[0]) { m[0] = v[0]; am.x = cell; }
-                if (v[1] > m[1]) { m[1] = v[1]; am.y = cell; }
-                if (v[2] > m[2]) { m[2] = v[2]; am.z = cell; }
-                if (v[3] > m[3]) { m[3] = v[3]; am.w = cell; }
+                const vec v = R::load(fm, (size_t)cell * C4 + c4);
+#pragma unroll
+                for (int j = 0; j < R::V; ++j)
+                    if (v[j] > m[j]) { m[j] = v[j]; am[j] = cell; }
             }
-        op[c4] = m;
+        R::store(out, o + c4, m);
         ap[c4] = am;
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(256)
 void ops_roi_pool_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
-                                  float scale, const int32_t* __restrict__ argmax, const float* __restrict__ dout, float* __restrict__ dx)
+                                  float scale, const int32_t* __restrict__ argmax, const E* __restrict__ dout, E* __restrict__ dx)
 {
+    typedef Run<E> R;
+    typedef typename R::vec vec;
+    typedef typename R::ivec ivec;
     __shared__ int s_list[OPS_LIST];
     __shared__ int s_cnt[4];
     __shared__ int s_n;
-    const int C4 = C >> 2, n_chunks = (C4 + 63) >> 6;
+    const int C4 = C / R::V, n_chunks = (C4 + 63) >> 6;
     const int img = blockIdx.z / n_chunks, chunk = blockIdx.z - img * n_chunks;
     const int ty0 = blockIdx.y * OPS_TILE, tx0 = blockIdx.x * OPS_TILE;
     const int ty1 = min(ty0 + OPS_TILE, fh) - 1, tx1 = min(tx0 + OPS_TILE, fw) - 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4 = chunk * 64 + lane;
     const bool act = c4 < C4;
-    f32x4* const dimg = reinterpret_cast<f32x4*>(dx + (size_t)img * fh * fw * C);
+    const int cy = ty0 + wave / OPS_TILE, cx = tx0 + wave % OPS_TILE;
+    const bool cell_ok = cy <= ty1 && cx <= tx1;
+    const int cell = cy * fw + cx;
 
     auto touches = [&](int r) {
         const float* roi = rois + (size_t)r * 5;
@@ -520,50 +586,39 @@ void ops_roi_pool_backward_kernel(const float* __restrict__ rois, int k, int n_i
         return eh >= (float)ty0 && (float)g.rs_h <= (float)ty1 && ew >= (float)tx0 && (float)g.rs_w <= (float)tx1;
     };
 
+    vec acc = 0.f;
     int r_next = 0;
-    bool first = true;
     do {
         r_next = cull_rois(r_next, k, touches, s_list, s_cnt, &s_n);
         const int n_list = s_n;
-        for (int ci = wave; ci < OPS_TILE * OPS_TILE; ci += 4) {
-            const int cy = ty0 + ci / OPS_TILE, cx = tx0 + ci % OPS_TILE;
-            if (cy > ty1 || cx > tx1) continue;
-            const int cell = cy * fw + cx;
-            f32x4* const dcell = dimg + (size_t)cell * C4;
-            {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (!first && act) acc = dcell[c4];
-                for (int li = 0; li < n_list; ++li) {
-                    const int r = s_list[li];
-                    const PoolGeom g = ops_pool_geom(rois + (size_t)r * 5, scale, out_h, out_w);
-                    // bin p holds offset t iff floor(p bin) <= t < ceil((p + 1) bin): p in (t / bin - 1, (t + 1) / bin), widened by one
-                    const int th = cy - g.rs_h, tw = cx - g.rs_w;
-                    const int ph0 = max((int)floorf((float)th / g.bin_h) - 2, 0), ph1 = min((int)ceilf((float)(th + 1) / g.bin_h) + 1, out_h - 1);
-                    const int pw0 = max((int)floorf((float)tw / g.bin_w) - 2, 0), pw1 = min((int)ceilf((float)(tw + 1) / g.bin_w) + 1, out_w - 1);
-                    const size_t rb = (size_t)r * out_h * out_w * C4;
-                    for (int ph = ph0; ph <= ph1; ++ph) {
-                        int hs, he;
-                        pool_bin(ph, g.bin_h, g.rs_h, fh, hs, he);
-                        if (cy < hs || cy >= he) continue;
-                        for (int pw = pw0; pw <= pw1; ++pw) {
-                            int ws, we;
-                            pool_bin(pw, g.bin_w, g.rs_w, fw, ws, we);
-                            if (cx < ws || cx >= we || !act) continue;
-                            const size_t o = rb + ((size_t)ph * out_w + pw) * C4 + c4;
-                            const int4 am = reinterpret_cast<const int4*>(argmax)[o];
-                            const f32x4 gv = reinterpret_cast<const f32x4*>(dout)[o];
-                            if (am.x == cell) acc[0] += gv[0];
-                            if (am.y == cell) acc[1] += gv[1];
-                            if (am.z == cell) acc[2] += gv[2];
-                            if (am.w == cell) acc[3] += gv[3];
-                        }
+        if (cell_ok)
+            for (int li = 0; li < n_list; ++li) {
+                const int r = s_list[li];
+                const PoolGeom g = ops_pool_geom(rois + (size_t)r * 5, scale, out_h, out_w);
+                // bin p holds offset t iff floor(p bin) <= t < ceil((p + 1) bin): p in (t / bin - 1, (t + 1) / bin), widened by one
+                const int th = cy - g.rs_h, tw = cx - g.rs_w;
+                const int ph0 = max((int)floorf((float)th / g.bin_h) - 2, 0), ph1 = min((int)ceilf((float)(th + 1) / g.bin_h) + 1, out_h - 1);
+                const int pw0 = max((int)floorf((float)tw / g.bin_w) - 2, 0), pw1 = min((int)ceilf((float)(tw + 1) / g.bin_w) + 1, out_w - 1);
+                const size_t rb = (size_t)r * out_h * out_w * C4;
+                for (int ph = ph0; ph <= ph1; ++ph) {
+                    int hs, he;
+                    pool_bin(ph, g.bin_h, g.rs_h, fh, hs, he);
+                    if (cy < hs || cy >= he) continue;
+                    for (int pw = pw0; pw <= pw1; ++pw) {
+                        int ws, we;
+                        pool_bin(pw, g.bin_w, g.rs_w, fw, ws, we);
+                        if (cx < ws || cx >= we || !act) continue;
+                        const size_t o = rb + ((size_t)ph * out_w + pw) * C4 + c4;
+                        const ivec am = reinterpret_cast<const ivec*>(argmax)[o];
+                        const vec gv = R::load(dout, o);
+#pragma unroll
+                        for (int j = 0; j < R::V; ++j)
+                            if (am[j] == cell) acc[j] += gv[j];
                     }
                 }
-                if (act) dcell[c4] = acc;
             }
-        }
-        first = false;
     } while (r_next < k);
+    if (cell_ok && act) R::store(dx + (size_t)img * fh * fw * C, (size_t)cell * C4 + c4, acc);
 }
 
 // ---- NMS ----------------------------------------------------------------------------------------------------------------------------
@@ -671,17 +726,19 @@ void ops_nms_reduce_kernel(const u64* __restrict__ mask, const int64_t* __restri
     }
 }
 
-static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w)
+// v: the channels of a lane's run (Run<E>::V)
+static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w, int v)
 {
-    return n_img >= 1 && fh >= 1 && fw >= 1 && c >= 4 && c % 4 == 0 && k >= 0 && out_h >= 1 && out_h <= OPS_MAX_OUT && out_w >= 1 &&
-           out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / 4, 64) <= 65535;   // backward grid z
+    return n_img >= 1 && fh >= 1 && fw >= 1 && c >= v && c % v == 0 && k >= 0 && out_h >= 1 && out_h <= OPS_MAX_OUT && out_w >= 1 &&
+           out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / v, 64) <= 65535;   // backward grid z
 }
 
 // Fills the multi-scale argument (without map pointers) and the size of the backward grid; false on an invalid request.
 static bool ms_args_ok(OpsMsArgs& a, long long& blocks, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
-                       int k, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level, int k_min, int k_max)
+                       int k, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level, int k_min, int k_max,
+                       int v)
 {
-    if (n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || !fh || !fw || !scales || n_img < 1 || c < 4 || c % 4 != 0 || k < 0 ||
+    if (n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || !fh || !fw || !scales || n_img < 1 || c < v || c % v != 0 || k < 0 ||
         out_h < 1 || out_h > OPS_MAX_OUT || out_w < 1 || out_w > OPS_MAX_OUT || sampling_ratio > OPS_MAX_SAMPLING ||
         (long long)n_levels * n_img > INT32_MAX / 2)
         return false;
@@ -696,68 +753,69 @@ static bool ms_args_ok(OpsMsArgs& a, long long& blocks, const int* fh, const int
         d.fh = fh[l]; d.fw = fw[l]; d.scale = scales[l];
         d.tiles_y = cdiv(fh[l], OPS_TILE); d.tiles_x = cdiv(fw[l], OPS_TILE);
         d.block0 = (int)min(blocks, (long long)INT32_MAX);
-        blocks += (long long)d.tiles_y * d.tiles_x * n_img * cdiv(c / 4, 64);
+        blocks += (long long)d.tiles_y * d.tiles_x * n_img * cdiv(c / v, 64);
     }
     return blocks <= INT32_MAX;
 }
 
-}  // namespace frcnn
-
-using namespace frcnn;
-
-extern "C" {
-
-int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
-                        float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream)
+// ---- the entry points' bodies, one per element type ---------------------------------------------------------------------------------
+template <typename E>
+static int roi_align_impl(const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                          float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream)
 {
-    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w, Run<E>::V) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
     if (k == 0) return FRCNN_OK;
     if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
-    hipLaunchKernelGGL(ops_roi_align_kernel, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, d_x, n_img, fh, fw, c, d_rois, out_h,
-                       out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0, d_out);
+    hipLaunchKernelGGL(ops_roi_align_kernel<E>, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, static_cast<const E*>(d_x), n_img, fh,
+                       fw, c, d_rois, out_h, out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0, static_cast<E*>(d_out));
     return check_launch();
 }
 
-int frcnn_ops_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
-                                 int sampling_ratio, int aligned, const float* d_dout, float* d_dx, void* stream)
+template <typename E>
+static int roi_align_backward_impl(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                   int sampling_ratio, int aligned, const void* d_dout, void* d_dx, void* stream)
 {
-    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w, Run<E>::V) || sampling_ratio > OPS_MAX_SAMPLING) return FRCNN_EINVAL;
     if (!d_dx || (k > 0 && (!d_rois || !d_dout))) return FRCNN_EINVAL;
-    hipLaunchKernelGGL(ops_roi_align_backward_kernel, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / 4, 64)), dim3(256), 0,
-                       (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0,
-                       d_dout, d_dx);
+    hipLaunchKernelGGL(ops_roi_align_backward_kernel<E>, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / Run<E>::V, 64)),
+                       dim3(256), 0, (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio,
+                       aligned ? 1 : 0, static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
     return check_launch();
 }
 
-int frcnn_ops_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
-                       float spatial_scale, float* d_out, int32_t* d_argmax, void* stream)
+template <typename E>
+static int roi_pool_impl(const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                         float spatial_scale, void* d_out, int32_t* d_argmax, void* stream)
 {
-    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w)) return FRCNN_EINVAL;
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w, Run<E>::V)) return FRCNN_EINVAL;
     if (k == 0) return FRCNN_OK;
     if (!d_x || !d_rois || !d_out || !d_argmax) return FRCNN_EINVAL;
-    hipLaunchKernelGGL(ops_roi_pool_kernel, dim3(k, out_h, out_w), dim3(128), 0, (hipStream_t)stream, d_x, n_img, fh, fw, c, d_rois,
-                       out_h, out_w, spatial_scale, d_out, d_argmax);
+    hipLaunchKernelGGL(ops_roi_pool_kernel<E>, dim3(k, out_h, out_w), dim3(128), 0, (hipStream_t)stream, static_cast<const E*>(d_x), n_img,
+                       fh, fw, c, d_rois, out_h, out_w, spatial_scale, static_cast<E*>(d_out), d_argmax);
     return check_launch();
 }
 
-int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
-                                const int32_t* d_argmax, const float* d_dout, float* d_dx, void* stream)
+template <typename E>
+static int roi_pool_backward_impl(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                  const int32_t* d_argmax, const void* d_dout, void* d_dx, void* stream)
 {
-    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w)) return FRCNN_EINVAL;
+    if (!roi_args_ok(n_img, fh, fw, c, k, out_h, out_w, Run<E>::V)) return FRCNN_EINVAL;
     if (!d_dx || (k > 0 && (!d_rois || !d_argmax || !d_dout))) return FRCNN_EINVAL;
-    hipLaunchKernelGGL(ops_roi_pool_backward_kernel, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / 4, 64)), dim3(256), 0,
-                       (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax, d_dout, d_dx);
+    hipLaunchKernelGGL(ops_roi_pool_backward_kernel<E>, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / Run<E>::V, 64)),
+                       dim3(256), 0, (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax,
+                       static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
     return check_launch();
 }
 
-int frcnn_ops_ms_roi_align(const float* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
-                           const float* d_rois, int k, int out_h, int out_w, int sampling_ratio, float canonical_scale,
-                           float canonical_level, int k_min, int k_max, float* d_out, void* stream)
+template <typename E>
+static int ms_roi_align_impl(const void* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
+                             const float* d_rois, int k, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                             float canonical_level, int k_min, int k_max, void* d_out, void* stream)
 {
     OpsMsArgs a;
     long long blocks;
     if (!ms_args_ok(a, blocks, fh, fw, scales, n_levels, n_img, c, k, out_h, out_w, sampling_ratio, canonical_scale, canonical_level,
-                    k_min, k_max))
+                    k_min, k_max, Run<E>::V))
         return FRCNN_EINVAL;
     if (k == 0) return FRCNN_OK;
     if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
@@ -765,25 +823,20 @@ int frcnn_ops_ms_roi_align(const float* const* d_x, const int* fh, const int* fw
         if (!d_x[l] && fh[l] * fw[l] > 0) return FRCNN_EINVAL;
         a.lv[l].x = d_x[l];
     }
-    hipLaunchKernelGGL(ops_ms_roi_align_kernel, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, a, d_rois, d_out);
+    hipLaunchKernelGGL(ops_ms_roi_align_kernel<E>, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, a, d_rois, static_cast<E*>(d_out));
     return check_launch();
 }
 
-size_t frcnn_ops_ms_roi_align_workspace_bytes(int k, int n_levels, int n_img)
-{
-    if (k < 0 || n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || n_img < 1 || (long long)n_levels * n_img > INT32_MAX / 2) return 0;
-    return ((size_t)k + 2 * (size_t)n_levels * n_img) * sizeof(int);
-}
-
-int frcnn_ops_ms_roi_align_backward(const float* d_rois, int k, const int* fh, const int* fw, const float* scales, int n_levels, int n_img,
-                                    int c, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level,
-                                    int k_min, int k_max, const float* d_dout, float* const* d_dx, void* d_ws, size_t ws_bytes,
-                                    void* stream)
+template <typename E>
+static int ms_roi_align_backward_impl(const float* d_rois, int k, const int* fh, const int* fw, const float* scales, int n_levels,
+                                      int n_img, int c, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                                      float canonical_level, int k_min, int k_max, const void* d_dout, void* const* d_dx, void* d_ws,
+                                      size_t ws_bytes, void* stream)
 {
     OpsMsArgs a;
     long long blocks;
     if (!ms_args_ok(a, blocks, fh, fw, scales, n_levels, n_img, c, k, out_h, out_w, sampling_ratio, canonical_scale, canonical_level,
-                    k_min, k_max))
+                    k_min, k_max, Run<E>::V))
         return FRCNN_EINVAL;
     if (!d_dx || !d_ws || ws_bytes < frcnn_ops_ms_roi_align_workspace_bytes(k, n_levels, n_img) || (k > 0 && (!d_rois || !d_dout)))
         return FRCNN_EINVAL;
@@ -798,8 +851,125 @@ int frcnn_ops_ms_roi_align_backward(const float* d_rois, int k, const int* fh, c
     hipLaunchKernelGGL(ops_ms_bucket_kernel, dim3(n_levels * n_img), dim3(256), 0, s, a, d_rois, k, ids, span);
     const int rc = check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(ops_ms_roi_align_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, d_rois, ids, span, d_dout);
+    hipLaunchKernelGGL(ops_ms_roi_align_backward_kernel<E>, dim3((unsigned)blocks), dim3(256), 0, s, a, d_rois, ids, span,
+                       static_cast<const E*>(d_dout));
     return check_launch();
+}
+
+}  // namespace frcnn
+
+using namespace frcnn;
+
+// A 16-bit entry point's body by element-type code, in runs of `run` channels; c must hold whole runs of OPS_HALF_RUN either way.
+#define OPS_DISPATCH_16(elem_type, c, run, impl, ...)                                        \
+    do {                                                                                     \
+        if ((c) % OPS_HALF_RUN != 0) return FRCNN_EINVAL;                                    \
+        const bool wide = (run) == OPS_HALF_RUN;                                             \
+        if ((elem_type) == FRCNN_OPS_F16)                                                    \
+            return wide ? impl<f16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<f16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__);   \
+        if ((elem_type) == FRCNN_OPS_BF16)                                                   \
+            return wide ? impl<bf16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<bf16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__); \
+        return FRCNN_EINVAL;                                                                 \
+    } while (0)
+
+// the run of a backward gather over c channels: the wide one when its runs fill the 64 lanes that share a cell
+static int backward_run(int c) { return c / OPS_HALF_RUN >= 64 ? OPS_HALF_RUN : OPS_HALF_RUN_NARROW; }
+
+extern "C" {
+
+int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                        float spatial_scale, int sampling_ratio, int aligned, float* d_out, void* stream)
+{
+    return roi_align_impl<float>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, sampling_ratio, aligned, d_out, stream);
+}
+
+int frcnn_ops_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                 int sampling_ratio, int aligned, const float* d_dout, float* d_dx, void* stream)
+{
+    return roi_align_backward_impl<float>(d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, aligned, d_dout, d_dx,
+                                          stream);
+}
+
+int frcnn_ops_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                       float spatial_scale, float* d_out, int32_t* d_argmax, void* stream)
+{
+    return roi_pool_impl<float>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, d_argmax, stream);
+}
+
+int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                const int32_t* d_argmax, const float* d_dout, float* d_dx, void* stream)
+{
+    return roi_pool_backward_impl<float>(d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax, d_dout, d_dx, stream);
+}
+
+size_t frcnn_ops_ms_roi_align_workspace_bytes(int k, int n_levels, int n_img)
+{
+    if (k < 0 || n_levels < 1 || n_levels > OPS_MS_MAX_LEVELS || n_img < 1 || (long long)n_levels * n_img > INT32_MAX / 2) return 0;
+    return ((size_t)k + 2 * (size_t)n_levels * n_img) * sizeof(int);
+}
+
+int frcnn_ops_ms_roi_align(const float* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels, int n_img, int c,
+                           const float* d_rois, int k, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                           float canonical_level, int k_min, int k_max, float* d_out, void* stream)
+{
+    return ms_roi_align_impl<float>(reinterpret_cast<const void* const*>(d_x), fh, fw, scales, n_levels, n_img, c, d_rois, k, out_h, out_w,
+                                    sampling_ratio, canonical_scale, canonical_level, k_min, k_max, d_out, stream);
+}
+
+int frcnn_ops_ms_roi_align_backward(const float* d_rois, int k, const int* fh, const int* fw, const float* scales, int n_levels, int n_img,
+                                    int c, int out_h, int out_w, int sampling_ratio, float canonical_scale, float canonical_level,
+                                    int k_min, int k_max, const float* d_dout, float* const* d_dx, void* d_ws, size_t ws_bytes,
+                                    void* stream)
+{
+    return ms_roi_align_backward_impl<float>(d_rois, k, fh, fw, scales, n_levels, n_img, c, out_h, out_w, sampling_ratio, canonical_scale,
+                                             canonical_level, k_min, k_max, d_dout, reinterpret_cast<void* const*>(d_dx), d_ws, ws_bytes,
+                                             stream);
+}
+
+int frcnn_ops_half_run(void) { return OPS_HALF_RUN; }
+
+int frcnn_ops_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                           int out_w, float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, OPS_HALF_RUN, roi_align_impl, d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, sampling_ratio, aligned,
+                    d_out, stream);
+}
+
+int frcnn_ops_roi_align_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                    float spatial_scale, int sampling_ratio, int aligned, const void* d_dout, void* d_dx, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, backward_run(c), roi_align_backward_impl, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, aligned,
+                    d_dout, d_dx, stream);
+}
+
+int frcnn_ops_roi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                          int out_w, float spatial_scale, void* d_out, int32_t* d_argmax, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, OPS_HALF_RUN, roi_pool_impl, d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, d_argmax, stream);
+}
+
+int frcnn_ops_roi_pool_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                   float spatial_scale, const int32_t* d_argmax, const void* d_dout, void* d_dx, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, backward_run(c), roi_pool_backward_impl, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_argmax, d_dout, d_dx,
+                    stream);
+}
+
+int frcnn_ops_ms_roi_align_16(int elem_type, const void* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels,
+                              int n_img, int c, const float* d_rois, int k, int out_h, int out_w, int sampling_ratio,
+                              float canonical_scale, float canonical_level, int k_min, int k_max, void* d_out, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, OPS_HALF_RUN, ms_roi_align_impl, d_x, fh, fw, scales, n_levels, n_img, c, d_rois, k, out_h, out_w, sampling_ratio,
+                    canonical_scale, canonical_level, k_min, k_max, d_out, stream);
+}
+
+int frcnn_ops_ms_roi_align_backward_16(int elem_type, const float* d_rois, int k, const int* fh, const int* fw, const float* scales,
+                                       int n_levels, int n_img, int c, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                                       float canonical_level, int k_min, int k_max, const void* d_dout, void* const* d_dx, void* d_ws,
+                                       size_t ws_bytes, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, backward_run(c), ms_roi_align_backward_impl, d_rois, k, fh, fw, scales, n_levels, n_img, c, out_h, out_w, sampling_ratio,
+                    canonical_scale, canonical_level, k_min, k_max, d_dout, d_dx, d_ws, ws_bytes, stream);
 }
 
 size_t frcnn_ops_nms_workspace_bytes(int n)

@@ -11,19 +11,30 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
                                                      score, ties by ascending index (torchvision's per-category loop, no coordinate offset).
   roi_pool(input, boxes, output_size, spatial_scale=1.0)
   roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False)
-      input float32 [N, C, H, W]; boxes Tensor[K, 5] (batch index, x1, y1, x2, y2) or list[Tensor[L_i, 4]]; output_size int or
-      (oh, ow), each <= 64; sampling_ratio <= 16.  The result is [K, C, oh, ow] in channels_last memory ([K, oh, ow, C]).  A batch
+      input float32, float16 or bfloat16 [N, C, H, W]; boxes float32 Tensor[K, 5] (batch index, x1, y1, x2, y2) or list[Tensor[L_i, 4]];
+      output_size int or (oh, ow), each <= 64; sampling_ratio <= 16.  The result is [K, C, oh, ow] in the input's dtype and channels_last
+      memory ([K, oh, ow, C]).  A batch
       index outside [0, N) pools to zeros and receives no gradient.  Backward passes are deterministic gathers (no atomics):
       RoIPool sends each bin's gradient to its first maximum in scan order, an empty bin sends none.  Double backward raises.
   MultiScaleRoIAlign(featmap_names, output_size, sampling_ratio, *, canonical_scale=224, canonical_level=4)(x, boxes, image_shapes)
   multi_scale_roi_align(features, boxes, output_size, spatial_scales, sampling_ratio=-1, canonical_scale=224, canonical_level=4)
-      torchvision's FPN pooler (ops/poolers.py): 1 to 8 float32 maps of the same N and C; each RoI's level by LevelMapper in float32 as
+      torchvision's FPN pooler (ops/poolers.py): 1 to 8 maps of the same N, C and dtype; each RoI's level by LevelMapper in float32 as
       torch computes it on the GPU, then roi_align(aligned=False) on that level, bit-identical to the per-level torch.where loop (forward
       and backward) in one launch each way and without a host sync.  A RoI without a level (negative or NaN area) pools to zeros.
 
+Mixed precision.  For T in {float16, bfloat16} the three RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
+torchvision's autocast definition as the contract, bit for bit:
+      op(x_T, boxes)  ==  op(x_T.float(), boxes).to(T)          backward:  dx_T  ==  op_backward(grad_T.float()).to(T)
+Values are widened exactly on load; geometry, weights and sums are the float32 kernels' (one shared body); the result is rounded once, to
+nearest even, on store, and backward sums never pass through 16-bit memory.  RoIPool's maximum and argmax are those of the float32 op.
+Boxes stay float32; boxes in the map's own 16-bit dtype are accepted too (torchvision requires equal dtypes outside autocast) and widened
+before the launch, so the kernels and the level mapper only ever see float32 RoIs.  Any other combination is a TypeError, as is a pyramid
+of mixed dtypes.  No autocast registration is needed: under torch.autocast the backbone hands the ops 16-bit maps and float32 boxes, which
+they take as they are.  nms / batched_nms keep float32 or float64 boxes (widen 16-bit boxes at the call).
+
 Inputs must be CUDA (HIP) tensors; there is no CPU implementation.  channels_last inputs go to the NHWC kernels as they are, contiguous
-NCHW inputs are converted once, a channel count that is not a multiple of 4 goes through a zero-padded copy; input gradients come back in
-the input's memory format.
+NCHW inputs are converted once, a channel count that is not a multiple of 4 (of the 16-bit kernels' run of 8 for 16-bit maps) goes through
+a zero-padded copy; input gradients come back in the input's dtype and memory format.
 """
 import ctypes as C
 from typing import List
@@ -69,26 +80,40 @@ def _output_size(output_size):
     return oh, ow
 
 
+_HALF = (torch.float16, torch.bfloat16)
+_MAP_DTYPES = (torch.float32,) + _HALF
+_MAP_WHAT = "float32, float16 or bfloat16"
+
+
+def _box_dtypes(input):
+    """Boxes are float32; with a 16-bit map, also that map's own dtype (widened before the launch)."""
+    if input.dtype in _HALF:
+        return (torch.float32, input.dtype), "float32 or the input's %s" % input.dtype
+    return (torch.float32,), "float32"
+
+
 def _roi_input(input, boxes):
-    """Checks the RoI ops' inputs; returns boxes as a Tensor[K, 5] (torchvision's convert_boxes_to_roi_format)."""
-    _check_tensor("input", input, (torch.float32,), "float32")
+    """Checks the RoI ops' inputs; returns boxes as a float32 Tensor[K, 5] (torchvision's convert_boxes_to_roi_format)."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
     if input.dim() != 4:
         raise ValueError("input must be [N, C, H, W], got shape %s" % (tuple(input.shape),))
+    dtypes, what = _box_dtypes(input)
     if isinstance(boxes, (list, tuple)):
         for i, b in enumerate(boxes):
-            _check_tensor("boxes[%d]" % i, b, (torch.float32,), "float32")
+            _check_tensor("boxes[%d]" % i, b, dtypes, what)
             _check_same_device(input, b, "input", "boxes[%d]" % i)
             if b.dim() != 2 or b.shape[1] != 4:
                 raise ValueError("boxes[%d] must be [L, 4], got shape %s" % (i, tuple(b.shape)))
         if not boxes:
-            return input.new_zeros((0, 5))
+            return input.new_zeros((0, 5), dtype=torch.float32)
+        boxes = [b.float() for b in boxes]
         return torch.cat([torch.cat([torch.full_like(b[:, :1], float(i)), b], dim=1) for i, b in enumerate(boxes)], dim=0)
-    _check_tensor("boxes", boxes, (torch.float32,), "float32")
+    _check_tensor("boxes", boxes, dtypes, what)
     _check_same_device(input, boxes, "input", "boxes")
     if boxes.dim() != 2 or boxes.shape[1] != 5:
         raise ValueError("boxes must be a Tensor[K, 5] (batch index, x1, y1, x2, y2) or a list of Tensor[L, 4], got shape %s"
                          % (tuple(boxes.shape),))
-    return boxes
+    return boxes.float()
 
 
 def _input_is_channels_last(x):
@@ -96,14 +121,31 @@ def _input_is_channels_last(x):
 
 
 # ---- layout helpers of the real implementations ------------------------------------------------------------------------------------
-def _padded_channels(c):
-    return (c + 3) // 4 * 4
+def _elem(dtype):
+    """The frcnn_ops_*_16 element-type code of a 16-bit dtype; None for float32 (the frcnn_ops_* entry points)."""
+    return {torch.float16: nv.OPS_F16, torch.bfloat16: nv.OPS_BF16}.get(dtype)
 
 
-def _nhwc(x, fill=0):
-    """x [A, C, B, D] as a channels_last tensor with C padded to a multiple of 4 (no copy when x already is one)."""
+def _call(name, like, *args):
+    """frcnn_ops_<name> on float32 tensors, frcnn_ops_<name>_16 with the element-type code first on 16-bit ones."""
+    e = _elem(like.dtype)
+    if e is None:
+        nv.check(getattr(nv.lib(), "frcnn_ops_" + name)(*args), "frcnn_ops_" + name)
+    else:
+        nv.check(getattr(nv.lib(), "frcnn_ops_%s_16" % name)(e, *args), "frcnn_ops_%s_16" % name)
+
+
+def _padded_channels(c, dtype):
+    """c rounded up to the channels a lane of the dtype's kernels owns: 4 floats, frcnn_ops_half_run() 16-bit values."""
+    v = nv.lib().frcnn_ops_half_run() if dtype in _HALF else 4
+    return (c + v - 1) // v * v
+
+
+def _nhwc(x, fill=0, like=None):
+    """x [A, C, B, D] as a channels_last tensor with C padded for the kernels of like's dtype (x's own by default); no copy when x
+    already is one."""
     c = x.shape[1]
-    cp = _padded_channels(c)
+    cp = _padded_channels(c, (x if like is None else like).dtype)
     if cp == c:
         return x.contiguous(memory_format=_CL)
     xp = torch.full((x.shape[0], cp) + tuple(x.shape[2:]), fill, dtype=x.dtype, device=x.device).contiguous(memory_format=_CL)
@@ -111,8 +153,8 @@ def _nhwc(x, fill=0):
     return xp
 
 
-def _empty_cl(shape, like, dtype=torch.float32):
-    return torch.empty(shape, dtype=dtype, device=like.device, memory_format=_CL)
+def _empty_cl(shape, like, dtype=None):
+    return torch.empty(shape, dtype=like.dtype if dtype is None else dtype, device=like.device, memory_format=_CL)
 
 
 def _stream(t):
@@ -150,9 +192,8 @@ def _roi_align(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height:
         r = rois.contiguous()
         cp = x.shape[1]
         dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
-        nv.check(nv.lib().frcnn_ops_roi_align(x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width,
-                                              spatial_scale, sampling_ratio, int(aligned), dst.data_ptr(), _stream(input)),
-                 "frcnn_ops_roi_align")
+        _call("roi_align", input, x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width, spatial_scale, sampling_ratio,
+              int(aligned), dst.data_ptr(), _stream(input))
         if dst is not out:
             out.copy_(dst[:, :c])
     return out
@@ -166,18 +207,16 @@ def _(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, a
 @torch.library.custom_op("frcnn::roi_align_backward", mutates_args=())
 def _roi_align_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
                         aligned: bool, batch_size: int, channels: int, height: int, width: int, channels_last: bool) -> Tensor:
-    cp = _padded_channels(channels)
     k = rois.shape[0]
     if channels == 0 or batch_size * height * width == 0:
         return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
     with torch.cuda.device(grad.device):
+        cp = _padded_channels(channels, grad.dtype)
         g = _nhwc(grad)
         r = rois.contiguous()
         dx = _empty_cl((batch_size, cp, height, width), grad)
-        nv.check(nv.lib().frcnn_ops_roi_align_backward(r.data_ptr() if k else None, k, batch_size, height, width, cp,
-                                                       pooled_height, pooled_width, spatial_scale, sampling_ratio, int(aligned),
-                                                       g.data_ptr() if k else None, dx.data_ptr(), _stream(grad)),
-                 "frcnn_ops_roi_align_backward")
+        _call("roi_align_backward", grad, r.data_ptr() if k else None, k, batch_size, height, width, cp, pooled_height, pooled_width,
+              spatial_scale, sampling_ratio, int(aligned), g.data_ptr() if k else None, dx.data_ptr(), _stream(grad))
         return _grad_layout(dx, channels, channels_last)
 
 
@@ -230,9 +269,8 @@ def _ms_roi_align(features: List[Tensor], rois: Tensor, scales: List[float], poo
         dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), x0)
         hs, ws, sc = _ms_levels([f.shape[2] for f in features], [f.shape[3] for f in features], scales)
         ptrs = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
-        nv.check(nv.lib().frcnn_ops_ms_roi_align(ptrs, hs, ws, sc, len(xs), n, cp, r.data_ptr(), k, pooled_height, pooled_width,
-                                                 sampling_ratio, canonical_scale, canonical_level, k_min, k_max, dst.data_ptr(),
-                                                 _stream(x0)), "frcnn_ops_ms_roi_align")
+        _call("ms_roi_align", x0, ptrs, hs, ws, sc, len(xs), n, cp, r.data_ptr(), k, pooled_height, pooled_width, sampling_ratio,
+              canonical_scale, canonical_level, k_min, k_max, dst.data_ptr(), _stream(x0))
         if dst is not out:
             out.copy_(dst[:, :c])
     return out
@@ -250,9 +288,9 @@ def _ms_roi_align_backward(grad: Tensor, rois: Tensor, scales: List[float], pool
     if channels == 0 or batch_size == 0:
         return [_grad_layout(grad.new_zeros((batch_size, channels, h, w)), channels, cl)
                 for h, w, cl in zip(heights, widths, channels_last)]
-    cp = _padded_channels(channels)
     k = rois.shape[0]
     with torch.cuda.device(grad.device):
+        cp = _padded_channels(channels, grad.dtype)
         g = _nhwc(grad)
         r = rois.contiguous()
         dxs = [_empty_cl((batch_size, cp, h, w), grad) for h, w in zip(heights, widths)]
@@ -260,10 +298,9 @@ def _ms_roi_align_backward(grad: Tensor, rois: Tensor, scales: List[float], pool
         ws = torch.empty((lib.frcnn_ops_ms_roi_align_workspace_bytes(k, len(scales), batch_size),), dtype=torch.uint8, device=grad.device)
         hs, wd, sc = _ms_levels(heights, widths, scales)
         ptrs = (C.c_void_p * len(dxs))(*[d.data_ptr() for d in dxs])
-        nv.check(lib.frcnn_ops_ms_roi_align_backward(r.data_ptr() if k else None, k, hs, wd, sc, len(scales), batch_size, cp, pooled_height,
-                                                     pooled_width, sampling_ratio, canonical_scale, canonical_level, k_min, k_max,
-                                                     g.data_ptr() if k else None, ptrs, ws.data_ptr(), ws.numel(), _stream(grad)),
-                 "frcnn_ops_ms_roi_align_backward")
+        _call("ms_roi_align_backward", grad, r.data_ptr() if k else None, k, hs, wd, sc, len(scales), batch_size, cp, pooled_height,
+              pooled_width, sampling_ratio, canonical_scale, canonical_level, k_min, k_max, g.data_ptr() if k else None, ptrs,
+              ws.data_ptr(), ws.numel(), _stream(grad))
         return [_grad_layout(d, channels, cl) for d, cl in zip(dxs, channels_last)]
 
 
@@ -313,8 +350,8 @@ def _roi_pool(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: 
         padded = cp != c
         dst = _empty_cl((k, cp, pooled_height, pooled_width), input) if padded else out
         am = _empty_cl((k, cp, pooled_height, pooled_width), input, torch.int32) if padded else argmax
-        nv.check(nv.lib().frcnn_ops_roi_pool(x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width,
-                                             spatial_scale, dst.data_ptr(), am.data_ptr(), _stream(input)), "frcnn_ops_roi_pool")
+        _call("roi_pool", input, x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width, spatial_scale, dst.data_ptr(),
+              am.data_ptr(), _stream(input))
         if padded:
             out.copy_(dst[:, :c])
             argmax.copy_(am[:, :c])
@@ -330,19 +367,17 @@ def _(input, rois, spatial_scale, pooled_height, pooled_width):
 @torch.library.custom_op("frcnn::roi_pool_backward", mutates_args=())
 def _roi_pool_backward(grad: Tensor, rois: Tensor, argmax: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int,
                        batch_size: int, channels: int, height: int, width: int, channels_last: bool) -> Tensor:
-    cp = _padded_channels(channels)
     k = rois.shape[0]
     if channels == 0 or batch_size * height * width == 0:
         return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
     with torch.cuda.device(grad.device):
+        cp = _padded_channels(channels, grad.dtype)
         g = _nhwc(grad)
         r = rois.contiguous()
-        am = _nhwc(argmax, fill=-1)
+        am = _nhwc(argmax, fill=-1, like=grad)
         dx = _empty_cl((batch_size, cp, height, width), grad)
-        nv.check(nv.lib().frcnn_ops_roi_pool_backward(r.data_ptr() if k else None, k, batch_size, height, width, cp,
-                                                      pooled_height, pooled_width, spatial_scale, am.data_ptr() if k else None,
-                                                      g.data_ptr() if k else None, dx.data_ptr(), _stream(grad)),
-                 "frcnn_ops_roi_pool_backward")
+        _call("roi_pool_backward", grad, r.data_ptr() if k else None, k, batch_size, height, width, cp, pooled_height, pooled_width,
+              spatial_scale, am.data_ptr() if k else None, g.data_ptr() if k else None, dx.data_ptr(), _stream(grad))
         return _grad_layout(dx, channels, channels_last)
 
 
@@ -479,7 +514,10 @@ def _ms_features(features):
     if not 1 <= len(features) <= MAX_LEVELS:
         raise ValueError("features must hold 1 to %d feature maps, got %d" % (MAX_LEVELS, len(features)))
     for i, f in enumerate(features):
-        _check_tensor("features[%d]" % i, f, (torch.float32,), "float32")
+        _check_tensor("features[%d]" % i, f, _MAP_DTYPES, _MAP_WHAT)
+        if f.dtype != features[0].dtype:
+            raise TypeError("every feature map must have one dtype (float32, float16 or bfloat16): features[0] is %s, features[%d] is %s"
+                            % (features[0].dtype, i, f.dtype))
         if f.dim() != 4:
             raise ValueError("features[%d] must be [N, C, H, W], got shape %s" % (i, tuple(f.shape)))
         _check_same_device(features[0], f, "features[0]", "features[%d]" % i)
@@ -518,8 +556,8 @@ def _multi_scale_roi_align(features, boxes, output_size, scales, sampling_ratio,
 
 
 def multi_scale_roi_align(features, boxes, output_size, spatial_scales, sampling_ratio=-1, canonical_scale=224, canonical_level=4):
-    """torchvision.ops.MultiScaleRoIAlign's pooling on explicit levels: [K, C, oh, ow] (channels_last memory).  features: 1 to 8 float32
-    maps [N, C, H_l, W_l] (the same N and C), finest first; spatial_scales: one per map.  Each RoI goes to level
+    """torchvision.ops.MultiScaleRoIAlign's pooling on explicit levels: [K, C, oh, ow] (channels_last memory).  features: 1 to 8
+    maps [N, C, H_l, W_l] (the same N, C and dtype: float32, float16 or bfloat16), finest first; spatial_scales: one per map.  Each RoI goes to level
     floor(canonical_level + log2(sqrt(area) / canonical_scale) + 1e-6), clamped to [k_min, k_max] = int(-log2) of the first and the last
     scale, minus k_min, and is pooled there by roi_align(aligned=False); a RoI without a level (negative or NaN area, an index outside the
     maps) pools to zeros.  One map: every RoI is pooled on it."""

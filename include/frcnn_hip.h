@@ -37,7 +37,7 @@ extern "C" {
 #define FRCNN_EUNSUPPORTED -4   /* valid request outside what this build implements */
 #define FRCNN_ENODEVICE    -5   /* no gfx950 device visible */
 
-#define FRCNN_ABI_VERSION 20  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
+#define FRCNN_ABI_VERSION 21  /* 2: training entry points, frcnn_forward_params.conv_blocks_target; 3: Winograd F(2x2,3x3) layers; 4: one-launch Winograd layers;
                                  5: bf16 gradient GEMMs (the *_math entry points); 6: x6t GEMM, x6 Winograd layers, frcnn_forward_params.winograd_x6_mask,
                                  timing classes 8 / 9; 7: batched feature extractor (frcnn_resnet_backbone, frcnn_resnet_forward_features,
                                  frcnn_ctx_create_backbone, frcnn_conv3x3_nhwc_winograd_fused_maps); 8: the f32x3 arithmetic (frcnn_*_x3t, frcnn_*_winograd_x3,
@@ -55,7 +55,8 @@ extern "C" {
                                  measured in DESIGN.md section 5);
                                  19: frcnn_ops_* (torchvision.ops-style roi_align / roi_pool / nms over N images, no context: fasterrcnn_amd.ops);
                                  20: frcnn_ops_ms_roi_align(_backward / _workspace_bytes): torchvision.ops.MultiScaleRoIAlign (FPN pooling) in one launch
-                                 per direction */
+                                 per direction;
+                                 21: frcnn_ops_*_16: the RoI operators on float16 / bfloat16 maps (widen, float32 arithmetic, one rounding) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -429,7 +430,8 @@ int frcnn_roi_align_backward(const float* d_rois, int n_rois, int fh, int fw, in
                              int sampling_ratio, int aligned, const float* d_dout, float* d_dfm, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * torchvision.ops-style operators (csrc/ops.hip; Python: fasterrcnn_amd.ops, torch custom ops frcnn::*).  No context; float32 maps.
+ * torchvision.ops-style operators (csrc/ops.hip; Python: fasterrcnn_amd.ops, torch custom ops frcnn::*).  No context; float32 maps
+ * (float16 / bfloat16 maps: the frcnn_ops_*_16 entry points below).
  *   d_x    : float32 NHWC [n_img][fh][fw][c] (a channels_last NCHW tensor), c % 4 == 0, c >= 4
  *   d_rois : float32 [k][5] torchvision rows (batch index, x1, y1, x2, y2); a batch index outside (-1, n_img) pools to zeros and
  *            receives no gradient (checked on the device: no host sync)
@@ -478,6 +480,34 @@ int frcnn_ops_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, i
 size_t frcnn_ops_nms_workspace_bytes(int n);
 int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
                   uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The RoI operators on 16-bit maps (ABI 21): float16 or bfloat16 d_x / d_out / d_dout / d_dx (elem_type, one for the whole call), in the
+ *   layouts of their float32 siblings above; d_rois and the level arithmetic stay float32, d_argmax int32.  Values are widened exactly
+ *   on load, every weight and sum is float32 in the float32 kernels' order (one shared body), and the result is rounded once, to nearest
+ *   even as torch's Tensor.to() rounds (bfloat16: every NaN becomes 0x7FC0), on store:
+ *       op_16(x) == op(float(x)) rounded,   op_backward_16(dout) == op_backward(float(dout)) rounded,   bit for bit
+ *   (torchvision's autocast definition); the backward sums live in registers over every culling pass, never in the 16-bit d_dx.
+ *   c % frcnn_ops_half_run() == 0 (8: the 16-bit channels a lane loads at once, 16 bytes; the backward gathers walk the same tensors in
+ *   runs of 4 while c / 8 would not fill a wave, c < 512).  Arguments are validated as by the float32
+ *   entry points; an unknown elem_type is FRCNN_EINVAL.  The multi-scale workspace is frcnn_ops_ms_roi_align_workspace_bytes's. */
+#define FRCNN_OPS_F16  1   /* IEEE binary16 (torch.float16) */
+#define FRCNN_OPS_BF16 2   /* bfloat16 (torch.bfloat16) */
+int frcnn_ops_half_run(void);
+int frcnn_ops_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                           int out_w, float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream);
+int frcnn_ops_roi_align_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                    float spatial_scale, int sampling_ratio, int aligned, const void* d_dout, void* d_dx, void* stream);
+int frcnn_ops_roi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                          int out_w, float spatial_scale, void* d_out, int32_t* d_argmax, void* stream);
+int frcnn_ops_roi_pool_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                   float spatial_scale, const int32_t* d_argmax, const void* d_dout, void* d_dx, void* stream);
+int frcnn_ops_ms_roi_align_16(int elem_type, const void* const* d_x, const int* fh, const int* fw, const float* scales, int n_levels,
+                              int n_img, int c, const float* d_rois, int k, int out_h, int out_w, int sampling_ratio,
+                              float canonical_scale, float canonical_level, int k_min, int k_max, void* d_out, void* stream);
+int frcnn_ops_ms_roi_align_backward_16(int elem_type, const float* d_rois, int k, const int* fh, const int* fw, const float* scales,
+                                       int n_levels, int n_img, int c, int out_h, int out_w, int sampling_ratio, float canonical_scale,
+                                       float canonical_level, int k_min, int k_max, const void* d_dout, void* const* d_dx, void* d_ws,
+                                       size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -15,7 +15,13 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     composition (LevelMapper, then torch.where + ops.roi_align + index_put per level), forward and forward + backward, the two timed in
     alternating windows of the same call.
 
+  * half: float16 and bfloat16 maps on the FPN pooler shape above (ops.multi_scale_roi_align, 512 and 1000 RoIs per image) and on the
+    VGG-16 map (1 x 512 x 37 x 62, 300 RoIs: ops.roi_align sampling_ratio 2 and ops.roi_pool), forward and forward + backward: the
+    native 16-bit op, the float32 op on the same values, and the composition op(x.float()).to(T) -- the only way before the 16-bit
+    kernels --, the three timed in alternating windows of the same process.
+
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
+    python tools/ops_bench.py --only half            # just the 16-bit leg
 """
 import argparse
 import json
@@ -67,6 +73,25 @@ def timed_pair(fa, fb, reps, warmup):
     return float(np.median(ts[0])), float(np.median(ts[1]))
 
 
+def timed_group(fns, reps, warmup):
+    """timed_pair for any number of callables: windows in the order a, b, c, a, b, c, ...; medians of 5 each"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(5):
+        for fn, t in zip(fns, ts):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            t.append(a.elapsed_time(b) * 1000.0 / reps)
+    return [float(np.median(t)) for t in ts]
+
+
 def tv_multiscale(features, rois, scales, k_min, k_max):
     """torchvision's _multiscale_roi_align over ops.roi_align (7 x 7, sampling_ratio 2): LevelMapper, then per level torch.where (a host
     sync each), roi_align and index_put"""
@@ -109,6 +134,56 @@ def multiscale_leg(rng, reps, warmup):
     return res
 
 
+def half_rows(op, x16, g, reps, warmup):
+    """op(list of maps) -> pooled, on the 16-bit maps x16: microseconds of the native op, of the float32 op on the same values and of the
+    composition op(x.float()).to(T), forward and forward + backward (gradient g in the maps' dtype), with the ratios to the native op"""
+    dtype = x16[0].dtype
+    x32 = [x.float() for x in x16]
+    x16g = [x.clone().requires_grad_(True) for x in x16]
+    x32g = [x.clone().requires_grad_(True) for x in x32]
+    g32 = g.float()
+
+    def composed(xs):
+        return op([x.float() for x in xs]).to(dtype)
+    r = {}
+    for name, fns in (("fwd", (lambda: op(x16), lambda: op(x32), lambda: composed(x16))),
+                      ("fwd+bwd", (lambda: op(x16g).backward(g), lambda: op(x32g).backward(g32), lambda: composed(x16g).backward(g)))):
+        native, f32, comp = timed_group(fns, reps, warmup)
+        r[name] = {"native 16-bit": round(native, 1), "float32 op": round(f32, 1), "op(x.float()).to(T)": round(comp, 1),
+                   "float32 / native": round(f32 / native, 2), "composition / native": round(comp / native, 2)}
+    return r
+
+
+def half_leg(rng, reps, warmup):
+    res = {}
+    n, c = 2, 256
+    shapes = [(200, 304), (100, 152), (50, 76), (25, 38)]
+    scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
+    feats = [torch.randn((n, c, h, w), device=DEV).contiguous(memory_format=torch.channels_last) for h, w in shapes]
+    vgg = torch.relu(torch.randn((1, 512, 37, 62), device=DEV)).contiguous(memory_format=torch.channels_last)
+    fpn_rois = {}
+    for per_img in (512, 1000):
+        k = n * per_img
+        side = np.exp(rng.uniform(np.log(16), np.log(800), (k, 2)))
+        x1, y1 = rng.uniform(0, 1216 - 16, k), rng.uniform(0, 800 - 16, k)
+        rois = np.stack([np.repeat(np.arange(n), per_img), x1, y1, np.minimum(x1 + side[:, 0], 1216), np.minimum(y1 + side[:, 1], 800)], 1)
+        fpn_rois[per_img] = torch.from_numpy(rois.astype(np.float32)).to(DEV)
+    props = torch.from_numpy(proposals(rng, 300, 600, 1000)).to(DEV)
+    vgg_rois = torch.cat([torch.zeros((300, 1), device=DEV), props[:, [1, 0, 3, 2]]], 1)
+    for dtype in (torch.float16, torch.bfloat16):
+        name = str(dtype).split(".")[-1]
+        for per_img, rois in fpn_rois.items():
+            g = torch.randn((rois.shape[0], c, 7, 7), device=DEV).to(dtype)
+            res["%s multi_scale_roi_align fpn 2 x 256 x 200 x 304 .. 25 x 38, %d RoIs per image" % (name, per_img)] = half_rows(
+                lambda xs: ops.multi_scale_roi_align(xs, rois, 7, scales, 2), [f.to(dtype) for f in feats], g, reps, warmup)
+        g = torch.randn((300, 512, 7, 7), device=DEV).to(dtype)
+        res["%s roi_align vgg16 map 512 x 37 x 62, 300 RoIs" % name] = half_rows(
+            lambda xs: ops.roi_align(xs[0], vgg_rois, 7, 1 / 16, 2), [vgg.to(dtype)], g, reps, warmup)
+        res["%s roi_pool vgg16 map 512 x 37 x 62, 300 RoIs" % name] = half_rows(
+            lambda xs: ops.roi_pool(xs[0], vgg_rois, 7, 1 / 16), [vgg.to(dtype)], g, reps, warmup)
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -118,7 +193,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -127,6 +202,9 @@ def main():
     res = {}
     if a.only == "multiscale":
         print(json.dumps(multiscale_leg(rng, 10, 3), indent=1))
+        return
+    if a.only == "half":
+        print(json.dumps(half_leg(rng, 10, 3), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -188,6 +266,7 @@ def main():
             lambda: ops.nms(boxes, scores, 0.7), 20, 3)
     res["nms"] = r
     res.update(multiscale_leg(rng, 10, 3))
+    res.update(half_leg(rng, 10, 3))
     print(json.dumps(res, indent=1))
 
 
