@@ -31,6 +31,7 @@ SYMBOLS = (
     "frcnn_nms", "frcnn_roi_pool", "frcnn_roi_pool_x3t", "frcnn_detections", "frcnn_ctx_create", "frcnn_ctx_create_proposals", "frcnn_ctx_destroy",
     "frcnn_ctx_bytes", "frcnn_vgg16_forward", "frcnn_ctx_tensor", "frcnn_ctx_timing_enable",
     "frcnn_ctx_timing_read",
+    "frcnn_output_block_layout", "frcnn_stream_depend", "frcnn_ctx_submit_stats", "frcnn_predict_submit", "frcnn_streams_share_queue",
     "frcnn_fold_bn_pack", "frcnn_conv_workspace_bytes", "frcnn_conv_nhwc", "frcnn_conv_nhwc_math", "frcnn_conv_nhwc_x3g", "frcnn_conv_nhwc_x3g_tickets", "frcnn_pack_conv_x3g_weights", "frcnn_x3_saturation_events", "frcnn_tensor_absmax", "frcnn_conv7x7_s2_c3",
     "frcnn_maxpool3x3_s2_nhwc", "frcnn_spatial_mean_nhwc", "frcnn_resnet_forward", "frcnn_rpn_targets",
     "frcnn_preprocess_workspace_bytes", "frcnn_preprocess",
@@ -368,7 +369,21 @@ _SIGNATURES = {
     "frcnn_sgd_step_fold": (C.c_int, [_vp, _vp, _vp, _sz, _f, _f, _f, _i, _vp, _vp, _i, _i, _vp]),
     "frcnn_ctx_timing_enable": (C.c_int, [_vp, _i]),
     "frcnn_ctx_timing_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), _i]),
+    "frcnn_output_block_layout": (C.c_int, [_i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "frcnn_stream_depend": (C.c_int, [_vp, _vp, _vp]),
+    "frcnn_streams_share_queue": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "frcnn_ctx_submit_stats": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # (weights: frcnn_vgg16_weights* or frcnn_resnet_weights*, by `backbone`)
+    "frcnn_predict_submit": (C.c_int, [_vp, _i, _vp, C.POINTER(ForwardParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                       _i, _f, _f, _i, _vp, _vp, _vp]),
 }
+
+
+def output_block_layout(max_rois, num_classes):
+    """(offset of counts, offset of det_cnt, offset of det, total bytes) of a slot's packed output block (frcnn_output_block_layout)."""
+    off, total = (C.c_size_t * 3)(), C.c_size_t()
+    check(lib().frcnn_output_block_layout(int(max_rois), int(num_classes), off, C.byref(total)), "frcnn_output_block_layout")
+    return int(off[0]), int(off[1]), int(off[2]), int(total.value)
 
 
 def lib():

@@ -70,6 +70,11 @@ struct frcnn_ctx {
     std::vector<hipEvent_t> free_events;
     double t_ms[FRCNN_NUM_KCLASS] = {0};
     int64_t t_cnt[FRCNN_NUM_KCLASS] = {0};
+    // frcnn_stream_depend: the events recorded on a busy producer stream (a ring, created on first use) and the two counters
+    static constexpr int DEP_RING = 8;
+    hipEvent_t dep_ring[DEP_RING] = {nullptr};
+    unsigned dep_next = 0;
+    int64_t dep_taken = 0, dep_skipped = 0;
 };
 
 namespace {
@@ -1052,6 +1057,7 @@ void frcnn_ctx_destroy(frcnn_ctx* ctx)
     if (!ctx) return;
     for (auto& r : ctx->recs) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
     for (auto e : ctx->free_events) (void)hipEventDestroy(e);
+    for (auto e : ctx->dep_ring) if (e) (void)hipEventDestroy(e);
     if (ctx->slab) (void)hipFree(ctx->slab);
     if (ctx->wino_ws) (void)hipFree(ctx->wino_ws);
     if (ctx->wx_ws) (void)hipFree(ctx->wx_ws);
@@ -1906,6 +1912,111 @@ int frcnn_resnet_forward(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcn
     if (fh > c->max_fh || fw > c->max_fw || C > 1024 || C % 64) return FRCNN_EINVAL;
     FRCNN_HIP_TRY(hipMemcpyAsync(c->fm, c->res_buf[cur], (size_t)fh * fw * C * sizeof(float), hipMemcpyDeviceToDevice, s));
     return resnet_tail(c, w, p, H, W, fh, fw, C, d_anchor_map, d_valid_map, d_props, d_classes, d_deltas, d_counts, s);
+}
+
+// ---- one in-flight image submitted natively (round 7) ---------------------------------------------------------------------------
+int frcnn_output_block_layout(int max_rois, int ncls, size_t offsets[3], size_t* total_bytes)
+{
+    if (!offsets || !total_bytes || max_rois < 1 || ncls < 2 || ncls > FRCNN_MAX_NUM_CLASSES) return FRCNN_EINVAL;
+    const size_t nfg = (size_t)ncls - 1;
+    offsets[FRCNN_OUT_COUNTS] = 0;
+    offsets[FRCNN_OUT_DET_CNT] = align_up(4 * sizeof(int32_t), 16);
+    offsets[FRCNN_OUT_DET] = align_up(offsets[FRCNN_OUT_DET_CNT] + nfg * sizeof(int32_t), 16);
+    *total_bytes = align_up(offsets[FRCNN_OUT_DET] + nfg * (size_t)max_rois * 5 * sizeof(double), 16);
+    return FRCNN_OK;
+}
+
+// frcnn_streams_share_queue: ~200 us of waiting on the device's constant-rate clock, bounded by an iteration count
+__global__ void queue_probe_wait_kernel(long long ticks)
+{
+    const long long t0 = wall_clock64();
+    for (unsigned n = 0; n < (1u << 20) && wall_clock64() - t0 < ticks; ++n) { }
+}
+
+int frcnn_streams_share_queue(void* stream_a, void* stream_b, int* shared)
+{
+    if (!shared || stream_a == stream_b) return FRCNN_EINVAL;
+    hipStream_t a = as_stream(stream_a), b = as_stream(stream_b);
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ta = 0.f, tb = 0.f;
+    auto run = [&]() -> hipError_t {
+        hipError_t e;
+        for (auto& x : ev) if ((e = hipEventCreate(&x)) != hipSuccess) return e;
+        // a stream gets its hardware queue with its first command, which takes the host far longer than the wait kernel runs: give both
+        // streams one command and let it complete before anything is timed
+        if ((e = hipEventRecord(ev[1], a)) != hipSuccess || (e = hipEventRecord(ev[2], b)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(a)) != hipSuccess || (e = hipStreamSynchronize(b)) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev[0], a)) != hipSuccess) return e;
+        queue_probe_wait_kernel<<<1, 1, 0, a>>>(20000);                      // 200 us at the clock's 100 MHz
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev[1], a)) != hipSuccess || (e = hipEventRecord(ev[2], b)) != hipSuccess) return e;
+        if ((e = hipEventSynchronize(ev[1])) != hipSuccess || (e = hipEventSynchronize(ev[2])) != hipSuccess) return e;
+        if ((e = hipEventElapsedTime(&ta, ev[0], ev[1])) != hipSuccess) return e;
+        return hipEventElapsedTime(&tb, ev[0], ev[2]);
+    };
+    const hipError_t e = run();
+    for (auto x : ev) if (x) (void)hipEventDestroy(x);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_hip_error(e); return FRCNN_EHIP; }
+    // b's marker was enqueued behind a's kernel: on a queue of its own it completes at once, on a's queue after the kernel
+    *shared = tb > 0.5f * ta ? 1 : 0;
+    return FRCNN_OK;
+}
+
+int frcnn_stream_depend(frcnn_ctx* c, void* producer, void* stream)
+{
+    if (!c) return FRCNN_EINVAL;
+    if (producer == stream) return FRCNN_OK;
+    const hipError_t q = hipStreamQuery(as_stream(producer));
+    if (q == hipSuccess) { ++c->dep_skipped; return FRCNN_OK; }
+    (void)hipGetLastError();                                    // (hipErrorNotReady is sticky in hipGetLastError otherwise)
+    if (q != hipErrorNotReady) { set_hip_error(q); return FRCNN_EHIP; }
+    hipEvent_t& ev = c->dep_ring[c->dep_next++ % frcnn_ctx::DEP_RING];
+    if (!ev) FRCNN_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    FRCNN_HIP_TRY(hipEventRecord(ev, as_stream(producer)));
+    FRCNN_HIP_TRY(hipStreamWaitEvent(as_stream(stream), ev, 0));
+    ++c->dep_taken;
+    return FRCNN_OK;
+}
+
+int frcnn_ctx_submit_stats(const frcnn_ctx* c, int64_t* taken, int64_t* skipped)
+{
+    if (!c || !taken || !skipped) return FRCNN_EINVAL;
+    *taken = c->dep_taken; *skipped = c->dep_skipped;
+    return FRCNN_OK;
+}
+
+int frcnn_predict_submit(frcnn_ctx* c, int backbone, const void* weights, const frcnn_forward_params* p,
+                         const float* d_image, int H, int W, const float* d_anchor_map, const float* d_valid_map,
+                         float* d_props, float* d_classes, float* d_deltas, void* d_block, void* h_block, int max_rois,
+                         int with_detections, float score_threshold, float nms_threshold,
+                         int depend, void* producer, void* stream, void* done_event)
+{
+    if (!c || !weights || !p || !d_block || !h_block || (backbone != 0 && backbone != 1)) return FRCNN_EINVAL;
+    const int ncls = backbone == 0 ? static_cast<const frcnn_vgg16_weights*>(weights)->num_classes
+                                   : static_cast<const frcnn_resnet_weights*>(weights)->num_classes;
+    size_t off[3], total = 0;
+    int rc = frcnn_output_block_layout(max_rois, ncls, off, &total);
+    if (rc) return rc;
+    if (p->post_nms > max_rois || max_rois > 512) return FRCNN_EINVAL;       // (a block row per RoI; frcnn_detections: max_rois <= 512)
+    unsigned char* db = static_cast<unsigned char*>(d_block);
+    int32_t* d_counts = reinterpret_cast<int32_t*>(db + off[FRCNN_OUT_COUNTS]);
+    if (depend) { rc = frcnn_stream_depend(c, producer, stream); if (rc) return rc; }
+    rc = backbone == 0
+        ? frcnn_vgg16_forward(c, static_cast<const frcnn_vgg16_weights*>(weights), p, d_image, H, W, d_anchor_map, d_valid_map,
+                              d_props, d_classes, d_deltas, d_counts, stream)
+        : frcnn_resnet_forward(c, static_cast<const frcnn_resnet_weights*>(weights), p, d_image, H, W, d_anchor_map, d_valid_map,
+                               d_props, d_classes, d_deltas, d_counts, stream);
+    if (rc) return rc;
+    size_t copy_bytes = off[FRCNN_OUT_DET_CNT];                               // the counts alone
+    if (with_detections) {
+        rc = frcnn_detections(d_props, d_classes, d_deltas, d_counts + 2, max_rois, ncls, H, W, score_threshold, nms_threshold,
+                              reinterpret_cast<double*>(db + off[FRCNN_OUT_DET]), reinterpret_cast<int32_t*>(db + off[FRCNN_OUT_DET_CNT]), stream);
+        if (rc) return rc;
+        copy_bytes = total;
+    }
+    FRCNN_HIP_TRY(hipMemcpyAsync(h_block, d_block, copy_bytes, hipMemcpyDeviceToHost, as_stream(stream)));
+    if (done_event) FRCNN_HIP_TRY(hipEventRecord(reinterpret_cast<hipEvent_t>(done_event), as_stream(stream)));
+    return FRCNN_OK;
 }
 
 // ---- the same forward in two calls: the feature extractor over a BATCH of images, then RPN + detector per image -----------------

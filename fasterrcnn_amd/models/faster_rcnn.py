@@ -180,6 +180,11 @@ class FasterRCNNModel(nn.Module):
         # Off by default: measured on the MI355X box it changes nothing (one image at a time: 333.3 img/s with graphs, 334.2
         # eager) -- the kernels are 20-230 us long and the eager launch path already keeps their boundaries at ~2 us.
         self.use_hip_graphs = False
+        # One image = one native call (frcnn_predict_submit, round 7): the producer stream gets an event only when it still has work in
+        # flight (an event on an idle default stream that shares a hardware queue with a slot waits behind that slot's whole image), and
+        # counts / det_cnt / det come back in one copy.  False: the Python sequence wait_stream -> forward -> detections -> 3 copies -> record
+        # (the comparison of tests/test_submit_gpu.py and tools/exp_submit_ab.py); the same launches, the same bits.
+        self.native_submit = True
         # predict_batch: the per-RoI head (layer4 + mean + classifier / regressor) of the whole batch as ONE set of launches on the lane's stream
         # (frcnn_resnet_head, round 6) instead of one set per image on B streams
         self.batch_head = False       # measured round 6: the head's kernel time falls by a third (1558 -> 1042 us per image) and images/sec do not
@@ -759,11 +764,36 @@ class FasterRCNNModel(nn.Module):
         if self.use_hip_graphs and amap is None and not slot.ctx.timing:
             gkey = (h, w, None if score_threshold is None else float(score_threshold), float(self.detector_nms_threshold),
                     tuple(getattr(params, f) for f, _ in params._fields_), self._wstruct_key)
+        native = bool(self.native_submit)
+        backbone_id = 1 if self._is_resnet else 0
+
+        def submit(img, sp, depend, producer, done_event):
+            """The same, natively (frcnn_predict_submit): one call, one packed D2H copy, the producer dependency only when it is busy."""
+            nv.check(lib.frcnn_predict_submit(slot.ctx.handle, backbone_id, C.byref(weights), C.byref(params), nv.ptr(img), h, w,
+                                              nv.ptr(amap), nv.ptr(vmap), nv.ptr(slot.props), nv.ptr(slot.classes), nv.ptr(slot.deltas),
+                                              nv.ptr(slot.block), nv.ptr(slot.h_block), slot.max_rois, 1 if with_det else 0,
+                                              float(score_threshold) if with_det else 0.0, float(self.detector_nms_threshold),
+                                              1 if depend else 0, producer, sp, done_event), "frcnn_predict_submit")
+
         with t.cuda.device(device):
             stream = slot.use_stream()
+            producer = t.cuda.current_stream(device)
+            if native and gkey is None:
+                # eager: everything of the image in one native call
+                if wait_event is not None:
+                    stream.wait_event(wait_event)
+                submit(image, stream.cuda_stream, slot.stream is not None, producer.cuda_stream, slot.done.cuda_event)
+                slot.graph, slot.graph_input, slot.graph_key = None, None, None
+                slot.busy = True
+                slot.keepalive = (image, amap, vmap)
+                return Pending(self, slot, with_det)
             if slot.stream is not None:
                 # the image (and packed weights) were produced on the caller's stream
-                stream.wait_stream(t.cuda.current_stream(device))
+                if native:
+                    # (decided on the host, OUTSIDE any captured body: a stream query is not allowed on a capturing stream)
+                    nv.check(lib.frcnn_stream_depend(slot.ctx.handle, producer.cuda_stream, stream.cuda_stream), "frcnn_stream_depend")
+                else:
+                    stream.wait_stream(producer)
             if wait_event is not None:
                 # ... or on another stream whose work up to `wait_event` is what this image needs (HostFeeder: the frame's own copy +
                 # preprocess, not whatever was staged on that feeder stream after it)
@@ -781,13 +811,20 @@ class FasterRCNNModel(nn.Module):
                     graph = t.cuda.CUDAGraph()
                     slot.capture_stream.wait_stream(stream)
                     with t.cuda.graph(graph, stream=slot.capture_stream, capture_error_mode="thread_local"):
-                        body(slot.graph_input, t.cuda.current_stream(device).cuda_stream)
+                        if native:
+                            # only the launches and the single copy are recorded
+                            submit(slot.graph_input, t.cuda.current_stream(device).cuda_stream, False, None, None)
+                        else:
+                            body(slot.graph_input, t.cuda.current_stream(device).cuda_stream)
                     stream.wait_stream(slot.capture_stream)
                     slot.graph = graph
                     graph.replay()
                 else:
                     slot.graph, slot.graph_input, slot.graph_key = None, None, gkey
-                    body(image, stream.cuda_stream)
+                    if native:
+                        submit(image, stream.cuda_stream, False, None, None)
+                    else:
+                        body(image, stream.cuda_stream)
                 slot.done.record(stream)
         slot.busy = True
         slot.keepalive = (image, amap, vmap)

@@ -57,6 +57,12 @@ class Context:
         nv.check(nv.lib().frcnn_ctx_timing_read(self.handle, ms, cnt, 1 if reset else 0), "frcnn_ctx_timing_read")
         return {nv.KCLASS_NAMES[i]: (ms[i], cnt[i]) for i in range(nv.NUM_KCLASS)}
 
+    def submit_stats(self):
+        """(taken, skipped): submissions of this ctx that made the slot's stream wait for the producer stream / found the producer idle."""
+        taken, skipped = C.c_int64(), C.c_int64()
+        nv.check(nv.lib().frcnn_ctx_submit_stats(self.handle, C.byref(taken), C.byref(skipped)), "frcnn_ctx_submit_stats")
+        return int(taken.value), int(skipped.value)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None) is not None and self.handle.value:
@@ -106,9 +112,41 @@ def slot_stream(device, index):
     key = (str(t.device(device)), index)
     st = _slot_streams.get(key)
     if st is None:
-        st = t.cuda.Stream(device=t.device(device))
+        st = _new_slot_stream(t.device(device), [s for (d, _), s in _slot_streams.items() if d == key[0]])
         _slot_streams[key] = st
     return st
+
+
+_SLOT_STREAM_TRIES = 8
+_passed_over_streams = []
+
+
+def streams_share_queue(a, b):
+    """Do torch streams `a` and `b` run on one hardware queue (frcnn_streams_share_queue: measured, ~0.3 ms, synchronises both)?"""
+    shared = C.c_int(0)
+    with t.cuda.device(a.device):
+        nv.check(nv.lib().frcnn_streams_share_queue(a.cuda_stream, b.cuda_stream, C.byref(shared)), "frcnn_streams_share_queue")
+    return bool(shared.value)
+
+
+def _new_slot_stream(device, others):
+    """
+    A new stream that shares its hardware queue with none of `others` (the slot streams made so far), if the process has such a queue left.
+    With GPU_MAX_HW_QUEUES=4 the default stream and slots 1-3 take the four queues and the runtime puts the next stream on the least-used queue,
+    first of equals: the trace of round 7 (profiles/r07/README.md) found slot 4 behind slot 3 while the idle default stream had a queue to
+    itself, 877 against 981 images/sec with eight queues.  Where a stream landed is measured (streams_share_queue); a stream that shares is
+    passed over and KEPT, so that the runtime counts its queue as used and hands out the next one.  At most _SLOT_STREAM_TRIES candidates;
+    when every one shares (fewer queues than slots), the first is as good as any.
+    """
+    first = None
+    for _ in range(_SLOT_STREAM_TRIES):
+        st = t.cuda.Stream(device=device)
+        # (shared = in both directions: one reading alone may be another process's moment on the chip)
+        if not any(o.cuda_stream == st.cuda_stream or (streams_share_queue(o, st) and streams_share_queue(st, o)) for o in others):
+            return st
+        _passed_over_streams.append(st)
+        first = first or st
+    return first
 
 
 class Slot:
@@ -126,13 +164,17 @@ class Slot:
         self.props = t.zeros((max_rois, 4), dtype=t.float32, device=d)
         self.classes = t.zeros((max_rois, num_classes), dtype=t.float32, device=d)
         self.deltas = t.zeros((max_rois, nfg * 4), dtype=t.float32, device=d)
-        self.counts = t.zeros((4,), dtype=t.int32, device=d)
-        self.det = t.zeros((nfg, max_rois, 5), dtype=t.float64, device=d)
-        self.det_cnt = t.zeros((nfg,), dtype=t.int32, device=d)
-        self.h_det = t.zeros((nfg, max_rois, 5), dtype=t.float64).pin_memory()
-        self.h_det_cnt = t.zeros((nfg,), dtype=t.int32).pin_memory()
-        self.h_counts = t.zeros((4,), dtype=t.int32).pin_memory()
+        # counts, det_cnt and det are three regions of ONE device block with ONE pinned host mirror (frcnn_output_block_layout: every region
+        # 16-byte aligned), so that frcnn_predict_submit brings them back with one copy; the tensors below are views with the shapes and dtypes
+        # they have always had
+        o_counts, o_cnt, o_det, total = nv.output_block_layout(max_rois, num_classes)
+        self.block = t.zeros((total,), dtype=t.uint8, device=d)
+        self.h_block = t.zeros((total,), dtype=t.uint8).pin_memory()
+        self.counts, self.det_cnt, self.det = block_views(self.block, (o_counts, o_cnt, o_det), max_rois, num_classes)
+        self.h_counts, self.h_det_cnt, self.h_det = block_views(self.h_block, (o_counts, o_cnt, o_det), max_rois, num_classes)
         self.done = t.cuda.Event()
+        with t.cuda.device(d):
+            self.done.record(t.cuda.current_stream(d))   # (creates the hipEvent_t: frcnn_predict_submit records it by handle)
         self.roi_ready = t.cuda.Event()          # predict_batch: this image's pooled RoIs are in the lane's batch buffer
         self.graph, self.graph_key, self.graph_input, self.capture_stream = None, None, None, None    # hipGraph of the last call shape
         self.busy = False
@@ -140,6 +182,15 @@ class Slot:
 
     def use_stream(self):
         return self.stream if self.stream is not None else t.cuda.current_stream(self.device)
+
+
+def block_views(block, offsets, max_rois, num_classes):
+    """(counts int32 [4], det_cnt int32 [nfg], det float64 [nfg][max_rois][5]) as views of the uint8 output block `block`."""
+    nfg = int(num_classes) - 1
+    o_counts, o_cnt, o_det = offsets
+    return (block[o_counts:o_counts + 16].view(t.int32),
+            block[o_cnt:o_cnt + 4 * nfg].view(t.int32),
+            block[o_det:o_det + 40 * nfg * int(max_rois)].view(t.float64).view(nfg, int(max_rois), 5))
 
 
 class BackboneLane:

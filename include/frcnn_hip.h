@@ -56,7 +56,10 @@ extern "C" {
                                  19: frcnn_ops_* (torchvision.ops-style roi_align / roi_pool / nms over N images, no context: fasterrcnn_amd.ops);
                                  20: frcnn_ops_ms_roi_align(_backward / _workspace_bytes): torchvision.ops.MultiScaleRoIAlign (FPN pooling) in one launch
                                  per direction;
-                                 21: frcnn_ops_*_16: the RoI operators on float16 / bfloat16 maps (widen, float32 arithmetic, one rounding) */
+                                 21: frcnn_ops_*_16: the RoI operators on float16 / bfloat16 maps (widen, float32 arithmetic, one rounding);
+                                 still 21 (round 7, additions only: no existing prototype or struct changed, and tests/test_ops_half_cpu.py pins the number):
+                                 frcnn_predict_submit (one image enqueued natively: producer dependency only when the producer is busy, one packed
+                                 D2H copy), frcnn_stream_depend, frcnn_output_block_layout, frcnn_ctx_submit_stats, frcnn_streams_share_queue */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -682,6 +685,55 @@ int frcnn_resnet_forward(frcnn_ctx* ctx, const frcnn_resnet_weights* w, const fr
                          const float* d_anchor_map, const float* d_valid_map,
                          float* d_props, float* d_classes, float* d_deltas, int32_t* d_counts,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * One in-flight image, submitted natively (round 7; additions within ABI 21).
+ *
+ * The packed output block of a slot: the three results the host reads after an image, as regions of ONE device allocation with ONE
+ * pinned host mirror of the same layout, so that one hipMemcpyAsync brings them back:
+ *   [FRCNN_OUT_COUNTS]  int32 [4]                          d_counts of the forward                      offset 0
+ *   [FRCNN_OUT_DET_CNT] int32 [(ncls-1)]                   d_out_cnt of frcnn_detections
+ *   [FRCNN_OUT_DET]     float64 [(ncls-1)][max_rois][5]    d_out of frcnn_detections
+ * Every region starts on a 16-byte boundary (the float64 rows are therefore 8-byte aligned).  frcnn_output_block_layout writes the three
+ * byte offsets and the block's size; no GPU needed. */
+#define FRCNN_OUT_COUNTS  0
+#define FRCNN_OUT_DET_CNT 1
+#define FRCNN_OUT_DET     2
+int frcnn_output_block_layout(int max_rois, int ncls, size_t offsets[3], size_t* total_bytes);
+
+/* Do two streams of this process share a hardware queue?  A process has GPU_MAX_HW_QUEUES in-order hardware queues (HIP's default: 4), and
+ * the runtime hands a new stream the least-used one once they are all taken; the default stream holds one.  Two in-flight slots whose streams
+ * land on one queue run their images one behind the other.  The runtime does not say where a stream went, so this
+ * measures it: a ~200 us wait kernel on stream_a, then an event on stream_b; *shared = 1 when that event completed only behind the kernel.
+ * Synchronises both streams; a few hundred microseconds, meant for set-up (runtime.slot_stream), never for the per-image path. */
+int frcnn_streams_share_queue(void* stream_a, void* stream_b, int* shared);
+
+/* Makes `stream` wait for the work enqueued so far on `producer` -- only when there is some.  hipStreamQuery(producer) == hipSuccess:
+ * everything enqueued there has completed, what it produced is in memory, and NOTHING is recorded on the producer (counted as skipped).
+ * hipErrorNotReady: an event of the ctx's ring (created once, on first use) is recorded on the producer and `stream` waits for it, as
+ * torch's Stream.wait_stream does (counted as taken).  Any other code is returned as FRCNN_EHIP.  producer == stream: nothing to do, not counted.
+ * The decision is taken on the host at the time of the call; work enqueued on the producer afterwards is not covered (nor was it by
+ * wait_stream).  Why it matters: a process has GPU_MAX_HW_QUEUES in-order hardware queues; with as many slot streams as queues, the
+ * producer (usually the default stream) shares a queue with one slot's stream, and an event recorded on it sits behind the whole image
+ * that slot has already enqueued -- every submission then waits for another slot's image for nothing.
+ * Must not be called while either stream is capturing. */
+int frcnn_stream_depend(frcnn_ctx* ctx, void* producer, void* stream);
+
+/* dependencies taken / skipped by frcnn_stream_depend and frcnn_predict_submit on this ctx since it was created */
+int frcnn_ctx_submit_stats(const frcnn_ctx* ctx, int64_t* taken, int64_t* skipped);
+
+/* Everything of one image on the slot's stream, in one call: [frcnn_stream_depend(producer, stream) if depend != 0] ->
+ * frcnn_vgg16_forward (backbone 0, `weights` = frcnn_vgg16_weights*) or frcnn_resnet_forward (backbone 1, frcnn_resnet_weights*) ->
+ * [frcnn_detections if with_detections != 0] -> ONE device-to-host copy of the packed block -> [hipEventRecord(done_event, stream) if
+ * done_event].  The launches, their order and their arguments are those of the separate calls: d_counts, d_out_cnt and d_out are the
+ * regions of d_block (frcnn_output_block_layout(max_rois, weights->num_classes)), h_block is pinned host memory of the same size.
+ * Without detections only the counts region is copied.  Inside a stream capture: depend = 0 and done_event = NULL (a stream query is not
+ * allowed on a capturing stream); the caller takes the dependency with frcnn_stream_depend before it replays the graph. */
+int frcnn_predict_submit(frcnn_ctx* ctx, int backbone, const void* weights, const frcnn_forward_params* p,
+                         const float* d_image, int H, int W, const float* d_anchor_map, const float* d_valid_map,
+                         float* d_props, float* d_classes, float* d_deltas, void* d_block, void* h_block, int max_rois,
+                         int with_detections, float score_threshold, float nms_threshold,
+                         int depend, void* producer, void* stream, void* done_event);
 
 /* The same forward in two calls, for a true batch of images (BASELINE configs[2] "batch=8"; the reference asserts batch 1 at
  * models/faster_rcnn.py:108, SURVEY 8b allows lifting it):
