@@ -64,6 +64,8 @@ SYMBOLS = (
     "frcnn_ops_ms_roi_align", "frcnn_ops_ms_roi_align_workspace_bytes", "frcnn_ops_ms_roi_align_backward",
     "frcnn_ops_half_run", "frcnn_ops_roi_align_16", "frcnn_ops_roi_align_backward_16", "frcnn_ops_roi_pool_16",
     "frcnn_ops_roi_pool_backward_16", "frcnn_ops_ms_roi_align_16", "frcnn_ops_ms_roi_align_backward_16",
+    "frcnn_ops_ps_roi_pool", "frcnn_ops_ps_roi_pool_backward", "frcnn_ops_ps_roi_align", "frcnn_ops_ps_roi_align_backward",
+    "frcnn_ops_ps_roi_pool_16", "frcnn_ops_ps_roi_pool_backward_16", "frcnn_ops_ps_roi_align_16", "frcnn_ops_ps_roi_align_backward_16",
 )
 
 
@@ -257,6 +259,15 @@ _SIGNATURES = {
     "frcnn_ops_ms_roi_align_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp]),
     "frcnn_ops_ms_roi_align_backward_16": (C.c_int, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp,
                                                      _sz, _vp]),
+    # position-sensitive RoI pooling on NCHW maps (csrc/ops_ps.hip); the _16 forms take the element-type code first
+    "frcnn_ops_ps_roi_pool": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "frcnn_ops_ps_roi_pool_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "frcnn_ops_ps_roi_align": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "frcnn_ops_ps_roi_align_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "frcnn_ops_ps_roi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "frcnn_ops_ps_roi_pool_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "frcnn_ops_ps_roi_align_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "frcnn_ops_ps_roi_align_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

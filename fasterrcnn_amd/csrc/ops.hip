@@ -24,7 +24,7 @@
 // one contiguous segment.  ops_nms_mask_kernel writes 64 x 64 IoU bit tiles (only tiles on or above the diagonal whose rows and
 // columns can share a category), ops_nms_reduce_kernel runs the greedy pass of every segment in its own wave, in parallel, with the
 // segment's removed-bits in LDS.  float32 decides with iou_gt (csrc/geometry.h), float64 with the division in float64.
-#include "geometry.h"
+#include "ops_geom.h"
 #include <cfloat>
 
 namespace frcnn {
@@ -38,25 +38,6 @@ static constexpr int OPS_MAX_OUT = 64;       // out_h, out_w <= 64
 static constexpr int OPS_MAX_SAMPLING = 16;  // sampling_ratio <= 16
 static constexpr int OPS_NMS_MAX_WORDS = 8192;   // removed-bits of one segment in 64 KB of LDS: n <= 524288
 static constexpr int OPS_MS_MAX_LEVELS = 8;  // multi-scale RoIAlign: feature maps per call
-
-// torchvision's `int roi_batch_ind = rois[0]` with the range check the op contract adds (NaN fails it)
-__device__ __forceinline__ bool roi_image(float v, int n_img, int& b)
-{
-    if (!(v > -1.0f && v < (float)n_img)) return false;
-    b = (int)v;
-    return true;
-}
-
-__device__ __forceinline__ RoiGeom ops_align_geom(const float* roi, float scale, int out_h, int out_w, int sampling_ratio, int aligned)
-{
-    return roi_align_geom(f32x4{roi[2], roi[1], roi[4], roi[3]}, scale, out_h, out_w, sampling_ratio, aligned);
-}
-
-// sample coordinate of bin p, sample i (roi_align_kernel's expression)
-__device__ __forceinline__ float sample_coord(float start, float bin, int grid, int p, int i)
-{
-    return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)grid;
-}
 
 // ---- storage types --------------------------------------------------------------------------------------------------------------
 // 16-bit elements carry the width N of a lane's run in their type, so that one tensor can be walked in runs of 8 or of 4 channels
@@ -185,17 +166,6 @@ __device__ __forceinline__ void sample_range(int cell, float start, float bin, i
     // clamped in float first (the conversion of an out-of-range float is undefined), then exactly in integers
     s_lo = (int)fminf(fmaxf(floorf(a), 0.f), 2.0e9f);
     s_hi = (int)min((long long)fmaxf(fminf(ceilf(e), 2.0e9f), -1.0f), last);
-}
-
-// the weight of `cell` in a sample's bilinear footprint along one axis; false when the sample does not touch it
-__device__ __forceinline__ bool cell_weight(float v, int n, int cell, float& w)
-{
-    int lo, hi; float wl, wh;
-    if (!axis_weights(v, n, lo, hi, wl, wh)) return false;
-    bool hit = false;
-    if (lo == cell) { w = wl; hit = true; }
-    if (hi == cell) { w = hit ? w + wh : wh; hit = true; }
-    return hit;
 }
 
 // Ordered culling shared by the two backward kernels: appends to s_list, in ascending order, the RoIs r >= r_begin for which

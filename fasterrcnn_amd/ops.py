@@ -2,6 +2,7 @@
 torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as torch custom ops with autograd.
 
     from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign, multi_scale_roi_align, MultiScaleRoIAlign
+    from fasterrcnn_amd.ops import ps_roi_pool, ps_roi_align, PSRoIPool, PSRoIAlign
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -21,8 +22,19 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       torchvision's FPN pooler (ops/poolers.py): 1 to 8 maps of the same N, C and dtype; each RoI's level by LevelMapper in float32 as
       torch computes it on the GPU, then roi_align(aligned=False) on that level, bit-identical to the per-level torch.where loop (forward
       and backward) in one launch each way and without a host sync.  A RoI without a level (negative or NaN area) pools to zeros.
+  ps_roi_pool(input, boxes, output_size, spatial_scale=1.0)
+  ps_roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1)
+      R-FCN's position-sensitive pooling (csrc/ops_ps.hip; torchvision's ps_roi_pool_kernel.cu / ps_roi_align_kernel.cu restated,
+      unpinned): inputs and limits as roi_pool / roi_align, C a multiple of oh * ow (else ValueError).  The result is
+      [K, C / (oh * ow), oh, ow] in the input's dtype, contiguous NCHW (torchvision's layout: the usual consumer is a mean over (oh, ow));
+      output channel c of bin (ph, pw) pools input channel (c * oh + ph) * ow + pw.  ps_roi_pool: start = roundf(coord * scale),
+      end = roundf((coord + 1) * scale), window bounds clamped to [0, size - 1], the window's mean, 0 for an empty window.
+      ps_roi_align: always aligned (coord * scale - 0.5), count = grid_h * grid_w without a lower bound, so an adaptive grid on a RoI
+      of no height or width gives 0.0 / count (NaN when count is 0), as torchvision does; such a RoI receives no gradient.  A
+      contiguous NCHW input is read as it is (every output element owns one plane of it: there is no layout copy); a channels_last
+      input is made contiguous by one copy.  Backward: deterministic gathers, input gradients in the input's memory format.
 
-Mixed precision.  For T in {float16, bfloat16} the three RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
+Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
       op(x_T, boxes)  ==  op(x_T.float(), boxes).to(T)          backward:  dx_T  ==  op_backward(grad_T.float()).to(T)
 Values are widened exactly on load; geometry, weights and sums are the float32 kernels' (one shared body); the result is rounded once, to
@@ -44,7 +56,8 @@ from torch import Tensor
 
 from . import _native as nv
 
-__all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign"]
+__all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
+           "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -406,6 +419,108 @@ torch.library.register_autograd("frcnn::roi_pool_backward", _no_double_backward(
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::ps_roi_pool, frcnn::ps_roi_align (plain NCHW in and out) --------------------------------------------------------------
+def _ps_forward(name, input, rois, pooled_height, pooled_width, *args):
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = torch.empty((k, c // (pooled_height * pooled_width), pooled_height, pooled_width), dtype=input.dtype, device=input.device)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = input.contiguous()
+        r = rois.contiguous()
+        _call(name, input, x.data_ptr(), n, h, w, c, r.data_ptr(), k, pooled_height, pooled_width, *args, out.data_ptr(), _stream(input))
+    return out
+
+
+def _ps_backward(name, grad, rois, pooled_height, pooled_width, batch_size, channels, height, width, channels_last, *args):
+    k = rois.shape[0]
+    if channels == 0 or batch_size * height * width == 0:
+        return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
+    with torch.cuda.device(grad.device):
+        g = grad.contiguous()
+        r = rois.contiguous()
+        dx = torch.empty((batch_size, channels, height, width), dtype=grad.dtype, device=grad.device)
+        _call(name, grad, r.data_ptr() if k else None, k, batch_size, height, width, channels, pooled_height, pooled_width, *args,
+              g.data_ptr() if k else None, dx.data_ptr(), _stream(grad))
+        return _grad_layout(dx, channels, channels_last)
+
+
+def _ps_fake(input, rois, pooled_height, pooled_width):
+    return input.new_empty((rois.shape[0], input.shape[1] // (pooled_height * pooled_width), pooled_height, pooled_width))
+
+
+@torch.library.custom_op("frcnn::ps_roi_pool", mutates_args=())
+def _ps_roi_pool(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int) -> Tensor:
+    return _ps_forward("ps_roi_pool", input, rois, pooled_height, pooled_width, spatial_scale)
+
+
+@_ps_roi_pool.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width):
+    return _ps_fake(input, rois, pooled_height, pooled_width)
+
+
+@torch.library.custom_op("frcnn::ps_roi_pool_backward", mutates_args=())
+def _ps_roi_pool_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, batch_size: int,
+                          channels: int, height: int, width: int, channels_last: bool) -> Tensor:
+    return _ps_backward("ps_roi_pool_backward", grad, rois, pooled_height, pooled_width, batch_size, channels, height, width, channels_last,
+                        spatial_scale)
+
+
+@_ps_roi_pool_backward.register_fake
+def _(grad, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height, width, channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+@torch.library.custom_op("frcnn::ps_roi_align", mutates_args=())
+def _ps_roi_align(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int) -> Tensor:
+    return _ps_forward("ps_roi_align", input, rois, pooled_height, pooled_width, spatial_scale, sampling_ratio)
+
+
+@_ps_roi_align.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio):
+    return _ps_fake(input, rois, pooled_height, pooled_width)
+
+
+@torch.library.custom_op("frcnn::ps_roi_align_backward", mutates_args=())
+def _ps_roi_align_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
+                           batch_size: int, channels: int, height: int, width: int, channels_last: bool) -> Tensor:
+    return _ps_backward("ps_roi_align_backward", grad, rois, pooled_height, pooled_width, batch_size, channels, height, width,
+                        channels_last, spatial_scale, sampling_ratio)
+
+
+@_ps_roi_align_backward.register_fake
+def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, batch_size, channels, height, width, channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+def _ps_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.args = tuple(inputs[2:])
+    ctx.shape = tuple(inputs[0].shape)
+    ctx.channels_last = _input_is_channels_last(inputs[0])
+
+
+def _ps_roi_pool_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    return (_ps_roi_pool_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 4
+
+
+def _ps_roi_align_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    return (_ps_roi_align_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 5
+
+
+torch.library.register_autograd("frcnn::ps_roi_pool", _ps_roi_pool_bwd, setup_context=_ps_setup)
+torch.library.register_autograd("frcnn::ps_roi_pool_backward", _no_double_backward("frcnn::ps_roi_pool"),
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("frcnn::ps_roi_align", _ps_roi_align_bwd, setup_context=_ps_setup)
+torch.library.register_autograd("frcnn::ps_roi_align_backward", _no_double_backward("frcnn::ps_roi_align"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
 def _score_order(scores):
     """The oracle's argsort(-scores, "stable"): descending score, ties in input order, NaN scores last in input order."""
@@ -506,6 +621,30 @@ def roi_pool(input, boxes, output_size, spatial_scale=1.0):
     rois = _roi_input(input, boxes)
     oh, ow = _output_size(output_size)
     return _roi_pool(input, rois, float(spatial_scale), oh, ow)[0]
+
+
+def _ps_output_size(input, output_size):
+    oh, ow = _output_size(output_size)
+    if input.shape[1] % (oh * ow) != 0:
+        raise ValueError("input channels must be a multiple of pooling height * pooling width, got %d channels for (%d, %d)"
+                         % (input.shape[1], oh, ow))
+    return oh, ow
+
+
+def ps_roi_pool(input, boxes, output_size, spatial_scale=1.0):
+    """torchvision.ops.ps_roi_pool: [K, C / (oh * ow), oh, ow], contiguous."""
+    rois = _roi_input(input, boxes)
+    oh, ow = _ps_output_size(input, output_size)
+    return _ps_roi_pool(input, rois, float(spatial_scale), oh, ow)
+
+
+def ps_roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1):
+    """torchvision.ops.ps_roi_align: [K, C / (oh * ow), oh, ow], contiguous."""
+    rois = _roi_input(input, boxes)
+    oh, ow = _ps_output_size(input, output_size)
+    if int(sampling_ratio) > MAX_SAMPLING_RATIO:
+        raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
+    return _ps_roi_align(input, rois, float(spatial_scale), oh, ow, int(sampling_ratio))
 
 
 def _ms_features(features):
@@ -628,3 +767,34 @@ class RoIPool(torch.nn.Module):
 
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s" % (self.output_size, self.spatial_scale)
+
+
+class PSRoIPool(torch.nn.Module):
+    """torchvision.ops.PSRoIPool."""
+
+    def __init__(self, output_size, spatial_scale):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+
+    def forward(self, input, rois):
+        return ps_roi_pool(input, rois, self.output_size, self.spatial_scale)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s" % (self.output_size, self.spatial_scale)
+
+
+class PSRoIAlign(torch.nn.Module):
+    """torchvision.ops.PSRoIAlign."""
+
+    def __init__(self, output_size, spatial_scale, sampling_ratio):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+        self.sampling_ratio = sampling_ratio
+
+    def forward(self, input, rois):
+        return ps_roi_align(input, rois, self.output_size, self.spatial_scale, self.sampling_ratio)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s, sampling_ratio=%s" % (self.output_size, self.spatial_scale, self.sampling_ratio)

@@ -59,7 +59,9 @@ extern "C" {
                                  21: frcnn_ops_*_16: the RoI operators on float16 / bfloat16 maps (widen, float32 arithmetic, one rounding);
                                  still 21 (round 7, additions only: no existing prototype or struct changed, and tests/test_ops_half_cpu.py pins the number):
                                  frcnn_predict_submit (one image enqueued natively: producer dependency only when the producer is busy, one packed
-                                 D2H copy), frcnn_stream_depend, frcnn_output_block_layout, frcnn_ctx_submit_stats, frcnn_streams_share_queue */
+                                 D2H copy), frcnn_stream_depend, frcnn_output_block_layout, frcnn_ctx_submit_stats, frcnn_streams_share_queue;
+                                 still 21 (additions only, the number stays pinned): frcnn_ops_ps_roi_pool / frcnn_ops_ps_roi_align, their _backward and
+                                 _16 forms (torchvision.ops.ps_roi_pool / ps_roi_align, R-FCN's position-sensitive pooling, on NCHW maps) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -511,6 +513,42 @@ int frcnn_ops_ms_roi_align_backward_16(int elem_type, const float* d_rois, int k
                                        int n_levels, int n_img, int c, int out_h, int out_w, int sampling_ratio, float canonical_scale,
                                        float canonical_level, int k_min, int k_max, const void* d_dout, void* const* d_dx, void* d_ws,
                                        size_t ws_bytes, void* stream);
+
+/* Position-sensitive RoI pooling (R-FCN; csrc/ops_ps.hip): torchvision.ops.ps_roi_pool and ps_roi_align, restated from the published
+ *   algorithm of torchvision/csrc/ops/cuda/ps_roi_pool_kernel.cu and ps_roi_align_kernel.cu (third party, absent here: restated,
+ *   unpinned, like nms / roi_align).  Unlike the operators above these read and write plain NCHW, with no layout copy:
+ *     d_x    : [n_img][c][fh][fw], c % (out_h * out_w) == 0, c >= out_h * out_w
+ *     d_out  : [k][c / (out_h * out_w)][out_h][out_w]; output channel co of bin (ph, pw) pools input plane (co * out_h + ph) * out_w + pw
+ *     d_rois, out_h, out_w, k, sampling_ratio: as above (a batch index outside (-1, n_img) pools to zeros and receives no gradient)
+ *   All arithmetic is float32.
+ * frcnn_ops_ps_roi_pool: start = roundf(coord * scale), end = roundf((coord + 1) * scale), integer size max(end - start, 1); bin p covers
+ *   [floor(p * bin), ceil((p + 1) * bin)) + start with every bound clamped to [0, size - 1] (torchvision's clamp for this operator); the
+ *   output is the (h, w) scan-order sum of the window divided by its area, 0 for an empty window.
+ * frcnn_ops_ps_roi_align: always aligned (coord * scale - 0.5), size = end - start unclamped, grid = sampling_ratio > 0 ? sampling_ratio
+ *   : ceil(size / out), count = grid_h * grid_w with no lower bound: samples and bilinear_interpolate are frcnn_ops_roi_align's (one
+ *   shared body), out = sum / count -- so an adaptive grid on a RoI of no height or width gives 0.0f / count (NaN for count == 0).
+ * The backwards overwrite every element of d_dx [n_img][c][fh][fw] (no zero fill).  Deterministic gathers, no atomics: one thread per
+ *   element of d_dx visits, in ascending order, the RoIs of its image whose bin (ph, pw) of its plane reaches it (each block first
+ *   lists those bins' windows in LDS), so the result is bit-identical from run to run.  ps_roi_pool sends dout / area to every cell of
+ *   a non-empty window; ps_roi_align sends dout * (the cell's summed sample weight) / count.
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above (widened exactly on
+ *   load, float32 sums in registers, one rounding to nearest even on store); any c that the float32 forms take. */
+int frcnn_ops_ps_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                          float spatial_scale, float* d_out, void* stream);
+int frcnn_ops_ps_roi_pool_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                   const float* d_dout, float* d_dx, void* stream);
+int frcnn_ops_ps_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                           float spatial_scale, int sampling_ratio, float* d_out, void* stream);
+int frcnn_ops_ps_roi_align_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w, float spatial_scale,
+                                    int sampling_ratio, const float* d_dout, float* d_dx, void* stream);
+int frcnn_ops_ps_roi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                             int out_w, float spatial_scale, void* d_out, void* stream);
+int frcnn_ops_ps_roi_pool_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                      float spatial_scale, const void* d_dout, void* d_dx, void* stream);
+int frcnn_ops_ps_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                              int out_w, float spatial_scale, int sampling_ratio, void* d_out, void* stream);
+int frcnn_ops_ps_roi_align_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                       float spatial_scale, int sampling_ratio, const void* d_dout, void* d_dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

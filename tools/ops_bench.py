@@ -20,7 +20,13 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     native 16-bit op, the float32 op on the same values, and the composition op(x.float()).to(T) -- the only way before the 16-bit
     kernels --, the three timed in alternating windows of the same process.
 
+  * ps: R-FCN's position-sensitive pooling at its VOC shape (1 x 1029 x 38 x 63 = 7 * 7 * 21 score maps, 300 RoIs, 7 x 7, scale 1 / 16,
+    sampling_ratio 2), float32 and bfloat16: ops.ps_roi_align beside the only composition there was before it -- ops.roi_align(aligned =
+    True) of all 1029 channels, then the diagonal gather [k, (c * 7 + ph) * 7 + pw, ph, pw] --, forward and forward + backward, in
+    alternating windows; and ops.ps_roi_pool alone.
+
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
+    python tools/ops_bench.py --only ps              # just the position-sensitive leg
     python tools/ops_bench.py --only half            # just the 16-bit leg
 """
 import argparse
@@ -184,6 +190,35 @@ def half_leg(rng, reps, warmup):
     return res
 
 
+def ps_leg(rng, reps, warmup):
+    oh = ow = 7
+    classes, k, h, w, scale, sr = 21, 300, 38, 63, 1 / 16, 2
+    c = oh * ow * classes
+    props = torch.from_numpy(proposals(rng, k, 600, 1000)).to(DEV)
+    rois = torch.cat([torch.zeros((k, 1), device=DEV), props[:, [1, 0, 3, 2]]], 1)
+    ph, pw = torch.meshgrid(torch.arange(oh, device=DEV), torch.arange(ow, device=DEV), indexing="ij")
+    ci = (torch.arange(classes, device=DEV)[:, None, None] * oh + ph[None]) * ow + pw[None]
+
+    def composed(x):
+        return ops.roi_align(x, rois, (oh, ow), scale, sr, aligned=True)[:, ci, ph[None], pw[None]]
+    res = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((1, c, h, w), device=DEV).to(dtype)
+        xg = x.clone().requires_grad_(True)
+        g = torch.randn((k, classes, oh, ow), device=DEV).to(dtype)
+        y, yc = ops.ps_roi_align(x, rois, (oh, ow), scale, sr), composed(x)
+        r = {"max |ps_roi_align - composition|": float((y.float() - yc.float()).abs().max())}
+        for name, fns in (("fwd", (lambda: ops.ps_roi_align(x, rois, (oh, ow), scale, sr), lambda: composed(x))),
+                          ("fwd+bwd", (lambda: ops.ps_roi_align(xg, rois, (oh, ow), scale, sr).backward(g), lambda: composed(xg).backward(g)))):
+            native, comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.ps_roi_align": round(native, 1), "roi_align(aligned) + diagonal gather": round(comp, 1),
+                       "composition / ps_roi_align": round(comp / native, 2)}
+        r["ops.ps_roi_pool fwd"] = round(timed(lambda: ops.ps_roi_pool(x, rois, (oh, ow), scale), reps, warmup), 1)
+        r["ops.ps_roi_pool fwd+bwd"] = round(timed(lambda: ops.ps_roi_pool(xg, rois, (oh, ow), scale).backward(g), reps, warmup), 1)
+        res["%s r-fcn voc 1 x %d x %d x %d, %d RoIs, 7 x 7, sr 2" % (str(dtype).split(".")[-1], c, h, w, k)] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -193,7 +228,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -205,6 +240,9 @@ def main():
         return
     if a.only == "half":
         print(json.dumps(half_leg(rng, 10, 3), indent=1))
+        return
+    if a.only == "ps":
+        print(json.dumps(ps_leg(rng, 10, 3), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -267,6 +305,7 @@ def main():
     res["nms"] = r
     res.update(multiscale_leg(rng, 10, 3))
     res.update(half_leg(rng, 10, 3))
+    res.update(ps_leg(rng, 10, 3))
     print(json.dumps(res, indent=1))
 
 
