@@ -66,6 +66,8 @@ SYMBOLS = (
     "frcnn_ops_roi_pool_backward_16", "frcnn_ops_ms_roi_align_16", "frcnn_ops_ms_roi_align_backward_16",
     "frcnn_ops_ps_roi_pool", "frcnn_ops_ps_roi_pool_backward", "frcnn_ops_ps_roi_align", "frcnn_ops_ps_roi_align_backward",
     "frcnn_ops_ps_roi_pool_16", "frcnn_ops_ps_roi_pool_backward_16", "frcnn_ops_ps_roi_align_16", "frcnn_ops_ps_roi_align_backward_16",
+    "frcnn_ops_deform_workspace_bytes", "frcnn_ops_deform_forward", "frcnn_ops_deform_backward_columns", "frcnn_ops_deform_backward_offset",
+    "frcnn_ops_deform_input_plan", "frcnn_ops_deform_backward_input", "frcnn_ops_deform_backward_weight",
 )
 
 
@@ -112,6 +114,12 @@ class ResNetWeights(C.Structure):
                 ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("num_classes", C.c_int32)]
 
 
+class DeformGeom(C.Structure):
+    """frcnn_deform_geom: the geometry of one deformable convolution (frcnn_ops_deform_*)."""
+    _fields_ = [(name, C.c_int32) for name in ("c_in", "height", "width", "c_out", "kernel_h", "kernel_w", "stride_h", "stride_w", "pad_h",
+                                               "pad_w", "dilation_h", "dilation_w", "groups", "offset_groups")]
+
+
 class ForwardParams(C.Structure):
     _fields_ = [("pre_nms", C.c_int32), ("post_nms", C.c_int32), ("rpn_nms_threshold", C.c_float),
                 ("min_side", C.c_float), ("allow_edge_proposals", C.c_int32), ("math_mode", C.c_int32),
@@ -127,6 +135,8 @@ MAX_POST_NMS_DETECT = 512   # DET_MAX of csrc/detect.hip (per-class NMS bit matr
 MAX_POST_NMS_CTX = 512      # frcnn_ctx_create's max_rois bound (forward() without detections is limited by the ctx only)
 MAX_PRE_NMS = 16384         # frcnn_ctx pre_cap (csrc/api.hip): one-block radix select + sort
 
+# FRCNN_DEFORM_WS_*: the stage whose workspace frcnn_ops_deform_workspace_bytes sizes (DEFORM_WS_COLUMNS: the column matrix itself)
+DEFORM_WS_FORWARD, DEFORM_WS_BACKWARD_COLUMNS, DEFORM_WS_BACKWARD_INPUT, DEFORM_WS_BACKWARD_WEIGHT, DEFORM_WS_COLUMNS = range(5)
 OPS_F16, OPS_BF16 = 1, 2     # FRCNN_OPS_F16 / FRCNN_OPS_BF16: element type of the frcnn_ops_*_16 entry points
 MATH_F32 = 0      # exact f32 MFMA
 MATH_F32_WINOGRAD = 2   # exact f32 MFMA; 3x3 layers with uses_winograd(cin, cout) as Winograd F(2x2,3x3) in float32
@@ -268,6 +278,14 @@ _SIGNATURES = {
     "frcnn_ops_ps_roi_pool_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "frcnn_ops_ps_roi_align_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
     "frcnn_ops_ps_roi_align_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    # deformable convolution (csrc/ops_deform.hip): the geometry, the images of the chunk, then pointers
+    "frcnn_ops_deform_workspace_bytes": (C.c_size_t, [C.POINTER(DeformGeom), _i, _i]),
+    "frcnn_ops_deform_forward": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_columns": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_offset": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_deform_input_plan": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_deform_backward_input": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_weight": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

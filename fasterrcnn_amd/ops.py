@@ -3,6 +3,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
 
     from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign, multi_scale_roi_align, MultiScaleRoIAlign
     from fasterrcnn_amd.ops import ps_roi_pool, ps_roi_align, PSRoIPool, PSRoIAlign
+    from fasterrcnn_amd.ops import deform_conv2d, DeformConv2d
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -33,6 +34,31 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       of no height or width gives 0.0 / count (NaN when count is 0), as torchvision does; such a RoI receives no gradient.  A
       contiguous NCHW input is read as it is (every output element owns one plane of it: there is no layout copy); a channels_last
       input is made contiguous by one copy.  Backward: deterministic gathers, input gradients in the input's memory format.
+  deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None)
+  DeformConv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True).forward(input, offset, mask=None)
+      Deformable convolution v1, and v2 when a mask is given (csrc/ops_deform.hip; torchvision's ops/deform_conv.py and
+      deform_conv2d_kernel.cu restated, unpinned).  input [N, C_in, H, W]; weight [C_out, C_in / groups, kh, kw], groups =
+      C_in // weight.shape[1]; offset [N, 2 G kh kw, oh, ow], G = offset.shape[1] // (2 kh kw) offset groups; mask [N, G kh kw, oh, ow]
+      or None (a mask of ones); bias [C_out] or None; stride, padding, dilation an int or a pair;
+      oh = (H + 2 pad_h - (dil_h (kh - 1) + 1)) // stride_h + 1, likewise ow.  Channel 2 (g kh kw + i kw + j) of offset is the y
+      displacement of tap (i, j) of offset group g, the next channel its x displacement; channel g kh kw + i kw + j of mask is the
+      tap's modulation; input channel c belongs to offset group c // (C_in / G) and to weight group c // (C_in / groups).  Tap (i, j)
+      at output (oy, ox) samples y = oy stride_h - pad_h + i dil_h + off_y, x = ox stride_w - pad_w + j dil_w + off_x: 0 when
+      y <= -1 or y >= H or x <= -1 or x >= W (a NaN coordinate too), else the bilinear value on floor / floor + 1 with the weights
+      hh hw, hh lw, lh hw, lh lw, a corner outside [0, H - 1] x [0, W - 1] counting 0.  The column value is mask * sample and
+      out[n, co, oy, ox] = bias[co] + the sum over (c in co's weight group, i, j) of weight[co, c', i, j] * column.
+      Gradients for input, offset, mask, weight and bias are torchvision's: the offset gradient uses get_coordinate_weight (the
+      difference of the validly indexed corner values weighted by the other axis's fractions: the right-hand slope at an integer
+      coordinate, without an early-out, so at exactly y == -1 the corner row 0 still counts while the forward sample is 0); d_mask is
+      the sum over c of dcol * sample; d_bias is grad.sum((0, 2, 3)).  The backward is deterministic and free of atomics -- the input
+      gradient sums, per cell, the sorted plan of the samples that reach it -- so two runs agree bit for bit, which torchvision's own
+      GPU backward does not promise; it skips the work of every argument that needs no gradient.  Double backward raises.
+      All tensors are float32 (torchvision's autocast rule casts this operator to float32; a 16-bit or float64 tensor is a TypeError:
+      pass .float()), on the GPU or on `meta`.  Contiguous NCHW is the native layout, a channels_last argument is made contiguous by
+      one copy, gradients come back in each argument's own memory format, the result is contiguous NCHW.  The products run on the
+      exact-float32 MFMA kernel of csrc/gemm_tn.hip over chunks of DEFORM_CHUNK_IMAGES images (the bound of the column workspace);
+      the forward, d_input, d_offset and d_mask do not depend on the chunking, d_weight sums the chunks in ascending order.  N == 0
+      or C_out == 0 return empty tensors (zero gradients).  The 32-bit indices of the kernels bound the sizes (MAX_DEFORM_INDEX).
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -49,7 +75,8 @@ NCHW inputs are converted once, a channel count that is not a multiple of 4 (of 
 a zero-padded copy; input gradients come back in the input's dtype and memory format.
 """
 import ctypes as C
-from typing import List
+import math
+from typing import List, Optional
 
 import torch
 from torch import Tensor
@@ -57,13 +84,15 @@ from torch import Tensor
 from . import _native as nv
 
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
-           "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign"]
+           "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
 MAX_LEVELS = 8
+DEFORM_CHUNK_IMAGES = 32                  # images per chunk of deform_conv2d's column workspace (torchvision processes 32 at a time too)
+MAX_DEFORM_INDEX = 2 ** 31 - 1 - 1024     # what the 32-bit indices of csrc/ops_deform.hip hold: columns, cells and plan entries of a chunk
 
 
 # ---- argument checks (the public functions; the custom ops assume them) -----------------------------------------------------------
@@ -521,6 +550,149 @@ torch.library.register_autograd("frcnn::ps_roi_align_backward", _no_double_backw
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::deform_conv2d (plain NCHW; csrc/ops_deform.hip) ------------------------------------------------------------------------
+def _deform_output_size(h, w, kh, kw, stride, padding, dilation):
+    oh = (h + 2 * padding[0] - (dilation[0] * (kh - 1) + 1)) // stride[0] + 1
+    ow = (w + 2 * padding[1] - (dilation[1] * (kw - 1) + 1)) // stride[1] + 1
+    return oh, ow
+
+
+def _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w):
+    c, h, w = input.shape[1:]
+    co, cg, kh, kw = weight.shape
+    return nv.DeformGeom(c, h, w, co, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, c // cg,
+                         offset.shape[1] // (2 * kh * kw))
+
+
+def _deform_bytes(geom, images, stage, like):
+    """A buffer of frcnn_ops_deform_workspace_bytes(stage) for a chunk of `images` (the allocator's alignment covers the kernels')."""
+    size = nv.lib().frcnn_ops_deform_workspace_bytes(C.byref(geom), images, stage)
+    if size == 0:
+        raise nv.FrcnnError(-1, "frcnn_ops_deform_workspace_bytes")
+    return torch.empty((size,), dtype=torch.uint8, device=like.device)
+
+
+def _opt_ptr(t, i0=0):
+    return None if t is None else t[i0:].data_ptr()
+
+
+def _opt_contiguous(t):
+    return None if t is None else t.contiguous()
+
+
+@torch.library.custom_op("frcnn::deform_conv2d", mutates_args=())
+def _deform_conv2d(input: Tensor, offset: Tensor, weight: Tensor, bias: Optional[Tensor], mask: Optional[Tensor], stride_h: int,
+                   stride_w: int, pad_h: int, pad_w: int, dilation_h: int, dilation_w: int, chunk: int) -> Tensor:
+    n = input.shape[0]
+    co = weight.shape[0]
+    out = torch.empty((n, co) + tuple(offset.shape[2:]), dtype=input.dtype, device=input.device)
+    if n == 0 or co == 0:
+        return out
+    with torch.cuda.device(input.device):
+        geom = _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
+        x, off, wgt, b, m = input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(bias), _opt_contiguous(mask)
+        nb = min(n, chunk)
+        ws = _deform_bytes(geom, nb, nv.DEFORM_WS_FORWARD, input)
+        lib = nv.lib()
+        for i0 in range(0, n, nb):
+            nv.check(lib.frcnn_ops_deform_forward(C.byref(geom), min(nb, n - i0), x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0),
+                                                  wgt.data_ptr(), _opt_ptr(b), out[i0:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  _stream(input)), "frcnn_ops_deform_forward")
+    return out
+
+
+@_deform_conv2d.register_fake
+def _(input, offset, weight, bias, mask, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, chunk):
+    return input.new_empty((input.shape[0], weight.shape[0]) + tuple(offset.shape[2:]))
+
+
+def _deform_grad_shapes(grad, input, offset, weight, mask, needs, channels_last):
+    """(shape or None, channels_last) of d_input, d_offset, d_weight, d_bias, d_mask; None: not asked for (an empty placeholder)."""
+    shapes = [tuple(input.shape), tuple(offset.shape), tuple(weight.shape), (weight.shape[0],), None if mask is None else tuple(mask.shape)]
+    formats = [channels_last[0], channels_last[1], channels_last[2], False, channels_last[3]]
+    return [(s if need else None, cl) for s, need, cl in zip(shapes, needs, formats)]
+
+
+@torch.library.custom_op("frcnn::deform_conv2d_backward", mutates_args=())
+def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight: Tensor, mask: Optional[Tensor], stride_h: int,
+                            stride_w: int, pad_h: int, pad_w: int, dilation_h: int, dilation_w: int, chunk: int, needs: List[bool],
+                            channels_last: List[bool]) -> List[Tensor]:
+    """[d_input, d_offset, d_weight, d_bias, d_mask]; needs: which of them are wanted (the others come back as empty placeholders and
+    cost nothing); channels_last: the memory format of input, offset, weight and mask, which their gradients take."""
+    plan = _deform_grad_shapes(grad, input, offset, weight, mask, needs, channels_last)
+    n = input.shape[0]
+    co, _, kh, kw = weight.shape
+    if n == 0 or co == 0:
+        return [grad.new_empty((0,)) if s is None else _grad_layout(grad.new_zeros(s), s[1], cl) if len(s) == 4 else grad.new_zeros(s)
+                for s, cl in plan]
+    want_input, want_offset, want_weight, want_bias, want_mask = [s is not None for s, _ in plan]
+    with torch.cuda.device(grad.device):
+        geom = _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
+        g, x, off, wgt, m = grad.contiguous(), input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(mask)
+        new = lambda want, like: torch.empty(like.shape, dtype=like.dtype, device=like.device) if want else None   # noqa: E731
+        dx, doff, dw, dm = new(want_input, x), new(want_offset, off), new(want_weight, wgt), new(want_mask, m)
+        nb = min(n, chunk)
+        lib, stream, ref = nv.lib(), _stream(grad), C.byref(geom)
+        want_columns = want_input or want_offset or want_mask
+        if want_columns:
+            dcol = _deform_bytes(geom, nb, nv.DEFORM_WS_COLUMNS, grad)
+            ws_col = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_COLUMNS, grad)
+        if want_input:
+            ws_in = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_INPUT, grad)
+        if want_weight:
+            ws_w = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_WEIGHT, grad)
+        samples = geom.offset_groups * kh * kw * offset.shape[2] * offset.shape[3]          # per image
+        for i0 in range(0, n, nb):
+            k = min(nb, n - i0)
+            if want_columns:
+                nv.check(lib.frcnn_ops_deform_backward_columns(ref, k, wgt.data_ptr(), g[i0:].data_ptr(), dcol.data_ptr(), ws_col.data_ptr(),
+                                                               ws_col.numel(), stream), "frcnn_ops_deform_backward_columns")
+            if want_offset or want_mask:
+                nv.check(lib.frcnn_ops_deform_backward_offset(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), dcol.data_ptr(),
+                                                              _opt_ptr(doff, i0), _opt_ptr(dm, i0), stream), "frcnn_ops_deform_backward_offset")
+            if want_input:
+                keys = torch.empty((k * samples * 4,), dtype=torch.int64, device=grad.device)
+                wts = torch.empty((k * samples * 4,), dtype=torch.float32, device=grad.device)
+                nv.check(lib.frcnn_ops_deform_input_plan(ref, k, off[i0:].data_ptr(), _opt_ptr(m, i0), keys.data_ptr(), wts.data_ptr(), stream),
+                         "frcnn_ops_deform_input_plan")
+                sorted_keys, order = torch.sort(keys, stable=True)
+                nv.check(lib.frcnn_ops_deform_backward_input(ref, k, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), dcol.data_ptr(),
+                                                             dx[i0:].data_ptr(), ws_in.data_ptr(), ws_in.numel(), stream),
+                         "frcnn_ops_deform_backward_input")
+            if want_weight:
+                nv.check(lib.frcnn_ops_deform_backward_weight(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), g[i0:].data_ptr(),
+                                                              dw.data_ptr(), int(i0 > 0), ws_w.data_ptr(), ws_w.numel(), stream),
+                         "frcnn_ops_deform_backward_weight")
+        db = g.sum((0, 2, 3)) if want_bias else None
+        return [grad.new_empty((0,)) if t is None else _grad_layout(t, t.shape[1], cl) if t.dim() == 4 else t
+                for t, (_, cl) in zip((dx, doff, dw, db, dm), plan)]
+
+
+@_deform_conv2d_backward.register_fake
+def _(grad, input, offset, weight, mask, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, chunk, needs, channels_last):
+    return [grad.new_empty((0,)) if s is None else _grad_empty(s, grad, cl) if len(s) == 4 else grad.new_empty(s)
+            for s, cl in _deform_grad_shapes(grad, input, offset, weight, mask, needs, channels_last)]
+
+
+def _deform_setup(ctx, inputs, output):
+    input, offset, weight, bias, mask = inputs[:5]
+    ctx.save_for_backward(input, offset, weight, mask)
+    ctx.args = tuple(inputs[5:])
+    ctx.channels_last = [_input_is_channels_last(t) if t is not None else False for t in (input, offset, weight, mask)]
+
+
+def _deform_bwd(ctx, grad):
+    input, offset, weight, mask = ctx.saved_tensors
+    needs = [bool(v) for v in ctx.needs_input_grad[:5]]                     # input, offset, weight, bias, mask
+    grads = _deform_conv2d_backward(grad, input, offset, weight, mask, *ctx.args, needs, ctx.channels_last)
+    return tuple(g if need else None for g, need in zip(grads, needs)) + (None,) * 7
+
+
+torch.library.register_autograd("frcnn::deform_conv2d", _deform_bwd, setup_context=_deform_setup)
+torch.library.register_autograd("frcnn::deform_conv2d_backward", _no_double_backward("frcnn::deform_conv2d"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
 def _score_order(scores):
     """The oracle's argsort(-scores, "stable"): descending score, ties in input order, NaN scores last in input order."""
@@ -645,6 +817,73 @@ def ps_roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1
     if int(sampling_ratio) > MAX_SAMPLING_RATIO:
         raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
     return _ps_roi_align(input, rois, float(spatial_scale), oh, ow, int(sampling_ratio))
+
+
+_F32_ONLY = "float32 (deform_conv2d computes in float32 only, as under torchvision's autocast rule: pass .float())"
+
+
+def _int_pair(name, v, low):
+    if isinstance(v, int) and not isinstance(v, bool):
+        v = (v, v)
+    if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) and not isinstance(e, bool) for e in v)):
+        raise TypeError("%s must be an int or a pair of ints, got %r" % (name, v))
+    if v[0] < low or v[1] < low:
+        raise ValueError("%s must be >= %d, got %r" % (name, low, tuple(v)))
+    return int(v[0]), int(v[1])
+
+
+def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
+    """torchvision.ops.deform_conv2d: deformable convolution v1, v2 with a mask; [N, C_out, oh, ow], contiguous."""
+    tensors = [("input", input), ("offset", offset), ("weight", weight)] + [(k, t) for k, t in (("bias", bias), ("mask", mask)) if t is not None]
+    for name, t in tensors:
+        _check_tensor(name, t, (torch.float32,), _F32_ONLY)
+    for name, t in tensors[1:]:
+        _check_same_device(input, t, "input", name)
+    if input.dim() != 4:
+        raise ValueError("input must be [N, C_in, H, W], got shape %s" % (tuple(input.shape),))
+    if weight.dim() != 4:
+        raise ValueError("weight must be [C_out, C_in / groups, kh, kw], got shape %s" % (tuple(weight.shape),))
+    if offset.dim() != 4:
+        raise ValueError("offset must be [N, 2 * offset_groups * kh * kw, oh, ow], got shape %s" % (tuple(offset.shape),))
+    if mask is not None and mask.dim() != 4:
+        raise ValueError("mask must be [N, offset_groups * kh * kw, oh, ow], got shape %s" % (tuple(mask.shape),))
+    stride, padding, dilation = _int_pair("stride", stride, 1), _int_pair("padding", padding, 0), _int_pair("dilation", dilation, 1)
+    n, c, h, w = input.shape
+    co, cg, kh, kw = weight.shape
+    if cg < 1 or kh < 1 or kw < 1 or h < 1 or w < 1:
+        raise ValueError("weight must have at least one input channel and one tap and input at least one cell, got weight %s, input %s"
+                         % (tuple(weight.shape), tuple(input.shape)))
+    if c % cg != 0:
+        raise ValueError("input channels must be a multiple of weight.shape[1] (C_in / groups), got %d and %d" % (c, cg))
+    groups = c // cg
+    if co % groups != 0:
+        raise ValueError("output channels must be a multiple of groups, got %d for %d groups" % (co, groups))
+    if offset.shape[1] == 0 or offset.shape[1] % (2 * kh * kw) != 0:
+        raise ValueError("offset.shape[1] must be a positive multiple of 2 * kh * kw = %d, got %d" % (2 * kh * kw, offset.shape[1]))
+    og = offset.shape[1] // (2 * kh * kw)
+    if c % og != 0:
+        raise ValueError("input channels must be a multiple of the offset groups, got %d for %d offset groups" % (c, og))
+    oh, ow = _deform_output_size(h, w, kh, kw, stride, padding, dilation)
+    if oh < 1 or ow < 1:
+        raise ValueError("the output would be empty: (%d, %d) for input %s, kernel (%d, %d), stride %s, padding %s, dilation %s"
+                         % (oh, ow, tuple(input.shape), kh, kw, stride, padding, dilation))
+    if tuple(offset.shape) != (n, 2 * og * kh * kw, oh, ow):
+        raise ValueError("offset must be [N, 2 * offset_groups * kh * kw, oh, ow] = [%d, %d, %d, %d], got shape %s"
+                         % (n, 2 * og * kh * kw, oh, ow, tuple(offset.shape)))
+    if mask is not None and tuple(mask.shape) != (n, og * kh * kw, oh, ow):
+        raise ValueError("mask must be [N, offset_groups * kh * kw, oh, ow] = [%d, %d, %d, %d], got shape %s"
+                         % (n, og * kh * kw, oh, ow, tuple(mask.shape)))
+    if bias is not None and tuple(bias.shape) != (co,):
+        raise ValueError("bias must be [C_out] = [%d], got shape %s" % (co, tuple(bias.shape)))
+    nb = max(1, min(n, DEFORM_CHUNK_IMAGES))
+    pp = (oh * ow + 3) // 4 * 4
+    largest = max(nb * pp, c * kh * kw, nb * og * h * w, nb * og * kh * kw * oh * ow * 4, h + padding[0] + dilation[0] * (kh - 1) + 1,
+                  w + padding[1] + dilation[1] * (kw - 1) + 1)
+    if largest > MAX_DEFORM_INDEX:
+        raise ValueError("deform_conv2d is too large for the kernels' 32-bit indices: %d > MAX_DEFORM_INDEX = %d (columns, cells or "
+                         "sample corners of %d images)" % (largest, MAX_DEFORM_INDEX, nb))
+    return _deform_conv2d(input, offset, weight, bias, mask, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+                          DEFORM_CHUNK_IMAGES)
 
 
 def _ms_features(features):
@@ -798,3 +1037,47 @@ class PSRoIAlign(torch.nn.Module):
 
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s, sampling_ratio=%s" % (self.output_size, self.spatial_scale, self.sampling_ratio)
+
+
+class DeformConv2d(torch.nn.Module):
+    """torchvision.ops.DeformConv2d: parameters weight [out, in / groups, kh, kw] and bias [out] (or None), initialised as nn.Conv2d's."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        super().__init__()
+        if in_channels % groups != 0:
+            raise ValueError("in_channels must be divisible by groups")
+        if out_channels % groups != 0:
+            raise ValueError("out_channels must be divisible by groups")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.kernel_size = _int_pair("kernel_size", kernel_size, 1)
+        self.stride = _int_pair("stride", stride, 1)
+        self.padding = _int_pair("padding", padding, 0)
+        self.dilation = _int_pair("dilation", dilation, 1)
+        self.groups = groups
+        self.weight = torch.nn.Parameter(torch.empty(out_channels, in_channels // groups, self.kernel_size[0], self.kernel_size[1]))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in = self.weight.shape[1] * self.weight.shape[2] * self.weight.shape[3]
+            bound = 1 / math.sqrt(fan_in)
+            torch.nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, input, offset, mask=None):
+        return deform_conv2d(input, offset, self.weight, self.bias, stride=self.stride, padding=self.padding, dilation=self.dilation,
+                             mask=mask)
+
+    def __repr__(self):
+        s = "%s(%s, %s, kernel_size=%s, stride=%s" % (self.__class__.__name__, self.in_channels, self.out_channels, self.kernel_size,
+                                                        self.stride)
+        s += ", padding=%s" % (self.padding,) if self.padding != (0, 0) else ""
+        s += ", dilation=%s" % (self.dilation,) if self.dilation != (1, 1) else ""
+        s += ", groups=%s" % self.groups if self.groups != 1 else ""
+        s += ", bias=False" if self.bias is None else ""
+        return s + ")"

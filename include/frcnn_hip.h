@@ -61,7 +61,9 @@ extern "C" {
                                  frcnn_predict_submit (one image enqueued natively: producer dependency only when the producer is busy, one packed
                                  D2H copy), frcnn_stream_depend, frcnn_output_block_layout, frcnn_ctx_submit_stats, frcnn_streams_share_queue;
                                  still 21 (additions only, the number stays pinned): frcnn_ops_ps_roi_pool / frcnn_ops_ps_roi_align, their _backward and
-                                 _16 forms (torchvision.ops.ps_roi_pool / ps_roi_align, R-FCN's position-sensitive pooling, on NCHW maps) */
+                                 _16 forms (torchvision.ops.ps_roi_pool / ps_roi_align, R-FCN's position-sensitive pooling, on NCHW maps);
+                                 still 21 (additions only): frcnn_ops_deform_* and frcnn_deform_geom (torchvision.ops.deform_conv2d, deformable
+                                 convolution v1 / v2, forward and backward on frcnn_gemm_tn's kernel) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -549,6 +551,59 @@ int frcnn_ops_ps_roi_align_16(int elem_type, const void* d_x, int n_img, int fh,
                               int out_w, float spatial_scale, int sampling_ratio, void* d_out, void* stream);
 int frcnn_ops_ps_roi_align_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
                                        float spatial_scale, int sampling_ratio, const void* d_dout, void* d_dx, void* stream);
+
+/* Deformable convolution v1 / v2 (csrc/ops_deform.hip): torchvision.ops.deform_conv2d in both directions, restated from the published
+ *   algorithm of torchvision/csrc/ops/cuda/deform_conv2d_kernel.cu (third party, absent here: restated, unpinned).  Float32, plain NCHW;
+ *   every entry point works on one chunk of n_img images (the caller walks the chunks and owns every buffer):
+ *     d_x      : [n_img][c_in][height][width]
+ *     d_weight : [c_out][c_in / groups][kernel_h][kernel_w]
+ *     d_offset : [n_img][2 * offset_groups * kh * kw][oh][ow]: channel 2 * (g * kh * kw + i * kw + j) is the y displacement of tap
+ *                (i, j) of offset group g, the next channel its x displacement
+ *     d_mask   : [n_img][offset_groups * kh * kw][oh][ow] or NULL (v1: a mask of ones)
+ *     d_out    : [n_img][c_out][oh][ow], oh = (height + 2 pad_h - (dilation_h (kh - 1) + 1)) / stride_h + 1, likewise ow
+ *   A sample at y = oy stride_h - pad_h + i dilation_h + off_y (likewise x) is 0 when y <= -1, y >= height, x <= -1 or x >= width (or
+ *   NaN), else the bilinear value on floor / floor + 1 with the weights hh hw, hh lw, lh hw, lh lw, a corner outside the map counting 0;
+ *   the column value is mask * sample and out = bias + sum over the weight group's (c, i, j) of weight * column.
+ *   With P = oh * ow and Pp = P rounded up to a multiple of 4, the column matrix is [c_in * kh * kw][n_img * Pp] floats
+ *   (frcnn_ops_deform_workspace_bytes(.., FRCNN_DEFORM_WS_COLUMNS)); the products run on the exact-float32 kernel of frcnn_gemm_tn.
+ *   Every function validates its arguments before touching the GPU (FRCNN_EINVAL: a NULL geometry, sizes < 1, channels not divisible
+ *   by groups / offset_groups, an empty output, an index beyond 32 bits, a NULL or misaligned pointer, a workspace that is too small);
+ *   workspaces and d_dcol are 16-byte aligned.  Nothing allocates.
+ * frcnn_ops_deform_forward: d_bias [c_out] or NULL.  The product is not split, so an output element does not depend on the chunking.
+ * frcnn_ops_deform_backward_columns: d_dcol = W^T dout in the column layout (d_dout: [n_img][c_out][oh][ow]).
+ * frcnn_ops_deform_backward_offset: d_doffset and / or d_dmask (either may be NULL, not both) by a gather over the channels of the
+ *   offset group: (mask * coordinate_weight) * dcol for y and x -- torchvision's get_coordinate_weight: the difference of the validly
+ *   indexed corner values, weighted by the other axis's fractions, without an early-out -- and dcol * sample for the mask.
+ * frcnn_ops_deform_input_plan + frcnn_ops_deform_backward_input: the input gradient without atomics.  The plan writes one entry per
+ *   sample and corner, e = (((b G + g) kh kw + tap) P + p) * 4 + corner (n_img * G * kh * kw * P * 4 entries): d_keys[e] = the cell
+ *   ((b G + g) height + y) width + x, or n_img * G * height * width for a corner outside the map or a rejected sample, and
+ *   d_weights[e] = corner weight * mask.  The caller sorts the keys stably; d_sorted_keys and d_order (the sort's permutation) come
+ *   back, and every element of d_dx [n_img][c_in][height][width] is written as the sum, in ascending e, of
+ *   d_weights[e] * dcol over the entries of its cell: bit-identical from run to run.
+ * frcnn_ops_deform_backward_weight: d_dweight (= or, with accumulate != 0, +=) dout col^T per group, the columns sampled again;
+ *   deterministic split reduction inside the chunk. */
+typedef struct frcnn_deform_geom {
+    int32_t c_in, height, width, c_out, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, groups,
+            offset_groups;
+} frcnn_deform_geom;
+#define FRCNN_DEFORM_WS_FORWARD          0
+#define FRCNN_DEFORM_WS_BACKWARD_COLUMNS 1
+#define FRCNN_DEFORM_WS_BACKWARD_INPUT   2
+#define FRCNN_DEFORM_WS_BACKWARD_WEIGHT  3
+#define FRCNN_DEFORM_WS_COLUMNS          4   /* not a workspace: the bytes of the column matrix d_dcol itself */
+size_t frcnn_ops_deform_workspace_bytes(const frcnn_deform_geom* g, int n_img, int stage);   /* 0 for a bad geometry or stage */
+int frcnn_ops_deform_forward(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
+                             const float* d_weight, const float* d_bias, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_deform_backward_columns(const frcnn_deform_geom* g, int n_img, const float* d_weight, const float* d_dout, float* d_dcol,
+                                      void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_deform_backward_offset(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
+                                     const float* d_dcol, float* d_doffset, float* d_dmask, void* stream);
+int frcnn_ops_deform_input_plan(const frcnn_deform_geom* g, int n_img, const float* d_offset, const float* d_mask, int64_t* d_keys,
+                                float* d_weights, void* stream);
+int frcnn_ops_deform_backward_input(const frcnn_deform_geom* g, int n_img, const int64_t* d_sorted_keys, const int64_t* d_order,
+                                    const float* d_weights, const float* d_dcol, float* d_dx, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_deform_backward_weight(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
+                                     const float* d_dout, float* d_dweight, int accumulate, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

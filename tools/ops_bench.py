@@ -25,7 +25,13 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     True) of all 1029 channels, then the diagonal gather [k, (c * 7 + ph) * 7 + pw, ph, pw] --, forward and forward + backward, in
     alternating windows; and ops.ps_roi_pool alone.
 
+  * deform: deformable convolution at a DCN stage (2 x 256 -> 256, 3 x 3, padding 1, 50 x 68 maps), 1 and 4 offset groups, with and
+    without a mask, offsets N(0, 2 px): ops.deform_conv2d beside the same operator composed from torch operations on the GPU (the
+    restatement of tests/deform_conv_cases.py: floor, index gathers and einsum), forward and forward + backward of all five gradients,
+    in alternating windows.
+
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
+    python tools/ops_bench.py --only deform          # just the deformable-convolution leg
     python tools/ops_bench.py --only ps              # just the position-sensitive leg
     python tools/ops_bench.py --only half            # just the 16-bit leg
 """
@@ -219,6 +225,37 @@ def ps_leg(rng, reps, warmup):
     return res
 
 
+def deform_leg(rng, reps, warmup):
+    from tests import deform_conv_cases as D
+    n, c, co, h, w = 2, 256, 256, 50, 68
+    gen = torch.Generator().manual_seed(0)
+    x = torch.randn((n, c, h, w), generator=gen).to(DEV)
+    weight = (torch.randn((co, c, 3, 3), generator=gen) / 48).to(DEV)
+    bias = torch.randn((co,), generator=gen).to(DEV)
+    g = torch.randn((n, co, h, w), generator=gen).to(DEV)
+    res = {}
+    for groups in (1, 4):
+        offset = (torch.randn((n, 2 * groups * 9, h, w), generator=gen) * 2).to(DEV)
+        for with_mask in (False, True):
+            mask = torch.rand((n, groups * 9, h, w), generator=gen).to(DEV) if with_mask else None
+            leaves = [t.clone().requires_grad_(True) if t is not None else None for t in (x, offset, weight, bias, mask)]
+
+            def native(a=(x, offset, weight, bias, mask)):
+                return ops.deform_conv2d(a[0], a[1], a[2], a[3], padding=1, mask=a[4])
+
+            def composed(a=(x, offset, weight, bias, mask)):
+                return D.deform_conv2d_ref(a[0], a[1], a[2], a[3], padding=(1, 1), mask=a[4])
+            y, yc = native(), composed()
+            r = {"max |deform_conv2d - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+            for name, fns in (("fwd", (native, composed)),
+                              ("fwd+bwd", (lambda: native(leaves).backward(g), lambda: composed(leaves).backward(g)))):
+                t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+                r[name] = {"ops.deform_conv2d": round(t_native, 1), "torch composition": round(t_comp, 1),
+                           "composition / deform_conv2d": round(t_comp / t_native, 2)}
+            res["deform 2 x 256 -> 256, 3 x 3, pad 1, 50 x 68, G %d, %s" % (groups, "mask" if with_mask else "no mask")] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -228,7 +265,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -243,6 +280,9 @@ def main():
         return
     if a.only == "ps":
         print(json.dumps(ps_leg(rng, 10, 3), indent=1))
+        return
+    if a.only == "deform":
+        print(json.dumps(deform_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -306,6 +346,7 @@ def main():
     res.update(multiscale_leg(rng, 10, 3))
     res.update(half_leg(rng, 10, 3))
     res.update(ps_leg(rng, 10, 3))
+    res.update(deform_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
