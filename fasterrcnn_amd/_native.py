@@ -68,6 +68,8 @@ SYMBOLS = (
     "frcnn_ops_ps_roi_pool_16", "frcnn_ops_ps_roi_pool_backward_16", "frcnn_ops_ps_roi_align_16", "frcnn_ops_ps_roi_align_backward_16",
     "frcnn_ops_deform_workspace_bytes", "frcnn_ops_deform_forward", "frcnn_ops_deform_backward_columns", "frcnn_ops_deform_backward_offset",
     "frcnn_ops_deform_input_plan", "frcnn_ops_deform_backward_input", "frcnn_ops_deform_backward_weight",
+    "frcnn_ops_deform_roi_pool_cull_list", "frcnn_ops_deform_roi_pool_workspace_bytes", "frcnn_ops_deform_roi_pool",
+    "frcnn_ops_deform_roi_pool_backward", "frcnn_ops_deform_roi_pool_16", "frcnn_ops_deform_roi_pool_backward_16",
 )
 
 
@@ -286,6 +288,14 @@ _SIGNATURES = {
     "frcnn_ops_deform_input_plan": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp]),
     "frcnn_ops_deform_backward_input": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_ops_deform_backward_weight": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    # deformable RoI pooling on NHWC maps (csrc/ops_droi.hip); the _16 forms take the element-type code first
+    "frcnn_ops_deform_roi_pool_cull_list": (C.c_int, []),
+    "frcnn_ops_deform_roi_pool_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "frcnn_ops_deform_roi_pool": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp]),
+    "frcnn_ops_deform_roi_pool_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_roi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp]),
+    "frcnn_ops_deform_roi_pool_backward_16": (C.c_int, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _sz,
+                                                        _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

@@ -4,6 +4,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import nms, batched_nms, roi_pool, roi_align, RoIPool, RoIAlign, multi_scale_roi_align, MultiScaleRoIAlign
     from fasterrcnn_amd.ops import ps_roi_pool, ps_roi_align, PSRoIPool, PSRoIAlign
     from fasterrcnn_amd.ops import deform_conv2d, DeformConv2d
+    from fasterrcnn_amd.ops import deform_roi_pool, DeformRoIPool, DeformRoIPoolPack, ModulatedDeformRoIPoolPack
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -59,6 +60,21 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       exact-float32 MFMA kernel of csrc/gemm_tn.hip over chunks of DEFORM_CHUNK_IMAGES images (the bound of the column workspace);
       the forward, d_input, d_offset and d_mask do not depend on the chunking, d_weight sums the chunks in ascending order.  N == 0
       or C_out == 0 return empty tensors (zero gradients).  The 32-bit indices of the kernels bound the sizes (MAX_DEFORM_INDEX).
+  deform_roi_pool(input, rois, offset, output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1)
+  DeformRoIPool(output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1).forward(input, rois, offset=None)
+  DeformRoIPoolPack / ModulatedDeformRoIPoolPack(output_size, output_channels, deform_fc_channels=1024, spatial_scale=1.0,
+                                                 sampling_ratio=0, gamma=0.1).forward(input, rois)
+      Deformable RoI pooling of DCN v1 / v2 (csrc/ops_droi.hip; mmcv's deform_roi_pool restated, unpinned: where the two differ
+      include/frcnn_hip.h holds).  Inputs, limits, dtypes and layouts as roi_align; offset [K, 2, oh, ow] in float32 or the map's
+      dtype, channel 0 the x (width) offset, channel 1 the y offset; None or an empty tensor: no offset.  Bin (ph, pw) of RoI k is
+      roi_align(aligned=True)'s bin with its window shifted by gamma * roi_w * offset[k, 0, ph, pw] along x and gamma * roi_h *
+      offset[k, 1, ph, pw] along y; a sample outside [-1, size] or at a NaN / infinite coordinate contributes nothing.  With no offset
+      or an all-zero one the result is roi_align(input, rois, output_size, spatial_scale, sampling_ratio, aligned=True) bit for bit
+      (sampling_ratio 0 is adaptive, as roi_align's -1).  Gradients for input and offset (the published offset formula: the sample
+      coordinate before the bilinear clamp); both are deterministic and free of atomics, each is skipped when its argument needs none;
+      RoIs get no gradient; double backward raises.  16-bit maps under the contract below for the output and d_input; the kernels read
+      the offset and write its gradient in float32, and the gradient is rounded once to the offset's dtype.  The Pack modules own
+      mmcv's offset_fc (and mask_fc) stacks with zero-initialised last layers, so mmcv / mmdetection checkpoints load strict.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -84,10 +100,12 @@ from torch import Tensor
 from . import _native as nv
 
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
-           "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d"]
+           "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
+           "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
+DEFORM_ROI_CULL_LIST = 256                # RoIs that deform_roi_pool's input-gradient gather lists per pass (DROI_LIST of csrc/ops_droi.hip)
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
 MAX_LEVELS = 8
@@ -693,6 +711,105 @@ torch.library.register_autograd("frcnn::deform_conv2d_backward", _no_double_back
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::deform_roi_pool (NHWC as roi_align; csrc/ops_droi.hip) -----------------------------------------------------------------
+def _droi_offset(offset):
+    """The offset as the kernels read it: float32, contiguous [K, 2, oh, ow]; None stays None."""
+    return None if offset is None else offset.float().contiguous()
+
+
+@torch.library.custom_op("frcnn::deform_roi_pool", mutates_args=())
+def _deform_roi_pool(input: Tensor, rois: Tensor, offset: Optional[Tensor], spatial_scale: float, pooled_height: int, pooled_width: int,
+                     sampling_ratio: int, gamma: float) -> Tensor:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        off = _droi_offset(offset)
+        cp = x.shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
+        _call("deform_roi_pool", input, x.data_ptr(), n, h, w, cp, r.data_ptr(), _opt_ptr(off), k, pooled_height, pooled_width,
+              spatial_scale, sampling_ratio, gamma, dst.data_ptr(), _stream(input))
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_deform_roi_pool.register_fake
+def _(input, rois, offset, spatial_scale, pooled_height, pooled_width, sampling_ratio, gamma):
+    return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
+
+
+def _droi_grad_format(t, channels_last):
+    return t.contiguous(memory_format=_CL if channels_last else torch.contiguous_format)
+
+
+@torch.library.custom_op("frcnn::deform_roi_pool_backward", mutates_args=())
+def _deform_roi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, offset: Optional[Tensor], spatial_scale: float,
+                              pooled_height: int, pooled_width: int, sampling_ratio: int, gamma: float, needs: List[bool],
+                              channels_last: List[bool]) -> List[Tensor]:
+    """[d_input, d_offset]; needs: which of them are wanted (the other comes back as an empty placeholder and costs nothing);
+    channels_last: the memory format of input and offset, which their gradients take.  d_offset is in the offset's dtype."""
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    want_input, want_offset = needs[0], needs[1] and offset is not None
+    none = lambda: grad.new_empty((0,))                                    # noqa: E731
+    if k == 0 or c == 0 or n * h * w == 0:
+        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last[0]) if want_input else none(),
+                _droi_grad_format(torch.zeros_like(offset), channels_last[1]) if want_offset else none()]
+    if not (want_input or want_offset):
+        return [none(), none()]
+    with torch.cuda.device(grad.device):
+        cp = _padded_channels(c, grad.dtype)
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        off = _droi_offset(offset)
+        x = _nhwc(input) if want_offset else None
+        dx = _empty_cl((n, cp, h, w), grad) if want_input else None
+        doff = torch.empty_like(off) if want_offset else None
+        ws = None
+        if want_input:
+            size = nv.lib().frcnn_ops_deform_roi_pool_workspace_bytes(k, pooled_height, pooled_width)
+            if size == 0:
+                raise nv.FrcnnError(-1, "frcnn_ops_deform_roi_pool_workspace_bytes")
+            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        _call("deform_roi_pool_backward", grad, _opt_ptr(x), r.data_ptr(), _opt_ptr(off), k, n, h, w, cp, pooled_height, pooled_width,
+              spatial_scale, sampling_ratio, gamma, g.data_ptr(), _opt_ptr(dx), _opt_ptr(doff), _opt_ptr(ws), 0 if ws is None else ws.numel(),
+              _stream(grad))
+        return [_grad_layout(dx, c, channels_last[0]) if want_input else none(),
+                _droi_grad_format(doff.to(offset.dtype), channels_last[1]) if want_offset else none()]
+
+
+@_deform_roi_pool_backward.register_fake
+def _(grad, input, rois, offset, spatial_scale, pooled_height, pooled_width, sampling_ratio, gamma, needs, channels_last):
+    return [_grad_empty(tuple(input.shape), grad, channels_last[0]) if needs[0] else grad.new_empty((0,)),
+            _droi_grad_format(torch.empty_like(offset), channels_last[1]) if needs[1] and offset is not None else grad.new_empty((0,))]
+
+
+def _deform_roi_pool_setup(ctx, inputs, output):
+    input, rois, offset = inputs[:3]
+    ctx.save_for_backward(input, rois, offset)
+    ctx.args = tuple(inputs[3:])
+    ctx.channels_last = [_input_is_channels_last(input), offset is not None and _input_is_channels_last(offset)]
+
+
+def _deform_roi_pool_bwd(ctx, grad):
+    input, rois, offset = ctx.saved_tensors
+    needs = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[2]) and offset is not None]
+    dx, doff = _deform_roi_pool_backward(grad, input, rois, offset, *ctx.args, needs, ctx.channels_last)
+    return (dx if needs[0] else None, None, doff if needs[1] else None) + (None,) * 5
+
+
+torch.library.register_autograd("frcnn::deform_roi_pool", _deform_roi_pool_bwd, setup_context=_deform_roi_pool_setup)
+torch.library.register_autograd("frcnn::deform_roi_pool_backward", _no_double_backward("frcnn::deform_roi_pool"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
 def _score_order(scores):
     """The oracle's argsort(-scores, "stable"): descending score, ties in input order, NaN scores last in input order."""
@@ -884,6 +1001,25 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
                          "sample corners of %d images)" % (largest, MAX_DEFORM_INDEX, nb))
     return _deform_conv2d(input, offset, weight, bias, mask, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
                           DEFORM_CHUNK_IMAGES)
+
+
+def deform_roi_pool(input, rois, offset, output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1):
+    """Deformable RoI pooling (mmcv's deform_roi_pool, restated, unpinned): [K, C, oh, ow] (channels_last memory).  offset [K, 2, oh, ow],
+    channel 0 the x offset, channel 1 the y offset, in float32 or the input's dtype; None or an empty tensor: no offset."""
+    r = _roi_input(input, rois)
+    oh, ow = _output_size(output_size)
+    if int(sampling_ratio) > MAX_SAMPLING_RATIO:
+        raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
+    if offset is not None:
+        what = "float32" if input.dtype == torch.float32 else "float32 or the input's %s" % input.dtype
+        _check_tensor("offset", offset, (torch.float32, input.dtype), what)
+        _check_same_device(input, offset, "input", "offset")
+        if tuple(offset.shape) != (r.shape[0], 2, oh, ow) and offset.numel() == 0:
+            offset = None
+        elif tuple(offset.shape) != (r.shape[0], 2, oh, ow):
+            raise ValueError("offset must be [K, 2, oh, ow] = [%d, 2, %d, %d] (x offsets, then y offsets), got shape %s"
+                             % (r.shape[0], oh, ow, tuple(offset.shape)))
+    return _deform_roi_pool(input, r, offset, float(spatial_scale), oh, ow, int(sampling_ratio), float(gamma))
 
 
 def _ms_features(features):
@@ -1081,3 +1217,76 @@ class DeformConv2d(torch.nn.Module):
         s += ", groups=%s" % self.groups if self.groups != 1 else ""
         s += ", bias=False" if self.bias is None else ""
         return s + ")"
+
+
+class DeformRoIPool(torch.nn.Module):
+    """mmcv.ops.DeformRoIPool: deformable RoI pooling with the offset given by the caller (None: aligned RoIAlign)."""
+
+    def __init__(self, output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1):
+        super().__init__()
+        self.output_size = _output_size(output_size)
+        self.spatial_scale = float(spatial_scale)
+        self.sampling_ratio = int(sampling_ratio)
+        self.gamma = float(gamma)
+
+    def forward(self, input, rois, offset=None):
+        return deform_roi_pool(input, rois, offset, self.output_size, self.spatial_scale, self.sampling_ratio, self.gamma)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, gamma=%s" % (
+            self.output_size, self.spatial_scale, self.sampling_ratio, self.gamma)
+
+
+def _zero_last(stack, index):
+    torch.nn.init.zeros_(stack[index].weight)
+    torch.nn.init.zeros_(stack[index].bias)
+
+
+class DeformRoIPoolPack(DeformRoIPool):
+    """mmcv.ops.DeformRoIPoolPack (DCN v1): pools without offset, computes the offset from the pooled features (flattened in the logical
+    (C, oh, ow) order) with offset_fc, whose last layer starts at zero, and pools again with it."""
+
+    def __init__(self, output_size, output_channels, deform_fc_channels=1024, spatial_scale=1.0, sampling_ratio=0, gamma=0.1):
+        super().__init__(output_size, spatial_scale, sampling_ratio, gamma)
+        self.output_channels = output_channels
+        self.deform_fc_channels = deform_fc_channels
+        oh, ow = self.output_size
+        nn = torch.nn
+        self.offset_fc = nn.Sequential(nn.Linear(oh * ow * output_channels, deform_fc_channels), nn.ReLU(inplace=True),
+                                       nn.Linear(deform_fc_channels, deform_fc_channels), nn.ReLU(inplace=True),
+                                       nn.Linear(deform_fc_channels, oh * ow * 2))
+        _zero_last(self.offset_fc, 4)
+
+    def _pool(self, input, rois):
+        """(the pooled features without offset flattened [K, C * oh * ow], the pooled features with the learned offset)"""
+        if input.dim() != 4 or input.shape[1] != self.output_channels:
+            raise ValueError("input must be [N, %d, H, W] (output_channels), got shape %s" % (self.output_channels, tuple(input.shape)))
+        oh, ow = self.output_size
+        x = deform_roi_pool(input, rois, None, self.output_size, self.spatial_scale, self.sampling_ratio, self.gamma)
+        flat = x.reshape(x.shape[0], -1)                                   # logical (C, oh, ow) order, whatever the memory format
+        offset = self.offset_fc(flat).view(x.shape[0], 2, oh, ow)
+        return flat, deform_roi_pool(input, rois, offset, self.output_size, self.spatial_scale, self.sampling_ratio, self.gamma)
+
+    def forward(self, input, rois):
+        return self._pool(input, rois)[1]
+
+    def extra_repr(self):
+        return "%s, output_channels=%s, deform_fc_channels=%s" % (super().extra_repr(), self.output_channels, self.deform_fc_channels)
+
+
+class ModulatedDeformRoIPoolPack(DeformRoIPoolPack):
+    """mmcv.ops.ModulatedDeformRoIPoolPack (DCN v2): DeformRoIPoolPack times a learned per-bin mask [K, 1, oh, ow] in (0, 1), which is
+    sigmoid(mask_fc(.)) with a zero-initialised last layer: 0.5 at the start."""
+
+    def __init__(self, output_size, output_channels, deform_fc_channels=1024, spatial_scale=1.0, sampling_ratio=0, gamma=0.1):
+        super().__init__(output_size, output_channels, deform_fc_channels, spatial_scale, sampling_ratio, gamma)
+        oh, ow = self.output_size
+        nn = torch.nn
+        self.mask_fc = nn.Sequential(nn.Linear(oh * ow * output_channels, deform_fc_channels), nn.ReLU(inplace=True),
+                                     nn.Linear(deform_fc_channels, oh * ow), nn.Sigmoid())
+        _zero_last(self.mask_fc, 2)
+
+    def forward(self, input, rois):
+        flat, pooled = self._pool(input, rois)
+        oh, ow = self.output_size
+        return pooled * self.mask_fc(flat).view(flat.shape[0], 1, oh, ow)

@@ -63,7 +63,9 @@ extern "C" {
                                  still 21 (additions only, the number stays pinned): frcnn_ops_ps_roi_pool / frcnn_ops_ps_roi_align, their _backward and
                                  _16 forms (torchvision.ops.ps_roi_pool / ps_roi_align, R-FCN's position-sensitive pooling, on NCHW maps);
                                  still 21 (additions only): frcnn_ops_deform_* and frcnn_deform_geom (torchvision.ops.deform_conv2d, deformable
-                                 convolution v1 / v2, forward and backward on frcnn_gemm_tn's kernel) */
+                                 convolution v1 / v2, forward and backward on frcnn_gemm_tn's kernel);
+                                 still 21 (additions only): frcnn_ops_deform_roi_pool, its _backward, _16, _workspace_bytes and _cull_list forms
+                                 (deformable RoI pooling of DCN v1 / v2, mmcv's deform_roi_pool) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -604,6 +606,51 @@ int frcnn_ops_deform_backward_input(const frcnn_deform_geom* g, int n_img, const
                                     const float* d_weights, const float* d_dcol, float* d_dx, void* d_ws, size_t ws_bytes, void* stream);
 int frcnn_ops_deform_backward_weight(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
                                      const float* d_dout, float* d_dweight, int accumulate, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Deformable RoI pooling (DCN v1 / v2; csrc/ops_droi.hip): mmcv's deform_roi_pool in both directions, restated from the published
+ *   definition of mmcv/ops/csrc/common/cuda/deform_roi_pool_cuda_kernel.cuh (third party, absent here: restated, unpinned; where the two
+ *   differ this text holds).  Layouts and element types as frcnn_ops_roi_align above (NHWC maps, c % 4 == 0; the _16 forms c % 8 == 0):
+ *     d_x      : [n_img][fh][fw][c]
+ *     d_rois   : [k][5] rows (b, x1, y1, x2, y2); a batch index outside (-1, n_img) pools to zeros and sends and receives no gradient
+ *     d_offset : float32 [k][2][out_h][out_w], channel 0 the x (width) offset, channel 1 the y offset; NULL: no offset
+ *     d_out    : [k][out_h][out_w][c]
+ *   Bin (ph, pw) of a RoI is frcnn_ops_roi_align(aligned = 1)'s bin -- start = coord * scale - 0.5, size = end - start with no lower
+ *   bound, bin = size / out, grid = sampling_ratio > 0 ? sampling_ratio : ceil(size / out), count = max(grid_h * grid_w, 1) -- with its
+ *   window shifted: start_w += gamma * roi_w * offset[k][0][ph][pw], start_h += gamma * roi_h * offset[k][1][ph][pw]; bin and grid are
+ *   unchanged.  out = (1 / count) * sum over iy (outer), ix (inner) of the bilinear sample, roi_align's expressions in roi_align's order:
+ *   with a NULL or all-zero offset and finite RoIs the output is frcnn_ops_roi_align(aligned = 1) bit for bit.  A sample outside
+ *   [-1, size] on either axis, or at a NaN or infinite coordinate (rejected before any conversion to an integer), contributes nothing.
+ * frcnn_ops_deform_roi_pool_backward: with g = dout / count per accepted sample at (y, x), corners (yl, yh, xl, xh), weights w1..w4:
+ *   d_dx (NULL: skipped; else every element overwritten) gets g w1 at (yl, xl), g w2 at (yl, xh), g w3 at (yh, xl), g w4 at (yh, xh);
+ *   d_doffset (NULL: skipped; float32 [k][2][out_h][out_w], needs d_offset and d_x) gets
+ *     [0] += gamma roi_w g (v(yh,xh) (y - yl) + v(yl,xh) (yh - y) + v(yh,xl) (yl - y) + v(yl,xl) (y - yh))
+ *     [1] += gamma roi_h g (v(yh,xh) (x - xl) + v(yh,xl) (xh - x) + v(yl,xh) (xl - x) + v(yl,xl) (x - xh))
+ *   summed over the channels, with y and x as computed, before the clamp of the bilinear weights (the published formula: the exact
+ *   derivative in the interior, deliberately not in the clamped bands (-1, 0] and [size - 1, size]).  Both are deterministic and free of
+ *   atomics: d_doffset by one wave per (RoI, bin) with a fixed cross-lane reduction; d_dx by a plan launch (per bin the shifted start
+ *   and the window of cells its samples can touch, per RoI their union) and a gather per 2 x 2 tile that culls RoIs in ascending order,
+ *   frcnn_ops_deform_roi_pool_cull_list() at a time, and sums in ascending (RoI, ph, pw) order into registers, stored once.  d_ws:
+ *   frcnn_ops_deform_roi_pool_workspace_bytes(k, out_h, out_w) bytes, 16-byte aligned, needed with d_dx only (0: invalid sizes).
+ *   At least one of d_dx and d_doffset is given.  k == 0 returns FRCNN_OK after zero-filling d_dx.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): out_h, out_w in [1, 64], sampling_ratio <= 16, k >= 0, sizes < 1,
+ *   c not in whole runs, k * out_h * out_w or fh * fw beyond 32 bits, fh > 131070 or n_img * ceil(c / run / 64) > 65535 (the gather's
+ *   launch grid), NULL pointers, a small workspace.
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; offsets and
+ *   d_doffset stay float32. */
+int frcnn_ops_deform_roi_pool_cull_list(void);
+size_t frcnn_ops_deform_roi_pool_workspace_bytes(int k, int out_h, int out_w);
+int frcnn_ops_deform_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, const float* d_offset, int k,
+                              int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma, float* d_out, void* stream);
+int frcnn_ops_deform_roi_pool_backward(const float* d_x, const float* d_rois, const float* d_offset, int k, int n_img, int fh, int fw,
+                                       int c, int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma,
+                                       const float* d_dout, float* d_dx, float* d_doffset, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_deform_roi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois,
+                                 const float* d_offset, int k, int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma,
+                                 void* d_out, void* stream);
+int frcnn_ops_deform_roi_pool_backward_16(int elem_type, const void* d_x, const float* d_rois, const float* d_offset, int k, int n_img,
+                                          int fh, int fw, int c, int out_h, int out_w, float spatial_scale, int sampling_ratio,
+                                          float gamma, const void* d_dout, void* d_dx, float* d_doffset, void* d_ws, size_t ws_bytes,
+                                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -30,7 +30,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     restatement of tests/deform_conv_cases.py: floor, index gathers and einsum), forward and forward + backward of all five gradients,
     in alternating windows.
 
+  * droi: deformable RoI pooling on a C4 map (2 x 256 x 50 x 68, 512 RoIs, 7 x 7, scale 1 / 16, sampling_ratio 2), with offsets N(0, 0.5)
+    and without, float32 and bfloat16: ops.deform_roi_pool beside the same operator composed from torch operations on the GPU (the
+    restatement of tests/deform_roi_cases.py: floor, index gathers and sums), forward and forward + backward, in alternating windows.
+
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
+    python tools/ops_bench.py --only droi            # just the deformable-RoI-pooling leg
     python tools/ops_bench.py --only deform          # just the deformable-convolution leg
     python tools/ops_bench.py --only ps              # just the position-sensitive leg
     python tools/ops_bench.py --only half            # just the 16-bit leg
@@ -256,6 +261,38 @@ def deform_leg(rng, reps, warmup):
     return res
 
 
+def droi_leg(rng, reps, warmup):
+    from tests import deform_roi_cases as D
+    n, c, h, w, k, out, scale, sr, gamma = 2, 256, 50, 68, 512, (7, 7), 1 / 16, 2, 0.1
+    gen = torch.Generator().manual_seed(0)
+    props = proposals(rng, k, 800, 1088)
+    rois = torch.from_numpy(np.concatenate([(np.arange(k) % n).astype(np.float32)[:, None], props[:, [1, 0, 3, 2]]], 1)).to(DEV)
+    res = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((k, c) + out, generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        for with_offset in (False, True):
+            offset = (torch.randn((k, 2) + out, generator=gen) * 0.5).to(DEV) if with_offset else None
+            case = {"rois": rois, "output_size": out, "sampling_ratio": sr, "gamma": D.f32(gamma), "spatial_scale": D.f32(scale),
+                    "input": x, "offset": offset}
+            leaves = [x.clone().requires_grad_(True), offset.clone().requires_grad_(True) if with_offset else None]
+
+            def native(a=(x, offset)):
+                return ops.deform_roi_pool(a[0], rois, a[1], out, scale, sr, gamma)
+
+            def composed(a=(x, offset)):
+                return D.forward_ref(dict(case, offset=a[1]), torch.float32, input=a[0]).to(dtype)     # float32 arithmetic, as the op's
+            y, yc = native().float(), composed().float()
+            r = {"max |deform_roi_pool - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+            for name, fns in (("fwd", (native, composed)),
+                              ("fwd+bwd", (lambda: native(leaves).backward(g), lambda: composed(leaves).backward(g)))):
+                t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+                r[name] = {"ops.deform_roi_pool": round(t_native, 1), "torch composition": round(t_comp, 1),
+                           "composition / deform_roi_pool": round(t_comp / t_native, 2)}
+            res["droi %s 2 x 256 x 50 x 68, 512 RoIs, 7 x 7, sr 2, %s" % (str(dtype).split(".")[-1], "offset" if with_offset else "no offset")] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -265,7 +302,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -283,6 +320,9 @@ def main():
         return
     if a.only == "deform":
         print(json.dumps(deform_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "droi":
+        print(json.dumps(droi_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -347,6 +387,7 @@ def main():
     res.update(half_leg(rng, 10, 3))
     res.update(ps_leg(rng, 10, 3))
     res.update(deform_leg(rng, 5, 2))
+    res.update(droi_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
