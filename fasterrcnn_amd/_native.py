@@ -70,6 +70,8 @@ SYMBOLS = (
     "frcnn_ops_deform_input_plan", "frcnn_ops_deform_backward_input", "frcnn_ops_deform_backward_weight",
     "frcnn_ops_deform_roi_pool_cull_list", "frcnn_ops_deform_roi_pool_workspace_bytes", "frcnn_ops_deform_roi_pool",
     "frcnn_ops_deform_roi_pool_backward", "frcnn_ops_deform_roi_pool_16", "frcnn_ops_deform_roi_pool_backward_16",
+    "frcnn_ops_box_iou_rotated", "frcnn_ops_nms_rotated", "frcnn_ops_roi_align_rotated_cull_list", "frcnn_ops_roi_align_rotated",
+    "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
 )
 
 
@@ -296,6 +298,14 @@ _SIGNATURES = {
     "frcnn_ops_deform_roi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp]),
     "frcnn_ops_deform_roi_pool_backward_16": (C.c_int, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _sz,
                                                         _vp]),
+    # rotated boxes (csrc/ops_rot.hip); the _16 forms take the element-type code first
+    "frcnn_ops_box_iou_rotated": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_nms_rotated": (C.c_int, [_vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_roi_align_rotated_cull_list": (C.c_int, []),
+    "frcnn_ops_roi_align_rotated": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_roi_align_rotated_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_roi_align_rotated_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_roi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

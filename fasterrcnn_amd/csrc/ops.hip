@@ -24,86 +24,10 @@
 // one contiguous segment.  ops_nms_mask_kernel writes 64 x 64 IoU bit tiles (only tiles on or above the diagonal whose rows and
 // columns can share a category), ops_nms_reduce_kernel runs the greedy pass of every segment in its own wave, in parallel, with the
 // segment's removed-bits in LDS.  float32 decides with iou_gt (csrc/geometry.h), float64 with the division in float64.
-#include "ops_geom.h"
+#include "ops_run.h"
 #include <cfloat>
 
 namespace frcnn {
-
-typedef unsigned long long u64;
-
-static constexpr int OPS_TILE = 2;           // backward tile: 2 x 2 cells, one per wave, 64 channel runs per block
-static_assert(OPS_TILE * OPS_TILE == 4, "the backward kernels give each of a block's four waves one cell of the tile");
-static constexpr int OPS_LIST = 1024;        // RoIs culled per pass of a tile
-static constexpr int OPS_MAX_OUT = 64;       // out_h, out_w <= 64
-static constexpr int OPS_MAX_SAMPLING = 16;  // sampling_ratio <= 16
-static constexpr int OPS_NMS_MAX_WORDS = 8192;   // removed-bits of one segment in 64 KB of LDS: n <= 524288
-static constexpr int OPS_MS_MAX_LEVELS = 8;  // multi-scale RoIAlign: feature maps per call
-
-// ---- storage types --------------------------------------------------------------------------------------------------------------
-// 16-bit elements carry the width N of a lane's run in their type, so that one tensor can be walked in runs of 8 or of 4 channels
-template <int N> struct f16_t { _Float16 v; };
-template <int N> struct bf16_t { unsigned short bits; };
-
-// 16-bit channels per lane.  8 = 16 B per load and store, as a float quad: measured faster than 4 in every forward kernel and in the
-// backward kernels once C / 8 fills a wave (C >= 512).  Below that a backward block, whose lanes are the channel runs of one cell,
-// would idle half of each wave: there the gather walks the same tensors in runs of 4 (C = 256: 7 % faster forward + backward).
-static constexpr int OPS_HALF_RUN = 8, OPS_HALF_RUN_NARROW = 4;
-
-// Run<E>: V consecutive channels of one pixel, in memory as E, in registers as float32 (vec).  load widens exactly; store rounds to
-// nearest even once, NaN and infinities as torch's Tensor.to(): float16 by the hardware conversion (v_cvt_f16_f32), bfloat16 by the
-// integer rounding of c10::BFloat16 (every NaN becomes 0x7FC0 there, which the packed hardware conversion would not give).
-template <typename E> struct Run;
-template <> struct Run<float> {
-    static constexpr int V = 4;
-    typedef f32x4 vec;
-    typedef int ivec __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ vec load(const float* p, size_t i) { return reinterpret_cast<const vec*>(p)[i]; }
-    static __device__ __forceinline__ void store(float* p, size_t i, vec v) { reinterpret_cast<vec*>(p)[i] = v; }
-};
-template <int N> struct Run<f16_t<N>> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef int ivec __attribute__((ext_vector_type(N)));
-    typedef _Float16 raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const f16_t<N>* p, size_t i)
-    {
-        return __builtin_convertvector(reinterpret_cast<const raw*>(p)[i], vec);
-    }
-    static __device__ __forceinline__ void store(f16_t<N>* p, size_t i, vec v)
-    {
-        reinterpret_cast<raw*>(p)[i] = __builtin_convertvector(v, raw);
-    }
-};
-template <int N> struct Run<bf16_t<N>> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef int ivec __attribute__((ext_vector_type(N)));
-    typedef unsigned short raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const bf16_t<N>* p, size_t i)
-    {
-        const raw u = reinterpret_cast<const raw*>(p)[i];
-        vec v;
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = __uint_as_float((unsigned)u[j] << 16);
-        return v;
-    }
-    static __device__ __forceinline__ void store(bf16_t<N>* p, size_t i, vec v)
-    {
-        raw u;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const unsigned b = __float_as_uint(v[j]);
-            u[j] = v[j] != v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-        }
-        reinterpret_cast<raw*>(p)[i] = u;
-    }
-};
-
-template <typename E> __device__ __forceinline__ void zero_row(E* orow, int n)
-{
-    const typename Run<E>::vec z = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) Run<E>::store(orow, i, z);
-}
 
 // Output row ph of one RoI (out_w x C / V runs at orow) pooled from the image map fm [fh][fw][C]: the loop body of ops_roi_align_kernel,
 // shared with ops_ms_roi_align_kernel so that the two stay bit-identical.  Block of 256 threads.
@@ -166,34 +90,6 @@ __device__ __forceinline__ void sample_range(int cell, float start, float bin, i
     // clamped in float first (the conversion of an out-of-range float is undefined), then exactly in integers
     s_lo = (int)fminf(fmaxf(floorf(a), 0.f), 2.0e9f);
     s_hi = (int)min((long long)fmaxf(fminf(ceilf(e), 2.0e9f), -1.0f), last);
-}
-
-// Ordered culling shared by the two backward kernels: appends to s_list, in ascending order, the RoIs r >= r_begin for which
-// touches(r) holds, until OPS_LIST are listed.  Returns the first RoI not examined (k when all were).  Block of 256 threads.
-template <typename Touches>
-__device__ int cull_rois(int r_begin, int k, Touches touches, int* s_list, int* s_cnt, int* s_n)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __syncthreads();                                     // the previous pass has finished reading s_list
-    if (tid == 0) *s_n = 0;
-    int r0 = r_begin;
-    for (; r0 < k; r0 += 256) {
-        const int r = r0 + tid;
-        const bool hit = r < k && touches(r);
-        const u64 m = __ballot(hit);
-        if (lane == 0) s_cnt[wave] = __popcll(m);
-        __syncthreads();
-        const int base = *s_n;
-        const int total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        if (base + total > OPS_LIST) break;              // uniform: the list is full; this group starts the next pass
-        int off = base;
-        for (int w = 0; w < wave; ++w) off += s_cnt[w];
-        if (hit) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = r;
-        __syncthreads();
-        if (tid == 0) *s_n = base + total;
-    }
-    __syncthreads();
-    return r0 < k ? r0 : k;
 }
 
 // whether a RoI's samples can touch the tile of cells [ty0, ty1] x [tx0, tx1]: conservative, the gather tests each sample exactly
@@ -696,11 +592,11 @@ void ops_nms_reduce_kernel(const u64* __restrict__ mask, const int64_t* __restri
     }
 }
 
-// v: the channels of a lane's run (Run<E>::V)
-static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w, int v)
+// the greedy pass over a finished bit mask (frcnn_ops_nms here, frcnn_ops_nms_rotated in ops_rot.hip)
+int launch_ops_nms_reduce(const u64* mask, const int64_t* order, const int64_t* cats, int n, int nw, uint8_t* keep, hipStream_t s)
 {
-    return n_img >= 1 && fh >= 1 && fw >= 1 && c >= v && c % v == 0 && k >= 0 && out_h >= 1 && out_h <= OPS_MAX_OUT && out_w >= 1 &&
-           out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / v, 64) <= 65535;   // backward grid z
+    hipLaunchKernelGGL(ops_nms_reduce_kernel, dim3(cats ? n : 1), dim3(64), (size_t)nw * sizeof(u64), s, mask, order, cats, n, nw, keep);
+    return check_launch();
 }
 
 // Fills the multi-scale argument (without map pointers) and the size of the backward grid; false on an invalid request.
@@ -830,21 +726,6 @@ static int ms_roi_align_backward_impl(const float* d_rois, int k, const int* fh,
 
 using namespace frcnn;
 
-// A 16-bit entry point's body by element-type code, in runs of `run` channels; c must hold whole runs of OPS_HALF_RUN either way.
-#define OPS_DISPATCH_16(elem_type, c, run, impl, ...)                                        \
-    do {                                                                                     \
-        if ((c) % OPS_HALF_RUN != 0) return FRCNN_EINVAL;                                    \
-        const bool wide = (run) == OPS_HALF_RUN;                                             \
-        if ((elem_type) == FRCNN_OPS_F16)                                                    \
-            return wide ? impl<f16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<f16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__);   \
-        if ((elem_type) == FRCNN_OPS_BF16)                                                   \
-            return wide ? impl<bf16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<bf16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__); \
-        return FRCNN_EINVAL;                                                                 \
-    } while (0)
-
-// the run of a backward gather over c channels: the wide one when its runs fill the 64 lanes that share a cell
-static int backward_run(int c) { return c / OPS_HALF_RUN >= 64 ? OPS_HALF_RUN : OPS_HALF_RUN_NARROW; }
-
 extern "C" {
 
 int frcnn_ops_roi_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
@@ -963,11 +844,9 @@ int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, co
     else
         hipLaunchKernelGGL(ops_nms_mask_kernel<float>, dim3(nw, nw), dim3(64), 0, s, static_cast<const float*>(d_boxes), d_order,
                            d_categories, n, nw, iou_threshold, mask);
-    int rc = check_launch();
+    const int rc = check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(ops_nms_reduce_kernel, dim3(d_categories ? n : 1), dim3(64), (size_t)nw * sizeof(u64), s, mask, d_order,
-                       d_categories, n, nw, d_keep);
-    return check_launch();
+    return launch_ops_nms_reduce(mask, d_order, d_categories, n, nw, d_keep, s);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import ps_roi_pool, ps_roi_align, PSRoIPool, PSRoIAlign
     from fasterrcnn_amd.ops import deform_conv2d, DeformConv2d
     from fasterrcnn_amd.ops import deform_roi_pool, DeformRoIPool, DeformRoIPoolPack, ModulatedDeformRoIPoolPack
+    from fasterrcnn_amd.ops import box_iou_rotated, nms_rotated, roi_align_rotated, RoIAlignRotated
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -75,6 +76,30 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       RoIs get no gradient; double backward raises.  16-bit maps under the contract below for the output and d_input; the kernels read
       the offset and write its gradient in float32, and the gradient is rounded once to the offset's dtype.  The Pack modules own
       mmcv's offset_fc (and mask_fc) stacks with zero-initialised last layers, so mmcv / mmdetection checkpoints load strict.
+  box_iou_rotated(boxes1, boxes2, mode="iou", aligned=False, clockwise=True) -> float32 [N, M], or [N] when aligned (N == M)
+  nms_rotated(boxes, scores, iou_threshold, labels=None, clockwise=True) -> (dets [K, 6], keep int64 [K])
+  roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True, clockwise=False)
+  RoIAlignRotated(output_size, spatial_scale, sampling_ratio=0, aligned=True, clockwise=False).forward(input, rois)
+      Rotated boxes for oriented detection (csrc/ops_rot.hip; mmcv's box_iou_rotated, nms_rotated and roi_align_rotated restated,
+      unpinned: where the two differ include/frcnn_hip.h holds).  A box is float32 (cx, cy, w, h, angle), angle in radians.  With
+      clockwise=True a local point (u, v) of the box, |u| <= w / 2, |v| <= h / 2, lies at the image point (cx + u cos a - v sin a,
+      cy + u sin a + v cos a); clockwise=False means the same with a replaced by -a (the wrapper negates the column: the kernels know
+      one convention).  IoU: inter is the area of the intersection of the two rectangles; mode "iou": inter / (w1 h1 + w2 h2 - inter),
+      mode "iof": inter / (w1 h1).  A pair gives exactly 0 if either box has w h < 1e-14, a negative w or h, or a non-finite component;
+      a box against itself gives exactly 1.  Empty inputs give empty outputs; there is no autograd (mmcv's has none).
+      nms_rotated: boxes are visited in a stable descending sort of the scores, NaN scores last; sorted box j goes iff a kept box i
+      before it, with the same label when labels are given, has iou(i, j) > float32(iou_threshold) -- box_iou_rotated's value, in that
+      argument order.  keep is ordered by descending score, ties by ascending index, as in batched_nms; dets =
+      cat(boxes[keep], scores[keep, None]).  N <= MAX_NMS_BOXES.  Boxes and scores are float32 only (float64 is a TypeError).
+      roi_align_rotated: rois float32 [K, 6] rows (batch index, cx, cy, w, h, angle).  off = 0.5 if aligned else 0; centre =
+      (cx, cy) * scale - off; rw = w * scale, rh = h * scale, each raised to >= 1 only when not aligned; bins rh / oh x rw / ow; grid =
+      sampling_ratio if sampling_ratio > 0 else ceil(rh / oh) (likewise w); count = max(grid_h * grid_w, 1); t = -angle if clockwise
+      else angle.  Sample (ph, iy, pw, ix) has local yy = -rh / 2 + ph * bin_h + (iy + .5) * bin_h / grid_h, xx likewise, and lies at
+      x = yy sin t + xx cos t + centre_x, y = yy cos t - xx sin t + centre_y, so clockwise=True agrees with the box convention above.
+      The value is roi_align's bilinear rule (nothing outside [-1, size] or at a NaN coordinate), the output the mean over count.
+      Limits, layouts ([K, C, oh, ow] channels_last), channel padding and the batch-index rule are roi_align's; 16-bit maps run under
+      the contract below, forward and backward, with RoIs in float32.  The gradient goes to input only; it is a deterministic gather
+      without atomics (RoIs ascending, ROI_ALIGN_ROTATED_CULL_LIST per pass, then bins in (ph, pw) order).  Double backward raises.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -101,13 +126,15 @@ from . import _native as nv
 
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
-           "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack"]
+           "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
 DEFORM_ROI_CULL_LIST = 256                # RoIs that deform_roi_pool's input-gradient gather lists per pass (DROI_LIST of csrc/ops_droi.hip)
+ROI_ALIGN_ROTATED_CULL_LIST = 1024        # RoIs that roi_align_rotated's backward gather lists per pass (OPS_LIST of csrc/ops_run.h)
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
+MAX_ROTATED_IOU_ROWS = 65535 * 64         # rows of box_iou_rotated's matrix (the tile rows of its launch grid)
 MAX_LEVELS = 8
 DEFORM_CHUNK_IMAGES = 32                  # images per chunk of deform_conv2d's column workspace (torchvision processes 32 at a time too)
 MAX_DEFORM_INDEX = 2 ** 31 - 1 - 1024     # what the 32-bit indices of csrc/ops_deform.hip hold: columns, cells and plan entries of a chunk
@@ -879,6 +906,124 @@ def _nms_input(boxes, scores):
         raise ValueError("nms takes at most %d boxes, got %d" % (MAX_NMS_BOXES, boxes.shape[0]))
 
 
+# ---- frcnn::box_iou_rotated, frcnn::nms_rotated, frcnn::roi_align_rotated (csrc/ops_rot.hip) --------------------------------------
+@torch.library.custom_op("frcnn::box_iou_rotated", mutates_args=())
+def _box_iou_rotated(boxes1: Tensor, boxes2: Tensor, mode: int, aligned: bool) -> Tensor:
+    n, m = boxes1.shape[0], boxes2.shape[0]
+    out = torch.empty((n,) if aligned else (n, m), dtype=torch.float32, device=boxes1.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(boxes1.device):
+        a, b = boxes1.contiguous(), boxes2.contiguous()
+        nv.check(nv.lib().frcnn_ops_box_iou_rotated(a.data_ptr(), n, b.data_ptr(), m, mode, int(aligned), out.data_ptr(), _stream(boxes1)),
+                 "frcnn_ops_box_iou_rotated")
+    return out
+
+
+@_box_iou_rotated.register_fake
+def _(boxes1, boxes2, mode, aligned):
+    n, m = boxes1.shape[0], boxes2.shape[0]
+    return boxes1.new_empty((n,) if aligned else (n, m), dtype=torch.float32)
+
+
+@torch.library.custom_op("frcnn::nms_rotated", mutates_args=())
+def _nms_rotated_op(boxes: Tensor, scores: Tensor, labels: Optional[Tensor], iou_threshold: float) -> Tensor:
+    """The kept indices; boxes in the kernels' (clockwise) convention.  _nms's sorting and merging around frcnn_ops_nms_rotated."""
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        order = _score_order(scores)
+        cats = None
+        if labels is not None:
+            cats = labels.to(torch.int64).contiguous()
+            order = order[torch.sort(cats[order], stable=True).indices]       # each label one run, by score inside it
+        lib = nv.lib()
+        ws = torch.empty((lib.frcnn_ops_nms_workspace_bytes(n),), dtype=torch.uint8, device=boxes.device)
+        keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
+        b = boxes.contiguous()
+        nv.check(lib.frcnn_ops_nms_rotated(b.data_ptr(), order.data_ptr(), cats.data_ptr() if cats is not None else None, n, iou_threshold,
+                                           keep.data_ptr(), ws.data_ptr(), ws.numel(), _stream(boxes)), "frcnn_ops_nms_rotated")
+        kept = order[keep.bool()]
+        if labels is not None:                                                 # merge: descending score, ties by ascending index
+            kept = torch.sort(kept).values
+            kept = kept[_score_order(scores[kept])]
+        return kept
+
+
+@_nms_rotated_op.register_fake
+def _(boxes, scores, labels, iou_threshold):
+    return _nms_fake_result(boxes)
+
+
+@torch.library.custom_op("frcnn::roi_align_rotated", mutates_args=())
+def _roi_align_rotated(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
+                       aligned: bool, clockwise: bool) -> Tensor:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        cp = x.shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
+        _call("roi_align_rotated", input, x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width, spatial_scale,
+              sampling_ratio, int(aligned), int(clockwise), dst.data_ptr(), _stream(input))
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_roi_align_rotated.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned, clockwise):
+    return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
+
+
+@torch.library.custom_op("frcnn::roi_align_rotated_backward", mutates_args=())
+def _roi_align_rotated_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int,
+                                sampling_ratio: int, aligned: bool, clockwise: bool, batch_size: int, channels: int, height: int,
+                                width: int, channels_last: bool) -> Tensor:
+    k = rois.shape[0]
+    if channels == 0 or batch_size * height * width == 0:
+        return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
+    with torch.cuda.device(grad.device):
+        cp = _padded_channels(channels, grad.dtype)
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        dx = _empty_cl((batch_size, cp, height, width), grad)
+        _call("roi_align_rotated_backward", grad, r.data_ptr() if k else None, k, batch_size, height, width, cp, pooled_height,
+              pooled_width, spatial_scale, sampling_ratio, int(aligned), int(clockwise), g.data_ptr() if k else None, dx.data_ptr(),
+              _stream(grad))
+        return _grad_layout(dx, channels, channels_last)
+
+
+@_roi_align_rotated_backward.register_fake
+def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned, clockwise, batch_size, channels, height, width,
+      channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+def _roi_align_rotated_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.args = tuple(inputs[2:])
+    ctx.shape = tuple(inputs[0].shape)
+    ctx.channels_last = _input_is_channels_last(inputs[0])
+
+
+def _roi_align_rotated_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    return (_roi_align_rotated_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 7
+
+
+torch.library.register_autograd("frcnn::roi_align_rotated", _roi_align_rotated_bwd, setup_context=_roi_align_rotated_setup)
+torch.library.register_autograd("frcnn::roi_align_rotated_backward", _no_double_backward("frcnn::roi_align_rotated"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- public interface -------------------------------------------------------------------------------------------------------------
 def nms(boxes, scores, iou_threshold):
     """torchvision.ops.nms: int64 indices of the kept boxes, by descending score."""
@@ -1022,6 +1167,66 @@ def deform_roi_pool(input, rois, offset, output_size, spatial_scale=1.0, samplin
     return _deform_roi_pool(input, r, offset, float(spatial_scale), oh, ow, int(sampling_ratio), float(gamma))
 
 
+def _rotated_boxes(name, boxes, clockwise):
+    """Checks a Tensor[N, 5] of rotated boxes; returns it in the kernels' convention (angles negated for clockwise=False)."""
+    _check_tensor(name, boxes, (torch.float32,), "float32 (rotated boxes are float32 only: pass .float())")
+    if boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise ValueError("%s must be [N, 5] (cx, cy, w, h, angle), got shape %s" % (name, tuple(boxes.shape)))
+    if clockwise:
+        return boxes
+    return torch.cat([boxes[:, :4], -boxes[:, 4:]], dim=1)
+
+
+def box_iou_rotated(boxes1, boxes2, mode="iou", aligned=False, clockwise=True):
+    """mmcv.ops.box_iou_rotated: the IoU (or, mode="iof", the intersection over the first box's area) of rotated boxes
+    (cx, cy, w, h, angle in radians): float32 [N, M], or [N] when aligned.  No autograd."""
+    if mode not in ("iou", "iof"):
+        raise ValueError("mode must be 'iou' or 'iof', got %r" % (mode,))
+    b1, b2 = _rotated_boxes("boxes1", boxes1, clockwise), _rotated_boxes("boxes2", boxes2, clockwise)
+    _check_same_device(boxes1, boxes2, "boxes1", "boxes2")
+    if aligned and b1.shape[0] != b2.shape[0]:
+        raise ValueError("aligned=True needs boxes1 and boxes2 of one length, got %d and %d" % (b1.shape[0], b2.shape[0]))
+    if b1.shape[0] > MAX_ROTATED_IOU_ROWS:
+        raise ValueError("boxes1 holds at most %d boxes, got %d" % (MAX_ROTATED_IOU_ROWS, b1.shape[0]))
+    return _box_iou_rotated(b1.detach(), b2.detach(), int(mode == "iof"), bool(aligned))
+
+
+def nms_rotated(boxes, scores, iou_threshold, labels=None, clockwise=True):
+    """mmcv.ops.nms_rotated: greedy NMS on box_iou_rotated, within each label when labels are given.  Returns (dets [K, 6] =
+    cat(boxes[keep], scores[keep, None]), keep int64 [K]), by descending score, ties by ascending index."""
+    b = _rotated_boxes("boxes", boxes, clockwise)
+    _check_tensor("scores", scores, (torch.float32,), "float32")
+    _check_same_device(boxes, scores, "boxes", "scores")
+    if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise ValueError("scores must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(scores.shape)))
+    if boxes.shape[0] > MAX_NMS_BOXES:
+        raise ValueError("nms_rotated takes at most %d boxes, got %d" % (MAX_NMS_BOXES, boxes.shape[0]))
+    if labels is not None:
+        _check_tensor("labels", labels, (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8), "an integer tensor")
+        _check_same_device(boxes, labels, "boxes", "labels")
+        if labels.dim() != 1 or labels.shape[0] != boxes.shape[0]:
+            raise ValueError("labels must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(labels.shape)))
+    keep = _nms_rotated_op(b.detach(), scores.detach(), labels, float(iou_threshold))
+    return torch.cat([boxes[keep], scores[keep, None]], dim=1), keep
+
+
+def roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True, clockwise=False):
+    """mmcv.ops.roi_align_rotated: RoIAlign on the rotated sampling grid of rois [K, 6] (batch index, cx, cy, w, h, angle in radians):
+    [K, C, oh, ow] (channels_last memory)."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
+    if input.dim() != 4:
+        raise ValueError("input must be [N, C, H, W], got shape %s" % (tuple(input.shape),))
+    dtypes, what = _box_dtypes(input)
+    _check_tensor("rois", rois, dtypes, what)
+    _check_same_device(input, rois, "input", "rois")
+    if rois.dim() != 2 or rois.shape[1] != 6:
+        raise ValueError("rois must be a Tensor[K, 6] (batch index, cx, cy, w, h, angle), got shape %s" % (tuple(rois.shape),))
+    oh, ow = _output_size(output_size)
+    if int(sampling_ratio) > MAX_SAMPLING_RATIO:
+        raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
+    return _roi_align_rotated(input, rois.float(), float(spatial_scale), oh, ow, int(sampling_ratio), bool(aligned), bool(clockwise))
+
+
 def _ms_features(features):
     if not isinstance(features, (list, tuple)):
         raise TypeError("features must be a list of tensors, got %s" % type(features).__name__)
@@ -1127,6 +1332,25 @@ class RoIAlign(torch.nn.Module):
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, aligned=%s" % (
             self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned)
+
+
+class RoIAlignRotated(torch.nn.Module):
+    """mmcv.ops.RoIAlignRotated."""
+
+    def __init__(self, output_size, spatial_scale, sampling_ratio=0, aligned=True, clockwise=False):
+        super().__init__()
+        self.output_size = _output_size(output_size)
+        self.spatial_scale = float(spatial_scale)
+        self.sampling_ratio = int(sampling_ratio)
+        self.aligned = bool(aligned)
+        self.clockwise = bool(clockwise)
+
+    def forward(self, input, rois):
+        return roi_align_rotated(input, rois, self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned, self.clockwise)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, aligned=%s, clockwise=%s" % (
+            self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned, self.clockwise)
 
 
 class RoIPool(torch.nn.Module):

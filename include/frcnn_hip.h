@@ -65,7 +65,9 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_deform_* and frcnn_deform_geom (torchvision.ops.deform_conv2d, deformable
                                  convolution v1 / v2, forward and backward on frcnn_gemm_tn's kernel);
                                  still 21 (additions only): frcnn_ops_deform_roi_pool, its _backward, _16, _workspace_bytes and _cull_list forms
-                                 (deformable RoI pooling of DCN v1 / v2, mmcv's deform_roi_pool) */
+                                 (deformable RoI pooling of DCN v1 / v2, mmcv's deform_roi_pool);
+                                 still 21 (additions only): frcnn_ops_box_iou_rotated, frcnn_ops_nms_rotated, frcnn_ops_roi_align_rotated, its
+                                 _backward, _16 and _cull_list forms (rotated boxes: mmcv's box_iou_rotated, nms_rotated, roi_align_rotated) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -651,6 +653,55 @@ int frcnn_ops_deform_roi_pool_backward_16(int elem_type, const void* d_x, const 
                                           int fh, int fw, int c, int out_h, int out_w, float spatial_scale, int sampling_ratio,
                                           float gamma, const void* d_dout, void* d_dx, float* d_doffset, void* d_ws, size_t ws_bytes,
                                           void* stream);
+
+/* Rotated boxes (oriented detection; csrc/ops_rot.hip): mmcv's box_iou_rotated, nms_rotated and roi_align_rotated, restated from their
+ *   published definitions (third party, absent here: restated, unpinned; where the two differ this text holds).
+ * Box: float32 (cx, cy, w, h, angle), angle in radians.  A local point (u, v) of the box, |u| <= w / 2, |v| <= h / 2, lies at the image
+ *   point (cx + u cos a - v sin a, cy + u sin a + v cos a): mmcv's clockwise = True.  The kernels know this one convention; for the
+ *   other the caller negates the angles.
+ * IoU: inter = the area of the intersection of the two rectangles; mode 0 (iou): inter / (w1 h1 + w2 h2 - inter), mode 1 (iof):
+ *   inter / (w1 h1).  A pair gives exactly 0 if either box has w h < 1e-14, a negative w or h, or a non-finite component.  Computed in
+ *   float32: the centre difference first, box 1's corners in box 2's frame, clipped against box 2's four half-planes (Sutherland-Hodgman),
+ *   the area as a fan of triangles.  A box against itself gives exactly 1.
+ * frcnn_ops_box_iou_rotated: d_out [n][m] = IoU(d_boxes1[i], d_boxes2[j]), or with aligned != 0 (n == m required) d_out [n] =
+ *   IoU(d_boxes1[i], d_boxes2[i]), bit-identical to the diagonal of the full matrix.  n or m == 0 returns FRCNN_OK.  n <= 4194240.
+ * frcnn_ops_nms_rotated: frcnn_ops_nms on rotated boxes d_boxes [n][5]: the same order / categories / keep / workspace arguments
+ *   (frcnn_ops_nms_workspace_bytes(n)), the same bit mask and the same greedy pass; sorted box j goes iff a kept box i before it, of
+ *   the same category, has IoU(box i, box j) > iou_threshold, with the IoU, and the argument order, of frcnn_ops_box_iou_rotated.
+ * frcnn_ops_roi_align_rotated: RoIAlign on a rotated sampling grid.  d_x [n_img][fh][fw][c], d_out [k][out_h][out_w][c] and the limits
+ *   as frcnn_ops_roi_align; d_rois [k][6] rows (b, cx, cy, w, h, angle), a batch index outside (-1, n_img) pools to zeros and gets no
+ *   gradient.  off = aligned ? 0.5 : 0; centre = (cx, cy) * scale - off; rw = w * scale, rh = h * scale, each raised to >= 1 only when
+ *   !aligned; bins rh / out_h x rw / out_w; grid = sampling_ratio > 0 ? sampling_ratio : ceil(rh / out_h) (likewise w; 0 for a size that
+ *   is not positive, NaN or gives more than 2^30 samples per bin); count = max(grid_h * grid_w, 1); t = clockwise ? -angle : angle.
+ *   Sample (ph, iy, pw, ix) has local yy = -rh / 2 + ph * bin_h + (iy + .5) * bin_h / grid_h, xx likewise, and lies at
+ *   x = yy sin t + xx cos t + centre_x, y = yy cos t - xx sin t + centre_y: clockwise != 0 agrees with the box convention above.  Its
+ *   value is frcnn_ops_roi_align's bilinear rule; nothing outside [-1, size] on either axis or at a NaN coordinate.  The output is the
+ *   sum over iy (outer), ix (inner) divided by count.
+ * frcnn_ops_roi_align_rotated_backward: d_dx [n_img][fh][fw][c], every element overwritten (k == 0: zeros).  Deterministic, no atomics:
+ *   a gather per 2 x 2 cell tile that culls RoIs in ascending order, frcnn_ops_roi_align_rotated_cull_list() at a time, against the
+ *   rotated RoI's bounding box grown by two pixels; per cell and listed RoI the candidate samples are bounded analytically (a rotation
+ *   is an isometry: a touching sample lies within sqrt(2) of the cell on both local axes) and each is tested exactly with the forward's
+ *   expressions.  The sum runs over RoIs ascending, then bins (ph, pw) ascending, each bin sending dout * (the sum of its samples' weights
+ *   in (iy, ix) order) / count; it stays in registers and is stored once.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): frcnn_ops_roi_align's limits, fh <= 131070, NULL pointers, mode
+ *   outside {0, 1}, aligned with n != m, n beyond the limits, a small workspace.
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; RoIs stay float32. */
+int frcnn_ops_box_iou_rotated(const float* d_boxes1, int n, const float* d_boxes2, int m, int mode, int aligned, float* d_out,
+                              void* stream);
+int frcnn_ops_nms_rotated(const float* d_boxes, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
+                          uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_roi_align_rotated_cull_list(void);
+int frcnn_ops_roi_align_rotated(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                                float spatial_scale, int sampling_ratio, int aligned, int clockwise, float* d_out, void* stream);
+int frcnn_ops_roi_align_rotated_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                         float spatial_scale, int sampling_ratio, int aligned, int clockwise, const float* d_dout,
+                                         float* d_dx, void* stream);
+int frcnn_ops_roi_align_rotated_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                                   int out_w, float spatial_scale, int sampling_ratio, int aligned, int clockwise, void* d_out,
+                                   void* stream);
+int frcnn_ops_roi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h,
+                                            int out_w, float spatial_scale, int sampling_ratio, int aligned, int clockwise,
+                                            const void* d_dout, void* d_dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

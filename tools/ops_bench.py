@@ -34,6 +34,11 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     and without, float32 and bfloat16: ops.deform_roi_pool beside the same operator composed from torch operations on the GPU (the
     restatement of tests/deform_roi_cases.py: floor, index gathers and sums), forward and forward + backward, in alternating windows.
 
+  * rot: rotated boxes.  ops.nms_rotated on 12000 boxes (threshold 0.5, the sort included) beside ops.nms on the same boxes at angle
+    0, and ops.roi_align_rotated on a C4 map (2 x 256 x 50 x 68, 512 RoIs with uniform angles, 7 x 7, scale 1 / 16, sampling_ratio 2),
+    float32 and bfloat16, forward and forward + backward, beside ops.roi_align on the RoIs' axis-aligned boxes.  Informational.
+
+    python tools/ops_bench.py --only rot             # just the rotated-box leg
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
     python tools/ops_bench.py --only droi            # just the deformable-RoI-pooling leg
     python tools/ops_bench.py --only deform          # just the deformable-convolution leg
@@ -293,6 +298,40 @@ def droi_leg(rng, reps, warmup):
     return res
 
 
+def rot_leg(rng, reps, warmup):
+    res = {}
+    nb = 12000
+    b = proposals(rng, nb, 600, 1000)[:, [1, 0, 3, 2]]
+    corners = torch.from_numpy(b).to(DEV)
+    angle = torch.from_numpy(rng.uniform(-np.pi, np.pi, nb).astype(np.float32)).to(DEV)
+    centre, size = (corners[:, :2] + corners[:, 2:]) / 2, corners[:, 2:] - corners[:, :2]
+    boxes = torch.cat([centre, size, angle[:, None]], 1)
+    scores = torch.rand((nb,), device=DEV)
+    kept = len(ops.nms_rotated(boxes, scores, 0.5)[1])
+    t_rot, t_plain = timed_pair(lambda: ops.nms_rotated(boxes, scores, 0.5), lambda: ops.nms(corners, scores, 0.5), reps, warmup)
+    res["nms_rotated %d boxes (0.5), %d kept" % (nb, kept)] = {"ops.nms_rotated": round(t_rot, 1), "ops.nms at angle 0": round(t_plain, 1)}
+    n, c, h, w, k, out, scale, sr = 2, 256, 50, 68, 512, (7, 7), 1 / 16, 2
+    props = proposals(rng, k, 800, 1088)[:, [1, 0, 3, 2]]
+    img = (np.arange(k) % n).astype(np.float32)[:, None]
+    plain = torch.from_numpy(np.concatenate([img, props], 1)).to(DEV)
+    rot = np.concatenate([img, (props[:, :2] + props[:, 2:]) / 2, props[:, 2:] - props[:, :2],
+                          rng.uniform(-np.pi, np.pi, (k, 1)).astype(np.float32)], 1)
+    rois = torch.from_numpy(rot.astype(np.float32)).to(DEV)
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((n, c, h, w), device=DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((k, c) + out, device=DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        xg = x.clone().requires_grad_(True)
+        r = {}
+        for name, fns in (("fwd", (lambda: ops.roi_align_rotated(x, rois, out, scale, sr), lambda: ops.roi_align(x, plain, out, scale, sr, True))),
+                          ("fwd+bwd", (lambda: ops.roi_align_rotated(xg, rois, out, scale, sr).backward(g),
+                                       lambda: ops.roi_align(xg, plain, out, scale, sr, True).backward(g)))):
+            t_rot, t_plain = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.roi_align_rotated": round(t_rot, 1), "ops.roi_align, axis-aligned": round(t_plain, 1),
+                       "rotated / axis-aligned": round(t_rot / t_plain, 2)}
+        res["rot %s 2 x 256 x 50 x 68, 512 RoIs, 7 x 7, sr 2" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -302,7 +341,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -323,6 +362,9 @@ def main():
         return
     if a.only == "droi":
         print(json.dumps(droi_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "rot":
+        print(json.dumps(rot_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -388,6 +430,7 @@ def main():
     res.update(ps_leg(rng, 10, 3))
     res.update(deform_leg(rng, 5, 2))
     res.update(droi_leg(rng, 5, 2))
+    res.update(rot_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
