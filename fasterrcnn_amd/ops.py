@@ -6,6 +6,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import deform_conv2d, DeformConv2d
     from fasterrcnn_amd.ops import deform_roi_pool, DeformRoIPool, DeformRoIPoolPack, ModulatedDeformRoIPoolPack
     from fasterrcnn_amd.ops import box_iou_rotated, nms_rotated, roi_align_rotated, RoIAlignRotated
+    from fasterrcnn_amd.ops import carafe, CARAFE, CARAFEPack
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -100,6 +101,28 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       Limits, layouts ([K, C, oh, ow] channels_last), channel padding and the batch-index rule are roi_align's; 16-bit maps run under
       the contract below, forward and backward, with RoIs in float32.  The gradient goes to input only; it is a deterministic gather
       without atomics (RoIs ascending, ROI_ALIGN_ROTATED_CULL_LIST per pass, then bins in (ph, pw) order).  Double backward raises.
+  carafe(features, masks, kernel_size, group_size, scale_factor) -> Tensor [N, C, s H, s W]
+  CARAFE(kernel_size, group_size, scale_factor).forward(features, masks)
+  CARAFEPack(channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1, compressed_channels=64).forward(x)
+      CARAFE, content-aware reassembly of features: the learned upsampler of mmdetection's FPN_CARAFE necks (csrc/ops_carafe.hip; mmcv's
+      carafe / CARAFE / CARAFEPack restated, unpinned: where the two differ include/frcnn_hip.h holds).  features [N, C, H, W]; masks
+      [N, G k k, s H, s W]; k = kernel_size odd, 1 <= k <= MAX_CARAFE_KERNEL = 7 (a thread keeps the k k mask values of its pixel in
+      registers); G = group_size >= 1 divides C; s = scale_factor in [1, MAX_CARAFE_SCALE = 8]; a violated limit is a ValueError that
+      names the value.  With r = (k - 1) / 2 and g = c // (C / G),
+          out[n, c, ph, pw] = sum over i, j in [0, k) of features[n, c, ph // s - r + i, pw // s - r + j] * masks[n, (g k + i) k + j, ph, pw]
+      where a tap outside the map contributes nothing (zero padding).  Gradients go to both tensors: d_features[n, c, y, x] sums
+      grad * mask over the k k s s output pixels whose window holds (y, x); d_masks[n, (g k + i) k + j, ph, pw] sums grad * feature over
+      the C / G channels of group g and is exactly 0 for a tap outside the map.  Both are gathers, deterministic and free of atomics
+      (two runs agree bit for bit); each is skipped when its argument needs none; double backward raises.  float32, and float16 /
+      bfloat16 under the contract below, forward and both gradients (sums in float32, one rounding on store); features and masks share
+      one dtype, else TypeError; float64 is a TypeError.  Contiguous NCHW is the native layout of features, masks and the result (what
+      torch's convolutions, pixel_shuffle and softmax produce); a channels_last argument is made contiguous by one copy; gradients come
+      back in each argument's own memory format.  N == 0 or C == 0 give empty tensors and zero gradients.  The kernels index a plane
+      with 32 bits: s H s W <= MAX_CARAFE_PLANE, N <= 65535, G ceil(C / G / 4) <= 65535 (the launch grid), else ValueError.
+      CARAFEPack owns mmcv's channel_compressor (1 x 1) and content_encoder convolutions under mmcv's names and init (Xavier-uniform,
+      then normal(0, 0.001) on content_encoder, zero biases), so mmcv / mmdetection checkpoints load strict; its forward is
+      content_encoder(channel_compressor(x)), pixel_shuffle(s), softmax over the k k taps of each group, then carafe: the convolutions,
+      the shuffle and the softmax are torch's.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -126,7 +149,8 @@ from . import _native as nv
 
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
-           "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated"]
+           "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
+           "carafe", "CARAFE", "CARAFEPack"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -138,6 +162,10 @@ MAX_ROTATED_IOU_ROWS = 65535 * 64         # rows of box_iou_rotated's matrix (th
 MAX_LEVELS = 8
 DEFORM_CHUNK_IMAGES = 32                  # images per chunk of deform_conv2d's column workspace (torchvision processes 32 at a time too)
 MAX_DEFORM_INDEX = 2 ** 31 - 1 - 1024     # what the 32-bit indices of csrc/ops_deform.hip hold: columns, cells and plan entries of a chunk
+MAX_CARAFE_KERNEL = 7                     # carafe's kernel_size: k k mask values in a thread's registers (CARAFE_MAX_KERNEL of csrc/ops_carafe.hip)
+MAX_CARAFE_SCALE = 8                      # carafe's scale_factor
+MAX_CARAFE_PLANE = 2 ** 31 - 1 - 1024     # elements of one upsampled plane, s H s W: the 32-bit indices inside a plane of csrc/ops_carafe.hip
+CARAFE_RUN = 4                            # channels a thread of carafe's d_features gather owns: G ceil(C / G / 4) blocks along the grid's y
 
 
 # ---- argument checks (the public functions; the custom ops assume them) -----------------------------------------------------------
@@ -1024,6 +1052,74 @@ torch.library.register_autograd("frcnn::roi_align_rotated_backward", _no_double_
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::carafe (plain NCHW; csrc/ops_carafe.hip) --------------------------------------------------------------------------------
+@torch.library.custom_op("frcnn::carafe", mutates_args=())
+def _carafe(features: Tensor, masks: Tensor, kernel_size: int, group_size: int, scale_factor: int) -> Tensor:
+    n, c, h, w = features.shape
+    out = torch.empty((n, c, h * scale_factor, w * scale_factor), dtype=features.dtype, device=features.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(features.device):
+        x, m = features.contiguous(), masks.contiguous()
+        _call("carafe", features, x.data_ptr(), m.data_ptr(), n, c, h, w, kernel_size, group_size, scale_factor, out.data_ptr(),
+              _stream(features))
+    return out
+
+
+@_carafe.register_fake
+def _(features, masks, kernel_size, group_size, scale_factor):
+    n, c, h, w = features.shape
+    return features.new_empty((n, c, h * scale_factor, w * scale_factor))
+
+
+@torch.library.custom_op("frcnn::carafe_backward", mutates_args=())
+def _carafe_backward(grad: Tensor, features: Tensor, masks: Tensor, kernel_size: int, group_size: int, scale_factor: int,
+                     needs: List[bool], channels_last: List[bool]) -> List[Tensor]:
+    """[d_features, d_masks]; needs: which of them are wanted (the other comes back as an empty placeholder and costs nothing);
+    channels_last: the memory format of features and masks, which their gradients take."""
+    n, c, h, w = features.shape
+    none = lambda: grad.new_empty((0,))                                    # noqa: E731
+    if grad.numel() == 0:
+        return [_droi_grad_format(torch.zeros_like(t, memory_format=torch.contiguous_format), cl) if need else none()
+                for t, need, cl in zip((features, masks), needs, channels_last)]
+    if not (needs[0] or needs[1]):
+        return [none(), none()]
+    with torch.cuda.device(grad.device):
+        g = grad.contiguous()
+        x = features.contiguous() if needs[1] else None
+        m = masks.contiguous() if needs[0] else None
+        dx = torch.empty(features.shape, dtype=grad.dtype, device=grad.device) if needs[0] else None
+        dm = torch.empty(masks.shape, dtype=grad.dtype, device=grad.device) if needs[1] else None
+        _call("carafe_backward", grad, _opt_ptr(x), _opt_ptr(m), g.data_ptr(), n, c, h, w, kernel_size, group_size, scale_factor,
+              _opt_ptr(dx), _opt_ptr(dm), _stream(grad))
+        return [_droi_grad_format(t, cl) if need else none() for t, need, cl in zip((dx, dm), needs, channels_last)]
+
+
+@_carafe_backward.register_fake
+def _(grad, features, masks, kernel_size, group_size, scale_factor, needs, channels_last):
+    return [_grad_empty(tuple(t.shape), grad, cl) if need else grad.new_empty((0,))
+            for t, need, cl in zip((features, masks), needs, channels_last)]
+
+
+def _carafe_setup(ctx, inputs, output):
+    features, masks = inputs[:2]
+    ctx.save_for_backward(features, masks)
+    ctx.args = tuple(inputs[2:])
+    ctx.channels_last = [_input_is_channels_last(features), _input_is_channels_last(masks)]
+
+
+def _carafe_bwd(ctx, grad):
+    features, masks = ctx.saved_tensors
+    needs = [bool(v) for v in ctx.needs_input_grad[:2]]
+    dx, dm = _carafe_backward(grad, features, masks, *ctx.args, needs, ctx.channels_last)
+    return (dx if needs[0] else None, dm if needs[1] else None, None, None, None)
+
+
+torch.library.register_autograd("frcnn::carafe", _carafe_bwd, setup_context=_carafe_setup)
+torch.library.register_autograd("frcnn::carafe_backward", _no_double_backward("frcnn::carafe"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- public interface -------------------------------------------------------------------------------------------------------------
 def nms(boxes, scores, iou_threshold):
     """torchvision.ops.nms: int64 indices of the kept boxes, by descending score."""
@@ -1225,6 +1321,50 @@ def roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_rati
     if int(sampling_ratio) > MAX_SAMPLING_RATIO:
         raise ValueError("sampling_ratio must be <= %d, got %d" % (MAX_SAMPLING_RATIO, sampling_ratio))
     return _roi_align_rotated(input, rois.float(), float(spatial_scale), oh, ow, int(sampling_ratio), bool(aligned), bool(clockwise))
+
+
+def _carafe_int(name, v, low, high, what=""):
+    if not isinstance(v, int) or isinstance(v, bool):
+        raise TypeError("%s must be an int, got %r" % (name, v))
+    if not low <= v <= high:
+        raise ValueError("%s must lie in [%d, %d]%s, got %d" % (name, low, high, what, v))
+    return v
+
+
+def carafe(features, masks, kernel_size, group_size, scale_factor):
+    """mmcv.ops.carafe: content-aware reassembly of features [N, C, H, W] with the per-pixel kernels masks [N, G * k * k, s * H, s * W]
+    (normally a softmax over each group's k * k taps): [N, C, s * H, s * W], contiguous."""
+    _check_tensor("features", features, _MAP_DTYPES, _MAP_WHAT)
+    _check_tensor("masks", masks, _MAP_DTYPES, _MAP_WHAT)
+    if features.dtype != masks.dtype:
+        raise TypeError("features and masks must have one dtype (float32, float16 or bfloat16), got %s and %s" % (features.dtype, masks.dtype))
+    _check_same_device(features, masks, "features", "masks")
+    if features.dim() != 4:
+        raise ValueError("features must be [N, C, H, W], got shape %s" % (tuple(features.shape),))
+    if masks.dim() != 4:
+        raise ValueError("masks must be [N, group_size * kernel_size ** 2, s * H, s * W], got shape %s" % (tuple(masks.shape),))
+    k = _carafe_int("kernel_size", kernel_size, 1, MAX_CARAFE_KERNEL, " (MAX_CARAFE_KERNEL)")
+    if k % 2 == 0:
+        raise ValueError("kernel_size must be odd, got %d" % k)
+    s = _carafe_int("scale_factor", scale_factor, 1, MAX_CARAFE_SCALE, " (MAX_CARAFE_SCALE)")
+    n, c, h, w = features.shape
+    g = _carafe_int("group_size", group_size, 1, 2 ** 31 - 1)
+    if c % g != 0:
+        raise ValueError("group_size must divide the channels of features, got group_size %d for %d channels" % (g, c))
+    if h < 1 or w < 1:
+        raise ValueError("features must have at least one cell, got shape %s" % (tuple(features.shape),))
+    if tuple(masks.shape) != (n, g * k * k, s * h, s * w):
+        raise ValueError("masks must be [N, group_size * kernel_size ** 2, s * H, s * W] = [%d, %d, %d, %d], got shape %s"
+                         % (n, g * k * k, s * h, s * w, tuple(masks.shape)))
+    if s * h * s * w > MAX_CARAFE_PLANE:
+        raise ValueError("carafe is too large for the kernels' 32-bit indices inside a plane: s * H * s * W = %d > MAX_CARAFE_PLANE = %d"
+                         % (s * h * s * w, MAX_CARAFE_PLANE))
+    if n > 65535:
+        raise ValueError("carafe takes at most 65535 images (the launch grid), got %d" % n)
+    if g * ((c // g + CARAFE_RUN - 1) // CARAFE_RUN) > 65535:
+        raise ValueError("carafe takes at most 65535 runs of %d channels over the groups (the launch grid), got %d for %d channels in %d "
+                         "groups" % (CARAFE_RUN, g * ((c // g + CARAFE_RUN - 1) // CARAFE_RUN), c, g))
+    return _carafe(features, masks, k, g, s)
 
 
 def _ms_features(features):
@@ -1514,3 +1654,65 @@ class ModulatedDeformRoIPoolPack(DeformRoIPoolPack):
         flat, pooled = self._pool(input, rois)
         oh, ow = self.output_size
         return pooled * self.mask_fc(flat).view(flat.shape[0], 1, oh, ow)
+
+
+class CARAFE(torch.nn.Module):
+    """mmcv.ops.CARAFE: carafe with the masks given by the caller."""
+
+    def __init__(self, kernel_size, group_size, scale_factor):
+        super().__init__()
+        self.kernel_size = int(kernel_size)
+        self.group_size = int(group_size)
+        self.scale_factor = int(scale_factor)
+
+    def forward(self, features, masks):
+        return carafe(features, masks, self.kernel_size, self.group_size, self.scale_factor)
+
+    def extra_repr(self):
+        return "kernel_size=%s, group_size=%s, scale_factor=%s" % (self.kernel_size, self.group_size, self.scale_factor)
+
+
+class CARAFEPack(torch.nn.Module):
+    """mmcv.ops.CARAFEPack: the upsampler with its kernel predictor.  channel_compressor (1 x 1) and content_encoder predict
+    up_group * up_kernel ** 2 * scale_factor ** 2 channels at the low resolution; pixel_shuffle spreads them over the s x s sub-pixels, a
+    softmax over the up_kernel ** 2 taps of each group normalises them, and carafe reassembles x with them."""
+
+    def __init__(self, channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1, compressed_channels=64):
+        super().__init__()
+        self.channels = channels
+        self.scale_factor = scale_factor
+        self.up_kernel = up_kernel
+        self.up_group = up_group
+        self.encoder_kernel = encoder_kernel
+        self.encoder_dilation = encoder_dilation
+        self.compressed_channels = compressed_channels
+        self.channel_compressor = torch.nn.Conv2d(channels, compressed_channels, 1)
+        self.content_encoder = torch.nn.Conv2d(compressed_channels, up_kernel * up_kernel * up_group * scale_factor * scale_factor,
+                                               encoder_kernel, padding=int((encoder_kernel - 1) * encoder_dilation / 2),
+                                               dilation=encoder_dilation)
+        self.init_weights()
+
+    def init_weights(self):
+        for m in (self.channel_compressor, self.content_encoder):
+            torch.nn.init.xavier_uniform_(m.weight)
+            torch.nn.init.zeros_(m.bias)
+        torch.nn.init.normal_(self.content_encoder.weight, mean=0.0, std=0.001)
+        torch.nn.init.zeros_(self.content_encoder.bias)
+
+    def kernel_normalizer(self, mask):
+        """pixel_shuffle to the high resolution, then a softmax over the up_kernel ** 2 taps of each group."""
+        mask = torch.nn.functional.pixel_shuffle(mask, self.scale_factor)
+        n, c, h, w = mask.shape
+        k2 = self.up_kernel * self.up_kernel
+        return torch.softmax(mask.view(n, c // k2, k2, h, w), dim=2).view(n, c, h, w).contiguous()
+
+    def masks(self, x):
+        return self.kernel_normalizer(self.content_encoder(self.channel_compressor(x)))
+
+    def forward(self, x):
+        return carafe(x, self.masks(x), self.up_kernel, self.up_group, self.scale_factor)
+
+    def extra_repr(self):
+        return "channels=%s, scale_factor=%s, up_kernel=%s, up_group=%s, encoder_kernel=%s, encoder_dilation=%s, compressed_channels=%s" % (
+            self.channels, self.scale_factor, self.up_kernel, self.up_group, self.encoder_kernel, self.encoder_dilation,
+            self.compressed_channels)

@@ -67,7 +67,9 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_deform_roi_pool, its _backward, _16, _workspace_bytes and _cull_list forms
                                  (deformable RoI pooling of DCN v1 / v2, mmcv's deform_roi_pool);
                                  still 21 (additions only): frcnn_ops_box_iou_rotated, frcnn_ops_nms_rotated, frcnn_ops_roi_align_rotated, its
-                                 _backward, _16 and _cull_list forms (rotated boxes: mmcv's box_iou_rotated, nms_rotated, roi_align_rotated) */
+                                 _backward, _16 and _cull_list forms (rotated boxes: mmcv's box_iou_rotated, nms_rotated, roi_align_rotated);
+                                 still 21 (additions only): frcnn_ops_carafe, its _backward and _16 forms and the frcnn_ops_carafe_max_kernel /
+                                 _channel_chunk / _tile_width / _tile_height getters (CARAFE upsampling: mmcv's carafe) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -702,6 +704,42 @@ int frcnn_ops_roi_align_rotated_16(int elem_type, const void* d_x, int n_img, in
 int frcnn_ops_roi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h,
                                             int out_w, float spatial_scale, int sampling_ratio, int aligned, int clockwise,
                                             const void* d_dout, void* d_dx, void* stream);
+
+/* CARAFE, content-aware reassembly of features (the learned upsampler of FPN_CARAFE necks; csrc/ops_carafe.hip): mmcv's carafe, restated
+ *   from its published definition (third party, absent here: restated, unpinned; where the two differ this text holds).
+ * Layouts: plain NCHW.  d_features [n][c][h][w], d_masks [n][group_size k k][s h][s w], d_out [n][c][s h][s w], with k = kernel_size odd,
+ *   1 <= k <= frcnn_ops_carafe_max_kernel() = 7 (k k mask values, or mask-gradient sums, live in a thread's registers), group_size >= 1
+ *   dividing c, s = scale_factor in [1, 8].  With r = (k - 1) / 2 and g = ch / (c / group_size):
+ *     out[b][ch][ph][pw] = sum over i (outer), j (inner) in [0, k) of
+ *         features[b][ch][ph / s - r + i][pw / s - r + j] * masks[b][(g k + i) k + j][ph][pw]
+ *   in float32, products and sums rounded separately, starting from +0; a tap outside the map counts as a feature of +0 (zero padding).
+ * frcnn_ops_carafe_backward: d_dfeatures [n][c][h][w] and d_dmasks [n][group_size k k][s h][s w], every element overwritten; either may
+ *   be NULL: that gradient is skipped (d_masks may then be NULL for d_dmasks alone, d_features for d_dfeatures alone).
+ *   d_dfeatures[b][ch][y][x] = the sum of dout * mask over the k k s s output pixels whose window holds (y, x), in the order
+ *   low-resolution cell (qy, qx) of the pixel row-major, then its sub-pixel (sy, sx) row-major; cells outside the map are skipped.
+ *   d_dmasks[b][(g k + i) k + j][ph][pw] = the sum of dout * feature over the c / group_size channels of group g ascending; exactly 0 for
+ *   a tap outside the map.  Both are gathers: deterministic, no atomics, no workspace.
+ * Tiling, exported because callers and tests place shapes on its seams: a forward block owns frcnn_ops_carafe_tile_height() = 4 rows of
+ *   frcnn_ops_carafe_tile_width() = 64 output pixels and walks frcnn_ops_carafe_channel_chunk() = 64 channels of one group per load of
+ *   its masks; the result does not depend on the tiling.
+ * The _16 forms take float16 / bfloat16 tensors (elem_type, one for the whole call) under the contract of the 16-bit operators above:
+ *   widened exactly on load, the float32 body, one rounding to nearest even on store.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): the limits above, n in [1, 65535], c, h, w >= 1,
+ *   s h s w <= 2^31 - 1025 (32-bit indices inside a plane, 64-bit plane bases), group_size * ceil(c / group_size / 4) <= 65535 (the launch
+ *   grid), NULL pointers, an elem_type other than FRCNN_OPS_F16 / FRCNN_OPS_BF16. */
+int frcnn_ops_carafe_max_kernel(void);
+int frcnn_ops_carafe_channel_chunk(void);
+int frcnn_ops_carafe_tile_width(void);
+int frcnn_ops_carafe_tile_height(void);
+int frcnn_ops_carafe(const float* d_features, const float* d_masks, int n, int c, int h, int w, int kernel_size, int group_size,
+                     int scale_factor, float* d_out, void* stream);
+int frcnn_ops_carafe_backward(const float* d_features, const float* d_masks, const float* d_dout, int n, int c, int h, int w,
+                              int kernel_size, int group_size, int scale_factor, float* d_dfeatures, float* d_dmasks, void* stream);
+int frcnn_ops_carafe_16(int elem_type, const void* d_features, const void* d_masks, int n, int c, int h, int w, int kernel_size,
+                        int group_size, int scale_factor, void* d_out, void* stream);
+int frcnn_ops_carafe_backward_16(int elem_type, const void* d_features, const void* d_masks, const void* d_dout, int n, int c, int h,
+                                 int w, int kernel_size, int group_size, int scale_factor, void* d_dfeatures, void* d_dmasks,
+                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -1,0 +1,179 @@
+"""CARAFE (fasterrcnn_amd.ops.carafe): two float64-capable restatements, the derived error bound and the cases of the CPU and GPU tests.
+No GPU is needed for anything in this file.
+
+Semantics (include/frcnn_hip.h): features [N, C, H, W], masks [N, G k k, s H, s W], r = (k - 1) / 2, g = c // (C / G),
+
+    out[n, c, ph, pw] = sum over i, j in [0, k) of features[n, c, ph // s - r + i, pw // s - r + j] * masks[n, (g k + i) k + j, ph, pw]
+
+with nothing from a tap outside the map.  carafe_ref states that with one term per tap; carafe_unfold states it independently with
+F.unfold, repeat_interleave and einsum.  Both are differentiable, so autograd in float64 gives the true gradients.
+
+The error bound is derived, not measured.  Any float32 evaluation of a sum of n products, in any order, with or without FMA, errs by at
+most (n + 1) * 2**-23 * sum|term_i| (gamma_n with u = 2**-24 is far below that).  So |got - truth| <= (n + 1) * 2**-23 * S elementwise,
+with S the same restatement on absolute values: the forward on (|x|, |m|) with n = k k; d_masks on (|grad|, |x|) with n = C / G;
+d_features on (|grad|, |m|) with n = k k s s.  Where S is 0 (a tap outside the map) the result must be exactly 0.  An indexing mistake
+is O(1) and lands orders of magnitude outside.  The bound assumes no underflow: the one case with denormal inputs draws masks and
+gradients from powers of two >= 1, so every product is exact and only additions round (an addition never underflows inexactly)."""
+import functools
+
+import torch
+import torch.nn.functional as F
+
+from fasterrcnn_amd import _native as nv
+
+F32, F64 = torch.float32, torch.float64
+CL = torch.channels_last
+UNIT = 2.0 ** -23
+
+_lib = nv.lib()
+MAX_KERNEL = _lib.frcnn_ops_carafe_max_kernel()
+CHUNK = _lib.frcnn_ops_carafe_channel_chunk()
+TILE_W = _lib.frcnn_ops_carafe_tile_width()
+TILE_H = _lib.frcnn_ops_carafe_tile_height()
+
+
+# ---- the restatements ----------------------------------------------------------------------------------------------------------------------
+def carafe_ref(features, masks, k, G, s, dtype=F64):
+    """The formula, one term per tap (i, j): the map shifted by the tap under zero padding, nearest-upsampled, times the tap's mask."""
+    x, m = features.to(dtype), masks.to(dtype)
+    n, c, h, w = x.shape
+    r = (k - 1) // 2
+    padded = F.pad(x, (r, r, r, r))                                         # padded[y + r, x + r] = x[y, x]; zeros outside
+    m = m.view(n, G, k * k, s * h, s * w)
+    out = torch.zeros((n, G, c // G if G else 0, s * h, s * w), dtype=dtype)
+    for i in range(k):
+        for j in range(k):
+            tap = padded[:, :, i:i + h, j:j + w]                             # tap[y, x] = x[y - r + i, x - r + j]
+            up = tap.repeat_interleave(s, dim=2).repeat_interleave(s, dim=3)  # up[ph, pw] = tap[ph // s, pw // s]
+            out = out + up.reshape(n, G, c // G, s * h, s * w) * m[:, :, i * k + j].unsqueeze(2)
+    return out.reshape(n, c, s * h, s * w)
+
+
+def carafe_unfold(features, masks, k, G, s, dtype=F64):
+    """The same function, independently: unfold the k x k neighbourhoods, upsample them, contract the taps with the masks."""
+    x, m = features.to(dtype), masks.to(dtype)
+    n, c, h, w = x.shape
+    cols = F.unfold(x, k, padding=(k - 1) // 2).view(n, G, c // G, k * k, h, w)
+    cols = cols.repeat_interleave(s, dim=4).repeat_interleave(s, dim=5)
+    return torch.einsum("ngckhw,ngkhw->ngchw", cols, m.view(n, G, k * k, s * h, s * w)).reshape(n, c, s * h, s * w)
+
+
+def gradients(fn, features, masks, grad, k, G, s, dtype=F64):
+    """(d_features, d_masks) of restatement fn by autograd, in dtype."""
+    x = features.to(dtype).clone().requires_grad_(True)
+    m = masks.to(dtype).clone().requires_grad_(True)
+    return torch.autograd.grad(fn(x, m, k, G, s, dtype), (x, m), grad.to(dtype))
+
+
+def d_features_ref(grad, masks, channels, k, G, s):
+    """d_features in float64: linear in (grad, masks) and independent of the features."""
+    n, _, oh, ow = grad.shape
+    return gradients(carafe_ref, torch.zeros((n, channels, oh // s, ow // s)), masks, grad, k, G, s)[0]
+
+
+def d_masks_ref(grad, features, k, G, s):
+    """d_masks in float64: linear in (grad, features) and independent of the masks."""
+    n, c, h, w = features.shape
+    return gradients(carafe_ref, features, torch.zeros((n, G * k * k, s * h, s * w)), grad, k, G, s)[1]
+
+
+def bounds(features, masks, grad, k, G, s):
+    """The derived elementwise bounds of the forward, d_features and d_masks (float64)."""
+    c = features.shape[1]
+    x, m, g = features.to(F64).abs(), masks.to(F64).abs(), grad.to(F64).abs()
+    return ((k * k + 1) * UNIT * carafe_ref(x, m, k, G, s),
+            (k * k * s * s + 1) * UNIT * d_features_ref(g, m, c, k, G, s),
+            (c // G + 1) * UNIT * d_masks_ref(g, x, k, G, s))
+
+
+def ratio(got, truth, bound):
+    """max err / bound over the elements with a positive bound; elements whose bound is 0 must be exact (returns inf otherwise)."""
+    err = (got.detach().cpu().to(F64) - truth).abs()
+    zero = bound == 0
+    if bool((err[zero] != 0).any()):
+        return float("inf")
+    if bool(zero.all()):
+        return 0.0
+    return float((err[~zero] / bound[~zero]).max())
+
+
+# ---- the hand-computed example -----------------------------------------------------------------------------------------------------------
+def hand_example():
+    """A 1 x 1 x 2 x 2 map [[1, 2], [3, 4]], k = 3, s = 2.  Tap t = 3 i + j of pixel (ph, pw) has mask (t + 1) * f with
+    f = 1 + 2 (ph % 2) + (pw % 2).  The pixels of cell (0, 0) see x00, x01, x10, x11 at taps 4, 5, 7, 8: 5 * 1 + 6 * 2 + 8 * 3 + 9 * 4 = 77;
+    cell (0, 1) sees them at taps 3, 4, 6, 7: 4 + 10 + 21 + 32 = 67; cell (1, 0) at taps 1, 2, 4, 5: 2 + 6 + 15 + 24 = 47; cell (1, 1)
+    at taps 0, 1, 3, 4: 1 + 4 + 12 + 20 = 37; each times the pixel's f."""
+    x = torch.tensor([[[[1.0, 2.0], [3.0, 4.0]]]], dtype=F64)
+    taps = torch.arange(1, 10, dtype=F64).view(1, 9, 1, 1)
+    f = torch.tensor([[1.0, 2.0, 1.0, 2.0], [3.0, 4.0, 3.0, 4.0], [1.0, 2.0, 1.0, 2.0], [3.0, 4.0, 3.0, 4.0]], dtype=F64)
+    want = torch.tensor([[77.0, 154.0, 67.0, 134.0],
+                         [231.0, 308.0, 201.0, 268.0],
+                         [47.0, 94.0, 37.0, 74.0],
+                         [141.0, 188.0, 111.0, 148.0]], dtype=F64).view(1, 1, 4, 4)
+    return x, taps * f.view(1, 1, 4, 4), want
+
+
+# ---- the cases ---------------------------------------------------------------------------------------------------------------------------
+# name: (N, C, H, W, k, G, s, flags).  The smallest shapes at which the kernels can go wrong; what each is for:
+CASES = {
+    "edges-2x3-k5": (1, 3, 2, 3, 5, 1, 2, ""),                    # the window hangs over every edge at once
+    "edges-1x1-k3": (1, 2, 1, 1, 3, 1, 2, ""),
+    "k1-g2": (1, 4, 5, 7, 1, 2, 2, ""),                           # k = 1; H != W
+    "k3-s3-c5": (1, 5, 4, 5, 3, 1, 3, ""),                        # s = 3: // s is no shift; C / G = 5, above one run of 4 channels
+    "k5-s1-g3": (1, 6, 5, 6, 5, 3, 1, ""),                        # s = 1; G = 3, C / G = 2
+    "k7-g2": (1, 6, 6, 9, 7, 2, 2, ""),                           # the largest kernel; C / G = 3
+    "tile+1-s1": (1, 2, TILE_H + 1, TILE_W + 1, 3, 1, 1, ""),     # s W and s H one past the forward tile (and the full LDS window)
+    "tile-1-s1": (1, 2, TILE_H - 1, TILE_W - 1, 3, 1, 1, ""),     # ... and one short of it
+    "65x5-s5": (1, 2, 1, 13, 3, 1, 5, ""),                        # s W = 65 = tile + 1 and s H = 5 = tile + 1 through s = 5
+    "63x3-s3": (1, 2, 1, 21, 5, 1, 3, ""),                        # s W = 63 and s H = 3: tile - 1 through s = 3
+    "two-tiles-s2": (1, 3, 3, 33, 5, 1, 2, ""),                   # 6 x 66 output: two tiles each way, a low-resolution cell on the seam
+    "chunk+1": (1, CHUNK + 1, 2, 3, 3, 1, 2, ""),                 # C one above the channel chunk
+    "chunk-1": (1, CHUNK - 1, 2, 3, 3, 1, 2, ""),                 # ... and one below
+    "chunk+1-g2": (1, 2 * (CHUNK + 1), 2, 2, 3, 2, 2, ""),        # chunks x groups along the grid
+    "n2": (2, 5, 3, 4, 3, 1, 2, ""),                              # the batch stride
+    "x-channels-last": (2, 6, 3, 4, 3, 3, 2, "x_cl"),
+    "m-channels-last": (2, 6, 3, 4, 3, 3, 2, "m_cl"),
+    "slices": (2, 6, 3, 4, 3, 3, 2, "slice"),                     # both arguments non-contiguous slices of larger tensors
+    "denormals": (1, 2, 4, 5, 3, 1, 2, "denormal"),               # +-0 and denormals among the features (see the module docstring)
+}
+HALF_CASES = ("edges-2x3-k5", "k3-s3-c5", "k7-g2")                # the 16-bit contract runs on these
+
+
+def seed_of(name):
+    return 1000 + list(CASES).index(name)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(features, masks, grad, k, G, s) of a case: float32 CPU tensors in the case's layout.  Cached: do not modify."""
+    n, c, h, w, k, G, s, flags = CASES[name]
+    gen = torch.Generator().manual_seed(seed_of(name))
+    rand = lambda *shape: torch.randn(shape, generator=gen, dtype=F32)      # noqa: E731
+    if flags == "slice":
+        x = rand(n, c + 2, h + 1, w + 3)[:, 1:c + 1, :h, 2:w + 2]
+        m = rand(n, G * k * k, s * h, s * w + 1)[..., 1:]
+        assert not x.is_contiguous() and not m.is_contiguous()
+    else:
+        x, m = rand(n, c, h, w), rand(n, G * k * k, s * h, s * w)
+    grad = rand(n, c, s * h, s * w)
+    if flags == "denormal":
+        pick = lambda t, values: torch.tensor(values, dtype=F32)[torch.randint(len(values), t.shape, generator=gen)]   # noqa: E731
+        m, grad = pick(m, [1.0, -1.0, 2.0, -2.0, 4.0]), pick(grad, [1.0, -1.0, 2.0, -2.0])
+        x = x.clone()
+        # the windows of the output pixels of cell (0, 0) see nothing but these four cells
+        x[0, :, :2, :2] = torch.tensor([[[0.0, 1e-40], [-3e-42, -0.0]], [[1.4e-45, -1e-39], [5e-41, 0.0]]], dtype=F32)
+        x[0, 0, 3, 4], x[0, 1, 2, 3] = -0.0, 2e-44
+    if flags == "x_cl":
+        x = x.contiguous(memory_format=CL)
+    if flags == "m_cl":
+        m = m.contiguous(memory_format=CL)
+    return x, m, grad, k, G, s
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """The float64 truth of a case, (out, d_features, d_masks), and the three bounds.  Cached and shared: do not modify."""
+    x, m, grad, k, G, s = case(name)
+    out = carafe_ref(x, m, k, G, s)
+    dx, dm = gradients(carafe_ref, x, m, grad, k, G, s)
+    return (out, dx, dm), bounds(x, m, grad, k, G, s)

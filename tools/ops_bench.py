@@ -38,6 +38,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     0, and ops.roi_align_rotated on a C4 map (2 x 256 x 50 x 68, 512 RoIs with uniform angles, 7 x 7, scale 1 / 16, sampling_ratio 2),
     float32 and bfloat16, forward and forward + backward, beside ops.roi_align on the RoIs' axis-aligned boxes.  Informational.
 
+  * carafe: CARAFE upsampling in an FPN top-down path (2 x 256 x 100 x 168 -> 200 x 336, k = 5, G = 1, masks a softmax over the 25
+    taps), float32 and float16: ops.carafe beside the torch composition (unfold, nearest upsample, multiply, sum over the taps, with
+    autograd's backward), forward and forward + backward of both gradients, in alternating windows; and the forward's algorithmic
+    bytes (features + masks + result, each once) per second as a share of the 8 TB/s HBM peak.
+
+    python tools/ops_bench.py --only carafe          # just the CARAFE leg
     python tools/ops_bench.py --only rot             # just the rotated-box leg
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
     python tools/ops_bench.py --only droi            # just the deformable-RoI-pooling leg
@@ -332,6 +338,39 @@ def rot_leg(rng, reps, warmup):
     return res
 
 
+HBM_PEAK = 8.0e12        # bytes / s, the MI355X's specified HBM3E peak
+
+
+def carafe_leg(rng, reps, warmup):
+    import torch.nn.functional as F
+    n, c, h, w, k, G, s = 2, 256, 100, 168, 5, 1, 2
+    gen = torch.Generator().manual_seed(0)
+
+    def composed(x, m):
+        cols = F.unfold(x, k, padding=(k - 1) // 2).view(n, c * k * k, h, w)
+        cols = F.interpolate(cols, scale_factor=s, mode="nearest").view(n, G, c // G, k * k, s * h, s * w)
+        return (cols * m.view(n, G, 1, k * k, s * h, s * w)).sum(3).view(n, c, s * h, s * w)
+    res = {}
+    for dtype in (torch.float32, torch.float16):
+        x = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype)
+        m = torch.softmax(torch.randn((n, G, k * k, s * h, s * w), generator=gen).to(DEV), dim=2).view(n, G * k * k, s * h, s * w).to(dtype)
+        g = torch.randn((n, c, s * h, s * w), generator=gen).to(DEV).to(dtype)
+        xg, mg = x.clone().requires_grad_(True), m.clone().requires_grad_(True)
+        y, yc = ops.carafe(x, m, k, G, s).float(), composed(x, m).float()
+        r = {"max |carafe - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        del y, yc
+        for name, fns in (("fwd", (lambda: ops.carafe(x, m, k, G, s), lambda: composed(x, m))),
+                          ("fwd+bwd", (lambda: ops.carafe(xg, mg, k, G, s).backward(g), lambda: composed(xg, mg).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.carafe": round(t_native, 1), "torch composition": round(t_comp, 1),
+                       "composition / carafe": round(t_comp / t_native, 2)}
+        nbytes = (x.numel() + m.numel() + g.numel()) * x.element_size()
+        r["fwd algorithmic bytes (features + masks + result)"] = nbytes
+        r["fwd bytes / s over the 8 TB/s HBM peak"] = round(nbytes / (r["fwd"]["ops.carafe"] * 1e-6) / HBM_PEAK, 3)
+        res["carafe %s 2 x 256 x 100 x 168 -> 200 x 336, k 5, G 1" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -341,7 +380,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -365,6 +404,9 @@ def main():
         return
     if a.only == "rot":
         print(json.dumps(rot_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "carafe":
+        print(json.dumps(carafe_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -431,6 +473,7 @@ def main():
     res.update(deform_leg(rng, 5, 2))
     res.update(droi_leg(rng, 5, 2))
     res.update(rot_leg(rng, 5, 2))
+    res.update(carafe_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
