@@ -13,7 +13,9 @@
 //   :147-153 torchvision.ops.nms(0.7)[0:N]     nms_mask_kernel (64x64 IoU bit tiles) +
 //                                              nms_reduce_kernel (one wave: 64 boxes per step,
 //                                              readlane over the diagonal word, a band of
-//                                              look-ahead words per row, early exit)
+//                                              look-ahead words per row, early exit); in two
+//                                              phases: the mask's leading NMS_BAND column chunks
+//                                              first, the rest only if the list needs them
 #include "geometry.h"
 #include <type_traits>
 
@@ -546,14 +548,36 @@ void topk_emit_kernel(const f32x4* __restrict__ tmp_boxes, const float* __restri
     else body(std::integral_constant<int, 1>());
 }
 
-// grid (nw, nw), one wave per 64x64 tile; only tiles on or above the diagonal are written.
+// The NMS runs in two phases where the kept list is short against the candidate list.  nms_reduce_kernel stops at the chunk in which
+// the last box is kept, and reads nothing of a row or a column behind it: on the workload's lists (6000 candidates, 300 kept) that is
+// chunk 15 to 19 of 94, i.e. about 200 of the 4465 tiles on or above the diagonal (profiles/r08/nms_band.txt).  So
+//   phase A: the mask's leading band, column chunks [0, NMS_BAND), and a reduce that may resolve NMS_BAND chunks.  If it keeps
+//            max_keep boxes, or runs out of boxes, it writes the outputs and sets the `done` word (ProposalScratch::keep[0]: written by
+//            every phase-A reduce, never cleared by the host);
+//   phase B: the other columns, [NMS_BAND, nw), with every row chunk by <= bx, and the whole reduce again from chunk 0.  Both launches
+//            read `done` first and return at once where it is set: a few microseconds of empty launches on every list the band covers,
+//            and the full cost (plus phase A's reduce) only on a list that keeps its boxes later than any measured one.
+// NMS_BAND = the smallest multiple of 8 that is >= 1.5 x the largest stopping chunk seen over the golden image, the hold-out images and
+// the benchmark's pool (19: tools/nms_band.py, profiles/r08/nms_band.txt).
+static constexpr int NMS_BAND = 32;
+
+__host__ __device__ __forceinline__ int nms_tri(int k) { return k * (k + 1) / 2; }       // tiles with by <= bx < k
+
+// One wave per 64x64 tile, over a one-dimensional grid of exactly the tiles with by <= bx and bx in [bx_begin, bx_end): block t is
+// tile number nms_tri(bx_begin) + t in column-major order (column bx holds tiles nms_tri(bx) .. nms_tri(bx + 1) - 1, by ascending).
+// `done` != NULL and *done != 0: the list is already reduced, nothing is read or written.
 __global__ __launch_bounds__(64)
 void nms_mask_kernel(const f32x4* __restrict__ boxes, const int32_t* __restrict__ n_ptr, float thr,
-                     int nw_stride, u64* __restrict__ mask)
+                     int nw_stride, u64* __restrict__ mask, int bx_begin, const int32_t* __restrict__ done)
 {
+    if (done != nullptr && *done != 0) return;
     const int n = *n_ptr;
-    const int by = blockIdx.y, bx = blockIdx.x;
-    if (bx < by || by * 64 >= n || bx * 64 >= n) return;
+    const int tile = nms_tri(bx_begin) + (int)blockIdx.x;        // < nms_tri(256) = 32896: exact in float
+    int bx = (int)((sqrtf(8.f * (float)tile + 1.f) - 1.f) * 0.5f);
+    while (nms_tri(bx + 1) <= tile) ++bx;                        // (the square root may be one off either way)
+    while (nms_tri(bx) > tile) --bx;
+    const int by = tile - nms_tri(bx);
+    if (bx * 64 >= n) return;                                    // (by <= bx: the row chunk exists where the column chunk does)
     __shared__ f32x4 colb[64];
     const int t = threadIdx.x;
     const int jn = bx * 64 + t;
@@ -603,7 +627,7 @@ static constexpr int NMS_LDS_BYTES = 2 * NMS_SLOT_BYTES;            // 50 KB of 
 typedef __attribute__((address_space(3))) void* nms_lds_ptr;
 static_assert(NMS_DMA <= 63, "the look-ahead must fit the 6-bit vmcnt");
 
-// -DNMS_CLOCKS (tools/nms_clocks.py; timing only, the last two proposals are overwritten): where the kernel's time goes, in 10 ns ticks
+// -DNMS_CLOCKS (tools/nms_clocks.py, tools/nms_band.py; timing only, the last four proposals are overwritten): where the kernel's time goes, in 10 ns ticks
 #ifdef NMS_CLOCKS
 #define NMS_T(k) do { const unsigned long long _t = __builtin_amdgcn_s_memrealtime(); if ((k) != 0 || nms_tl != 0) nms_acc[k] += (float)(_t - nms_tl); nms_tl = _t; } while (0)
 #else
@@ -615,8 +639,12 @@ void nms_reduce_kernel(const u64* __restrict__ mask, int nw_stride, const int32_
                        int max_keep, const f32x4* __restrict__ cand_boxes,
                        const int32_t* __restrict__ order,      // optional map to input indices
                        int32_t* __restrict__ keep, f32x4* __restrict__ props,
-                       int32_t* __restrict__ n_keep_out)
+                       int32_t* __restrict__ n_keep_out,
+                       int c_limit,                            // chunks this launch may resolve
+                       const int32_t* __restrict__ done_in,    // optional: non-zero = an earlier launch has reduced this list, return at once
+                       int32_t* __restrict__ done_out)         // optional: 1 = the outputs are written, 0 = c_limit chunks were not enough (no output)
 {
+    if (done_in != nullptr && *done_in != 0) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char nms_ring_lds[];               // NMS_LDS_BYTES
     unsigned char* const ring = nms_ring_lds;
     __shared__ int32_t kept_list[2048];
@@ -670,7 +698,13 @@ void nms_reduce_kernel(const u64* __restrict__ mask, int nw_stride, const int32_
             //  128 .. 255 -- the lower half there made box 0 remove candidate 8192 + j with every box j it removes: ADVICE r5)
             for (int u = 0; u < NMS_PIECES; ++u) dma_piece(0, wide && (u & 1), slot + 1024 + u * 1024);
         }
-        for (int c = 0; c < nw; ++c) {
+        // c_limit < nw is phase A of a banded NMS: only the mask's column chunks < c_limit are written, every word >= c_limit of a row holds
+        // stale bytes (the storage doubles as the top-N's scratch).  The kept rows are fetched whole, so removed[] carries garbage in its
+        // words >= c_limit, and so does `fq` after chunk c_limit - 1 (word c_limit of the band).  Nothing is ever decided from them: a chunk
+        // c reads word c of removed[] and the `fq` of chunk c - 1 only, and this loop resolves no chunk >= c_limit; a launch that stops here
+        // unfinished writes no output, and the launch that finishes the list starts again from chunk 0 on a complete mask.
+        const int c_end = min(nw, c_limit);
+        for (int c = 0; c < c_end; ++c) {
             NMS_T(0);
             unsigned char* slot = ring + (c & 1) * NMS_SLOT_BYTES;
             // The slot of this chunk was filled two chunks ago (or above): the previous chunk's NMS_DMA instructions are the only younger ones.
@@ -794,6 +828,11 @@ void nms_reduce_kernel(const u64* __restrict__ mask, int nw_stride, const int32_
         NMS_T(7);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (no DMA may still be writing the block's LDS when it ends)
     }
+    if (room > 0 && c_done < nw) {                               // unfinished (wave-uniform): the list needs chunks this launch may not resolve
+        if (lane == 0 && done_out != nullptr) *done_out = 0;
+        return;
+    }
+    if (lane == 0 && done_out != nullptr) *done_out = 1;
     __syncthreads();
     // kept_list from the chunks' kept bits: lane l expands chunks l, l + 64, ... (its boxes start behind those of all earlier chunks)
     int kept = 0;
@@ -832,6 +871,7 @@ void nms_reduce_kernel(const u64* __restrict__ mask, int nw_stride, const int32_
         props[max_keep - 1] = f32x4{nms_acc[1], nms_acc[2], nms_acc[3], nms_acc[4]};
         props[max_keep - 2] = f32x4{nms_acc[5], nms_acc[6], (float)(t_out - nms_t_in), (float)c_done};
         props[max_keep - 3] = f32x4{nms_acc[0], nms_acc[7], (float)n, (float)kept};
+        props[max_keep - 4] = f32x4{done_in != nullptr ? 1.f : 0.f, (float)c_limit, 0.f, 0.f};      // 1 = written by phase B's reduce: `done` read 0 behind phase A
     }
 #endif
 }
@@ -906,6 +946,39 @@ static int launch_topk(const u64* keys, int n_keys, int K, const float* boxes_sr
     return check_launch();
 }
 
+// The NMS of ps.cand_boxes (score-descending, *n_ptr <= 64 nw of them): mask and reduce, in one phase or in two (see NMS_BAND)
+static int launch_nms_phases(const ProposalScratch& ps, const int32_t* n_ptr, int nw, bool banded, float thr, int max_keep,
+                             const int32_t* order, int32_t* keep, f32x4* props, int32_t* n_keep, hipStream_t s)
+{
+    const int nw_stride = ps.pre_cap / 64;
+    const f32x4* boxes = reinterpret_cast<const f32x4*>(ps.cand_boxes);
+    int32_t* done = ps.keep;                     // (nothing else lives there)
+    FRCNN_MAX_LDS_ONCE(nms_reduce_kernel, NMS_LDS_BYTES);
+    int rc;
+    if (!banded) {
+        hipLaunchKernelGGL(nms_mask_kernel, dim3(nms_tri(nw)), dim3(64), 0, s, boxes, n_ptr, thr, nw_stride, ps.mask, 0, (const int32_t*)nullptr);
+        rc = check_launch();
+        if (rc) return rc;
+        hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(64), NMS_LDS_BYTES, s, ps.mask, nw_stride, n_ptr, max_keep, boxes, order, keep,
+                           props, n_keep, nw, (const int32_t*)nullptr, (int32_t*)nullptr);
+        return check_launch();
+    }
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(nms_tri(NMS_BAND)), dim3(64), 0, s, boxes, n_ptr, thr, nw_stride, ps.mask, 0, (const int32_t*)nullptr);
+    rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(64), NMS_LDS_BYTES, s, ps.mask, nw_stride, n_ptr, max_keep, boxes, order, keep,
+                       props, n_keep, NMS_BAND, (const int32_t*)nullptr, done);
+    rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(nms_tri(nw) - nms_tri(NMS_BAND)), dim3(64), 0, s, boxes, n_ptr, thr, nw_stride, ps.mask, NMS_BAND,
+                       (const int32_t*)done);
+    rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(64), NMS_LDS_BYTES, s, ps.mask, nw_stride, n_ptr, max_keep, boxes, order, keep,
+                       props, n_keep, nw, (const int32_t*)done, done);
+    return check_launch();
+}
+
 int launch_rpn_proposals(const ProposalScratch& ps, const float* head, int ld_head,
                          const float* anchor_map, const float* valid_map, int fh, int fw,
                          int image_h, int image_w, int pre_nms, int post_nms, float nms_thr,
@@ -924,17 +997,9 @@ int launch_rpn_proposals(const ProposalScratch& ps, const float* head, int ld_he
     rc = launch_topk<0>(ps.keys, A, pre_nms, ps.boxes_all, (float)image_h, (float)image_w, min_side,
                         sorted_idx, ps.cand_boxes, ps.cand_scores, counts, s, ps.mask);
     if (rc) return rc;
-    const int nw = cdiv(pre_nms, 64);
-    const int nw_stride = ps.pre_cap / 64;
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(nw, nw), dim3(64), 0, s,
-                       reinterpret_cast<const f32x4*>(ps.cand_boxes), counts + 1, nms_thr, nw_stride, ps.mask);
-    rc = check_launch();
-    if (rc) return rc;
-    FRCNN_MAX_LDS_ONCE(nms_reduce_kernel, NMS_LDS_BYTES);
-    hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(64), NMS_LDS_BYTES, s, ps.mask, nw_stride, counts + 1, post_nms,
-                       reinterpret_cast<const f32x4*>(ps.cand_boxes), (const int32_t*)nullptr,
-                       (int32_t*)nullptr, reinterpret_cast<f32x4*>(props), counts + 2);
-    return check_launch();
+    // post_nms is small against pre_nms in every use of the RPN: banded wherever there is anything behind the band
+    return launch_nms_phases(ps, counts + 1, cdiv(pre_nms, 64), cdiv(pre_nms, 64) > NMS_BAND, nms_thr, post_nms, nullptr, nullptr,
+                             reinterpret_cast<f32x4*>(props), counts + 2, s);
 }
 
 int launch_nms(const ProposalScratch& ps, const float* boxes, const float* scores, int n, float thr,
@@ -953,16 +1018,14 @@ int launch_nms(const ProposalScratch& ps, const float* boxes, const float* score
     int32_t* counts = order + ps.a_cap;          // boxes_all holds 4*a_cap floats; use [a_cap, a_cap+4)
     rc = launch_topk<1>(ps.keys, n, n, boxes, 0.f, 0.f, 0.f, order, ps.cand_boxes, ps.cand_scores, counts, s);
     if (rc) return rc;
+    // Two phases only where they can pay.  The band was measured on lists that keep a box in four of their best-scored candidates (300
+    // within 19 chunks of 64), with a margin of 1.5: a caller that wants more than a quarter of the band's 64 NMS_BAND boxes is likely
+    // to need phase B, and then pays phase A's reduce twice.  And what the band saves must outweigh phase B's two empty launches (a few
+    // microseconds, about a thousand tiles of the mask): at least as many column chunks behind the band as in it, i.e. under a quarter
+    // of the tiles in phase A.  Every other call is one mask over the triangle and one reduce.
     const int nw = cdiv(n, 64);
-    const int nw_stride = ps.pre_cap / 64;
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(nw, nw), dim3(64), 0, s,
-                       reinterpret_cast<const f32x4*>(ps.cand_boxes), counts + 1, thr, nw_stride, ps.mask);
-    rc = check_launch();
-    if (rc) return rc;
-    FRCNN_MAX_LDS_ONCE(nms_reduce_kernel, NMS_LDS_BYTES);
-    hipLaunchKernelGGL(nms_reduce_kernel, dim3(1), dim3(64), NMS_LDS_BYTES, s, ps.mask, nw_stride, counts + 1, max_keep,
-                       reinterpret_cast<const f32x4*>(ps.cand_boxes), order, keep, (f32x4*)nullptr, n_keep);
-    return check_launch();
+    const bool banded = nw >= 2 * NMS_BAND && 4 * max_keep <= 64 * NMS_BAND;
+    return launch_nms_phases(ps, counts + 1, nw, banded, thr, max_keep, order, keep, nullptr, n_keep, s);
 }
 
 }  // namespace frcnn

@@ -1,6 +1,6 @@
 """tools/nms_clocks.py -- where nms_reduce_kernel (csrc/proposals.hip) spends its time on the workload's candidate lists.
 Needs a library built with -DNMS_CLOCKS:  SRC=proposals tools/build_ablate.sh nmsclk -DNMS_CLOCKS ; FRCNN_LIB_PATH=build/libfrcnn_nmsclk.so
-(the kernel leaves its clocks in the last three proposals: the forward's results are wrong in that build)."""
+(the kernel leaves its clocks in the last four proposals: the forward's results are wrong in that build)."""
 import sys
 import torch
 sys.path.insert(0, ".")
