@@ -74,6 +74,9 @@ SYMBOLS = (
     "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
     "frcnn_ops_carafe", "frcnn_ops_carafe_backward", "frcnn_ops_carafe_16", "frcnn_ops_carafe_backward_16",
+    "frcnn_ops_msda_max_levels", "frcnn_ops_msda_max_points", "frcnn_ops_msda_max_channels", "frcnn_ops_msda_block_items",
+    "frcnn_ops_msda_segment", "frcnn_ops_msda_workspace_bytes", "frcnn_ops_msda_forward", "frcnn_ops_msda_backward_loc", "frcnn_ops_msda_plan",
+    "frcnn_ops_msda_backward_value", "frcnn_ops_msda_forward_16", "frcnn_ops_msda_backward_loc_16", "frcnn_ops_msda_backward_value_16",
 )
 
 
@@ -317,6 +320,20 @@ _SIGNATURES = {
     "frcnn_ops_carafe_backward": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_carafe_16": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "frcnn_ops_carafe_backward_16": (C.c_int, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    # multi-scale deformable attention (csrc/ops_msda.hip); the _16 forms take the element-type code first
+    "frcnn_ops_msda_max_levels": (C.c_int, []),
+    "frcnn_ops_msda_max_points": (C.c_int, []),
+    "frcnn_ops_msda_max_channels": (C.c_int, []),
+    "frcnn_ops_msda_block_items": (C.c_int, [_i, _i, _i, _i]),
+    "frcnn_ops_msda_segment": (C.c_int, []),
+    "frcnn_ops_msda_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "frcnn_ops_msda_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_msda_backward_loc": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_msda_plan": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_msda_backward_value": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_msda_forward_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_msda_backward_loc_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_msda_backward_value_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

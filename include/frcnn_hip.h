@@ -69,7 +69,10 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_box_iou_rotated, frcnn_ops_nms_rotated, frcnn_ops_roi_align_rotated, its
                                  _backward, _16 and _cull_list forms (rotated boxes: mmcv's box_iou_rotated, nms_rotated, roi_align_rotated);
                                  still 21 (additions only): frcnn_ops_carafe, its _backward and _16 forms and the frcnn_ops_carafe_max_kernel /
-                                 _channel_chunk / _tile_width / _tile_height getters (CARAFE upsampling: mmcv's carafe) */
+                                 _channel_chunk / _tile_width / _tile_height getters (CARAFE upsampling: mmcv's carafe);
+                                 still 21 (additions only): frcnn_ops_msda_forward, _backward_loc, _plan, _backward_value, _workspace_bytes, the _16
+                                 forms and the frcnn_ops_msda_max_levels / _max_points / _max_channels / _block_items / _segment getters (multi-scale deformable
+                                 attention: mmcv's ms_deform_attn) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -740,6 +743,68 @@ int frcnn_ops_carafe_16(int elem_type, const void* d_features, const void* d_mas
 int frcnn_ops_carafe_backward_16(int elem_type, const void* d_features, const void* d_masks, const void* d_dout, int n, int c, int h,
                                  int w, int kernel_size, int group_size, int scale_factor, void* d_dfeatures, void* d_dmasks,
                                  void* stream);
+
+/* Multi-scale deformable attention, the sampling core of Deformable DETR (csrc/ops_msda.hip): mmcv's ms_deform_attn, restated from the
+ *   published algorithm (third party, absent here: restated, unpinned; where the two differ this text holds).
+ * Tensors: d_value [n][s][m][d] (s cells over all levels, m heads, d channels per head); d_shapes int64 [levels][2] rows (H_l, W_l);
+ *   d_starts int64 [levels]; d_loc float32 [n][q][m][levels][points][2], last axis (x, y) with [0, 1] spanning the level; d_attn float32
+ *   [n][q][m][levels][points]; d_out and d_dout [n][q][m d].  Sample (b, q, m, l, p): x = fmaf(loc_x, W_l, -0.5f), y = fmaf(loc_y, H_l,
+ *   -0.5f) in float32; it counts iff x > -1 && y > -1 && x < W_l && y < H_l (a NaN coordinate fails); its corners are (y0, x0), (y0, x1),
+ *   (y1, x0), (y1, x1) with y0 = floor(y), y1 = y0 + 1, ly = y - y0, hy = 1 - ly (likewise x) and the weights hy hx, hy lx, ly hx, ly lx;
+ *   corner (yy, xx) is cell start_l + yy W_l + xx of value[b][:][m][:] and counts 0 outside [0, H_l - 1] x [0, W_l - 1].
+ *     out[b][q][m d + c] = sum over (l, p) ascending of attn * (w0 v0 + w1 v1 + w2 v2 + w3 v3)      (float32, rounded separately)
+ * The shape tensors are device memory that the kernels read; no entry point copies them to the host.  They are not trusted: a level
+ *   with H_l or W_l outside [1, 2^24] or start_l outside [-2^50, s) contributes nothing, a corner whose cell index falls outside [0, s)
+ *   contributes nothing and receives nothing, a cell no sample reaches gets a zero gradient.
+ * frcnn_ops_msda_backward_loc: d_dloc (shaped as d_loc) and d_dattn (as d_attn), every element overwritten, one store each; either may
+ *   be NULL (not both).  d_dattn = sum over c of dout * sample; d_dloc x = W_l * sum over c of (dout * attn) * ((hy v1 - hy v0) + (ly v3
+ *   - ly v2)) and y = H_l * sum of (dout * attn) * ((hx v2 - hx v0) + (lx v3 - lx v1)) over the validly indexed corners (a corner that
+ *   counts 0 enters as 0): the right-hand slope at an integer coordinate; both 0 for a sample that does not count.  The sum over c is
+ *   a lane's channels ascending, then an xor butterfly over the lanes of the item: a fixed order.
+ * frcnn_ops_msda_plan + frcnn_ops_msda_backward_value: the value gradient without atomics.  The plan writes one entry per sample and
+ *   corner, e = ((((b q_n + q) m_n + m) levels + l) points + p) 4 + corner: d_keys[e] = (b s + cell) m_n + m, or the sentinel n s m for a
+ *   corner that counts 0, and d_weights[e] = corner weight * attn.  The caller sorts the keys STABLY (sorted keys + the permutation,
+ *   int64 each) and passes them on; d_dvalue[b][cell][m][:] = the sum over the cell's entries in ascending e of weight *
+ *   dout[b][q][m][:], every cell written.  A cell with more than frcnn_ops_msda_segment() = 512 entries (every query samples the
+ *   few cells of a coarse level) is summed in pieces of 512 entries, cut from the segment's own start: each piece's sum ascending, then
+ *   the pieces' sums in ascending order.  A cell's entries belong to its own image and the cuts depend on the segment alone: chunking
+ *   the images changes no bit.  d_ws: frcnn_ops_msda_workspace_bytes(n, s, m, d, q, levels, points) bytes (the segment starts and the
+ *   pieces' sums), 16-byte aligned.
+ * Mapping, exported because callers and tests place shapes on its seams: a group of lanes serves one (b, q, m); a lane owns runs of 4
+ *   float32 (8 16-bit) channels when d holds whole runs and the tensors are 16-byte aligned, else single channels;
+ *   frcnn_ops_msda_block_items(d, levels, points, elem_type) (elem_type 0: float32) is the number of (b, q, m) a block serves for
+ *   aligned tensors, 0 for arguments out of range.  The result does not depend on the mapping's block size.
+ * The _16 forms take float16 / bfloat16 value, dout, out and d_value (elem_type) under the contract of the 16-bit operators above:
+ *   widened exactly on load, the float32 body, one rounding to nearest even on store; loc, attn and their gradients stay float32.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): n, s, m, q >= 1, 1 <= d <= frcnn_ops_msda_max_channels() = 256,
+ *   1 <= levels <= frcnn_ops_msda_max_levels() = 8, 1 <= points <= frcnn_ops_msda_max_points() = 16, n s m <= 2^31 - 1025 and
+ *   n q m levels points 4 <= 2^31 - 1025 (32-bit cell and entry indices; element offsets are 64-bit), NULL pointers, a workspace that
+ *   is NULL, misaligned or too small, an unknown elem_type. */
+int frcnn_ops_msda_max_levels(void);
+int frcnn_ops_msda_max_points(void);
+int frcnn_ops_msda_max_channels(void);
+int frcnn_ops_msda_block_items(int d, int levels, int points, int elem_type);
+int frcnn_ops_msda_segment(void);
+size_t frcnn_ops_msda_workspace_bytes(int n_img, int s, int m, int d, int q, int levels, int points);
+int frcnn_ops_msda_forward(const float* d_value, const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc, const float* d_attn,
+                           int n_img, int s, int m, int d, int q, int levels, int points, float* d_out, void* stream);
+int frcnn_ops_msda_backward_loc(const float* d_value, const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc,
+                                const float* d_attn, const float* d_dout, int n_img, int s, int m, int d, int q, int levels, int points,
+                                float* d_dloc, float* d_dattn, void* stream);
+int frcnn_ops_msda_plan(const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc, const float* d_attn, int n_img, int s, int m,
+                        int q, int levels, int points, int64_t* d_keys, float* d_weights, void* stream);
+int frcnn_ops_msda_backward_value(const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights, const float* d_dout,
+                                  int n_img, int s, int m, int d, int q, int levels, int points, float* d_dvalue, void* d_ws,
+                                  size_t ws_bytes, void* stream);
+int frcnn_ops_msda_forward_16(int elem_type, const void* d_value, const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc,
+                              const float* d_attn, int n_img, int s, int m, int d, int q, int levels, int points, void* d_out,
+                              void* stream);
+int frcnn_ops_msda_backward_loc_16(int elem_type, const void* d_value, const int64_t* d_shapes, const int64_t* d_starts,
+                                   const float* d_loc, const float* d_attn, const void* d_dout, int n_img, int s, int m, int d, int q,
+                                   int levels, int points, float* d_dloc, float* d_dattn, void* stream);
+int frcnn_ops_msda_backward_value_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
+                                     const void* d_dout, int n_img, int s, int m, int d, int q, int levels, int points, void* d_dvalue,
+                                     void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -43,6 +43,13 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     autograd's backward), forward and forward + backward of both gradients, in alternating windows; and the forward's algorithmic
     bytes (features + masks + result, each once) per second as a share of the 8 TB/s HBM peak.
 
+  * msda: multi-scale deformable attention in a Deformable-DETR encoder layer (B 2; levels 100 x 134, 50 x 67, 25 x 34, 13 x 17, so
+    S = 17821; M 8, D 32, P 4; Q = S, every query's reference point its own cell's centre on every level, offsets N(0, 2 px), weights a
+    softmax over the 16 samples), float32 and float16: ops.multi_scale_deformable_attn beside ops.multi_scale_deformable_attn_pytorch
+    (one grid_sample per level, autograd's backward), forward and forward + backward of all three gradients, in alternating windows;
+    and the forward's algorithmic bytes (value + locations + weights + result, each once) per second as a share of the HBM peak.
+
+    python tools/ops_bench.py --only msda            # just the deformable-attention leg
     python tools/ops_bench.py --only carafe          # just the CARAFE leg
     python tools/ops_bench.py --only rot             # just the rotated-box leg
     python tools/ops_bench.py --only multiscale      # just the multi-scale leg
@@ -371,6 +378,42 @@ def carafe_leg(rng, reps, warmup):
     return res
 
 
+def msda_leg(rng, reps, warmup):
+    b, m, d, p = 2, 8, 32, 4
+    shapes = [(100, 134), (50, 67), (25, 34), (13, 17)]
+    gen = torch.Generator().manual_seed(0)
+    spatial = torch.tensor(shapes, dtype=torch.int64, device=DEV)
+    starts = torch.tensor([sum(h * w for h, w in shapes[:l]) for l in range(len(shapes))], dtype=torch.int64, device=DEV)
+    s = q = sum(h * w for h, w in shapes)
+    # the encoder's reference points: the centre of the query's own cell, normalised, the same on every level
+    centres = torch.cat([torch.stack(torch.meshgrid((torch.arange(h) + 0.5) / h, (torch.arange(w) + 0.5) / w, indexing="ij"), -1).view(-1, 2)
+                         for h, w in shapes])[:, [1, 0]]                                    # (x, y)
+    norm = torch.tensor([[w, h] for h, w in shapes], dtype=torch.float32)
+    loc = (centres.view(1, q, 1, 1, 1, 2) + 2.0 * torch.randn((b, q, m, len(shapes), p, 2), generator=gen) / norm.view(1, 1, 1, -1, 1, 2))
+    res = {}
+    for dtype in (torch.float32, torch.float16):
+        v = torch.randn((b, s, m, d), generator=gen).to(DEV).to(dtype)
+        lo = loc.to(DEV).to(dtype)
+        a = torch.softmax(torch.randn((b, q, m, len(shapes) * p), generator=gen), -1).view(b, q, m, len(shapes), p).to(DEV).to(dtype)
+        g = torch.randn((b, q, m * d), generator=gen).to(DEV).to(dtype)
+        vg, lg, ag = (t.clone().requires_grad_(True) for t in (v, lo, a))
+        native = lambda *t: ops.multi_scale_deformable_attn(t[0], spatial, starts, t[1], t[2])          # noqa: E731
+        composed = lambda *t: ops.multi_scale_deformable_attn_pytorch(t[0], spatial, t[1], t[2])       # noqa: E731
+        y, yc = native(v, lo, a).float(), composed(v, lo, a).float()
+        r = {"max |ops - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        del y, yc
+        for name, fns in (("fwd", (lambda: native(v, lo, a), lambda: composed(v, lo, a))),
+                          ("fwd+bwd", (lambda: native(vg, lg, ag).backward(g), lambda: composed(vg, lg, ag).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.multi_scale_deformable_attn": round(t_native, 1), "multi_scale_deformable_attn_pytorch": round(t_comp, 1),
+                       "composition / ops": round(t_comp / t_native, 2)}
+        nbytes = (v.numel() + lo.numel() + a.numel() + g.numel()) * v.element_size()
+        r["fwd algorithmic bytes (value + locations + weights + result)"] = nbytes
+        r["fwd bytes / s over the 8 TB/s HBM peak"] = round(nbytes / (r["fwd"]["ops.multi_scale_deformable_attn"] * 1e-6) / HBM_PEAK, 3)
+        res["msda %s encoder layer B 2, S = Q = 17821 over 4 levels, M 8, D 32, P 4" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -380,7 +423,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -407,6 +450,9 @@ def main():
         return
     if a.only == "carafe":
         print(json.dumps(carafe_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "msda":
+        print(json.dumps(msda_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -474,6 +520,7 @@ def main():
     res.update(droi_leg(rng, 5, 2))
     res.update(rot_leg(rng, 5, 2))
     res.update(carafe_leg(rng, 5, 2))
+    res.update(msda_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
