@@ -77,6 +77,8 @@ SYMBOLS = (
     "frcnn_ops_msda_max_levels", "frcnn_ops_msda_max_points", "frcnn_ops_msda_max_channels", "frcnn_ops_msda_block_items",
     "frcnn_ops_msda_segment", "frcnn_ops_msda_workspace_bytes", "frcnn_ops_msda_forward", "frcnn_ops_msda_backward_loc", "frcnn_ops_msda_plan",
     "frcnn_ops_msda_backward_value", "frcnn_ops_msda_forward_16", "frcnn_ops_msda_backward_loc_16", "frcnn_ops_msda_backward_value_16",
+    "frcnn_ops_prroi_pool_cull_list", "frcnn_ops_prroi_pool_workspace_bytes", "frcnn_ops_prroi_pool", "frcnn_ops_prroi_pool_backward",
+    "frcnn_ops_prroi_pool_16", "frcnn_ops_prroi_pool_backward_16",
 )
 
 
@@ -334,6 +336,13 @@ _SIGNATURES = {
     "frcnn_ops_msda_forward_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "frcnn_ops_msda_backward_loc_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_msda_backward_value_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    # Precise RoI Pooling (csrc/ops_prroi.hip); the _16 forms take the element-type code first
+    "frcnn_ops_prroi_pool_cull_list": (C.c_int, []),
+    "frcnn_ops_prroi_pool_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "frcnn_ops_prroi_pool": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "frcnn_ops_prroi_pool_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_prroi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "frcnn_ops_prroi_pool_backward_16": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

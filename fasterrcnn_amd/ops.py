@@ -8,6 +8,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import box_iou_rotated, nms_rotated, roi_align_rotated, RoIAlignRotated
     from fasterrcnn_amd.ops import carafe, CARAFE, CARAFEPack
     from fasterrcnn_amd.ops import multi_scale_deformable_attn, MultiScaleDeformableAttnFunction, MultiScaleDeformableAttention
+    from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -160,6 +161,31 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       strict; forward(query, key=None, value=None, identity=None, query_pos=None, key_padding_mask=None, reference_points=None,
       spatial_shapes=None, level_start_index=None) serves reference points with 2 or 4 last-axis entries (else ValueError); the linear
       layers, the softmax over L P and the dropout are torch's; on the GPU the sampler is this operator, elsewhere the composition.
+  prroi_pool(input, rois, output_size, spatial_scale=1.0) -> Tensor [K, C, oh, ow]
+  PrRoIPool(output_size, spatial_scale=1.0).forward(input, rois)
+  prroi_pool_pytorch(input, rois, output_size, spatial_scale=1.0)
+      Precise RoI Pooling, the pooler of IoU-Net and of the ATOM / DiMP trackers, the one RoI pooler with a gradient for the boxes
+      (csrc/ops_prroi.hip; mmcv's prroi_pool restated, unpinned: where the two differ include/frcnn_hip.h holds).  Inputs, limits, dtypes
+      and layouts as roi_align.  The map is extended to the surface f(x, y) = sum of hat(y - j) hat(x - i) input[b, c, j, i], hat(t) =
+      max(0, 1 - |t|): cell (j, i) at the integer point (i, j), no half-pixel shift, zero beyond one cell outside the map.  In float32,
+      with s = spatial_scale: X1 = x1 s (likewise Y1, X2, Y2), bw = max(X2 - X1, 0) / ow, bh = max(Y2 - Y1, 0) / oh, A = bw bh; bin
+      (ph, pw) spans xs = X1 + pw bw .. xe = xs + bw and ys = Y1 + ph bh .. ye = ys + bh, and out[k, c, ph, pw] is the exact integral of f
+      over the bin divided by A = (sum of Wy(j) Wx(i) input[b, c, j, i]) / A with Wx(i) the integral of hat(x - i) over [xs, xe], formed
+      on the two unit pieces either side of i (no difference of antiderivatives: a bin much narrower than a cell does not cancel).  There
+      is no sampling grid.  A RoI is pooled iff 0 < A < +inf and its batch index lies in [0, N): a box of no or negative width or
+      height, a NaN or infinite coordinate, or an area that overflows float32 pools to exact zeros and sends and receives no gradient;
+      the kernels are memory-safe for any box.  Gradients go to input (roi_align's culled, ordered gather) and to rois: the analytic
+      derivative d out / d xs = (-Lx(xs) + out bh) / A, d out / d xe = (Lx(xe) - out bh) / A with the line integral Lx(t) of f along
+      x = t over [ys, ye] (likewise in y), chained to (x1, y1, x2, y2); column 0 of the RoI gradient is 0.  The operator is C1 in the box
+      wherever A > 0: integer coordinates are no seams.  The box gradient is recomputed from the map, not from the saved output.  Both
+      gradients are deterministic and free of atomics (two runs agree bit for bit), each is skipped when its argument needs none; a
+      list of boxes gets its gradient in the list's tensors; double backward raises.  16-bit maps under the contract below for the
+      output and d_input; the kernels compute the box gradient in float32 (bit for bit that of the widened map) and it is rounded once
+      to the RoIs' dtype.  K == 0, N == 0 and C == 0 give empty or zero results without a launch.  prroi_pool_pytorch is the same
+      operator from torch operations with autograd to input and rois, on any device and in float64 too: the weight matrices
+      Wy [K, oh, H] and Wx [K, ow, W] in the clamped antiderivative form (C1, so autograd gives the analytic box gradient at integer
+      coordinates too; it does cancel for very narrow bins) and two einsums per image, rows then columns.  It decides which RoIs are
+      pooled in the dtype it computes in: a float64 map pools a box whose area overflows only float32, which the kernels do not.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -188,12 +214,13 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
-           "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention"]
+           "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
 DEFORM_ROI_CULL_LIST = 256                # RoIs that deform_roi_pool's input-gradient gather lists per pass (DROI_LIST of csrc/ops_droi.hip)
 ROI_ALIGN_ROTATED_CULL_LIST = 1024        # RoIs that roi_align_rotated's backward gather lists per pass (OPS_LIST of csrc/ops_run.h)
+PRROI_CULL_LIST = 1024                    # RoIs that prroi_pool's input-gradient gather lists per pass (OPS_LIST of csrc/ops_run.h)
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
 MAX_ROTATED_IOU_ROWS = 65535 * 64         # rows of box_iou_rotated's matrix (the tile rows of its launch grid)
@@ -908,6 +935,89 @@ torch.library.register_autograd("frcnn::deform_roi_pool_backward", _no_double_ba
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::prroi_pool (NHWC as roi_align; csrc/ops_prroi.hip) ----------------------------------------------------------------------
+@torch.library.custom_op("frcnn::prroi_pool", mutates_args=())
+def _prroi_pool(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int) -> Tensor:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        cp = x.shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
+        _call("prroi_pool", input, x.data_ptr(), n, h, w, cp, r.data_ptr(), k, pooled_height, pooled_width, spatial_scale, dst.data_ptr(),
+              _stream(input))
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_prroi_pool.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width):
+    return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
+
+
+@torch.library.custom_op("frcnn::prroi_pool_backward", mutates_args=())
+def _prroi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int,
+                         needs: List[bool], channels_last: bool) -> List[Tensor]:
+    """[d_input, d_rois]; needs: which of them are wanted (the other comes back as an empty placeholder and costs nothing);
+    channels_last: the memory format of input, which its gradient takes.  d_rois is float32 [K, 5] with a zero column 0."""
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    none = lambda: grad.new_empty((0,))                                    # noqa: E731
+    if k == 0 or c == 0 or n * h * w == 0:
+        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last) if needs[0] else none(),
+                torch.zeros_like(rois) if needs[1] else none()]
+    if not (needs[0] or needs[1]):
+        return [none(), none()]
+    with torch.cuda.device(grad.device):
+        cp = _padded_channels(c, grad.dtype)
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        x = _nhwc(input) if needs[1] else None
+        dx = _empty_cl((n, cp, h, w), grad) if needs[0] else None
+        drois = torch.empty_like(r) if needs[1] else None
+        ws = None
+        if needs[1]:
+            size = nv.lib().frcnn_ops_prroi_pool_workspace_bytes(k, pooled_height, pooled_width)
+            if size == 0:
+                raise nv.FrcnnError(-1, "frcnn_ops_prroi_pool_workspace_bytes")
+            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        _call("prroi_pool_backward", grad, _opt_ptr(x), r.data_ptr(), k, n, h, w, cp, pooled_height, pooled_width, spatial_scale,
+              g.data_ptr(), _opt_ptr(dx), _opt_ptr(drois), _opt_ptr(ws), 0 if ws is None else ws.numel(), _stream(grad))
+        return [_grad_layout(dx, c, channels_last) if needs[0] else none(), drois if needs[1] else none()]
+
+
+@_prroi_pool_backward.register_fake
+def _(grad, input, rois, spatial_scale, pooled_height, pooled_width, needs, channels_last):
+    return [_grad_empty(tuple(input.shape), grad, channels_last) if needs[0] else grad.new_empty((0,)),
+            torch.empty_like(rois, memory_format=torch.contiguous_format) if needs[1] else grad.new_empty((0,))]
+
+
+def _prroi_pool_setup(ctx, inputs, output):
+    input, rois = inputs[:2]
+    ctx.save_for_backward(input, rois)
+    ctx.args = tuple(inputs[2:])
+    ctx.channels_last = _input_is_channels_last(input)
+
+
+def _prroi_pool_bwd(ctx, grad):
+    input, rois = ctx.saved_tensors
+    needs = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+    dx, drois = _prroi_pool_backward(grad, input, rois, *ctx.args, needs, ctx.channels_last)
+    return (dx if needs[0] else None, drois if needs[1] else None, None, None, None)
+
+
+torch.library.register_autograd("frcnn::prroi_pool", _prroi_pool_bwd, setup_context=_prroi_pool_setup)
+torch.library.register_autograd("frcnn::prroi_pool_backward", _no_double_backward("frcnn::prroi_pool"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
 def _score_order(scores):
     """The oracle's argsort(-scores, "stable"): descending score, ties in input order, NaN scores last in input order."""
@@ -1409,6 +1519,78 @@ def deform_roi_pool(input, rois, offset, output_size, spatial_scale=1.0, samplin
     return _deform_roi_pool(input, r, offset, float(spatial_scale), oh, ow, int(sampling_ratio), float(gamma))
 
 
+def prroi_pool(input, rois, output_size, spatial_scale=1.0):
+    """Precise RoI Pooling (IoU-Net's PrRoIPool; mmcv's prroi_pool, restated, unpinned): [K, C, oh, ow] (channels_last memory), the exact
+    integral of the bilinear surface over each bin divided by the bin's area; differentiable in input and in rois."""
+    r = _roi_input(input, rois)
+    oh, ow = _output_size(output_size)
+    return _prroi_pool(input, r, float(spatial_scale), oh, ow)
+
+
+def _prroi_antiderivative(t):
+    """The integral of hat from -inf to t: C1, so autograd through the clamp gives hat(t) everywhere, ties included."""
+    u = t.clamp(-1.0, 1.0)
+    return torch.where(u < 0, (u + 1) ** 2 / 2, 1 - (1 - u) ** 2 / 2)
+
+
+def _prroi_axis_weights(start, size, n_out, cells):
+    """[K, n_out, cells]: the integral of hat(x - i) over bin p = [start + p size, start + (p + 1) size] of each RoI."""
+    p = torch.arange(n_out, dtype=start.dtype, device=start.device)[None, :]
+    i = torch.arange(cells, dtype=start.dtype, device=start.device)
+    s = start[:, None] + p * size[:, None]
+    e = s + size[:, None]
+    return _prroi_antiderivative(e[..., None] - i) - _prroi_antiderivative(s[..., None] - i)
+
+
+def prroi_pool_pytorch(input, rois, output_size, spatial_scale=1.0):
+    """prroi_pool from torch operations, on any device, with autograd to input and rois: the fallback, and what tools/ops_bench.py
+    measures the kernels against.  input [N, C, H, W] of any floating dtype (16-bit maps compute in float32, float64 in float64);
+    rois a Tensor[K, 5] or a list of Tensor[L_i, 4] of any floating dtype.  Returns [K, C, oh, ow] in the input's dtype.  The rule
+    0 < A < +inf is applied in the computing dtype, so with a float64 map a box whose area overflows only float32 (1e30 x 1e30) is pooled,
+    where the kernels and the float32 composition return zeros."""
+    if not isinstance(input, torch.Tensor) or not input.is_floating_point():
+        raise TypeError("input must be a floating-point torch.Tensor, got %s" % (input.dtype if isinstance(input, torch.Tensor)
+                                                                                 else type(input).__name__))
+    if input.dim() != 4:
+        raise ValueError("input must be [N, C, H, W], got shape %s" % (tuple(input.shape),))
+    oh, ow = _output_size(output_size)
+    dtype = torch.float64 if input.dtype == torch.float64 else torch.float32
+    if isinstance(rois, (list, tuple)):
+        for j, b in enumerate(rois):
+            if not isinstance(b, torch.Tensor) or not b.is_floating_point() or b.dim() != 2 or b.shape[1] != 4:
+                raise ValueError("rois[%d] must be a floating-point Tensor[L, 4]" % j)
+        parts = [torch.cat([torch.full_like(b[:, :1], float(j)), b], dim=1).to(dtype) for j, b in enumerate(rois)]
+        r = torch.cat(parts, dim=0) if parts else input.new_zeros((0, 5), dtype=dtype)
+    elif isinstance(rois, torch.Tensor) and rois.is_floating_point() and rois.dim() == 2 and rois.shape[1] == 5:
+        r = rois.to(dtype)
+    else:
+        raise ValueError("rois must be a floating-point Tensor[K, 5] (batch index, x1, y1, x2, y2) or a list of Tensor[L, 4]")
+    n, c, h, w = input.shape
+    k = r.shape[0]
+    scale = float(torch.tensor(spatial_scale, dtype=torch.float32))         # as the kernels receive it
+    def bins(rows):
+        x1, y1, x2, y2 = (rows[:, j] * scale for j in (1, 2, 3, 4))
+        return x1, y1, (x2 - x1).clamp(min=0) / ow, (y2 - y1).clamp(min=0) / oh
+
+    # which RoIs are pooled is decided without autograd, and only their rows are computed on: a NaN never meets a gradient
+    with torch.no_grad():
+        _, _, bw, bh = bins(r)
+        valid = (bw * bh > 0) & torch.isfinite(bw * bh) & (r[:, 0] > -1) & (r[:, 0] < n)
+        image = torch.where(valid, r[:, 0], torch.zeros_like(r[:, 0])).long()
+    out = torch.zeros((k, c, oh, ow), dtype=dtype, device=input.device)
+    for b in range(n):
+        pick = (valid & (image == b)).nonzero()[:, 0]
+        if pick.numel() == 0:
+            continue
+        x1, y1, bw, bh = bins(r[pick])
+        wy = _prroi_axis_weights(y1, bh, oh, h)
+        wx = _prroi_axis_weights(x1, bw, ow, w)
+        rows = torch.einsum("kph,chw->kcpw", wy, input[b].to(dtype))
+        vals = torch.einsum("kcpw,kqw->kcpq", rows, wx) / (bw * bh)[:, None, None, None]
+        out = out.index_add(0, pick, vals)
+    return out.to(input.dtype)
+
+
 def _rotated_boxes(name, boxes, clockwise):
     """Checks a Tensor[N, 5] of rotated boxes; returns it in the kernels' convention (angles negated for clockwise=False)."""
     _check_tensor(name, boxes, (torch.float32,), "float32 (rotated boxes are float32 only: pass .float())")
@@ -1814,6 +1996,21 @@ class DeformRoIPool(torch.nn.Module):
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, gamma=%s" % (
             self.output_size, self.spatial_scale, self.sampling_ratio, self.gamma)
+
+
+class PrRoIPool(torch.nn.Module):
+    """mmcv.ops.PrRoIPool: Precise RoI Pooling, differentiable in the map and in the boxes."""
+
+    def __init__(self, output_size, spatial_scale=1.0):
+        super().__init__()
+        self.output_size = _output_size(output_size)
+        self.spatial_scale = float(spatial_scale)
+
+    def forward(self, input, rois):
+        return prroi_pool(input, rois, self.output_size, self.spatial_scale)
+
+    def extra_repr(self):
+        return "output_size=%s, spatial_scale=%s" % (self.output_size, self.spatial_scale)
 
 
 def _zero_last(stack, index):

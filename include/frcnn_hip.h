@@ -72,7 +72,9 @@ extern "C" {
                                  _channel_chunk / _tile_width / _tile_height getters (CARAFE upsampling: mmcv's carafe);
                                  still 21 (additions only): frcnn_ops_msda_forward, _backward_loc, _plan, _backward_value, _workspace_bytes, the _16
                                  forms and the frcnn_ops_msda_max_levels / _max_points / _max_channels / _block_items / _segment getters (multi-scale deformable
-                                 attention: mmcv's ms_deform_attn) */
+                                 attention: mmcv's ms_deform_attn);
+                                 still 21 (additions only): frcnn_ops_prroi_pool, its _backward, _16, _workspace_bytes and _cull_list forms
+                                 (Precise RoI Pooling with box gradients: IoU-Net's PrRoIPool, mmcv's prroi_pool) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -658,6 +660,55 @@ int frcnn_ops_deform_roi_pool_backward_16(int elem_type, const void* d_x, const 
                                           int fh, int fw, int c, int out_h, int out_w, float spatial_scale, int sampling_ratio,
                                           float gamma, const void* d_dout, void* d_dx, float* d_doffset, void* d_ws, size_t ws_bytes,
                                           void* stream);
+
+/* Precise RoI Pooling (PrRoIPool of IoU-Net; csrc/ops_prroi.hip): mmcv's prroi_pool in both directions, with the gradient for the boxes,
+ *   restated from the published definition (third party, absent here: restated, unpinned; where the two differ this text holds).
+ *   Layouts and element types as frcnn_ops_roi_align above (NHWC maps, c % 4 == 0; the _16 forms c % 8 == 0):
+ *     d_x    : [n_img][fh][fw][c]
+ *     d_rois : float32 [k][5] rows (b, x1, y1, x2, y2)
+ *     d_out  : [k][out_h][out_w][c]
+ *   The map of image b, channel c is extended to the surface f(x, y) = sum over j, i of hat(y - j) hat(x - i) x[b][j][i][c] with
+ *   hat(t) = max(0, 1 - |t|): cell (j, i) sits at the integer point (i, j), no half-pixel shift, zero beyond one cell outside the map.
+ *   In float32: X1 = x1 * scale (likewise Y1, X2, Y2), rw = max(X2 - X1, 0), rh = max(Y2 - Y1, 0), bw = rw / out_w, bh = rh / out_h,
+ *   A = bw * bh; bin (ph, pw): xs = X1 + pw * bw, xe = xs + bw, ys = Y1 + ph * bh, ye = ys + bh, and
+ *     out[k][ph][pw][c] = (sum over j, i of Wy(j) Wx(i) x[b][j][i][c]) / A,   Wx(i) = the integral of hat(x - i) over [xs, xe],
+ *   Wx(i) formed on the unit pieces [i - 1, i] and [i, i + 1] cut to [xs, xe]: a piece [p, q] with q > p and m = (p + q) / 2 gives
+ *   (q - p) (m - i + 1) on the rising side, (q - p) (1 - (m - i)) on the falling side (never a difference of antiderivatives, which
+ *   cancels for a bin much narrower than a cell); Wy(j) likewise with ys, ye.
+ *   A RoI is pooled iff 0 < A < +inf and its batch index lies in (-1, n_img); any other -- no or negative width or height, a NaN or
+ *   infinite coordinate, an area that overflows -- pools to exact zeros and sends and receives no gradient.  A pooled RoI has finite bin
+ *   edges; every cell range is clamped to the map in float before it is converted: the kernels are memory-safe for any box.
+ * frcnn_ops_prroi_pool_backward:
+ *   d_dx (NULL: skipped; else every element overwritten) = sum over the RoIs of image b and their bins of dout Wy(j) Wx(i) / A: a gather
+ *   per 2 x 2 tile that culls the RoIs in ascending order, frcnn_ops_prroi_pool_cull_list() at a time (a RoI is listed if its scaled box,
+ *   grown by one cell and rounded outwards, meets the tile), sums in ascending (RoI, ph, pw) order into registers and stores once.
+ *   d_drois (NULL: skipped; float32 [k][5], needs d_x and d_ws) is the analytic derivative.  With
+ *   Lx(t) = sum_j Wy(j) sum_i hat(t - i) x[j][i] and Ly(t) = sum_i Wx(i) sum_j hat(t - j) x[j][i], per bin and channel:
+ *     d out / d xs = (-Lx(xs) + out bh) / A,  d out / d xe = (Lx(xe) - out bh) / A,  d out / d ys = (-Ly(ys) + out bw) / A,
+ *     d out / d ye = (Ly(ye) - out bw) / A;  d xs / d X1 = 1 - pw / out_w, d xs / d X2 = pw / out_w, d xe / d X1 = 1 - (pw + 1) / out_w,
+ *     d xe / d X2 = (pw + 1) / out_w, the same in y; d_drois[k][1..4] = scale * (dX1, dY1, dX2, dY2), d_drois[k][0] = 0.
+ *   It is recomputed from d_x (the saved output is not read: a 16-bit output has been rounded): one wave per (RoI, bin) sums dout times
+ *   the five integrals over its channels in runs of 4 whatever the element type, with a fixed cross-lane reduction, into d_ws
+ *   (frcnn_ops_prroi_pool_workspace_bytes(k, out_h, out_w) bytes, 16-byte aligned; 0: invalid sizes); one wave per RoI then sums the bins
+ *   in a fixed order.  Both gradients are deterministic and free of atomics.  At least one of d_dx and d_drois is given.  k == 0 returns
+ *   FRCNN_OK after zero-filling d_dx.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): out_h, out_w in [1, 64], k >= 0, sizes < 1, c not in whole runs,
+ *   k * out_h * out_w or fh * fw beyond 32 bits, fh > 131070 or n_img * ceil(c / run / 64) > 65535 (the gather's launch grid), NULL
+ *   pointers, a small or misaligned workspace.
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; RoIs and d_drois
+ *   stay float32, and d_drois of a 16-bit map equals that of the widened map bit for bit. */
+int frcnn_ops_prroi_pool_cull_list(void);
+size_t frcnn_ops_prroi_pool_workspace_bytes(int k, int out_h, int out_w);
+int frcnn_ops_prroi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
+                         float spatial_scale, float* d_out, void* stream);
+int frcnn_ops_prroi_pool_backward(const float* d_x, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
+                                  float spatial_scale, const float* d_dout, float* d_dx, float* d_drois, void* d_ws, size_t ws_bytes,
+                                  void* stream);
+int frcnn_ops_prroi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
+                            int out_w, float spatial_scale, void* d_out, void* stream);
+int frcnn_ops_prroi_pool_backward_16(int elem_type, const void* d_x, const float* d_rois, int k, int n_img, int fh, int fw, int c,
+                                     int out_h, int out_w, float spatial_scale, const void* d_dout, void* d_dx, float* d_drois, void* d_ws,
+                                     size_t ws_bytes, void* stream);
 
 /* Rotated boxes (oriented detection; csrc/ops_rot.hip): mmcv's box_iou_rotated, nms_rotated and roi_align_rotated, restated from their
  *   published definitions (third party, absent here: restated, unpinned; where the two differ this text holds).

@@ -49,6 +49,11 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     (one grid_sample per level, autograd's backward), forward and forward + backward of all three gradients, in alternating windows;
     and the forward's algorithmic bytes (value + locations + weights + result, each once) per second as a share of the HBM peak.
 
+  * prroi: Precise RoI Pooling on a C4 map (2 x 256 x 50 x 68, 512 RoIs, 7 x 7, scale 1 / 16), float32 and bfloat16:
+    ops.prroi_pool beside ops.prroi_pool_pytorch (the weight matrices and one einsum per image, autograd's backward), forward and
+    forward + backward of both gradients (the map's and the boxes'), in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only prroi           # just the Precise-RoI-Pooling leg
     python tools/ops_bench.py --only msda            # just the deformable-attention leg
     python tools/ops_bench.py --only carafe          # just the CARAFE leg
     python tools/ops_bench.py --only rot             # just the rotated-box leg
@@ -414,6 +419,33 @@ def msda_leg(rng, reps, warmup):
     return res
 
 
+def prroi_leg(rng, reps, warmup):
+    n, c, h, w, k, out, scale = 2, 256, 50, 68, 512, (7, 7), 1 / 16
+    gen = torch.Generator().manual_seed(0)
+    props = proposals(rng, k, 800, 1088)
+    rois = torch.from_numpy(np.concatenate([(np.arange(k) % n).astype(np.float32)[:, None], props[:, [1, 0, 3, 2]]], 1)).to(DEV)
+    res = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((k, c) + out, generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        leaves = (x.clone().requires_grad_(True), rois.clone().requires_grad_(True))
+
+        def native(a=(x, rois)):
+            return ops.prroi_pool(a[0], a[1], out, scale)
+
+        def composed(a=(x, rois)):
+            return ops.prroi_pool_pytorch(a[0], a[1], out, scale)
+        y, yc = native().float(), composed().float()
+        r = {"max |prroi_pool - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        for name, fns in (("fwd", (native, composed)),
+                          ("fwd+bwd (d_input and d_rois)", (lambda: native(leaves).backward(g), lambda: composed(leaves).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.prroi_pool": round(t_native, 1), "ops.prroi_pool_pytorch": round(t_comp, 1),
+                       "composition / prroi_pool": round(t_comp / t_native, 2)}
+        res["prroi %s 2 x 256 x 50 x 68, 512 RoIs, 7 x 7" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -423,7 +455,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -453,6 +485,9 @@ def main():
         return
     if a.only == "msda":
         print(json.dumps(msda_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "prroi":
+        print(json.dumps(prroi_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -521,6 +556,7 @@ def main():
     res.update(rot_leg(rng, 5, 2))
     res.update(carafe_leg(rng, 5, 2))
     res.update(msda_leg(rng, 5, 2))
+    res.update(prroi_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
