@@ -79,6 +79,9 @@ SYMBOLS = (
     "frcnn_ops_msda_backward_value", "frcnn_ops_msda_forward_16", "frcnn_ops_msda_backward_loc_16", "frcnn_ops_msda_backward_value_16",
     "frcnn_ops_prroi_pool_cull_list", "frcnn_ops_prroi_pool_workspace_bytes", "frcnn_ops_prroi_pool", "frcnn_ops_prroi_pool_backward",
     "frcnn_ops_prroi_pool_16", "frcnn_ops_prroi_pool_backward_16",
+    "frcnn_ops_dcnv3_max_kernel", "frcnn_ops_dcnv3_max_channels", "frcnn_ops_dcnv3_block_items", "frcnn_ops_dcnv3_workspace_bytes",
+    "frcnn_ops_dcnv3_forward", "frcnn_ops_dcnv3_backward_offset", "frcnn_ops_dcnv3_plan", "frcnn_ops_dcnv3_backward_input",
+    "frcnn_ops_dcnv3_forward_16", "frcnn_ops_dcnv3_backward_offset_16", "frcnn_ops_dcnv3_backward_input_16",
 )
 
 
@@ -343,6 +346,19 @@ _SIGNATURES = {
     "frcnn_ops_prroi_pool_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_ops_prroi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "frcnn_ops_prroi_pool_backward_16": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # DCNv3 (csrc/ops_dcnv3.hip): n, h, w, g, gc, kernel, stride, padding and dilation (h, w each), offset_scale; the _16 forms take the
+    # element-type code first
+    "frcnn_ops_dcnv3_max_kernel": (C.c_int, []),
+    "frcnn_ops_dcnv3_max_channels": (C.c_int, []),
+    "frcnn_ops_dcnv3_block_items": (C.c_int, [_i, _i, _i, _i]),
+    "frcnn_ops_dcnv3_workspace_bytes": (C.c_size_t, [_i] * 13),
+    "frcnn_ops_dcnv3_forward": (C.c_int, [_vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp]),
+    "frcnn_ops_dcnv3_backward_offset": (C.c_int, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp, _vp]),
+    "frcnn_ops_dcnv3_plan": (C.c_int, [_vp, _vp] + [_i] * 12 + [_f, _vp, _vp, _vp]),
+    "frcnn_ops_dcnv3_backward_input": (C.c_int, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _vp, _sz, _vp]),
+    "frcnn_ops_dcnv3_forward_16": (C.c_int, [_i, _vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp]),
+    "frcnn_ops_dcnv3_backward_offset_16": (C.c_int, [_i, _vp, _vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp, _vp]),
+    "frcnn_ops_dcnv3_backward_input_16": (C.c_int, [_i, _vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _vp, _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

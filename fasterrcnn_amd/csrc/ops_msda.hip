@@ -33,102 +33,15 @@
 //
 // Element types: templates over the storage type E of value, dout, out and d_value (float, float16, bfloat16): widened exactly on load,
 // the float32 body, one rounding to nearest even on store as Tensor.to() rounds.  loc, attn, d_loc and d_attn are float32.
-#include "common.h"
+#include "ops_msda.h"
 
 namespace frcnn {
 
 static constexpr int MSDA_MAX_LEVELS = 8;
 static constexpr int MSDA_MAX_POINTS = 16;
-static constexpr int MSDA_MAX_CHANNELS = 256;            // D, the channels of one head
-static constexpr int MSDA_BLOCK = 256;
-static constexpr int MSDA_LDS_SAMPLES = 1024;            // (l, p) samples of a block's items staged in LDS: 12 KB
-static constexpr int MSDA_SCALAR_PASSES = MSDA_MAX_CHANNELS / 64;
-static constexpr int MSDA_SEGMENT = 512;                 // entries of one piece of a long d_value segment
-static constexpr long long MSDA_MAX_SIDE = 1 << 24;      // H_l, W_l: exact in float32
 static constexpr long long MSDA_MAX_START = 1LL << 50;
-static constexpr long long MSDA_MAX_INDEX = (long long)INT32_MAX - 1024;   // plan entries and cells of one call
-static constexpr int MSDA_MAX_BLOCKS = 16384;            // of the one-thread-per-element kernels: grid-stride beyond
 
 static_assert(MSDA_MAX_LEVELS * MSDA_MAX_POINTS <= MSDA_LDS_SAMPLES, "one item's samples fit the staging buffer");
-
-struct ms_f16 { _Float16 v; };
-struct ms_bf16 { unsigned short bits; };
-
-template <int R> struct MsVec { float v[R]; };
-
-template <typename E> struct MsElem;
-template <> struct MsElem<float> { static constexpr int RUN = 4; };
-template <> struct MsElem<ms_f16> { static constexpr int RUN = 8; };
-template <> struct MsElem<ms_bf16> { static constexpr int RUN = 8; };
-
-// R consecutive channels from p (16-byte aligned when R > 1), widened exactly
-template <typename E, int R> __device__ __forceinline__ MsVec<R> ms_load(const E* p)
-{
-    MsVec<R> r;
-    if constexpr (sizeof(E) == 4) {
-        if constexpr (R == 4) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r.v[j] = t[j];
-        } else {
-            r.v[0] = p[0];
-        }
-    } else {
-        typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-        unsigned short u[R];
-        if constexpr (R == 8) {
-            const u16x8 t = *reinterpret_cast<const u16x8*>(p);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) u[j] = t[j];
-        } else {
-            u[0] = *reinterpret_cast<const unsigned short*>(p);
-        }
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            if constexpr (__is_same(E, ms_f16)) {
-                _Float16 h;
-                __builtin_memcpy(&h, &u[j], 2);
-                r.v[j] = (float)h;
-            } else {
-                r.v[j] = __uint_as_float((unsigned)u[j] << 16);
-            }
-        }
-    }
-    return r;
-}
-
-// one rounding to nearest even, NaN as Tensor.to(): float16 by the hardware conversion, bfloat16 by c10::BFloat16's integer rounding
-template <typename E, int R> __device__ __forceinline__ void ms_store(E* p, const MsVec<R>& a)
-{
-    if constexpr (sizeof(E) == 4) {
-        if constexpr (R == 4) {
-            *reinterpret_cast<f32x4*>(p) = f32x4{a.v[0], a.v[1], a.v[2], a.v[3]};
-        } else {
-            p[0] = a.v[0];
-        }
-    } else {
-        typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-        unsigned short u[R];
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            if constexpr (__is_same(E, ms_f16)) {
-                const _Float16 h = (_Float16)a.v[j];
-                __builtin_memcpy(&u[j], &h, 2);
-            } else {
-                const unsigned b = __float_as_uint(a.v[j]);
-                u[j] = a.v[j] != a.v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-            }
-        }
-        if constexpr (R == 8) {
-            u16x8 t;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t[j] = u[j];
-            *reinterpret_cast<u16x8*>(p) = t;
-        } else {
-            *reinterpret_cast<unsigned short*>(p) = u[0];
-        }
-    }
-}
 
 // ---- geometry ----------------------------------------------------------------------------------------------------------------------
 struct MsLevel { long long start; int h, w; bool ok; };
@@ -166,24 +79,6 @@ __device__ __forceinline__ MsSample ms_sample(const MsLevel& lv, float loc_x, fl
         if (c >= 0 && c < S) s.cell[k] = c;
     }
     return s;
-}
-
-// what the host and the kernels agree on for one (D, L, P, element type): the lanes of a group, a lane's passes, the items of a block
-struct MsMap { int R, T, nruns, passes, ipb, threads; };
-
-static inline int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-static MsMap ms_map(int d, int lp, int run, bool vector)
-{
-    MsMap m;
-    m.R = vector ? run : 1;
-    m.nruns = d / m.R;
-    m.T = pow2_ceil(m.nruns) < 64 ? pow2_ceil(m.nruns) : 64;
-    m.passes = (m.nruns + m.T - 1) / m.T;
-    const int by_lds = MSDA_LDS_SAMPLES / (lp > 0 ? lp : 1);
-    m.ipb = MSDA_BLOCK / m.T < by_lds ? MSDA_BLOCK / m.T : by_lds;
-    m.threads = (m.ipb * m.T + 63) / 64 * 64;
-    return m;
 }
 
 // the tensors of one call as the sampling kernels see them
@@ -495,22 +390,15 @@ static bool msda_args_ok(int n_img, int s, int m, int d, int q, int levels, int 
     return true;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int msda_windows(int n_entries) { return (n_entries + MSDA_SEGMENT - 1) / MSDA_SEGMENT; }
 
 // the segment starts, then two rows of d float32 per window of MSDA_SEGMENT sorted entries (the sums of the long segments' pieces)
-static inline size_t msda_starts_bytes(int n_img, int s, int m) { return align256(((size_t)n_img * s * m + 1) * sizeof(int)); }
-static inline size_t msda_workspace(int n_img, int s, int m, int d, int q, int levels, int points)
-{
-    return msda_starts_bytes(n_img, s, m) + align256((size_t)msda_windows(n_img * q * m * levels * points * 4) * 2 * d * sizeof(float));
-}
+static inline size_t msda_starts_bytes(int n_cells) { return align256(((size_t)n_cells + 1) * sizeof(int)); }
 
-static inline unsigned msda_blocks(long long total)
+size_t msda_gather_workspace(int n_cells, int n_entries, int d)
 {
-    const long long b = (total + MSDA_BLOCK - 1) / MSDA_BLOCK;
-    return (unsigned)(b < MSDA_MAX_BLOCKS ? (b ? b : 1) : MSDA_MAX_BLOCKS);
+    return msda_starts_bytes(n_cells) + align256((size_t)msda_windows(n_entries) * 2 * d * sizeof(float));
 }
 
 template <typename E>
@@ -557,21 +445,22 @@ static int msda_backward_loc_impl(const void* value, const int64_t* shapes, cons
     return check_launch();
 }
 
+// the gather uses the samples of an item only as their number: multi-scale deformable attention has levels * points of them, DCNv3
+// kh * kw
 template <typename E>
-static int msda_backward_value_impl(const int64_t* sorted_keys, const int64_t* order, const float* wts, const void* dout, int n_img, int s,
-                                    int m, int d, int q, int levels, int points, void* dvalue, void* ws, size_t ws_bytes, void* stream)
+static int msda_gather_impl(const int64_t* sorted_keys, const int64_t* order, const float* wts, const void* dout, int n_cells,
+                            int n_entries, int samples4, int d, void* dvalue, void* ws, size_t ws_bytes, hipStream_t st)
 {
-    if (!msda_args_ok(n_img, s, m, d, q, levels, points) || !sorted_keys || !order || !wts || !dout || !dvalue) return FRCNN_EINVAL;
-    if (!ws || !aligned16(ws) || ws_bytes < msda_workspace(n_img, s, m, d, q, levels, points)) return FRCNN_EINVAL;
+    if (!sorted_keys || !order || !wts || !dout || !dvalue) return FRCNN_EINVAL;
+    if (!ws || !aligned16(ws) || ws_bytes < msda_gather_workspace(n_cells, n_entries, d)) return FRCNN_EINVAL;
     constexpr int RUN = MsElem<E>::RUN;
     const bool vector = d % RUN == 0 && aligned16(dvalue) && aligned16(dout);
-    const MsMap mp = ms_map(d, levels * points, RUN, vector);
+    const MsMap mp = ms_map(d, samples4 / 4, RUN, vector);
     MsGather g;
-    g.n_cells = n_img * s * m; g.LP4 = levels * points * 4; g.n_entries = n_img * q * m * g.LP4; g.D = d; g.T = mp.T; g.nruns = mp.nruns;
+    g.n_cells = n_cells; g.LP4 = samples4; g.n_entries = n_entries; g.D = d; g.T = mp.T; g.nruns = mp.nruns;
     g.n_windows = msda_windows(g.n_entries);
-    hipStream_t st = (hipStream_t)stream;
     int* start = static_cast<int*>(ws);
-    float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + msda_starts_bytes(n_img, s, m));
+    float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + msda_starts_bytes(n_cells));
     const long long* keys = reinterpret_cast<const long long*>(sorted_keys);
     const long long* ord = reinterpret_cast<const long long*>(order);
     hipLaunchKernelGGL(msda_segments_kernel, dim3(msda_blocks((long long)g.n_cells + 1)), dim3(MSDA_BLOCK), 0, st, keys, g.n_entries,
@@ -595,6 +484,29 @@ static int msda_backward_value_impl(const int64_t* sorted_keys, const int64_t* o
                            static_cast<E*>(dvalue));
     }
     return check_launch();
+}
+
+int msda_gather(int elem_type, const int64_t* sorted_keys, const int64_t* order, const float* wts, const void* dout, int n_cells,
+                int n_entries, int samples4, int d, void* dvalue, void* ws, size_t ws_bytes, hipStream_t stream)
+{
+    if (n_cells < 1 || n_entries < 1 || samples4 < 4 || d < 1 || d > MSDA_MAX_CHANNELS) return FRCNN_EINVAL;
+    if (elem_type == 0)
+        return msda_gather_impl<float>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
+    if (elem_type == FRCNN_OPS_F16)
+        return msda_gather_impl<ms_f16>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
+    if (elem_type == FRCNN_OPS_BF16)
+        return msda_gather_impl<ms_bf16>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
+    return FRCNN_EINVAL;
+}
+
+static int msda_backward_value(int elem_type, const int64_t* sorted_keys, const int64_t* order, const float* wts, const void* dout,
+                               int n_img, int s, int m, int d, int q, int levels, int points, void* dvalue, void* ws, size_t ws_bytes,
+                               void* stream)
+{
+    if (!msda_args_ok(n_img, s, m, d, q, levels, points)) return FRCNN_EINVAL;
+    const int lp4 = levels * points * 4;
+    return msda_gather(elem_type, sorted_keys, order, wts, dout, n_img * s * m, n_img * q * m * lp4, lp4, d, dvalue, ws, ws_bytes,
+                       (hipStream_t)stream);
 }
 
 }  // namespace frcnn
@@ -628,7 +540,7 @@ int frcnn_ops_msda_segment(void) { return MSDA_SEGMENT; }
 size_t frcnn_ops_msda_workspace_bytes(int n_img, int s, int m, int d, int q, int levels, int points)
 {
     if (!msda_args_ok(n_img, s, m, d, q, levels, points)) return 0;
-    return msda_workspace(n_img, s, m, d, q, levels, points);
+    return msda_gather_workspace(n_img * s * m, n_img * q * m * levels * points * 4, d);
 }
 
 int frcnn_ops_msda_forward(const float* d_value, const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc, const float* d_attn,
@@ -661,8 +573,8 @@ int frcnn_ops_msda_backward_value(const int64_t* d_sorted_keys, const int64_t* d
                                   int n_img, int s, int m, int d, int q, int levels, int points, float* d_dvalue, void* d_ws,
                                   size_t ws_bytes, void* stream)
 {
-    return msda_backward_value_impl<float>(d_sorted_keys, d_order, d_weights, d_dout, n_img, s, m, d, q, levels, points, d_dvalue, d_ws,
-                                           ws_bytes, stream);
+    return msda_backward_value(0, d_sorted_keys, d_order, d_weights, d_dout, n_img, s, m, d, q, levels, points, d_dvalue, d_ws, ws_bytes,
+                               stream);
 }
 
 int frcnn_ops_msda_forward_16(int elem_type, const void* d_value, const int64_t* d_shapes, const int64_t* d_starts, const float* d_loc,
@@ -685,8 +597,9 @@ int frcnn_ops_msda_backward_value_16(int elem_type, const int64_t* d_sorted_keys
                                      const void* d_dout, int n_img, int s, int m, int d, int q, int levels, int points, void* d_dvalue,
                                      void* d_ws, size_t ws_bytes, void* stream)
 {
-    MSDA_DISPATCH_16(elem_type, msda_backward_value_impl, d_sorted_keys, d_order, d_weights, d_dout, n_img, s, m, d, q, levels, points,
-                     d_dvalue, d_ws, ws_bytes, stream);
+    if (elem_type != FRCNN_OPS_F16 && elem_type != FRCNN_OPS_BF16) return FRCNN_EINVAL;
+    return msda_backward_value(elem_type, d_sorted_keys, d_order, d_weights, d_dout, n_img, s, m, d, q, levels, points, d_dvalue, d_ws,
+                               ws_bytes, stream);
 }
 
 }  // extern "C"

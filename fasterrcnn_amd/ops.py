@@ -9,6 +9,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import carafe, CARAFE, CARAFEPack
     from fasterrcnn_amd.ops import multi_scale_deformable_attn, MultiScaleDeformableAttnFunction, MultiScaleDeformableAttention
     from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
+    from fasterrcnn_amd.ops import dcnv3, DCNv3Function, dcnv3_core_pytorch, DCNv3
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -186,6 +187,38 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       Wy [K, oh, H] and Wx [K, ow, W] in the clamped antiderivative form (C1, so autograd gives the analytic box gradient at integer
       coordinates too; it does cancel for very narrow bins) and two einsums per image, rows then columns.  It decides which RoIs are
       pooled in the dtype it computes in: a float64 map pools a box whose area overflows only float32, which the kernels do not.
+  dcnv3(input, offset, mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256)
+  DCNv3Function.apply(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                      group_channels, offset_scale, im2col_step)
+  dcnv3_core_pytorch(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                     group_channels, offset_scale)
+  DCNv3(channels=64, kernel_size=3, dw_kernel_size=None, stride=1, pad=1, dilation=1, group=4, offset_scale=1.0)
+      DCNv3, the deformable convolution v3 of the InternImage backbones (csrc/ops_dcnv3.hip; InternImage's DCNv3 restated, unpinned:
+      where the two differ include/frcnn_hip.h holds): a grouped, weight-free deformable sampling on channels-last maps.  input
+      [N, H, W, G Gc]; offset [N, Ho, Wo, G K 2], the pair of (g, p) at (g K + p) 2 as (dx, dy); mask [N, Ho, Wo, G K]; the result is
+      [N, Ho, Wo, G Gc], contiguous, in the input's dtype.  K = kh kw, Ho = (H + 2 pad_h - (dil_h (kh - 1) + 1)) // stride_h + 1 (Wo
+      likewise); kernel_size, stride, padding and dilation are ints or pairs (h, w); Gc = input.shape[-1] // group.  Point p = i kh + j has
+      i in [0, kw) along x as the outer index and j in [0, kh) along y.  With bx = dil_w (kw - 1) // 2 and by = dil_h (kh - 1) // 2 the
+      sample (n, oy, ox, g, p) lies at x = (ox stride_w - pad_w + bx) + ((i dil_w - bx) + dx) * offset_scale, y likewise, the integer parts
+      in integers and the rest in float32, in pixels of the unpadded map; it counts only if x > -1 and y > -1 and x < W and y < H (a NaN
+      coordinate fails); its value is the bilinear mix of the corners floor / floor + 1, a corner outside the map counting 0;
+      out[n, oy, ox, g Gc + c] = the sum over p ascending of mask * sample_c in float32.  Gradients go to input, offset and mask (d_offset
+      over the forward's accepted range and corners, the right-hand slope at an integer coordinate, times offset_scale; d_mask = sum over c
+      of grad * sample); all three are deterministic and free of atomics (d_input sums, per cell and group, the stably sorted plan of the
+      corners that reach it with multi_scale_deformable_attn's gather, every cell written), so two runs agree bit for bit; each is
+      skipped when its argument needs none; double backward raises.  im2col_step bounds the images per launch and per plan; it need not
+      divide N and no bit of any result depends on it.  float32, and float16 / bfloat16 input under the contract below (output and
+      d_input); offset and mask are float32 or the input's own 16-bit dtype (widened before the launch, their gradients rounded once to
+      that dtype); anything else is a TypeError.  Limits, each a ValueError naming the argument: 1 <= kh, kw <= MAX_DCNV3_KERNEL = 7,
+      1 <= Gc <= MAX_DCNV3_CHANNELS = 256, stride and dilation in [1, MAX_DCNV3_STEP], padding in [0, MAX_DCNV3_STEP], a finite
+      offset_scale, H, W <= 2 ** 24, and for a chunk of n images n H W G <= MAX_MSDA_INDEX and n Ho Wo G K 4 <= MAX_MSDA_INDEX.  N == 0 or
+      Ho Wo == 0 give empty results and zero gradients without a launch.  dcnv3_core_pytorch is InternImage's grid_sample composition,
+      the fallback users know, on any device: pad, reference points and the dilated grid in normalised coordinates of the padded map,
+      one grid_sample, the masked sum over K (it materialises an [N G, Gc, Ho Wo, K] tensor).  The module has InternImage's parameter
+      names (dw_conv.0, dw_conv.1.1, offset, mask, input_proj, output_proj) and init (zeros on offset and mask, Xavier-uniform with zero
+      bias on the projections), so InternImage checkpoints load strict; the depthwise convolution, LayerNorm, GELU, the linear layers
+      and the softmax over K are torch's; on the GPU the sampler is this operator, elsewhere the composition.  center_feature_scale
+      and remove_center are not implemented (NotImplementedError).
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -214,7 +247,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
-           "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch"]
+           "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
+           "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -235,6 +269,10 @@ MAX_MSDA_POINTS = 16                      # csrc/ops_msda.hip: the L P samples o
 MAX_MSDA_CHANNELS = 256                   # live in registers)
 MSDA_SEGMENT = 512                        # entries of one piece of a long d_value segment (frcnn_ops_msda_segment())
 MAX_MSDA_INDEX = 2 ** 31 - 1 - 1024       # what the 32-bit indices of csrc/ops_msda.hip hold: cells n S M and plan entries n Q M L P 4 of a chunk
+MAX_DCNV3_KERNEL = 7                      # dcnv3: kh and kw (frcnn_ops_dcnv3_max_kernel(): the K samples of a block's items are staged in LDS)
+MAX_DCNV3_CHANNELS = 256                  # dcnv3: channels of one group (frcnn_ops_dcnv3_max_channels())
+MAX_DCNV3_STEP = 65536                    # dcnv3: stride, dilation and padding (the integer part of a coordinate stays far inside 32 bits)
+MAX_DCNV3_SIDE = 2 ** 24                  # dcnv3: H and W, exact in float32
 CARAFE_RUN = 4                            # channels a thread of carafe's d_features gather owns: G ceil(C / G / 4) blocks along the grid's y
 
 
@@ -1376,6 +1414,107 @@ torch.library.register_autograd("frcnn::ms_deform_attn_backward", _no_double_bac
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::dcnv3 (csrc/ops_dcnv3.hip) ----------------------------------------------------------------------------------------------
+def _dcnv3_out_size(size, kernel, stride, pad, dil):
+    return max((size + 2 * pad - (dil * (kernel - 1) + 1)) // stride + 1, 0)
+
+
+@torch.library.custom_op("frcnn::dcnv3", mutates_args=())
+def _dcnv3(input: Tensor, offset: Tensor, mask: Tensor, kernel_h: int, kernel_w: int, stride_h: int, stride_w: int, pad_h: int, pad_w: int,
+           dilation_h: int, dilation_w: int, group: int, group_channels: int, offset_scale: float, im2col_step: int) -> Tensor:
+    n, h, w, _ = input.shape
+    ho, wo = offset.shape[1], offset.shape[2]
+    out = torch.empty((n, ho, wo, group * group_channels), dtype=input.dtype, device=input.device)
+    if out.numel() == 0:
+        return out
+    if h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x, off, msk = input.contiguous(), _msda_float(offset), _msda_float(mask)
+        nb, stream = min(n, im2col_step), _stream(input)
+        for i0 in range(0, n, nb):
+            _call("dcnv3_forward", input, x[i0:].data_ptr(), off[i0:].data_ptr(), msk[i0:].data_ptr(), min(nb, n - i0), h, w, group,
+                  group_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, offset_scale,
+                  out[i0:].data_ptr(), stream)
+    return out
+
+
+@_dcnv3.register_fake
+def _(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+      offset_scale, im2col_step):
+    return input.new_empty((input.shape[0], offset.shape[1], offset.shape[2], group * group_channels))
+
+
+@torch.library.custom_op("frcnn::dcnv3_backward", mutates_args=())
+def _dcnv3_backward(grad: Tensor, input: Tensor, offset: Tensor, mask: Tensor, kernel_h: int, kernel_w: int, stride_h: int, stride_w: int,
+                    pad_h: int, pad_w: int, dilation_h: int, dilation_w: int, group: int, group_channels: int, offset_scale: float,
+                    im2col_step: int, needs: List[bool]) -> List[Tensor]:
+    """[d_input, d_offset, d_mask], each in its argument's dtype; needs: which of them are wanted (the others come back as empty
+    placeholders and cost nothing)."""
+    n, h, w, _ = input.shape
+    ho, wo = offset.shape[1], offset.shape[2]
+    k = kernel_h * kernel_w
+    none = lambda: grad.new_empty((0,))                                    # noqa: E731
+    if grad.numel() == 0 or h * w == 0:
+        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else none()
+                for t, need in zip((input, offset, mask), needs)]
+    if not any(needs):
+        return [none(), none(), none()]
+    geom = (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
+    with torch.cuda.device(grad.device):
+        g, off, msk = grad.contiguous(), _msda_float(offset), _msda_float(mask)
+        x = input.contiguous() if needs[1] or needs[2] else None
+        dx = torch.empty(input.shape, dtype=input.dtype, device=grad.device) if needs[0] else None
+        doff = torch.empty_like(off) if needs[1] else None
+        dmsk = torch.empty_like(msk) if needs[2] else None
+        nb, stream, lib = min(n, im2col_step), _stream(grad), nv.lib()
+        if needs[0]:
+            size = lib.frcnn_ops_dcnv3_workspace_bytes(nb, h, w, group, group_channels, *geom)
+            if size == 0:
+                raise nv.FrcnnError(-1, "frcnn_ops_dcnv3_workspace_bytes")
+            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        for i0 in range(0, n, nb):
+            c = min(nb, n - i0)
+            if needs[1] or needs[2]:
+                _call("dcnv3_backward_offset", input, x[i0:].data_ptr(), off[i0:].data_ptr(), msk[i0:].data_ptr(), g[i0:].data_ptr(), c, h, w,
+                      group, group_channels, *geom, offset_scale, _opt_ptr(doff, i0), _opt_ptr(dmsk, i0), stream)
+            if needs[0]:
+                entries = c * ho * wo * group * k * 4
+                keys = torch.empty((entries,), dtype=torch.int64, device=grad.device)
+                wts = torch.empty((entries,), dtype=torch.float32, device=grad.device)
+                nv.check(lib.frcnn_ops_dcnv3_plan(off[i0:].data_ptr(), msk[i0:].data_ptr(), c, h, w, group, *geom, offset_scale,
+                                                  keys.data_ptr(), wts.data_ptr(), stream), "frcnn_ops_dcnv3_plan")
+                sorted_keys, order = torch.sort(keys, stable=True)
+                _call("dcnv3_backward_input", input, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), g[i0:].data_ptr(), c, h, w,
+                      group, group_channels, *geom, dx[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        return [dx if needs[0] else none(),
+                doff.to(offset.dtype) if needs[1] else none(),
+                dmsk.to(mask.dtype) if needs[2] else none()]
+
+
+@_dcnv3_backward.register_fake
+def _(grad, input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+      offset_scale, im2col_step, needs):
+    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else grad.new_empty((0,))
+            for t, need in zip((input, offset, mask), needs)]
+
+
+def _dcnv3_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:3])
+    ctx.args = tuple(inputs[3:])
+
+
+def _dcnv3_bwd(ctx, grad):
+    needs = [bool(v) for v in ctx.needs_input_grad[:3]]
+    dx, doff, dmsk = _dcnv3_backward(grad, *ctx.saved_tensors, *ctx.args, needs)
+    return (dx if needs[0] else None, doff if needs[1] else None, dmsk if needs[2] else None) + (None,) * 12
+
+
+torch.library.register_autograd("frcnn::dcnv3", _dcnv3_bwd, setup_context=_dcnv3_setup)
+torch.library.register_autograd("frcnn::dcnv3_backward", _no_double_backward("frcnn::dcnv3"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- public interface -------------------------------------------------------------------------------------------------------------
 def nms(boxes, scores, iou_threshold):
     """torchvision.ops.nms: int64 indices of the kept boxes, by descending score."""
@@ -1762,6 +1901,98 @@ def multi_scale_deformable_attn_pytorch(value, value_spatial_shapes, sampling_lo
     attention_weights = attention_weights.transpose(1, 2).reshape(bs * num_heads, 1, num_queries, num_levels * num_points)
     output = (torch.stack(sampling_value_list, dim=-2).flatten(-2) * attention_weights).sum(-1)
     return output.view(bs, num_heads * embed_dims, num_queries).transpose(1, 2).contiguous()
+
+
+def _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step):
+    """The argument rules of dcnv3 / DCNv3Function: kernel, stride, pad and dil pairs (h, w) of ints."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
+    dtypes, what = _box_dtypes(input)
+    _check_tensor("offset", offset, dtypes, what)
+    _check_tensor("mask", mask, dtypes, what)
+    _check_same_device(input, offset, "input", "offset")
+    _check_same_device(input, mask, "input", "mask")
+    if input.dim() != 4:
+        raise ValueError("input must be [N, H, W, C] (channels last), got shape %s" % (tuple(input.shape),))
+    for name, v in (("group", group), ("group_channels", group_channels), ("im2col_step", im2col_step)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise TypeError("%s must be an int, got %r" % (name, v))
+    if isinstance(offset_scale, bool) or not isinstance(offset_scale, (int, float)):
+        raise TypeError("offset_scale must be a float, got %r" % (offset_scale,))
+    if not math.isfinite(offset_scale):
+        raise ValueError("offset_scale must be finite, got %r" % (offset_scale,))
+    if im2col_step < 1:
+        raise ValueError("im2col_step must be at least 1, got %d" % im2col_step)
+    if group < 1:
+        raise ValueError("group must be at least 1, got %d" % group)
+    n, h, w, c = input.shape
+    if group * group_channels != c:
+        raise ValueError("group * group_channels must equal input's %d channels, got group %d and group_channels %d"
+                         % (c, group, group_channels))
+    if not 1 <= group_channels <= MAX_DCNV3_CHANNELS:
+        raise ValueError("group_channels must lie in [1, MAX_DCNV3_CHANNELS = %d], got %d" % (MAX_DCNV3_CHANNELS, group_channels))
+    if not (1 <= kernel[0] <= MAX_DCNV3_KERNEL and 1 <= kernel[1] <= MAX_DCNV3_KERNEL):
+        raise ValueError("kernel_size must lie in [1, MAX_DCNV3_KERNEL = %d], got %r" % (MAX_DCNV3_KERNEL, tuple(kernel)))
+    for name, v, low in (("stride", stride, 1), ("padding", pad, 0), ("dilation", dil, 1)):
+        if not (low <= v[0] <= MAX_DCNV3_STEP and low <= v[1] <= MAX_DCNV3_STEP):
+            raise ValueError("%s must lie in [%d, MAX_DCNV3_STEP = %d], got %r" % (name, low, MAX_DCNV3_STEP, tuple(v)))
+    if h > MAX_DCNV3_SIDE or w > MAX_DCNV3_SIDE:
+        raise ValueError("input must have H and W of at most MAX_DCNV3_SIDE = %d, got shape %s" % (MAX_DCNV3_SIDE, tuple(input.shape)))
+    k = kernel[0] * kernel[1]
+    ho, wo = _dcnv3_out_size(h, kernel[0], stride[0], pad[0], dil[0]), _dcnv3_out_size(w, kernel[1], stride[1], pad[1], dil[1])
+    if tuple(offset.shape) != (n, ho, wo, group * k * 2):
+        raise ValueError("offset must be [N, Ho, Wo, G K 2] = [%d, %d, %d, %d], got shape %s" % (n, ho, wo, group * k * 2, tuple(offset.shape)))
+    if tuple(mask.shape) != (n, ho, wo, group * k):
+        raise ValueError("mask must be [N, Ho, Wo, G K] = [%d, %d, %d, %d], got shape %s" % (n, ho, wo, group * k, tuple(mask.shape)))
+    nb = min(n, im2col_step)
+    if nb * h * w * group > MAX_MSDA_INDEX:
+        raise ValueError("input is too large for the kernels' 32-bit cell indices: %d images x H x W x G = %d > MAX_MSDA_INDEX = %d "
+                         "(lower im2col_step)" % (nb, nb * h * w * group, MAX_MSDA_INDEX))
+    if nb * ho * wo * group * k * 4 > MAX_MSDA_INDEX:
+        raise ValueError("offset is too large for the kernels' 32-bit plan indices: %d images x Ho x Wo x G x K x 4 = %d > MAX_MSDA_INDEX = "
+                         "%d (lower im2col_step)" % (nb, nb * ho * wo * group * k * 4, MAX_MSDA_INDEX))
+
+
+def dcnv3(input, offset, mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256):
+    """DCNv3's sampling core: input [N, H, W, G Gc] sampled at kh kw learned positions per output pixel and group (offset
+    [N, Ho, Wo, G K 2], pairs (dx, dy)), the samples weighted by mask [N, Ho, Wo, G K] and summed: [N, Ho, Wo, G Gc]."""
+    kernel = _int_pair("kernel_size", kernel_size, 1)
+    stride, pad, dil = _int_pair("stride", stride, 1), _int_pair("padding", padding, 0), _int_pair("dilation", dilation, 1)
+    if not isinstance(group, int) or isinstance(group, bool):
+        raise TypeError("group must be an int, got %r" % (group,))
+    if group < 1:
+        raise ValueError("group must be at least 1, got %d" % group)
+    if isinstance(input, torch.Tensor) and input.dim() == 4 and input.shape[3] % group != 0:
+        raise ValueError("input's %d channels must be divisible by group, got %d" % (input.shape[3], group))
+    gc = input.shape[3] // group if isinstance(input, torch.Tensor) and input.dim() == 4 else 1
+    _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, gc, offset_scale, im2col_step)
+    return _dcnv3(input, offset, mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, gc,
+                  float(offset_scale), im2col_step)
+
+
+def dcnv3_core_pytorch(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                       group_channels, offset_scale):
+    """InternImage's dcnv3_core_pytorch: the same operator composed from F.pad and one F.grid_sample, on any device.  It materialises an
+    [N G, Gc, Ho Wo, K] tensor."""
+    F = torch.nn.functional
+    x = F.pad(input, [0, 0, pad_w, pad_w, pad_h, pad_h])
+    n, hp, wp, _ = x.shape
+    ho, wo = offset.shape[1], offset.shape[2]
+    k = kernel_h * kernel_w
+    bx, by = (dilation_w * (kernel_w - 1)) // 2, (dilation_h * (kernel_h - 1)) // 2
+    new = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device)     # noqa: E731
+    steps = lambda count: torch.arange(count, dtype=x.dtype, device=x.device)   # noqa: E731
+    ref = torch.stack(torch.broadcast_tensors(((steps(wo) * stride_w + bx + 0.5) / wp).view(1, wo),
+                                              ((steps(ho) * stride_h + by + 0.5) / hp).view(ho, 1)), -1)           # [Ho, Wo, 2] (x, y)
+    grid = torch.stack([((steps(kernel_w) * dilation_w - bx) / wp).repeat_interleave(kernel_h),                     # x: the outer index
+                        ((steps(kernel_h) * dilation_h - by) / hp).repeat(kernel_w)], -1) * offset_scale            # [K, 2]
+    loc = (ref.view(1, ho, wo, 1, 1, 2) + grid.view(1, 1, 1, 1, k, 2)
+           + offset.view(n, ho, wo, group, k, 2) * offset_scale / new([wp, hp]))
+    maps = x.reshape(n, hp * wp, group, group_channels).permute(0, 2, 3, 1).reshape(n * group, group_channels, hp, wp)
+    grids = (2 * loc - 1).view(n, ho * wo, group, k, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, K, 2]
+    sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, K]
+    weights = mask.view(n, ho * wo, group, k).transpose(1, 2).reshape(n * group, 1, ho * wo, k)
+    out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
+    return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
 
 
 def _ms_features(features):
@@ -2220,3 +2451,80 @@ class MultiScaleDeformableAttention(torch.nn.Module):
     def extra_repr(self):
         return "embed_dims=%s, num_heads=%s, num_levels=%s, num_points=%s, im2col_step=%s, batch_first=%s" % (
             self.embed_dims, self.num_heads, self.num_levels, self.num_points, self.im2col_step, self.batch_first)
+
+
+class DCNv3Function:
+    """InternImage's DCNv3Function: .apply(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h,
+    dilation_w, group, group_channels, offset_scale, im2col_step), upstream's fifteen positional arguments, on frcnn::dcnv3 (whose
+    autograd is registered with the custom op)."""
+
+    @staticmethod
+    def apply(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+              offset_scale, im2col_step):
+        kernel, stride = _int_pair("kernel_h, kernel_w", (kernel_h, kernel_w), 1), _int_pair("stride_h, stride_w", (stride_h, stride_w), 1)
+        pad, dil = _int_pair("pad_h, pad_w", (pad_h, pad_w), 0), _int_pair("dilation_h, dilation_w", (dilation_h, dilation_w), 1)
+        _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step)
+        return _dcnv3(input, offset, mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group,
+                      group_channels, float(offset_scale), im2col_step)
+
+
+class _ToChannelsLast(torch.nn.Module):
+    def forward(self, x):
+        return x.permute(0, 2, 3, 1)
+
+
+class DCNv3(torch.nn.Module):
+    """InternImage's DCNv3 module on [N, H, W, C] input.  input_proj projects the input; a depthwise convolution, LayerNorm and GELU on
+    the input feed the offset and mask heads (a softmax over the K points of each group); the sampler mixes the projected input;
+    output_proj projects back."""
+
+    def __init__(self, channels=64, kernel_size=3, dw_kernel_size=None, stride=1, pad=1, dilation=1, group=4, offset_scale=1.0,
+                 center_feature_scale=False, remove_center=False):
+        super().__init__()
+        if center_feature_scale or remove_center:
+            raise NotImplementedError("DCNv3: center_feature_scale and remove_center are not implemented")
+        if channels % group != 0:
+            raise ValueError("channels must be divisible by group, got %d and %d" % (channels, group))
+        dw_kernel_size = dw_kernel_size if dw_kernel_size is not None else kernel_size
+        nn = torch.nn
+        self.offset_scale = offset_scale
+        self.channels = channels
+        self.kernel_size = kernel_size
+        self.dw_kernel_size = dw_kernel_size
+        self.stride = stride
+        self.dilation = dilation
+        self.pad = pad
+        self.group = group
+        self.group_channels = channels // group
+        self.dw_conv = nn.Sequential(nn.Conv2d(channels, channels, dw_kernel_size, 1, (dw_kernel_size - 1) // 2, groups=channels),
+                                     nn.Sequential(_ToChannelsLast(), nn.LayerNorm(channels, eps=1e-6)), nn.GELU())
+        self.offset = nn.Linear(channels, group * kernel_size * kernel_size * 2)
+        self.mask = nn.Linear(channels, group * kernel_size * kernel_size)
+        self.input_proj = nn.Linear(channels, channels)
+        self.output_proj = nn.Linear(channels, channels)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        for head in (self.offset, self.mask):
+            torch.nn.init.zeros_(head.weight)
+            torch.nn.init.zeros_(head.bias)
+        for proj in (self.input_proj, self.output_proj):
+            torch.nn.init.xavier_uniform_(proj.weight)
+            torch.nn.init.zeros_(proj.bias)
+
+    def forward(self, input):
+        n, h, w, _ = input.shape
+        x = self.input_proj(input)
+        x1 = self.dw_conv(input.permute(0, 3, 1, 2))
+        offset = self.offset(x1)
+        mask = torch.softmax(self.mask(x1).reshape(n, h, w, self.group, -1), -1).reshape(n, h, w, -1)
+        k, s, p, d = self.kernel_size, self.stride, self.pad, self.dilation
+        if x.device.type == "cuda":
+            x = DCNv3Function.apply(x, offset, mask, k, k, s, s, p, p, d, d, self.group, self.group_channels, self.offset_scale, 256)
+        else:
+            x = dcnv3_core_pytorch(x, offset, mask, k, k, s, s, p, p, d, d, self.group, self.group_channels, self.offset_scale)
+        return self.output_proj(x)
+
+    def extra_repr(self):
+        return "channels=%s, kernel_size=%s, dw_kernel_size=%s, stride=%s, pad=%s, dilation=%s, group=%s, offset_scale=%s" % (
+            self.channels, self.kernel_size, self.dw_kernel_size, self.stride, self.pad, self.dilation, self.group, self.offset_scale)

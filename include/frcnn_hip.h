@@ -74,7 +74,10 @@ extern "C" {
                                  forms and the frcnn_ops_msda_max_levels / _max_points / _max_channels / _block_items / _segment getters (multi-scale deformable
                                  attention: mmcv's ms_deform_attn);
                                  still 21 (additions only): frcnn_ops_prroi_pool, its _backward, _16, _workspace_bytes and _cull_list forms
-                                 (Precise RoI Pooling with box gradients: IoU-Net's PrRoIPool, mmcv's prroi_pool) */
+                                 (Precise RoI Pooling with box gradients: IoU-Net's PrRoIPool, mmcv's prroi_pool);
+                                 still 21 (additions only): frcnn_ops_dcnv3_forward, _backward_offset, _plan, _backward_input, _workspace_bytes, the
+                                 _16 forms and the frcnn_ops_dcnv3_max_kernel / _max_channels / _block_items getters (DCNv3: InternImage's deformable
+                                 convolution v3) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -856,6 +859,73 @@ int frcnn_ops_msda_backward_loc_16(int elem_type, const void* d_value, const int
 int frcnn_ops_msda_backward_value_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
                                      const void* d_dout, int n_img, int s, int m, int d, int q, int levels, int points, void* d_dvalue,
                                      void* d_ws, size_t ws_bytes, void* stream);
+
+/* DCNv3, the deformable convolution v3 of the InternImage backbones (csrc/ops_dcnv3.hip): a grouped, weight-free deformable sampling on
+ *   channels-last maps, restated from the published operator (third party, absent here: restated, unpinned; where the two differ this
+ *   text holds).
+ * Tensors: d_input [n][h][w][g gc] (g groups of gc channels); d_offset float32 [n][ho][wo][g K 2], the pair of (group, point p) at
+ *   (group K + p) 2 as (dx, dy); d_mask float32 [n][ho][wo][g K], that of (group, p) at group K + p; d_out and d_dout [n][ho][wo][g gc].
+ *   K = kernel_h kernel_w; ho = (h + 2 pad_h - (dil_h (kernel_h - 1) + 1)) / stride_h + 1, wo likewise.  Point p = i kernel_h + j has i in
+ *   [0, kernel_w) along x as the OUTER index and j in [0, kernel_h) along y (x-major).  With bx = dil_w (kernel_w - 1) / 2 and by =
+ *   dil_h (kernel_h - 1) / 2 (integer division) the sample (b, oy, ox, group, p) lies at
+ *       x = (ox stride_w - pad_w + bx) + ((i dil_w - bx) + dx) * offset_scale
+ *       y = (oy stride_h - pad_h + by) + ((j dil_h - by) + dy) * offset_scale
+ *   in pixels of the unpadded map: the two integer parts formed in int and converted exactly, the sum with the offset, the product and the
+ *   final sum in float32, each rounded.  The sample counts iff x > -1 && y > -1 && x < w && y < h (a NaN coordinate fails, so no index is
+ *   formed from it); its corners are (y0, x0), (y0, x1), (y1, x0), (y1, x1) with y0 = floor(y), y1 = y0 + 1, ly = y - y0, hy = 1 - ly
+ *   (likewise x) and the weights hy hx, hy lx, ly hx, ly lx; a corner outside [0, h - 1] x [0, w - 1] counts 0.
+ *     out[b][oy][ox][group gc + c] = sum over p ascending of mask * (((w0 v0 + w1 v1) + w2 v2) + w3 v3)     (float32, rounded separately)
+ * frcnn_ops_dcnv3_backward_offset: d_doffset (shaped as d_offset) and d_dmask (as d_mask), every element overwritten, one store each;
+ *   either may be NULL (not both).  d_dmask = sum over c of dout * sample; d_doffset dx = offset_scale * sum over c of (dout * mask) *
+ *   ((hy v1 - hy v0) + (ly v3 - ly v2)) and dy = offset_scale * sum of (dout * mask) * ((hx v2 - hx v0) + (lx v3 - lx v1)), over the
+ *   forward's accepted range and corners (a corner that counts 0 enters as 0): at an integer coordinate this is the RIGHT-HAND slope, the
+ *   slope of the cell [x0, x0 + 1) that floor selects; all three are 0 for a sample that does not count (x == -1 included).  The sum over
+ *   c is a lane's channels ascending, then an xor butterfly over the lanes of the item: a fixed order.
+ * frcnn_ops_dcnv3_plan + frcnn_ops_dcnv3_backward_input: the input gradient without atomics.  The plan writes one entry per sample and
+ *   corner, e = (((b ho wo + oy wo + ox) g_n + group) K + p) 4 + corner: d_keys[e] = (b h w + cell) g_n + group with cell = yy w + xx, or the
+ *   sentinel n h w g for a corner that counts 0, and d_weights[e] = corner weight * mask.  The caller sorts the keys STABLY (sorted keys +
+ *   the permutation, int64 each) and passes them on; d_dinput[b][yy][xx][group][:] = the sum over the cell's entries in ascending e of
+ *   weight * dout[b][oy][ox][group][:], every cell written (zeros included), by the gather of frcnn_ops_msda_backward_value: a cell with
+ *   more than frcnn_ops_msda_segment() entries is summed in pieces, cut from the segment's own start.  A cell's entries belong to its
+ *   own image: chunking the images changes no bit.  d_ws: frcnn_ops_dcnv3_workspace_bytes(...) bytes, 16-byte aligned (0: invalid sizes).
+ * Mapping, exported because callers and tests place shapes on its seams: a group of lanes serves one (b, oy, ox, group); a lane owns runs
+ *   of 4 float32 (8 16-bit) channels when gc holds whole runs and the tensors are 16-byte aligned, else single channels;
+ *   frcnn_ops_dcnv3_block_items(gc, kernel_h, kernel_w, elem_type) (elem_type 0: float32) is the number of items a block serves for
+ *   aligned tensors, 0 for arguments out of range.  The result does not depend on the mapping's block size.
+ * The _16 forms take float16 / bfloat16 input, dout, out and d_input (elem_type) under the contract of the 16-bit operators above:
+ *   widened exactly on load, the float32 body, one rounding to nearest even on store; offset, mask and their gradients stay float32.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): n, g >= 1, 1 <= h, w <= 2^24, 1 <= gc <=
+ *   frcnn_ops_dcnv3_max_channels() = 256, 1 <= kernel_h, kernel_w <= frcnn_ops_dcnv3_max_kernel() = 7, stride and dilation in [1, 65536],
+ *   padding in [0, 65536], ho and wo >= 1, a finite offset_scale, n h w g <= 2^31 - 1025 and n ho wo g K 4 <= 2^31 - 1025 (32-bit cell and
+ *   entry indices; element offsets are 64-bit), NULL pointers, a workspace that is NULL, misaligned or too small, an unknown elem_type. */
+int frcnn_ops_dcnv3_max_kernel(void);
+int frcnn_ops_dcnv3_max_channels(void);
+int frcnn_ops_dcnv3_block_items(int gc, int kernel_h, int kernel_w, int elem_type);
+size_t frcnn_ops_dcnv3_workspace_bytes(int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                       int pad_h, int pad_w, int dil_h, int dil_w);
+int frcnn_ops_dcnv3_forward(const float* d_input, const float* d_offset, const float* d_mask, int n_img, int h, int w, int g, int gc,
+                            int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                            float offset_scale, float* d_out, void* stream);
+int frcnn_ops_dcnv3_backward_offset(const float* d_input, const float* d_offset, const float* d_mask, const float* d_dout, int n_img, int h,
+                                    int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
+                                    int dil_h, int dil_w, float offset_scale, float* d_doffset, float* d_dmask, void* stream);
+int frcnn_ops_dcnv3_plan(const float* d_offset, const float* d_mask, int n_img, int h, int w, int g, int kernel_h, int kernel_w,
+                         int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, int64_t* d_keys,
+                         float* d_weights, void* stream);
+int frcnn_ops_dcnv3_backward_input(const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights, const float* d_dout,
+                                   int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                   int pad_h, int pad_w, int dil_h, int dil_w, float* d_dinput, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_dcnv3_forward_16(int elem_type, const void* d_input, const float* d_offset, const float* d_mask, int n_img, int h, int w,
+                               int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                               int dil_w, float offset_scale, void* d_out, void* stream);
+int frcnn_ops_dcnv3_backward_offset_16(int elem_type, const void* d_input, const float* d_offset, const float* d_mask, const void* d_dout,
+                                       int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                       int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, float* d_doffset, float* d_dmask,
+                                       void* stream);
+int frcnn_ops_dcnv3_backward_input_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
+                                      const void* d_dout, int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h,
+                                      int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, void* d_dinput, void* d_ws, size_t ws_bytes,
+                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

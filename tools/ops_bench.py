@@ -53,6 +53,11 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     ops.prroi_pool beside ops.prroi_pool_pytorch (the weight matrices and one einsum per image, autograd's backward), forward and
     forward + backward of both gradients (the map's and the boxes'), in alternating windows.  Informational: no speed bound is set.
 
+  * dcnv3: DCNv3 in an InternImage-T stage at detection size (2 x 100 x 160 x 128, G 8, Gc 16, 3 x 3, pad 1, offsets N(0, 2 px), masks
+    a softmax over the 9 points), float32 and bfloat16: ops.dcnv3 beside ops.dcnv3_core_pytorch (pad, one grid_sample, autograd's
+    backward), forward and forward + backward of all three gradients, in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only dcnv3           # just the DCNv3 leg
     python tools/ops_bench.py --only prroi           # just the Precise-RoI-Pooling leg
     python tools/ops_bench.py --only msda            # just the deformable-attention leg
     python tools/ops_bench.py --only carafe          # just the CARAFE leg
@@ -419,6 +424,30 @@ def msda_leg(rng, reps, warmup):
     return res
 
 
+def dcnv3_leg(rng, reps, warmup):
+    n, h, w, group, gc, k = 2, 100, 160, 8, 16, 3
+    geom = (k, k, 1, 1, 1, 1, 1, 1, group, gc, 1.0)
+    gen = torch.Generator().manual_seed(0)
+    res = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((n, h, w, group * gc), generator=gen).to(DEV).to(dtype)
+        off = (2.0 * torch.randn((n, h, w, group * k * k * 2), generator=gen)).to(DEV).to(dtype)
+        m = torch.softmax(torch.randn((n, h, w, group, k * k), generator=gen), -1).view(n, h, w, -1).to(DEV).to(dtype)
+        g = torch.randn((n, h, w, group * gc), generator=gen).to(DEV).to(dtype)
+        xg, og, mg = (t.clone().requires_grad_(True) for t in (x, off, m))
+        native = lambda *t: ops.DCNv3Function.apply(*t, *geom, 256)              # noqa: E731
+        composed = lambda *t: ops.dcnv3_core_pytorch(*t, *geom)                  # noqa: E731
+        y, yc = native(x, off, m).float(), composed(x, off, m).float()
+        r = {"max |ops - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        del y, yc
+        for name, fns in (("fwd", (lambda: native(x, off, m), lambda: composed(x, off, m))),
+                          ("fwd+bwd", (lambda: native(xg, og, mg).backward(g), lambda: composed(xg, og, mg).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.dcnv3": round(t_native, 1), "dcnv3_core_pytorch": round(t_comp, 1), "composition / ops": round(t_comp / t_native, 2)}
+        res["dcnv3 %s InternImage-T stage 2 x 100 x 160 x 128, G 8, Gc 16, 3 x 3, pad 1" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def prroi_leg(rng, reps, warmup):
     n, c, h, w, k, out, scale = 2, 256, 50, 68, 512, (7, 7), 1 / 16
     gen = torch.Generator().manual_seed(0)
@@ -455,7 +484,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -488,6 +517,9 @@ def main():
         return
     if a.only == "prroi":
         print(json.dumps(prroi_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "dcnv3":
+        print(json.dumps(dcnv3_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -557,6 +589,7 @@ def main():
     res.update(carafe_leg(rng, 5, 2))
     res.update(msda_leg(rng, 5, 2))
     res.update(prroi_leg(rng, 5, 2))
+    res.update(dcnv3_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
