@@ -82,6 +82,9 @@ SYMBOLS = (
     "frcnn_ops_dcnv3_max_kernel", "frcnn_ops_dcnv3_max_channels", "frcnn_ops_dcnv3_block_items", "frcnn_ops_dcnv3_workspace_bytes",
     "frcnn_ops_dcnv3_forward", "frcnn_ops_dcnv3_backward_offset", "frcnn_ops_dcnv3_plan", "frcnn_ops_dcnv3_backward_input",
     "frcnn_ops_dcnv3_forward_16", "frcnn_ops_dcnv3_backward_offset_16", "frcnn_ops_dcnv3_backward_input_16",
+    "frcnn_ops_dcnv4_record", "frcnn_ops_dcnv4_block_items", "frcnn_ops_dcnv4_workspace_bytes",
+    "frcnn_ops_dcnv4_forward", "frcnn_ops_dcnv4_backward_offset_mask", "frcnn_ops_dcnv4_plan", "frcnn_ops_dcnv4_backward_input",
+    "frcnn_ops_dcnv4_forward_16", "frcnn_ops_dcnv4_backward_offset_mask_16", "frcnn_ops_dcnv4_backward_input_16",
 )
 
 
@@ -359,6 +362,17 @@ _SIGNATURES = {
     "frcnn_ops_dcnv3_forward_16": (C.c_int, [_i, _vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp]),
     "frcnn_ops_dcnv3_backward_offset_16": (C.c_int, [_i, _vp, _vp, _vp, _vp] + [_i] * 13 + [_f, _vp, _vp, _vp]),
     "frcnn_ops_dcnv3_backward_input_16": (C.c_int, [_i, _vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _vp, _sz, _vp]),
+    # DCNv4 (csrc/ops_dcnv4.hip): DCNv3's arguments with one packed offset_mask tensor and remove_center after the geometry
+    "frcnn_ops_dcnv4_record": (C.c_int, [_i, _i, _i, _i]),
+    "frcnn_ops_dcnv4_block_items": (C.c_int, [_i, _i, _i, _i, _i]),
+    "frcnn_ops_dcnv4_workspace_bytes": (C.c_size_t, [_i] * 14),
+    "frcnn_ops_dcnv4_forward": (C.c_int, [_vp, _vp] + [_i] * 13 + [_f, _i, _vp, _vp]),
+    "frcnn_ops_dcnv4_backward_offset_mask": (C.c_int, [_vp, _vp, _vp] + [_i] * 13 + [_f, _i, _vp, _vp]),
+    "frcnn_ops_dcnv4_plan": (C.c_int, [_vp] + [_i] * 12 + [_f, _i, _vp, _vp, _vp]),
+    "frcnn_ops_dcnv4_backward_input": (C.c_int, [_vp, _vp, _vp, _vp] + [_i] * 14 + [_vp, _vp, _sz, _vp]),
+    "frcnn_ops_dcnv4_forward_16": (C.c_int, [_i, _vp, _vp] + [_i] * 13 + [_f, _i, _vp, _vp]),
+    "frcnn_ops_dcnv4_backward_offset_mask_16": (C.c_int, [_i, _vp, _vp, _vp] + [_i] * 13 + [_f, _i, _vp, _vp]),
+    "frcnn_ops_dcnv4_backward_input_16": (C.c_int, [_i, _vp, _vp, _vp, _vp] + [_i] * 14 + [_vp, _vp, _sz, _vp]),
     "frcnn_x6t_record_bytes": (C.c_size_t, [_i, _i]),
     "frcnn_split_rows_x6t": (C.c_int, [_vp, _i, _sz, _vp, _i, _i, _i, _i, _vp]),
     "frcnn_gemm_x6t_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),

@@ -1,4 +1,5 @@
-// ops_msda.h -- what the channels-last deformable samplers share (ops_msda.hip: multi-scale deformable attention; ops_dcnv3.hip: DCNv3):
+// ops_msda.h -- what the channels-last deformable samplers share (ops_msda.hip: multi-scale deformable attention; ops_dcn.h: DCNv3 and
+// DCNv4):
 // the element types and their 16-byte runs, the lanes-along-channels mapping, and the sorted-plan gather of the value / input gradient.
 #pragma once
 #include "common.h"

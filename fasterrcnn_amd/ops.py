@@ -10,6 +10,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import multi_scale_deformable_attn, MultiScaleDeformableAttnFunction, MultiScaleDeformableAttention
     from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
     from fasterrcnn_amd.ops import dcnv3, DCNv3Function, dcnv3_core_pytorch, DCNv3
+    from fasterrcnn_amd.ops import dcnv4, DCNv4Function, dcnv4_core_pytorch, DCNv4
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -219,6 +220,31 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       bias on the projections), so InternImage checkpoints load strict; the depthwise convolution, LayerNorm, GELU, the linear layers
       and the softmax over K are torch's; on the GPU the sampler is this operator, elsewhere the composition.  center_feature_scale
       and remove_center are not implemented (NotImplementedError).
+  dcnv4(input, offset_mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256, remove_center=False)
+  DCNv4Function.apply(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                      group_channels, offset_scale, im2col_step, remove_center)
+  dcnv4_core_pytorch(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                     group_channels, offset_scale, remove_center)
+  DCNv4(channels=64, kernel_size=3, stride=1, pad=1, dilation=1, group=4, offset_scale=1.0, dw_kernel_size=None,
+        center_feature_scale=False, remove_center=False, output_bias=True, without_pointwise=False)
+      DCNv4, the deformable convolution v4 of the FlashInternImage backbones (csrc/ops_dcnv4.hip; restated, unpinned: where upstream
+      differs include/frcnn_hip.h holds): dcnv3's sampling on ONE packed tensor, with masks that are not soft-maxed (unbounded, signed)
+      and optionally without the centre point.  input [N, H, W, G Gc]; offset_mask [N, Ho, Wo, L], the raw output of one nn.Linear: the
+      record of a pixel holds one slice per group g at [3 P g, 3 P (g + 1)), inside it (dx, dy) of point p at [2 p, 2 p + 1] and its mask
+      value at [2 P + p]; L = ceil(3 G P / 8) 8, and the last L - 3 G P values are padding, never read (a NaN there changes nothing),
+      their gradient 0.  P = kh kw, points enumerated as dcnv3's (x the outer index); with remove_center (kh == kw, odd, >= 3, else a
+      ValueError) the point (kw // 2, kh // 2) is skipped, the later points move down by one and P = kh kw - 1.  Ho, Wo, the coordinate of
+      a sample, the sample test, corners, weights and every sum are dcnv3's, by the same kernels: with remove_center=False
+      dcnv4(x, pack(offset, mask)) equals dcnv3(x, offset, mask) bit for bit, forward and all gradients.  Gradients go to input and to
+      offset_mask as ONE tensor laid out as offset_mask, every element written once by one launch (pad lanes zeros); deterministic, no
+      atomics; d_input by dcnv3's plan, sort and gather; each is skipped when not needed; double backward raises.  im2col_step, the
+      16-bit contract (input, output, d_input; offset_mask float32 or the input's 16-bit dtype, widened before the launch -- the kernels
+      do not read 16-bit records -- its gradient rounded once to that dtype) and the limits are dcnv3's with K = P.
+      dcnv4_core_pytorch is the grid_sample composition on any device (it unpacks the record, drops the centre location when asked,
+      applies no softmax): the CPU fallback.  The module takes [N, L, C] with shape=(H, W) (or L a perfect square) and has upstream's
+      parameter names (offset_mask, and value_proj / output_proj unless without_pointwise; offset_mask_dw, a depthwise Conv2d, only with
+      dw_kernel_size) and init (zeros on offset_mask, Xavier-uniform with zero bias on the projections), so checkpoints load strict; any
+      Gc in [1, 256] works (upstream's Gc % 16 == 0 is not required); center_feature_scale is not implemented (NotImplementedError).
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -248,7 +274,7 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
-           "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3"]
+           "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -1515,6 +1541,111 @@ torch.library.register_autograd("frcnn::dcnv3_backward", _no_double_backward("fr
                                 setup_context=lambda ctx, inputs, output: None)
 
 
+# ---- frcnn::dcnv4 (csrc/ops_dcnv4.hip) ----------------------------------------------------------------------------------------------
+def _dcnv4_points(kernel_h, kernel_w, remove_center):
+    return kernel_h * kernel_w - (1 if remove_center else 0)
+
+
+def _dcnv4_record(group, points):
+    """L: the 3 G P values of a pixel's record padded to a multiple of 8 (frcnn_ops_dcnv4_record())."""
+    return (group * points * 3 + 7) // 8 * 8
+
+
+@torch.library.custom_op("frcnn::dcnv4", mutates_args=())
+def _dcnv4(input: Tensor, offset_mask: Tensor, kernel_h: int, kernel_w: int, stride_h: int, stride_w: int, pad_h: int, pad_w: int,
+           dilation_h: int, dilation_w: int, group: int, group_channels: int, offset_scale: float, im2col_step: int,
+           remove_center: bool) -> Tensor:
+    n, h, w, _ = input.shape
+    ho, wo = offset_mask.shape[1], offset_mask.shape[2]
+    out = torch.empty((n, ho, wo, group * group_channels), dtype=input.dtype, device=input.device)
+    if out.numel() == 0:
+        return out
+    if h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x, om = input.contiguous(), _msda_float(offset_mask)
+        nb, stream = min(n, im2col_step), _stream(input)
+        for i0 in range(0, n, nb):
+            _call("dcnv4_forward", input, x[i0:].data_ptr(), om[i0:].data_ptr(), min(nb, n - i0), h, w, group, group_channels, kernel_h,
+                  kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, offset_scale, int(remove_center), out[i0:].data_ptr(),
+                  stream)
+    return out
+
+
+@_dcnv4.register_fake
+def _(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+      offset_scale, im2col_step, remove_center):
+    return input.new_empty((input.shape[0], offset_mask.shape[1], offset_mask.shape[2], group * group_channels))
+
+
+@torch.library.custom_op("frcnn::dcnv4_backward", mutates_args=())
+def _dcnv4_backward(grad: Tensor, input: Tensor, offset_mask: Tensor, kernel_h: int, kernel_w: int, stride_h: int, stride_w: int,
+                    pad_h: int, pad_w: int, dilation_h: int, dilation_w: int, group: int, group_channels: int, offset_scale: float,
+                    im2col_step: int, remove_center: bool, needs: List[bool]) -> List[Tensor]:
+    """[d_input, d_offset_mask], each in its argument's dtype; needs: which of them are wanted (the other comes back as an empty
+    placeholder and costs nothing)."""
+    n, h, w, _ = input.shape
+    ho, wo = offset_mask.shape[1], offset_mask.shape[2]
+    p = _dcnv4_points(kernel_h, kernel_w, remove_center)
+    none = lambda: grad.new_empty((0,))                                    # noqa: E731
+    if grad.numel() == 0 or h * w == 0:
+        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else none()
+                for t, need in zip((input, offset_mask), needs)]
+    if not any(needs):
+        return [none(), none()]
+    geom = (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
+    rc = int(remove_center)
+    with torch.cuda.device(grad.device):
+        g, om = grad.contiguous(), _msda_float(offset_mask)
+        x = input.contiguous() if needs[1] else None
+        dx = torch.empty(input.shape, dtype=input.dtype, device=grad.device) if needs[0] else None
+        dom = torch.empty_like(om) if needs[1] else None                   # the kernel writes every element, pad lanes included
+        nb, stream, lib = min(n, im2col_step), _stream(grad), nv.lib()
+        if needs[0]:
+            size = lib.frcnn_ops_dcnv4_workspace_bytes(nb, h, w, group, group_channels, *geom, rc)
+            if size == 0:
+                raise nv.FrcnnError(-1, "frcnn_ops_dcnv4_workspace_bytes")
+            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        for i0 in range(0, n, nb):
+            c = min(nb, n - i0)
+            if needs[1]:
+                _call("dcnv4_backward_offset_mask", input, x[i0:].data_ptr(), om[i0:].data_ptr(), g[i0:].data_ptr(), c, h, w, group,
+                      group_channels, *geom, offset_scale, rc, dom[i0:].data_ptr(), stream)
+            if needs[0]:
+                entries = c * ho * wo * group * p * 4
+                keys = torch.empty((entries,), dtype=torch.int64, device=grad.device)
+                wts = torch.empty((entries,), dtype=torch.float32, device=grad.device)
+                nv.check(lib.frcnn_ops_dcnv4_plan(om[i0:].data_ptr(), c, h, w, group, *geom, offset_scale, rc, keys.data_ptr(),
+                                                  wts.data_ptr(), stream), "frcnn_ops_dcnv4_plan")
+                sorted_keys, order = torch.sort(keys, stable=True)
+                _call("dcnv4_backward_input", input, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), g[i0:].data_ptr(), c, h, w,
+                      group, group_channels, *geom, rc, dx[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        return [dx if needs[0] else none(), dom.to(offset_mask.dtype) if needs[1] else none()]
+
+
+@_dcnv4_backward.register_fake
+def _(grad, input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+      offset_scale, im2col_step, remove_center, needs):
+    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else grad.new_empty((0,))
+            for t, need in zip((input, offset_mask), needs)]
+
+
+def _dcnv4_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:2])
+    ctx.args = tuple(inputs[2:])
+
+
+def _dcnv4_bwd(ctx, grad):
+    needs = [bool(v) for v in ctx.needs_input_grad[:2]]
+    dx, dom = _dcnv4_backward(grad, *ctx.saved_tensors, *ctx.args, needs)
+    return (dx if needs[0] else None, dom if needs[1] else None) + (None,) * 13
+
+
+torch.library.register_autograd("frcnn::dcnv4", _dcnv4_bwd, setup_context=_dcnv4_setup)
+torch.library.register_autograd("frcnn::dcnv4_backward", _no_double_backward("frcnn::dcnv4"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
 # ---- public interface -------------------------------------------------------------------------------------------------------------
 def nms(boxes, scores, iou_threshold):
     """torchvision.ops.nms: int64 indices of the kept boxes, by descending score."""
@@ -1991,6 +2122,109 @@ def dcnv3_core_pytorch(input, offset, mask, kernel_h, kernel_w, stride_h, stride
     grids = (2 * loc - 1).view(n, ho * wo, group, k, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, K, 2]
     sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, K]
     weights = mask.view(n, ho * wo, group, k).transpose(1, 2).reshape(n * group, 1, ho * wo, k)
+    out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
+    return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
+
+
+def _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step, remove_center):
+    """The argument rules of dcnv4 / DCNv4Function: kernel, stride, pad and dil pairs (h, w) of ints."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
+    dtypes, what = _box_dtypes(input)
+    _check_tensor("offset_mask", offset_mask, dtypes, what)
+    _check_same_device(input, offset_mask, "input", "offset_mask")
+    if input.dim() != 4:
+        raise ValueError("input must be [N, H, W, C] (channels last), got shape %s" % (tuple(input.shape),))
+    for name, v in (("group", group), ("group_channels", group_channels), ("im2col_step", im2col_step)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise TypeError("%s must be an int, got %r" % (name, v))
+    if not isinstance(remove_center, (bool, int)):
+        raise TypeError("remove_center must be a bool, got %r" % (remove_center,))
+    if remove_center not in (0, 1):
+        raise ValueError("remove_center must be False or True (0 or 1), got %r" % (remove_center,))
+    if isinstance(offset_scale, bool) or not isinstance(offset_scale, (int, float)):
+        raise TypeError("offset_scale must be a float, got %r" % (offset_scale,))
+    if not math.isfinite(offset_scale):
+        raise ValueError("offset_scale must be finite, got %r" % (offset_scale,))
+    if im2col_step < 1:
+        raise ValueError("im2col_step must be at least 1, got %d" % im2col_step)
+    if group < 1:
+        raise ValueError("group must be at least 1, got %d" % group)
+    n, h, w, c = input.shape
+    if group * group_channels != c:
+        raise ValueError("group * group_channels must equal input's %d channels, got group %d and group_channels %d"
+                         % (c, group, group_channels))
+    if not 1 <= group_channels <= MAX_DCNV3_CHANNELS:
+        raise ValueError("group_channels must lie in [1, MAX_DCNV3_CHANNELS = %d], got %d" % (MAX_DCNV3_CHANNELS, group_channels))
+    if not (1 <= kernel[0] <= MAX_DCNV3_KERNEL and 1 <= kernel[1] <= MAX_DCNV3_KERNEL):
+        raise ValueError("kernel_size must lie in [1, MAX_DCNV3_KERNEL = %d], got %r" % (MAX_DCNV3_KERNEL, tuple(kernel)))
+    if remove_center and (kernel[0] != kernel[1] or kernel[0] % 2 == 0 or kernel[0] < 3):
+        raise ValueError("remove_center requires a square kernel of odd size >= 3, got %r" % (tuple(kernel),))
+    for name, v, low in (("stride", stride, 1), ("padding", pad, 0), ("dilation", dil, 1)):
+        if not (low <= v[0] <= MAX_DCNV3_STEP and low <= v[1] <= MAX_DCNV3_STEP):
+            raise ValueError("%s must lie in [%d, MAX_DCNV3_STEP = %d], got %r" % (name, low, MAX_DCNV3_STEP, tuple(v)))
+    if h > MAX_DCNV3_SIDE or w > MAX_DCNV3_SIDE:
+        raise ValueError("input must have H and W of at most MAX_DCNV3_SIDE = %d, got shape %s" % (MAX_DCNV3_SIDE, tuple(input.shape)))
+    p = _dcnv4_points(kernel[0], kernel[1], remove_center)
+    rec = _dcnv4_record(group, p)
+    ho, wo = _dcnv3_out_size(h, kernel[0], stride[0], pad[0], dil[0]), _dcnv3_out_size(w, kernel[1], stride[1], pad[1], dil[1])
+    if tuple(offset_mask.shape) != (n, ho, wo, rec):
+        raise ValueError("offset_mask must be [N, Ho, Wo, L] = [%d, %d, %d, %d] with L = ceil(G P 3 / 8) 8 for G = %d groups of P = %d "
+                         "points (2 P offsets, then P masks; the record padded to a multiple of 8), got shape %s"
+                         % (n, ho, wo, rec, group, p, tuple(offset_mask.shape)))
+    nb = min(n, im2col_step)
+    if nb * h * w * group > MAX_MSDA_INDEX:
+        raise ValueError("input is too large for the kernels' 32-bit cell indices: %d images x H x W x G = %d > MAX_MSDA_INDEX = %d "
+                         "(lower im2col_step)" % (nb, nb * h * w * group, MAX_MSDA_INDEX))
+    if nb * ho * wo * group * p * 4 > MAX_MSDA_INDEX:
+        raise ValueError("offset_mask is too large for the kernels' 32-bit plan indices: %d images x Ho x Wo x G x P x 4 = %d > "
+                         "MAX_MSDA_INDEX = %d (lower im2col_step)" % (nb, nb * ho * wo * group * p * 4, MAX_MSDA_INDEX))
+
+
+def dcnv4(input, offset_mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256,
+          remove_center=False):
+    """DCNv4's sampling core: input [N, H, W, G Gc] sampled at P learned positions per output pixel and group, the samples weighted by
+    unnormalised masks and summed: [N, Ho, Wo, G Gc].  offset_mask [N, Ho, Wo, L] holds, per pixel and group, the 2 P offsets (pairs
+    (dx, dy)) and then the P masks, the record padded to L = ceil(G P 3 / 8) 8; P = kh kw, less the centre point with remove_center."""
+    kernel = _int_pair("kernel_size", kernel_size, 1)
+    stride, pad, dil = _int_pair("stride", stride, 1), _int_pair("padding", padding, 0), _int_pair("dilation", dilation, 1)
+    if not isinstance(group, int) or isinstance(group, bool):
+        raise TypeError("group must be an int, got %r" % (group,))
+    if group < 1:
+        raise ValueError("group must be at least 1, got %d" % group)
+    if isinstance(input, torch.Tensor) and input.dim() == 4 and input.shape[3] % group != 0:
+        raise ValueError("input's %d channels must be divisible by group, got %d" % (input.shape[3], group))
+    gc = input.shape[3] // group if isinstance(input, torch.Tensor) and input.dim() == 4 else 1
+    _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, gc, offset_scale, im2col_step, remove_center)
+    return _dcnv4(input, offset_mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, gc,
+                  float(offset_scale), im2col_step, bool(remove_center))
+
+
+def dcnv4_core_pytorch(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                       group_channels, offset_scale, remove_center):
+    """The same operator composed from F.pad and one F.grid_sample, on any device, differentiable to input and offset_mask: it unpacks
+    the record, drops the centre location when asked and applies no softmax.  It materialises an [N G, Gc, Ho Wo, P] tensor."""
+    F = torch.nn.functional
+    x = F.pad(input, [0, 0, pad_w, pad_w, pad_h, pad_h])
+    n, hp, wp, _ = x.shape
+    ho, wo = offset_mask.shape[1], offset_mask.shape[2]
+    points = [(i, j) for i in range(kernel_w) for j in range(kernel_h)]                                             # x: the outer index
+    if remove_center:
+        points.remove((kernel_w // 2, kernel_h // 2))
+    p = len(points)
+    rec = offset_mask[..., :group * p * 3].reshape(n, ho, wo, group, p * 3)
+    offset, mask = rec[..., :2 * p].reshape(n, ho, wo, group, p, 2), rec[..., 2 * p:]
+    bx, by = (dilation_w * (kernel_w - 1)) // 2, (dilation_h * (kernel_h - 1)) // 2
+    new = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device)     # noqa: E731
+    steps = lambda count: torch.arange(count, dtype=x.dtype, device=x.device)   # noqa: E731
+    ref = torch.stack(torch.broadcast_tensors(((steps(wo) * stride_w + bx + 0.5) / wp).view(1, wo),
+                                              ((steps(ho) * stride_h + by + 0.5) / hp).view(ho, 1)), -1)           # [Ho, Wo, 2] (x, y)
+    grid = torch.stack([new([float(i * dilation_w - bx) for i, j in points]) / wp,
+                        new([float(j * dilation_h - by) for i, j in points]) / hp], -1) * offset_scale              # [P, 2]
+    loc = ref.view(1, ho, wo, 1, 1, 2) + grid.view(1, 1, 1, 1, p, 2) + offset * offset_scale / new([wp, hp])
+    maps = x.reshape(n, hp * wp, group, group_channels).permute(0, 2, 3, 1).reshape(n * group, group_channels, hp, wp)
+    grids = (2 * loc - 1).view(n, ho * wo, group, p, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, P, 2]
+    sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, P]
+    weights = mask.reshape(n, ho * wo, group, p).transpose(1, 2).reshape(n * group, 1, ho * wo, p)
     out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
     return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
 
@@ -2528,3 +2762,94 @@ class DCNv3(torch.nn.Module):
     def extra_repr(self):
         return "channels=%s, kernel_size=%s, dw_kernel_size=%s, stride=%s, pad=%s, dilation=%s, group=%s, offset_scale=%s" % (
             self.channels, self.kernel_size, self.dw_kernel_size, self.stride, self.pad, self.dilation, self.group, self.offset_scale)
+
+
+class DCNv4Function:
+    """Upstream's DCNv4Function: .apply(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
+    group, group_channels, offset_scale, im2col_step, remove_center), its fifteen positional arguments, on frcnn::dcnv4 (whose autograd
+    is registered with the custom op)."""
+
+    @staticmethod
+    def apply(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+              offset_scale, im2col_step, remove_center):
+        kernel, stride = _int_pair("kernel_h, kernel_w", (kernel_h, kernel_w), 1), _int_pair("stride_h, stride_w", (stride_h, stride_w), 1)
+        pad, dil = _int_pair("pad_h, pad_w", (pad_h, pad_w), 0), _int_pair("dilation_h, dilation_w", (dilation_h, dilation_w), 1)
+        _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step, remove_center)
+        return _dcnv4(input, offset_mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group,
+                      group_channels, float(offset_scale), im2col_step, bool(remove_center))
+
+
+class DCNv4(torch.nn.Module):
+    """FlashInternImage's DCNv4 module on [N, L, C] input with L = H W.  value_proj projects the input; offset_mask, one linear layer on
+    the input (after the depthwise convolution offset_mask_dw when dw_kernel_size is given), yields the packed offsets and masks -- no
+    softmax; the sampler mixes the projected input; output_proj projects back.  without_pointwise drops both projections."""
+
+    def __init__(self, channels=64, kernel_size=3, stride=1, pad=1, dilation=1, group=4, offset_scale=1.0, dw_kernel_size=None,
+                 center_feature_scale=False, remove_center=False, output_bias=True, without_pointwise=False):
+        super().__init__()
+        if center_feature_scale:
+            raise NotImplementedError("DCNv4: center_feature_scale is not implemented")
+        if channels % group != 0:
+            raise ValueError("channels must be divisible by group, got %d and %d" % (channels, group))
+        if remove_center and (kernel_size % 2 == 0 or kernel_size < 3):
+            raise ValueError("remove_center requires a square kernel of odd size >= 3, got %r" % ((kernel_size, kernel_size),))
+        nn = torch.nn
+        self.offset_scale = offset_scale
+        self.channels = channels
+        self.kernel_size = kernel_size
+        self.dw_kernel_size = dw_kernel_size
+        self.stride = stride
+        self.dilation = dilation
+        self.pad = pad
+        self.group = group
+        self.group_channels = channels // group
+        self.remove_center = bool(remove_center)
+        self.without_pointwise = without_pointwise
+        self.K = group * _dcnv4_points(kernel_size, kernel_size, remove_center)
+        if dw_kernel_size is not None:
+            self.offset_mask_dw = nn.Conv2d(channels, channels, dw_kernel_size, stride=1, padding=(dw_kernel_size - 1) // 2, groups=channels)
+        self.offset_mask = nn.Linear(channels, _dcnv4_record(group, self.K // group))
+        if not without_pointwise:
+            self.value_proj = nn.Linear(channels, channels)
+            self.output_proj = nn.Linear(channels, channels, bias=output_bias)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        torch.nn.init.zeros_(self.offset_mask.weight)
+        torch.nn.init.zeros_(self.offset_mask.bias)
+        if not self.without_pointwise:
+            for proj in (self.value_proj, self.output_proj):
+                torch.nn.init.xavier_uniform_(proj.weight)
+                if proj.bias is not None:
+                    torch.nn.init.zeros_(proj.bias)
+
+    def forward(self, input, shape=None):
+        n, length, c = input.shape
+        if shape is not None:
+            h, w = shape
+        else:
+            h = w = math.isqrt(length)
+        if h * w != length:
+            raise ValueError("input's length %d is not H W: pass shape=(H, W) (got %r)" % (length, shape))
+        x = input if self.without_pointwise else self.value_proj(input)
+        x = x.reshape(n, h, w, c)
+        if self.dw_kernel_size is not None:
+            head = self.offset_mask_dw(input.reshape(n, h, w, c).permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        else:
+            head = input.reshape(n, h, w, c)
+        offset_mask = self.offset_mask(head)
+        k, s, p, d = self.kernel_size, self.stride, self.pad, self.dilation
+        if x.device.type == "cuda":
+            x = DCNv4Function.apply(x, offset_mask, k, k, s, s, p, p, d, d, self.group, self.group_channels, self.offset_scale, 256,
+                                    self.remove_center)
+        else:
+            x = dcnv4_core_pytorch(x, offset_mask, k, k, s, s, p, p, d, d, self.group, self.group_channels, self.offset_scale,
+                                   self.remove_center)
+        x = x.reshape(n, -1, c)
+        return x if self.without_pointwise else self.output_proj(x)
+
+    def extra_repr(self):
+        return ("channels=%s, kernel_size=%s, stride=%s, pad=%s, dilation=%s, group=%s, offset_scale=%s, dw_kernel_size=%s, "
+                "remove_center=%s, without_pointwise=%s" % (self.channels, self.kernel_size, self.stride, self.pad, self.dilation, self.group,
+                                                           self.offset_scale, self.dw_kernel_size, self.remove_center,
+                                                           self.without_pointwise))

@@ -77,7 +77,10 @@ extern "C" {
                                  (Precise RoI Pooling with box gradients: IoU-Net's PrRoIPool, mmcv's prroi_pool);
                                  still 21 (additions only): frcnn_ops_dcnv3_forward, _backward_offset, _plan, _backward_input, _workspace_bytes, the
                                  _16 forms and the frcnn_ops_dcnv3_max_kernel / _max_channels / _block_items getters (DCNv3: InternImage's deformable
-                                 convolution v3) */
+                                 convolution v3);
+                                 still 21 (additions only): frcnn_ops_dcnv4_forward, _backward_offset_mask, _plan, _backward_input, _workspace_bytes,
+                                 the _16 forms and the frcnn_ops_dcnv4_block_items / _record getters (DCNv4: FlashInternImage's deformable
+                                 convolution v4, one packed offset_mask tensor, optionally without the centre point) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -926,6 +929,65 @@ int frcnn_ops_dcnv3_backward_input_16(int elem_type, const int64_t* d_sorted_key
                                       const void* d_dout, int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h,
                                       int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, void* d_dinput, void* d_ws, size_t ws_bytes,
                                       void* stream);
+
+/* DCNv4, the deformable convolution v4 of the FlashInternImage backbones (csrc/ops_dcnv4.hip): DCNv3's sampling on ONE packed tensor of
+ *   offsets and masks, the masks not soft-maxed (unbounded, signed), optionally without the centre point.  Restated from the published
+ *   operator (third party, absent here: restated, unpinned; where the two differ this text holds).
+ * Tensors: d_input [n][h][w][g gc]; d_offset_mask float32 [n][ho][wo][L], one record for each output pixel, L = ceil(3 g P / 8) 8 =
+ *   frcnn_ops_dcnv4_record(g, kernel_h, kernel_w, remove_center) (0 for bad arguments); d_out and d_dout [n][ho][wo][g gc]; ho and wo as for
+ *   DCNv3.  The record of pixel (b, oy, ox) holds one slice for each group, at [3 P group, 3 P (group + 1)); inside a slice [2 p, 2 p + 1]
+ *   is (dx, dy) of point p and [2 P + p] its mask value.  The last L - 3 g P values of a record are padding: never read (a NaN there
+ *   changes nothing), their gradient 0.
+ * Points: the grid points are enumerated as DCNv3's, i in [0, kernel_w) along x as the OUTER index and j in [0, kernel_h) along y.
+ *   remove_center == 0: P = kernel_h kernel_w and point p is grid point p.  remove_center == 1 (it requires kernel_h == kernel_w, odd,
+ *   >= 3): the grid point (kernel_w / 2, kernel_h / 2) is skipped and the later points move down by one, P = kernel_h kernel_w - 1.
+ * Sampling: the coordinate of a sample, the test x > -1 && y > -1 && x < w && y < h (a NaN fails), the corners, the weights, the order of
+ *   the four-corner sum and the ascending sum over p are exactly DCNv3's above (the integer parts in int, the rest in float32, in pixels
+ *   of the unpadded map), by the same kernels: with remove_center == 0 and the same offsets and masks, d_out, d_dinput and the gradient
+ *   of every offset and mask value EQUAL DCNv3's bit for bit.
+ * frcnn_ops_dcnv4_backward_offset_mask: d_doffset_mask, shaped and laid out as d_offset_mask, every element written exactly once by one
+ *   launch: the offset and mask parts by DCNv3's formulas (the right-hand slope at an integer coordinate, 0 for a sample that does not
+ *   count), the pad lanes as zeros.  No atomics, a fixed summation order.
+ * frcnn_ops_dcnv4_plan + frcnn_ops_dcnv4_backward_input: as DCNv3's, the plan read from the records: entry e = (((b ho wo + oy wo + ox) g_n +
+ *   group) P + p) 4 + corner, keys, sentinel and weights as there; the gather is frcnn_ops_msda_backward_value's with P samples an item;
+ *   every cell is written; chunking the images changes no bit.  d_ws: frcnn_ops_dcnv4_workspace_bytes(...) bytes, 16-byte aligned.
+ * Mapping: DCNv3's, with P samples an item; frcnn_ops_dcnv4_block_items(gc, kernel_h, kernel_w, remove_center, elem_type) is the number of
+ *   items (b, oy, ox, group) a block serves for aligned tensors, 0 for arguments out of range.  A block stages its items' slices in LDS
+ *   from the records themselves (16-byte loads when d_offset_mask is 16-byte aligned), whether or not it begins or ends inside a record.
+ * The _16 forms take float16 / bfloat16 input, dout, out and d_input (elem_type) under the contract of the 16-bit operators above;
+ *   offset_mask and its gradient stay float32.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): DCNv3's limits with K = P (kernel <= 7, gc <= 256, stride and
+ *   dilation in [1, 65536], padding in [0, 65536], ho and wo >= 1, a finite offset_scale, n h w g <= 2^31 - 1025 and n ho wo g P 4 <=
+ *   2^31 - 1025), remove_center outside {0, 1}, remove_center == 1 with kernel_h != kernel_w, an even kernel or a kernel below 3, NULL
+ *   pointers, a workspace that is NULL, misaligned or too small, an unknown elem_type. */
+int frcnn_ops_dcnv4_record(int g, int kernel_h, int kernel_w, int remove_center);
+int frcnn_ops_dcnv4_block_items(int gc, int kernel_h, int kernel_w, int remove_center, int elem_type);
+size_t frcnn_ops_dcnv4_workspace_bytes(int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                       int pad_h, int pad_w, int dil_h, int dil_w, int remove_center);
+int frcnn_ops_dcnv4_forward(const float* d_input, const float* d_offset_mask, int n_img, int h, int w, int g, int gc, int kernel_h,
+                            int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale,
+                            int remove_center, float* d_out, void* stream);
+int frcnn_ops_dcnv4_backward_offset_mask(const float* d_input, const float* d_offset_mask, const float* d_dout, int n_img, int h, int w,
+                                         int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w,
+                                         int dil_h, int dil_w, float offset_scale, int remove_center, float* d_doffset_mask, void* stream);
+int frcnn_ops_dcnv4_plan(const float* d_offset_mask, int n_img, int h, int w, int g, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                         int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, int remove_center, int64_t* d_keys,
+                         float* d_weights, void* stream);
+int frcnn_ops_dcnv4_backward_input(const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights, const float* d_dout,
+                                   int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                   int pad_h, int pad_w, int dil_h, int dil_w, int remove_center, float* d_dinput, void* d_ws,
+                                   size_t ws_bytes, void* stream);
+int frcnn_ops_dcnv4_forward_16(int elem_type, const void* d_input, const float* d_offset_mask, int n_img, int h, int w, int g, int gc,
+                               int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                               float offset_scale, int remove_center, void* d_out, void* stream);
+int frcnn_ops_dcnv4_backward_offset_mask_16(int elem_type, const void* d_input, const float* d_offset_mask, const void* d_dout, int n_img,
+                                            int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h,
+                                            int pad_w, int dil_h, int dil_w, float offset_scale, int remove_center, float* d_doffset_mask,
+                                            void* stream);
+int frcnn_ops_dcnv4_backward_input_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
+                                      const void* d_dout, int n_img, int h, int w, int g, int gc, int kernel_h, int kernel_w, int stride_h,
+                                      int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int remove_center, void* d_dinput,
+                                      void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Final detections.  Replaces models/faster_rcnn.py:179-224 (the numpy float64 decode with

@@ -57,6 +57,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     a softmax over the 9 points), float32 and bfloat16: ops.dcnv3 beside ops.dcnv3_core_pytorch (pad, one grid_sample, autograd's
     backward), forward and forward + backward of all three gradients, in alternating windows.  Informational: no speed bound is set.
 
+  * dcnv4: DCNv4 at the same size (2 x 100 x 160 x 128, G 8, Gc 16, 3 x 3, pad 1, offsets N(0, 2 px), masks N(0, 1), one packed
+    offset_mask tensor of 216 values a pixel), float32 and bfloat16: ops.dcnv4 beside ops.dcnv4_core_pytorch and beside ops.dcnv3 fed the
+    unpacked tensors, with the two unpacking copies (and, backward, autograd's re-packing of the gradients) inside the timed region;
+    forward and forward + backward of both gradients, in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only dcnv4           # just the DCNv4 leg
     python tools/ops_bench.py --only dcnv3           # just the DCNv3 leg
     python tools/ops_bench.py --only prroi           # just the Precise-RoI-Pooling leg
     python tools/ops_bench.py --only msda            # just the deformable-attention leg
@@ -448,6 +454,41 @@ def dcnv3_leg(rng, reps, warmup):
     return res
 
 
+def dcnv4_leg(rng, reps, warmup):
+    n, h, w, group, gc, k = 2, 100, 160, 8, 16, 3
+    p = k * k
+    geom = (k, k, 1, 1, 1, 1, 1, 1, group, gc, 1.0)
+    length = (group * p * 3 + 7) // 8 * 8
+    gen = torch.Generator().manual_seed(0)
+    res = {}
+
+    def unpack(om):
+        rec = om[..., :group * p * 3].reshape(n, h, w, group, p * 3)
+        return rec[..., :2 * p].reshape(n, h, w, group * p * 2), rec[..., 2 * p:].reshape(n, h, w, group * p)       # two strided copies
+
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.randn((n, h, w, group * gc), generator=gen).to(DEV).to(dtype)
+        rec = torch.cat([2.0 * torch.randn((n, h, w, group, 2 * p), generator=gen), torch.randn((n, h, w, group, p), generator=gen)], -1)
+        om = torch.nn.functional.pad(rec.reshape(n, h, w, group * p * 3), [0, length - group * p * 3]).to(DEV).to(dtype)
+        g = torch.randn((n, h, w, group * gc), generator=gen).to(DEV).to(dtype)
+        xg, omg = (t.clone().requires_grad_(True) for t in (x, om))
+        native = lambda a, b: ops.DCNv4Function.apply(a, b, *geom, 256, False)       # noqa: E731
+        composed = lambda a, b: ops.dcnv4_core_pytorch(a, b, *geom, False)           # noqa: E731
+        via_v3 = lambda a, b: ops.DCNv3Function.apply(a, *unpack(b), *geom, 256)     # noqa: E731
+        y, yc, y3 = native(x, om), composed(x, om).float(), via_v3(x, om)
+        r = {"max |ops - composition| / max |composition|": float((y.float() - yc).abs().max() / yc.abs().max()),
+             "ops.dcnv4 == ops.dcnv3 on the unpacked tensors": bool(torch.equal(y, y3))}
+        del y, yc, y3
+        for name, fns in (("fwd", (lambda: native(x, om), lambda: composed(x, om), lambda: via_v3(x, om))),
+                          ("fwd+bwd", (lambda: native(xg, omg).backward(g), lambda: composed(xg, omg).backward(g),
+                                       lambda: via_v3(xg, omg).backward(g)))):
+            t_native, t_comp, t_v3 = timed_group(fns, reps, warmup)
+            r[name] = {"ops.dcnv4": round(t_native, 1), "dcnv4_core_pytorch": round(t_comp, 1), "ops.dcnv3 with the copies": round(t_v3, 1),
+                       "composition / ops": round(t_comp / t_native, 2), "dcnv3 with the copies / ops": round(t_v3 / t_native, 2)}
+        res["dcnv4 %s 2 x 100 x 160 x 128, G 8, Gc 16, 3 x 3, pad 1, L %d" % (str(dtype).split(".")[-1], length)] = r
+    return res
+
+
 def prroi_leg(rng, reps, warmup):
     n, c, h, w, k, out, scale = 2, 256, 50, 68, 512, (7, 7), 1 / 16
     gen = torch.Generator().manual_seed(0)
@@ -484,7 +525,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -520,6 +561,9 @@ def main():
         return
     if a.only == "dcnv3":
         print(json.dumps(dcnv3_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "dcnv4":
+        print(json.dumps(dcnv4_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -590,6 +634,7 @@ def main():
     res.update(msda_leg(rng, 5, 2))
     res.update(prroi_leg(rng, 5, 2))
     res.update(dcnv3_leg(rng, 5, 2))
+    res.update(dcnv4_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
