@@ -410,19 +410,65 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _format(t, channels_last):
+    return t.contiguous(memory_format=_CL if channels_last else torch.contiguous_format)
+
+
 def _grad_layout(dx, c, channels_last):
-    dx = dx[:, :c]
-    return dx.contiguous(memory_format=_CL if channels_last else torch.contiguous_format)
+    return _format(dx[:, :c], channels_last)
 
 
 def _grad_empty(shape, like, channels_last):
     return torch.empty(shape, dtype=like.dtype, device=like.device, memory_format=_CL if channels_last else torch.contiguous_format)
 
 
-def _no_double_backward(name):
-    def backward(ctx, *grads):
-        raise RuntimeError("%s: double backward is not supported (the backward of %s is not differentiable)" % (name, name))
-    return backward
+# ---- the host-side scaffolds the operators share ------------------------------------------------------------------------------------
+def _register_autograd(name, backward, setup):
+    """frcnn::<name> differentiates through `backward`; frcnn::<name>_backward is not differentiable."""
+    def double_backward(ctx, *grads):
+        raise RuntimeError("frcnn::%s: double backward is not supported (the backward of frcnn::%s is not differentiable)" % (name, name))
+    torch.library.register_autograd("frcnn::" + name, backward, setup_context=setup)
+    torch.library.register_autograd("frcnn::%s_backward" % name, double_backward, setup_context=lambda ctx, inputs, output: None)
+
+
+def _workspace(getter, like, *args):
+    """A buffer of frcnn_ops_<getter>_workspace_bytes(*args) on like's device (the allocator's alignment covers the kernels'); a size
+    of 0 is the library refusing the arguments."""
+    name = "frcnn_ops_%s_workspace_bytes" % getter
+    size = getattr(nv.lib(), name)(*args)
+    if size == 0:
+        raise nv.FrcnnError(-1, name)
+    return torch.empty((size,), dtype=torch.uint8, device=like.device)
+
+
+def _placeholder(grad):
+    """What a `needs`-style backward returns for a gradient that is not wanted: it costs nothing."""
+    return grad.new_empty((0,))
+
+
+def _needs_fake(grad, tensors, needs):
+    """The fake result of a `needs`-style backward whose gradients are contiguous and in their arguments' dtypes."""
+    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else _placeholder(grad) for t, need in zip(tensors, needs)]
+
+
+def _chunks(n, step):
+    """(first image, images) of each chunk of at most `step` of n images."""
+    nb = min(n, step)
+    for i0 in range(0, n, nb):
+        yield i0, min(nb, n - i0)
+
+
+def _sorted_gather(plan, gather, entries, device):
+    """The deterministic scatter of the sampler backwards: plan(keys, weights) fills `entries` int64 keys and float32 weights, the keys
+    are sorted stably, gather(sorted keys, order, weights) sums each cell's run.  All arguments of the two call-backs are pointers.
+    Returns the four buffers: the caller holds them until its next chunk or its end, so that the allocator does not hand pieces of
+    these large blocks to the small tensors the caller makes next."""
+    keys = torch.empty((entries,), dtype=torch.int64, device=device)
+    wts = torch.empty((entries,), dtype=torch.float32, device=device)
+    plan(keys.data_ptr(), wts.data_ptr())
+    sorted_keys, order = torch.sort(keys, stable=True)
+    gather(sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr())
+    return keys, wts, sorted_keys, order
 
 
 # ---- frcnn::roi_align -------------------------------------------------------------------------------------------------------------
@@ -474,24 +520,20 @@ def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, al
     return _grad_empty((batch_size, channels, height, width), grad, channels_last)
 
 
-def _roi_align_setup(ctx, inputs, output):
-    input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned = inputs
-    ctx.save_for_backward(rois)
-    ctx.args = (spatial_scale, pooled_height, pooled_width, sampling_ratio, aligned)
-    ctx.shape = tuple(input.shape)
-    ctx.channels_last = _input_is_channels_last(input)
+def _roi_setup(ctx, inputs, output):
+    """Of an op (input, rois, *args) whose one gradient is the map's: what its backward op takes after (grad, rois)."""
+    ctx.save_for_backward(inputs[1])
+    ctx.args = tuple(inputs[2:])
+    ctx.shape = tuple(inputs[0].shape)
+    ctx.channels_last = _input_is_channels_last(inputs[0])
 
 
 def _roi_align_bwd(ctx, grad):
     rois, = ctx.saved_tensors
-    n, c, h, w = ctx.shape
-    dx = _roi_align_backward(grad, rois, *ctx.args, n, c, h, w, ctx.channels_last)
-    return dx, None, None, None, None, None, None
+    return (_roi_align_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 6
 
 
-torch.library.register_autograd("frcnn::roi_align", _roi_align_bwd, setup_context=_roi_align_setup)
-torch.library.register_autograd("frcnn::roi_align_backward", _no_double_backward("frcnn::roi_align"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("roi_align", _roi_align_bwd, _roi_setup)
 
 
 # ---- frcnn::multi_scale_roi_align -------------------------------------------------------------------------------------------------
@@ -576,9 +618,7 @@ def _ms_roi_align_bwd(ctx, grad):
     return (list(dxs),) + (None,) * 9
 
 
-torch.library.register_autograd("frcnn::multi_scale_roi_align", _ms_roi_align_bwd, setup_context=_ms_roi_align_setup)
-torch.library.register_autograd("frcnn::multi_scale_roi_align_backward", _no_double_backward("frcnn::multi_scale_roi_align"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("multi_scale_roi_align", _ms_roi_align_bwd, _ms_roi_align_setup)
 
 
 # ---- frcnn::roi_pool --------------------------------------------------------------------------------------------------------------
@@ -650,9 +690,7 @@ def _roi_pool_bwd(ctx, grad, grad_argmax):
     return dx, None, None, None, None
 
 
-torch.library.register_autograd("frcnn::roi_pool", _roi_pool_bwd, setup_context=_roi_pool_setup)
-torch.library.register_autograd("frcnn::roi_pool_backward", _no_double_backward("frcnn::roi_pool"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("roi_pool", _roi_pool_bwd, _roi_pool_setup)
 
 
 # ---- frcnn::ps_roi_pool, frcnn::ps_roi_align (plain NCHW in and out) --------------------------------------------------------------
@@ -732,13 +770,6 @@ def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, ba
     return _grad_empty((batch_size, channels, height, width), grad, channels_last)
 
 
-def _ps_setup(ctx, inputs, output):
-    ctx.save_for_backward(inputs[1])
-    ctx.args = tuple(inputs[2:])
-    ctx.shape = tuple(inputs[0].shape)
-    ctx.channels_last = _input_is_channels_last(inputs[0])
-
-
 def _ps_roi_pool_bwd(ctx, grad):
     rois, = ctx.saved_tensors
     return (_ps_roi_pool_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 4
@@ -749,12 +780,8 @@ def _ps_roi_align_bwd(ctx, grad):
     return (_ps_roi_align_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 5
 
 
-torch.library.register_autograd("frcnn::ps_roi_pool", _ps_roi_pool_bwd, setup_context=_ps_setup)
-torch.library.register_autograd("frcnn::ps_roi_pool_backward", _no_double_backward("frcnn::ps_roi_pool"),
-                                setup_context=lambda ctx, inputs, output: None)
-torch.library.register_autograd("frcnn::ps_roi_align", _ps_roi_align_bwd, setup_context=_ps_setup)
-torch.library.register_autograd("frcnn::ps_roi_align_backward", _no_double_backward("frcnn::ps_roi_align"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("ps_roi_pool", _ps_roi_pool_bwd, _roi_setup)
+_register_autograd("ps_roi_align", _ps_roi_align_bwd, _roi_setup)
 
 
 # ---- frcnn::deform_conv2d (plain NCHW; csrc/ops_deform.hip) ------------------------------------------------------------------------
@@ -769,14 +796,6 @@ def _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilati
     co, cg, kh, kw = weight.shape
     return nv.DeformGeom(c, h, w, co, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, c // cg,
                          offset.shape[1] // (2 * kh * kw))
-
-
-def _deform_bytes(geom, images, stage, like):
-    """A buffer of frcnn_ops_deform_workspace_bytes(stage) for a chunk of `images` (the allocator's alignment covers the kernels')."""
-    size = nv.lib().frcnn_ops_deform_workspace_bytes(C.byref(geom), images, stage)
-    if size == 0:
-        raise nv.FrcnnError(-1, "frcnn_ops_deform_workspace_bytes")
-    return torch.empty((size,), dtype=torch.uint8, device=like.device)
 
 
 def _opt_ptr(t, i0=0):
@@ -799,7 +818,7 @@ def _deform_conv2d(input: Tensor, offset: Tensor, weight: Tensor, bias: Optional
         geom = _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
         x, off, wgt, b, m = input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(bias), _opt_contiguous(mask)
         nb = min(n, chunk)
-        ws = _deform_bytes(geom, nb, nv.DEFORM_WS_FORWARD, input)
+        ws = _workspace("deform", input, C.byref(geom), nb, nv.DEFORM_WS_FORWARD)
         lib = nv.lib()
         for i0 in range(0, n, nb):
             nv.check(lib.frcnn_ops_deform_forward(C.byref(geom), min(nb, n - i0), x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0),
@@ -830,7 +849,7 @@ def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight:
     n = input.shape[0]
     co, _, kh, kw = weight.shape
     if n == 0 or co == 0:
-        return [grad.new_empty((0,)) if s is None else _grad_layout(grad.new_zeros(s), s[1], cl) if len(s) == 4 else grad.new_zeros(s)
+        return [_placeholder(grad) if s is None else _grad_layout(grad.new_zeros(s), s[1], cl) if len(s) == 4 else grad.new_zeros(s)
                 for s, cl in plan]
     want_input, want_offset, want_weight, want_bias, want_mask = [s is not None for s, _ in plan]
     with torch.cuda.device(grad.device):
@@ -838,19 +857,18 @@ def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight:
         g, x, off, wgt, m = grad.contiguous(), input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(mask)
         new = lambda want, like: torch.empty(like.shape, dtype=like.dtype, device=like.device) if want else None   # noqa: E731
         dx, doff, dw, dm = new(want_input, x), new(want_offset, off), new(want_weight, wgt), new(want_mask, m)
-        nb = min(n, chunk)
         lib, stream, ref = nv.lib(), _stream(grad), C.byref(geom)
+        stage = lambda which: _workspace("deform", grad, ref, min(n, chunk), which)                                 # noqa: E731
         want_columns = want_input or want_offset or want_mask
         if want_columns:
-            dcol = _deform_bytes(geom, nb, nv.DEFORM_WS_COLUMNS, grad)
-            ws_col = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_COLUMNS, grad)
+            dcol = stage(nv.DEFORM_WS_COLUMNS)
+            ws_col = stage(nv.DEFORM_WS_BACKWARD_COLUMNS)
         if want_input:
-            ws_in = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_INPUT, grad)
+            ws_in = stage(nv.DEFORM_WS_BACKWARD_INPUT)
         if want_weight:
-            ws_w = _deform_bytes(geom, nb, nv.DEFORM_WS_BACKWARD_WEIGHT, grad)
+            ws_w = stage(nv.DEFORM_WS_BACKWARD_WEIGHT)
         samples = geom.offset_groups * kh * kw * offset.shape[2] * offset.shape[3]          # per image
-        for i0 in range(0, n, nb):
-            k = min(nb, n - i0)
+        for i0, k in _chunks(n, chunk):
             if want_columns:
                 nv.check(lib.frcnn_ops_deform_backward_columns(ref, k, wgt.data_ptr(), g[i0:].data_ptr(), dcol.data_ptr(), ws_col.data_ptr(),
                                                                ws_col.numel(), stream), "frcnn_ops_deform_backward_columns")
@@ -858,26 +876,26 @@ def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight:
                 nv.check(lib.frcnn_ops_deform_backward_offset(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), dcol.data_ptr(),
                                                               _opt_ptr(doff, i0), _opt_ptr(dm, i0), stream), "frcnn_ops_deform_backward_offset")
             if want_input:
-                keys = torch.empty((k * samples * 4,), dtype=torch.int64, device=grad.device)
-                wts = torch.empty((k * samples * 4,), dtype=torch.float32, device=grad.device)
-                nv.check(lib.frcnn_ops_deform_input_plan(ref, k, off[i0:].data_ptr(), _opt_ptr(m, i0), keys.data_ptr(), wts.data_ptr(), stream),
-                         "frcnn_ops_deform_input_plan")
-                sorted_keys, order = torch.sort(keys, stable=True)
-                nv.check(lib.frcnn_ops_deform_backward_input(ref, k, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), dcol.data_ptr(),
-                                                             dx[i0:].data_ptr(), ws_in.data_ptr(), ws_in.numel(), stream),
-                         "frcnn_ops_deform_backward_input")
+                def fill(keys, wts):
+                    nv.check(lib.frcnn_ops_deform_input_plan(ref, k, off[i0:].data_ptr(), _opt_ptr(m, i0), keys, wts, stream),
+                             "frcnn_ops_deform_input_plan")
+
+                def gather(keys, order, wts):
+                    nv.check(lib.frcnn_ops_deform_backward_input(ref, k, keys, order, wts, dcol.data_ptr(), dx[i0:].data_ptr(),
+                                                                 ws_in.data_ptr(), ws_in.numel(), stream), "frcnn_ops_deform_backward_input")
+                held = _sorted_gather(fill, gather, k * samples * 4, grad.device)       # noqa: F841 (kept alive)
             if want_weight:
                 nv.check(lib.frcnn_ops_deform_backward_weight(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), g[i0:].data_ptr(),
                                                               dw.data_ptr(), int(i0 > 0), ws_w.data_ptr(), ws_w.numel(), stream),
                          "frcnn_ops_deform_backward_weight")
         db = g.sum((0, 2, 3)) if want_bias else None
-        return [grad.new_empty((0,)) if t is None else _grad_layout(t, t.shape[1], cl) if t.dim() == 4 else t
+        return [_placeholder(grad) if t is None else _grad_layout(t, t.shape[1], cl) if t.dim() == 4 else t
                 for t, (_, cl) in zip((dx, doff, dw, db, dm), plan)]
 
 
 @_deform_conv2d_backward.register_fake
 def _(grad, input, offset, weight, mask, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, chunk, needs, channels_last):
-    return [grad.new_empty((0,)) if s is None else _grad_empty(s, grad, cl) if len(s) == 4 else grad.new_empty(s)
+    return [_placeholder(grad) if s is None else _grad_empty(s, grad, cl) if len(s) == 4 else grad.new_empty(s)
             for s, cl in _deform_grad_shapes(grad, input, offset, weight, mask, needs, channels_last)]
 
 
@@ -895,9 +913,7 @@ def _deform_bwd(ctx, grad):
     return tuple(g if need else None for g, need in zip(grads, needs)) + (None,) * 7
 
 
-torch.library.register_autograd("frcnn::deform_conv2d", _deform_bwd, setup_context=_deform_setup)
-torch.library.register_autograd("frcnn::deform_conv2d_backward", _no_double_backward("frcnn::deform_conv2d"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("deform_conv2d", _deform_bwd, _deform_setup)
 
 
 # ---- frcnn::deform_roi_pool (NHWC as roi_align; csrc/ops_droi.hip) -----------------------------------------------------------------
@@ -934,10 +950,6 @@ def _(input, rois, offset, spatial_scale, pooled_height, pooled_width, sampling_
     return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
 
 
-def _droi_grad_format(t, channels_last):
-    return t.contiguous(memory_format=_CL if channels_last else torch.contiguous_format)
-
-
 @torch.library.custom_op("frcnn::deform_roi_pool_backward", mutates_args=())
 def _deform_roi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, offset: Optional[Tensor], spatial_scale: float,
                               pooled_height: int, pooled_width: int, sampling_ratio: int, gamma: float, needs: List[bool],
@@ -947,12 +959,11 @@ def _deform_roi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, offset:
     n, c, h, w = input.shape
     k = rois.shape[0]
     want_input, want_offset = needs[0], needs[1] and offset is not None
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
     if k == 0 or c == 0 or n * h * w == 0:
-        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last[0]) if want_input else none(),
-                _droi_grad_format(torch.zeros_like(offset), channels_last[1]) if want_offset else none()]
+        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last[0]) if want_input else _placeholder(grad),
+                _format(torch.zeros_like(offset), channels_last[1]) if want_offset else _placeholder(grad)]
     if not (want_input or want_offset):
-        return [none(), none()]
+        return [_placeholder(grad), _placeholder(grad)]
     with torch.cuda.device(grad.device):
         cp = _padded_channels(c, grad.dtype)
         g = _nhwc(grad)
@@ -961,23 +972,18 @@ def _deform_roi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, offset:
         x = _nhwc(input) if want_offset else None
         dx = _empty_cl((n, cp, h, w), grad) if want_input else None
         doff = torch.empty_like(off) if want_offset else None
-        ws = None
-        if want_input:
-            size = nv.lib().frcnn_ops_deform_roi_pool_workspace_bytes(k, pooled_height, pooled_width)
-            if size == 0:
-                raise nv.FrcnnError(-1, "frcnn_ops_deform_roi_pool_workspace_bytes")
-            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        ws = _workspace("deform_roi_pool", grad, k, pooled_height, pooled_width) if want_input else None
         _call("deform_roi_pool_backward", grad, _opt_ptr(x), r.data_ptr(), _opt_ptr(off), k, n, h, w, cp, pooled_height, pooled_width,
               spatial_scale, sampling_ratio, gamma, g.data_ptr(), _opt_ptr(dx), _opt_ptr(doff), _opt_ptr(ws), 0 if ws is None else ws.numel(),
               _stream(grad))
-        return [_grad_layout(dx, c, channels_last[0]) if want_input else none(),
-                _droi_grad_format(doff.to(offset.dtype), channels_last[1]) if want_offset else none()]
+        return [_grad_layout(dx, c, channels_last[0]) if want_input else _placeholder(grad),
+                _format(doff.to(offset.dtype), channels_last[1]) if want_offset else _placeholder(grad)]
 
 
 @_deform_roi_pool_backward.register_fake
 def _(grad, input, rois, offset, spatial_scale, pooled_height, pooled_width, sampling_ratio, gamma, needs, channels_last):
-    return [_grad_empty(tuple(input.shape), grad, channels_last[0]) if needs[0] else grad.new_empty((0,)),
-            _droi_grad_format(torch.empty_like(offset), channels_last[1]) if needs[1] and offset is not None else grad.new_empty((0,))]
+    return [_grad_empty(tuple(input.shape), grad, channels_last[0]) if needs[0] else _placeholder(grad),
+            _format(torch.empty_like(offset), channels_last[1]) if needs[1] and offset is not None else _placeholder(grad)]
 
 
 def _deform_roi_pool_setup(ctx, inputs, output):
@@ -994,9 +1000,7 @@ def _deform_roi_pool_bwd(ctx, grad):
     return (dx if needs[0] else None, None, doff if needs[1] else None) + (None,) * 5
 
 
-torch.library.register_autograd("frcnn::deform_roi_pool", _deform_roi_pool_bwd, setup_context=_deform_roi_pool_setup)
-torch.library.register_autograd("frcnn::deform_roi_pool_backward", _no_double_backward("frcnn::deform_roi_pool"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("deform_roi_pool", _deform_roi_pool_bwd, _deform_roi_pool_setup)
 
 
 # ---- frcnn::prroi_pool (NHWC as roi_align; csrc/ops_prroi.hip) ----------------------------------------------------------------------
@@ -1033,12 +1037,11 @@ def _prroi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, spatial_scal
     channels_last: the memory format of input, which its gradient takes.  d_rois is float32 [K, 5] with a zero column 0."""
     n, c, h, w = input.shape
     k = rois.shape[0]
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
     if k == 0 or c == 0 or n * h * w == 0:
-        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last) if needs[0] else none(),
-                torch.zeros_like(rois) if needs[1] else none()]
+        return [_grad_layout(grad.new_zeros((n, c, h, w)), c, channels_last) if needs[0] else _placeholder(grad),
+                torch.zeros_like(rois) if needs[1] else _placeholder(grad)]
     if not (needs[0] or needs[1]):
-        return [none(), none()]
+        return [_placeholder(grad), _placeholder(grad)]
     with torch.cuda.device(grad.device):
         cp = _padded_channels(c, grad.dtype)
         g = _nhwc(grad)
@@ -1046,21 +1049,16 @@ def _prroi_pool_backward(grad: Tensor, input: Tensor, rois: Tensor, spatial_scal
         x = _nhwc(input) if needs[1] else None
         dx = _empty_cl((n, cp, h, w), grad) if needs[0] else None
         drois = torch.empty_like(r) if needs[1] else None
-        ws = None
-        if needs[1]:
-            size = nv.lib().frcnn_ops_prroi_pool_workspace_bytes(k, pooled_height, pooled_width)
-            if size == 0:
-                raise nv.FrcnnError(-1, "frcnn_ops_prroi_pool_workspace_bytes")
-            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
+        ws = _workspace("prroi_pool", grad, k, pooled_height, pooled_width) if needs[1] else None
         _call("prroi_pool_backward", grad, _opt_ptr(x), r.data_ptr(), k, n, h, w, cp, pooled_height, pooled_width, spatial_scale,
               g.data_ptr(), _opt_ptr(dx), _opt_ptr(drois), _opt_ptr(ws), 0 if ws is None else ws.numel(), _stream(grad))
-        return [_grad_layout(dx, c, channels_last) if needs[0] else none(), drois if needs[1] else none()]
+        return [_grad_layout(dx, c, channels_last) if needs[0] else _placeholder(grad), drois if needs[1] else _placeholder(grad)]
 
 
 @_prroi_pool_backward.register_fake
 def _(grad, input, rois, spatial_scale, pooled_height, pooled_width, needs, channels_last):
-    return [_grad_empty(tuple(input.shape), grad, channels_last) if needs[0] else grad.new_empty((0,)),
-            torch.empty_like(rois, memory_format=torch.contiguous_format) if needs[1] else grad.new_empty((0,))]
+    return [_grad_empty(tuple(input.shape), grad, channels_last) if needs[0] else _placeholder(grad),
+            torch.empty_like(rois, memory_format=torch.contiguous_format) if needs[1] else _placeholder(grad)]
 
 
 def _prroi_pool_setup(ctx, inputs, output):
@@ -1077,9 +1075,7 @@ def _prroi_pool_bwd(ctx, grad):
     return (dx if needs[0] else None, drois if needs[1] else None, None, None, None)
 
 
-torch.library.register_autograd("frcnn::prroi_pool", _prroi_pool_bwd, setup_context=_prroi_pool_setup)
-torch.library.register_autograd("frcnn::prroi_pool_backward", _no_double_backward("frcnn::prroi_pool"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("prroi_pool", _prroi_pool_bwd, _prroi_pool_setup)
 
 
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
@@ -1090,7 +1086,9 @@ def _score_order(scores):
     return order[torch.sort(nan[order].to(torch.uint8), stable=True).indices]
 
 
-def _nms(boxes, scores, idxs, iou_threshold):
+def _nms(boxes, scores, idxs, iou_threshold, rotated=False):
+    """The kept indices of greedy NMS, within each category of idxs when given: the sorting and merging around frcnn_ops_nms, or around
+    frcnn_ops_nms_rotated on boxes in the kernels' (clockwise) convention."""
     n = boxes.shape[0]
     if n == 0:
         return torch.empty((0,), dtype=torch.int64, device=boxes.device)
@@ -1104,9 +1102,12 @@ def _nms(boxes, scores, idxs, iou_threshold):
         ws = torch.empty((lib.frcnn_ops_nms_workspace_bytes(n),), dtype=torch.uint8, device=boxes.device)
         keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
         b = boxes.contiguous()
-        nv.check(lib.frcnn_ops_nms(b.data_ptr(), int(b.dtype == torch.float64), order.data_ptr(),
-                                   cats.data_ptr() if cats is not None else None, n, iou_threshold, keep.data_ptr(), ws.data_ptr(),
-                                   ws.numel(), _stream(boxes)), "frcnn_ops_nms")
+        tail = (order.data_ptr(), cats.data_ptr() if cats is not None else None, n, iou_threshold, keep.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream(boxes))
+        if rotated:
+            nv.check(lib.frcnn_ops_nms_rotated(b.data_ptr(), *tail), "frcnn_ops_nms_rotated")
+        else:
+            nv.check(lib.frcnn_ops_nms(b.data_ptr(), int(b.dtype == torch.float64), *tail), "frcnn_ops_nms")
         kept = order[keep.bool()]
         if idxs is not None:                                                   # merge: descending score, ties by ascending index
             kept = torch.sort(kept).values
@@ -1173,27 +1174,8 @@ def _(boxes1, boxes2, mode, aligned):
 
 @torch.library.custom_op("frcnn::nms_rotated", mutates_args=())
 def _nms_rotated_op(boxes: Tensor, scores: Tensor, labels: Optional[Tensor], iou_threshold: float) -> Tensor:
-    """The kept indices; boxes in the kernels' (clockwise) convention.  _nms's sorting and merging around frcnn_ops_nms_rotated."""
-    n = boxes.shape[0]
-    if n == 0:
-        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
-    with torch.cuda.device(boxes.device):
-        order = _score_order(scores)
-        cats = None
-        if labels is not None:
-            cats = labels.to(torch.int64).contiguous()
-            order = order[torch.sort(cats[order], stable=True).indices]       # each label one run, by score inside it
-        lib = nv.lib()
-        ws = torch.empty((lib.frcnn_ops_nms_workspace_bytes(n),), dtype=torch.uint8, device=boxes.device)
-        keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
-        b = boxes.contiguous()
-        nv.check(lib.frcnn_ops_nms_rotated(b.data_ptr(), order.data_ptr(), cats.data_ptr() if cats is not None else None, n, iou_threshold,
-                                           keep.data_ptr(), ws.data_ptr(), ws.numel(), _stream(boxes)), "frcnn_ops_nms_rotated")
-        kept = order[keep.bool()]
-        if labels is not None:                                                 # merge: descending score, ties by ascending index
-            kept = torch.sort(kept).values
-            kept = kept[_score_order(scores[kept])]
-        return kept
+    """The kept indices; boxes in the kernels' (clockwise) convention."""
+    return _nms(boxes, scores, labels, iou_threshold, rotated=True)
 
 
 @_nms_rotated_op.register_fake
@@ -1252,21 +1234,12 @@ def _(grad, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, al
     return _grad_empty((batch_size, channels, height, width), grad, channels_last)
 
 
-def _roi_align_rotated_setup(ctx, inputs, output):
-    ctx.save_for_backward(inputs[1])
-    ctx.args = tuple(inputs[2:])
-    ctx.shape = tuple(inputs[0].shape)
-    ctx.channels_last = _input_is_channels_last(inputs[0])
-
-
 def _roi_align_rotated_bwd(ctx, grad):
     rois, = ctx.saved_tensors
     return (_roi_align_rotated_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 7
 
 
-torch.library.register_autograd("frcnn::roi_align_rotated", _roi_align_rotated_bwd, setup_context=_roi_align_rotated_setup)
-torch.library.register_autograd("frcnn::roi_align_rotated_backward", _no_double_backward("frcnn::roi_align_rotated"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("roi_align_rotated", _roi_align_rotated_bwd, _roi_setup)
 
 
 # ---- frcnn::carafe (plain NCHW; csrc/ops_carafe.hip) --------------------------------------------------------------------------------
@@ -1295,12 +1268,11 @@ def _carafe_backward(grad: Tensor, features: Tensor, masks: Tensor, kernel_size:
     """[d_features, d_masks]; needs: which of them are wanted (the other comes back as an empty placeholder and costs nothing);
     channels_last: the memory format of features and masks, which their gradients take."""
     n, c, h, w = features.shape
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
     if grad.numel() == 0:
-        return [_droi_grad_format(torch.zeros_like(t, memory_format=torch.contiguous_format), cl) if need else none()
+        return [_format(torch.zeros_like(t, memory_format=torch.contiguous_format), cl) if need else _placeholder(grad)
                 for t, need, cl in zip((features, masks), needs, channels_last)]
     if not (needs[0] or needs[1]):
-        return [none(), none()]
+        return [_placeholder(grad), _placeholder(grad)]
     with torch.cuda.device(grad.device):
         g = grad.contiguous()
         x = features.contiguous() if needs[1] else None
@@ -1309,12 +1281,12 @@ def _carafe_backward(grad: Tensor, features: Tensor, masks: Tensor, kernel_size:
         dm = torch.empty(masks.shape, dtype=grad.dtype, device=grad.device) if needs[1] else None
         _call("carafe_backward", grad, _opt_ptr(x), _opt_ptr(m), g.data_ptr(), n, c, h, w, kernel_size, group_size, scale_factor,
               _opt_ptr(dx), _opt_ptr(dm), _stream(grad))
-        return [_droi_grad_format(t, cl) if need else none() for t, need, cl in zip((dx, dm), needs, channels_last)]
+        return [_format(t, cl) if need else _placeholder(grad) for t, need, cl in zip((dx, dm), needs, channels_last)]
 
 
 @_carafe_backward.register_fake
 def _(grad, features, masks, kernel_size, group_size, scale_factor, needs, channels_last):
-    return [_grad_empty(tuple(t.shape), grad, cl) if need else grad.new_empty((0,))
+    return [_grad_empty(tuple(t.shape), grad, cl) if need else _placeholder(grad)
             for t, need, cl in zip((features, masks), needs, channels_last)]
 
 
@@ -1332,9 +1304,7 @@ def _carafe_bwd(ctx, grad):
     return (dx if needs[0] else None, dm if needs[1] else None, None, None, None)
 
 
-torch.library.register_autograd("frcnn::carafe", _carafe_bwd, setup_context=_carafe_setup)
-torch.library.register_autograd("frcnn::carafe_backward", _no_double_backward("frcnn::carafe"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("carafe", _carafe_bwd, _carafe_setup)
 
 
 # ---- frcnn::ms_deform_attn (csrc/ops_msda.hip) ---------------------------------------------------------------------------------------
@@ -1379,12 +1349,11 @@ def _ms_deform_attn_backward(grad: Tensor, value: Tensor, spatial_shapes: Tensor
     """[d_value, d_sampling_locations, d_attention_weights], each in its argument's dtype; needs: which of them are wanted (the others
     come back as empty placeholders and cost nothing)."""
     b, s, m, d, q, levels, points = _msda_dims(value, sampling_locations)
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
     if grad.numel() == 0 or s == 0 or levels * points == 0:
-        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else none()
+        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else _placeholder(grad)
                 for t, need in zip((value, sampling_locations, attention_weights), needs)]
     if not any(needs):
-        return [none(), none(), none()]
+        return [_placeholder(grad) for _ in needs]
     with torch.cuda.device(grad.device):
         g, shp, st = grad.contiguous().view(b, q, m, d), spatial_shapes.contiguous(), level_start_index.contiguous()
         loc, attn = _msda_float(sampling_locations), _msda_float(attention_weights)
@@ -1392,35 +1361,30 @@ def _ms_deform_attn_backward(grad: Tensor, value: Tensor, spatial_shapes: Tensor
         dv = torch.empty(value.shape, dtype=value.dtype, device=grad.device) if needs[0] else None
         dloc = torch.empty_like(loc) if needs[1] else None
         dattn = torch.empty_like(attn) if needs[2] else None
-        nb, stream, lib = min(b, im2col_step), _stream(grad), nv.lib()
+        stream, lib = _stream(grad), nv.lib()
         if needs[0]:
-            size = lib.frcnn_ops_msda_workspace_bytes(nb, s, m, d, q, levels, points)
-            if size == 0:
-                raise nv.FrcnnError(-1, "frcnn_ops_msda_workspace_bytes")
-            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
-        for i0 in range(0, b, nb):
-            k = min(nb, b - i0)
+            ws = _workspace("msda", grad, min(b, im2col_step), s, m, d, q, levels, points)
+        for i0, k in _chunks(b, im2col_step):
             if needs[1] or needs[2]:
                 _call("msda_backward_loc", value, v[i0:].data_ptr(), shp.data_ptr(), st.data_ptr(), loc[i0:].data_ptr(), attn[i0:].data_ptr(),
                       g[i0:].data_ptr(), k, s, m, d, q, levels, points, _opt_ptr(dloc, i0), _opt_ptr(dattn, i0), stream)
             if needs[0]:
-                entries = k * q * m * levels * points * 4
-                keys = torch.empty((entries,), dtype=torch.int64, device=grad.device)
-                wts = torch.empty((entries,), dtype=torch.float32, device=grad.device)
-                nv.check(lib.frcnn_ops_msda_plan(shp.data_ptr(), st.data_ptr(), loc[i0:].data_ptr(), attn[i0:].data_ptr(), k, s, m, q, levels,
-                                                 points, keys.data_ptr(), wts.data_ptr(), stream), "frcnn_ops_msda_plan")
-                sorted_keys, order = torch.sort(keys, stable=True)
-                _call("msda_backward_value", value, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), g[i0:].data_ptr(), k, s, m, d, q,
-                      levels, points, dv[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        return [dv if needs[0] else none(),
-                dloc.to(sampling_locations.dtype) if needs[1] else none(),
-                dattn.to(attention_weights.dtype) if needs[2] else none()]
+                def plan(keys, wts):
+                    nv.check(lib.frcnn_ops_msda_plan(shp.data_ptr(), st.data_ptr(), loc[i0:].data_ptr(), attn[i0:].data_ptr(), k, s, m, q,
+                                                     levels, points, keys, wts, stream), "frcnn_ops_msda_plan")
+
+                def gather(keys, order, wts):
+                    _call("msda_backward_value", value, keys, order, wts, g[i0:].data_ptr(), k, s, m, d, q, levels, points,
+                          dv[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                held = _sorted_gather(plan, gather, k * q * m * levels * points * 4, grad.device)       # noqa: F841 (kept alive)
+        return [dv if needs[0] else _placeholder(grad),
+                dloc.to(sampling_locations.dtype) if needs[1] else _placeholder(grad),
+                dattn.to(attention_weights.dtype) if needs[2] else _placeholder(grad)]
 
 
 @_ms_deform_attn_backward.register_fake
 def _(grad, value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step, needs):
-    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else grad.new_empty((0,))
-            for t, need in zip((value, sampling_locations, attention_weights), needs)]
+    return _needs_fake(grad, (value, sampling_locations, attention_weights), needs)
 
 
 def _msda_setup(ctx, inputs, output):
@@ -1435,14 +1399,61 @@ def _msda_bwd(ctx, grad):
     return (dv if needs[0] else None, None, None, dloc if needs[1] else None, dattn if needs[2] else None, None)
 
 
-torch.library.register_autograd("frcnn::ms_deform_attn", _msda_bwd, setup_context=_msda_setup)
-torch.library.register_autograd("frcnn::ms_deform_attn_backward", _no_double_backward("frcnn::ms_deform_attn"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("ms_deform_attn", _msda_bwd, _msda_setup)
 
 
-# ---- frcnn::dcnv3 (csrc/ops_dcnv3.hip) ----------------------------------------------------------------------------------------------
+# ---- frcnn::dcnv3, frcnn::dcnv4 (csrc/ops_dcnv3.hip, csrc/ops_dcnv4.hip: one sampler, two layouts of the learned tensors) -----------
 def _dcnv3_out_size(size, kernel, stride, pad, dil):
     return max((size + 2 * pad - (dil * (kernel - 1) + 1)) // stride + 1, 0)
+
+
+def _dcnv4_points(kernel_h, kernel_w, remove_center):
+    return kernel_h * kernel_w - (1 if remove_center else 0)
+
+
+def _dcnv4_record(group, points):
+    """L: the 3 G P values of a pixel's record padded to a multiple of 8 (frcnn_ops_dcnv4_record())."""
+    return (group * points * 3 + 7) // 8 * 8
+
+
+def _dcn_backward(op, grad, input, learned, geom, group, group_channels, offset_scale, im2col_step, needs, remove_center=False):
+    """The backward of op "dcnv3" on learned = (offset, mask), or of op "dcnv4" on learned = (offset_mask,) with its remove_center, which
+    dcnv4's entry points take after the geometry; geom = (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w).
+    Returns [d_input, then the gradient of each learned tensor], each in its argument's dtype; needs: which of them are wanted (the
+    others come back as empty placeholders and cost nothing)."""
+    tail = (int(remove_center),) if op == "dcnv4" else ()
+    n, h, w, _ = input.shape
+    ho, wo = learned[0].shape[1], learned[0].shape[2]
+    points = _dcnv4_points(geom[0], geom[1], remove_center)
+    if grad.numel() == 0 or h * w == 0:
+        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else _placeholder(grad)
+                for t, need in zip((input,) + learned, needs)]
+    if not any(needs):
+        return [_placeholder(grad) for _ in needs]
+    with torch.cuda.device(grad.device):
+        g, fs = grad.contiguous(), [_msda_float(t) for t in learned]
+        x = input.contiguous() if any(needs[1:]) else None
+        dx = torch.empty(input.shape, dtype=input.dtype, device=grad.device) if needs[0] else None
+        dfs = [torch.empty_like(f) if need else None for f, need in zip(fs, needs[1:])]     # dcnv4's kernel writes the pad lanes too
+        stream, plan_entry = _stream(grad), getattr(nv.lib(), "frcnn_ops_%s_plan" % op)
+        learned_backward = op + ("_backward_offset_mask" if op == "dcnv4" else "_backward_offset")
+        if needs[0]:
+            ws = _workspace(op, grad, min(n, im2col_step), h, w, group, group_channels, *geom, *tail)
+        for i0, c in _chunks(n, im2col_step):
+            if any(needs[1:]):
+                _call(learned_backward, input, x[i0:].data_ptr(), *[f[i0:].data_ptr() for f in fs], g[i0:].data_ptr(), c, h, w, group,
+                      group_channels, *geom, offset_scale, *tail, *[_opt_ptr(d, i0) for d in dfs], stream)
+            if needs[0]:
+                def plan(keys, wts):
+                    nv.check(plan_entry(*[f[i0:].data_ptr() for f in fs], c, h, w, group, *geom, offset_scale, *tail, keys, wts, stream),
+                             "frcnn_ops_%s_plan" % op)
+
+                def gather(keys, order, wts):
+                    _call(op + "_backward_input", input, keys, order, wts, g[i0:].data_ptr(), c, h, w, group, group_channels, *geom, *tail,
+                          dx[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                held = _sorted_gather(plan, gather, c * ho * wo * group * points * 4, grad.device)       # noqa: F841 (kept alive)
+        return [dx if needs[0] else _placeholder(grad)] + [d.to(t.dtype) if need else _placeholder(grad)
+                                                           for d, t, need in zip(dfs, learned, needs[1:])]
 
 
 @torch.library.custom_op("frcnn::dcnv3", mutates_args=())
@@ -1477,52 +1488,14 @@ def _dcnv3_backward(grad: Tensor, input: Tensor, offset: Tensor, mask: Tensor, k
                     im2col_step: int, needs: List[bool]) -> List[Tensor]:
     """[d_input, d_offset, d_mask], each in its argument's dtype; needs: which of them are wanted (the others come back as empty
     placeholders and cost nothing)."""
-    n, h, w, _ = input.shape
-    ho, wo = offset.shape[1], offset.shape[2]
-    k = kernel_h * kernel_w
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
-    if grad.numel() == 0 or h * w == 0:
-        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else none()
-                for t, need in zip((input, offset, mask), needs)]
-    if not any(needs):
-        return [none(), none(), none()]
-    geom = (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
-    with torch.cuda.device(grad.device):
-        g, off, msk = grad.contiguous(), _msda_float(offset), _msda_float(mask)
-        x = input.contiguous() if needs[1] or needs[2] else None
-        dx = torch.empty(input.shape, dtype=input.dtype, device=grad.device) if needs[0] else None
-        doff = torch.empty_like(off) if needs[1] else None
-        dmsk = torch.empty_like(msk) if needs[2] else None
-        nb, stream, lib = min(n, im2col_step), _stream(grad), nv.lib()
-        if needs[0]:
-            size = lib.frcnn_ops_dcnv3_workspace_bytes(nb, h, w, group, group_channels, *geom)
-            if size == 0:
-                raise nv.FrcnnError(-1, "frcnn_ops_dcnv3_workspace_bytes")
-            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
-        for i0 in range(0, n, nb):
-            c = min(nb, n - i0)
-            if needs[1] or needs[2]:
-                _call("dcnv3_backward_offset", input, x[i0:].data_ptr(), off[i0:].data_ptr(), msk[i0:].data_ptr(), g[i0:].data_ptr(), c, h, w,
-                      group, group_channels, *geom, offset_scale, _opt_ptr(doff, i0), _opt_ptr(dmsk, i0), stream)
-            if needs[0]:
-                entries = c * ho * wo * group * k * 4
-                keys = torch.empty((entries,), dtype=torch.int64, device=grad.device)
-                wts = torch.empty((entries,), dtype=torch.float32, device=grad.device)
-                nv.check(lib.frcnn_ops_dcnv3_plan(off[i0:].data_ptr(), msk[i0:].data_ptr(), c, h, w, group, *geom, offset_scale,
-                                                  keys.data_ptr(), wts.data_ptr(), stream), "frcnn_ops_dcnv3_plan")
-                sorted_keys, order = torch.sort(keys, stable=True)
-                _call("dcnv3_backward_input", input, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), g[i0:].data_ptr(), c, h, w,
-                      group, group_channels, *geom, dx[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        return [dx if needs[0] else none(),
-                doff.to(offset.dtype) if needs[1] else none(),
-                dmsk.to(mask.dtype) if needs[2] else none()]
+    return _dcn_backward("dcnv3", grad, input, (offset, mask), (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w),
+                         group, group_channels, offset_scale, im2col_step, needs)
 
 
 @_dcnv3_backward.register_fake
 def _(grad, input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
       offset_scale, im2col_step, needs):
-    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else grad.new_empty((0,))
-            for t, need in zip((input, offset, mask), needs)]
+    return _needs_fake(grad, (input, offset, mask), needs)
 
 
 def _dcnv3_setup(ctx, inputs, output):
@@ -1536,19 +1509,7 @@ def _dcnv3_bwd(ctx, grad):
     return (dx if needs[0] else None, doff if needs[1] else None, dmsk if needs[2] else None) + (None,) * 12
 
 
-torch.library.register_autograd("frcnn::dcnv3", _dcnv3_bwd, setup_context=_dcnv3_setup)
-torch.library.register_autograd("frcnn::dcnv3_backward", _no_double_backward("frcnn::dcnv3"),
-                                setup_context=lambda ctx, inputs, output: None)
-
-
-# ---- frcnn::dcnv4 (csrc/ops_dcnv4.hip) ----------------------------------------------------------------------------------------------
-def _dcnv4_points(kernel_h, kernel_w, remove_center):
-    return kernel_h * kernel_w - (1 if remove_center else 0)
-
-
-def _dcnv4_record(group, points):
-    """L: the 3 G P values of a pixel's record padded to a multiple of 8 (frcnn_ops_dcnv4_record())."""
-    return (group * points * 3 + 7) // 8 * 8
+_register_autograd("dcnv3", _dcnv3_bwd, _dcnv3_setup)
 
 
 @torch.library.custom_op("frcnn::dcnv4", mutates_args=())
@@ -1584,50 +1545,14 @@ def _dcnv4_backward(grad: Tensor, input: Tensor, offset_mask: Tensor, kernel_h: 
                     im2col_step: int, remove_center: bool, needs: List[bool]) -> List[Tensor]:
     """[d_input, d_offset_mask], each in its argument's dtype; needs: which of them are wanted (the other comes back as an empty
     placeholder and costs nothing)."""
-    n, h, w, _ = input.shape
-    ho, wo = offset_mask.shape[1], offset_mask.shape[2]
-    p = _dcnv4_points(kernel_h, kernel_w, remove_center)
-    none = lambda: grad.new_empty((0,))                                    # noqa: E731
-    if grad.numel() == 0 or h * w == 0:
-        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else none()
-                for t, need in zip((input, offset_mask), needs)]
-    if not any(needs):
-        return [none(), none()]
-    geom = (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
-    rc = int(remove_center)
-    with torch.cuda.device(grad.device):
-        g, om = grad.contiguous(), _msda_float(offset_mask)
-        x = input.contiguous() if needs[1] else None
-        dx = torch.empty(input.shape, dtype=input.dtype, device=grad.device) if needs[0] else None
-        dom = torch.empty_like(om) if needs[1] else None                   # the kernel writes every element, pad lanes included
-        nb, stream, lib = min(n, im2col_step), _stream(grad), nv.lib()
-        if needs[0]:
-            size = lib.frcnn_ops_dcnv4_workspace_bytes(nb, h, w, group, group_channels, *geom, rc)
-            if size == 0:
-                raise nv.FrcnnError(-1, "frcnn_ops_dcnv4_workspace_bytes")
-            ws = torch.empty((size,), dtype=torch.uint8, device=grad.device)
-        for i0 in range(0, n, nb):
-            c = min(nb, n - i0)
-            if needs[1]:
-                _call("dcnv4_backward_offset_mask", input, x[i0:].data_ptr(), om[i0:].data_ptr(), g[i0:].data_ptr(), c, h, w, group,
-                      group_channels, *geom, offset_scale, rc, dom[i0:].data_ptr(), stream)
-            if needs[0]:
-                entries = c * ho * wo * group * p * 4
-                keys = torch.empty((entries,), dtype=torch.int64, device=grad.device)
-                wts = torch.empty((entries,), dtype=torch.float32, device=grad.device)
-                nv.check(lib.frcnn_ops_dcnv4_plan(om[i0:].data_ptr(), c, h, w, group, *geom, offset_scale, rc, keys.data_ptr(),
-                                                  wts.data_ptr(), stream), "frcnn_ops_dcnv4_plan")
-                sorted_keys, order = torch.sort(keys, stable=True)
-                _call("dcnv4_backward_input", input, sorted_keys.data_ptr(), order.data_ptr(), wts.data_ptr(), g[i0:].data_ptr(), c, h, w,
-                      group, group_channels, *geom, rc, dx[i0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        return [dx if needs[0] else none(), dom.to(offset_mask.dtype) if needs[1] else none()]
+    return _dcn_backward("dcnv4", grad, input, (offset_mask,), (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w),
+                         group, group_channels, offset_scale, im2col_step, needs, remove_center)
 
 
 @_dcnv4_backward.register_fake
 def _(grad, input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
       offset_scale, im2col_step, remove_center, needs):
-    return [torch.empty(t.shape, dtype=t.dtype, device=t.device) if need else grad.new_empty((0,))
-            for t, need in zip((input, offset_mask), needs)]
+    return _needs_fake(grad, (input, offset_mask), needs)
 
 
 def _dcnv4_setup(ctx, inputs, output):
@@ -1641,9 +1566,7 @@ def _dcnv4_bwd(ctx, grad):
     return (dx if needs[0] else None, dom if needs[1] else None) + (None,) * 13
 
 
-torch.library.register_autograd("frcnn::dcnv4", _dcnv4_bwd, setup_context=_dcnv4_setup)
-torch.library.register_autograd("frcnn::dcnv4_backward", _no_double_backward("frcnn::dcnv4"),
-                                setup_context=lambda ctx, inputs, output: None)
+_register_autograd("dcnv4", _dcnv4_bwd, _dcnv4_setup)
 
 
 # ---- public interface -------------------------------------------------------------------------------------------------------------
@@ -1704,6 +1627,12 @@ def ps_roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1
 
 
 _F32_ONLY = "float32 (deform_conv2d computes in float32 only, as under torchvision's autocast rule: pass .float())"
+
+
+def _check_int(name, v):
+    """An int, and no bool (True would pass for 1)."""
+    if not isinstance(v, int) or isinstance(v, bool):
+        raise TypeError("%s must be an int, got %r" % (name, v))
 
 
 def _int_pair(name, v, low):
@@ -1922,8 +1851,7 @@ def roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_rati
 
 
 def _carafe_int(name, v, low, high, what=""):
-    if not isinstance(v, int) or isinstance(v, bool):
-        raise TypeError("%s must be an int, got %r" % (name, v))
+    _check_int(name, v)
     if not low <= v <= high:
         raise ValueError("%s must lie in [%d, %d]%s, got %d" % (name, low, high, what, v))
     return v
@@ -1995,8 +1923,7 @@ def multi_scale_deformable_attn(value, value_spatial_shapes, value_level_start_i
         raise ValueError("value_spatial_shapes must be [L, 2] = [%d, 2], got shape %s" % (levels, tuple(value_spatial_shapes.shape)))
     if tuple(value_level_start_index.shape) != (levels,):
         raise ValueError("value_level_start_index must be [L] = [%d], got shape %s" % (levels, tuple(value_level_start_index.shape)))
-    if not isinstance(im2col_step, int) or isinstance(im2col_step, bool):
-        raise TypeError("im2col_step must be an int, got %r" % (im2col_step,))
+    _check_int("im2col_step", im2col_step)
     if im2col_step < 1:
         raise ValueError("im2col_step must be at least 1, got %d" % im2col_step)
     if levels > MAX_MSDA_LEVELS:
@@ -2034,112 +1961,44 @@ def multi_scale_deformable_attn_pytorch(value, value_spatial_shapes, sampling_lo
     return output.view(bs, num_heads * embed_dims, num_queries).transpose(1, 2).contiguous()
 
 
-def _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step):
-    """The argument rules of dcnv3 / DCNv3Function: kernel, stride, pad and dil pairs (h, w) of ints."""
-    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
-    dtypes, what = _box_dtypes(input)
-    _check_tensor("offset", offset, dtypes, what)
-    _check_tensor("mask", mask, dtypes, what)
-    _check_same_device(input, offset, "input", "offset")
-    _check_same_device(input, mask, "input", "mask")
-    if input.dim() != 4:
-        raise ValueError("input must be [N, H, W, C] (channels last), got shape %s" % (tuple(input.shape),))
-    for name, v in (("group", group), ("group_channels", group_channels), ("im2col_step", im2col_step)):
-        if not isinstance(v, int) or isinstance(v, bool):
-            raise TypeError("%s must be an int, got %r" % (name, v))
-    if isinstance(offset_scale, bool) or not isinstance(offset_scale, (int, float)):
-        raise TypeError("offset_scale must be a float, got %r" % (offset_scale,))
-    if not math.isfinite(offset_scale):
-        raise ValueError("offset_scale must be finite, got %r" % (offset_scale,))
-    if im2col_step < 1:
-        raise ValueError("im2col_step must be at least 1, got %d" % im2col_step)
-    if group < 1:
-        raise ValueError("group must be at least 1, got %d" % group)
-    n, h, w, c = input.shape
-    if group * group_channels != c:
-        raise ValueError("group * group_channels must equal input's %d channels, got group %d and group_channels %d"
-                         % (c, group, group_channels))
-    if not 1 <= group_channels <= MAX_DCNV3_CHANNELS:
-        raise ValueError("group_channels must lie in [1, MAX_DCNV3_CHANNELS = %d], got %d" % (MAX_DCNV3_CHANNELS, group_channels))
-    if not (1 <= kernel[0] <= MAX_DCNV3_KERNEL and 1 <= kernel[1] <= MAX_DCNV3_KERNEL):
-        raise ValueError("kernel_size must lie in [1, MAX_DCNV3_KERNEL = %d], got %r" % (MAX_DCNV3_KERNEL, tuple(kernel)))
-    for name, v, low in (("stride", stride, 1), ("padding", pad, 0), ("dilation", dil, 1)):
-        if not (low <= v[0] <= MAX_DCNV3_STEP and low <= v[1] <= MAX_DCNV3_STEP):
-            raise ValueError("%s must lie in [%d, MAX_DCNV3_STEP = %d], got %r" % (name, low, MAX_DCNV3_STEP, tuple(v)))
-    if h > MAX_DCNV3_SIDE or w > MAX_DCNV3_SIDE:
-        raise ValueError("input must have H and W of at most MAX_DCNV3_SIDE = %d, got shape %s" % (MAX_DCNV3_SIDE, tuple(input.shape)))
-    k = kernel[0] * kernel[1]
-    ho, wo = _dcnv3_out_size(h, kernel[0], stride[0], pad[0], dil[0]), _dcnv3_out_size(w, kernel[1], stride[1], pad[1], dil[1])
-    if tuple(offset.shape) != (n, ho, wo, group * k * 2):
-        raise ValueError("offset must be [N, Ho, Wo, G K 2] = [%d, %d, %d, %d], got shape %s" % (n, ho, wo, group * k * 2, tuple(offset.shape)))
-    if tuple(mask.shape) != (n, ho, wo, group * k):
-        raise ValueError("mask must be [N, Ho, Wo, G K] = [%d, %d, %d, %d], got shape %s" % (n, ho, wo, group * k, tuple(mask.shape)))
-    nb = min(n, im2col_step)
-    if nb * h * w * group > MAX_MSDA_INDEX:
-        raise ValueError("input is too large for the kernels' 32-bit cell indices: %d images x H x W x G = %d > MAX_MSDA_INDEX = %d "
-                         "(lower im2col_step)" % (nb, nb * h * w * group, MAX_MSDA_INDEX))
-    if nb * ho * wo * group * k * 4 > MAX_MSDA_INDEX:
-        raise ValueError("offset is too large for the kernels' 32-bit plan indices: %d images x Ho x Wo x G x K x 4 = %d > MAX_MSDA_INDEX = "
-                         "%d (lower im2col_step)" % (nb, nb * ho * wo * group * k * 4, MAX_MSDA_INDEX))
+_DCN_NAMES = ("kernel_size", "stride", "padding", "dilation")                                                      # of dcnv3(), dcnv4()
+_DCN_APPLY_NAMES = ("kernel_h, kernel_w", "stride_h, stride_w", "pad_h, pad_w", "dilation_h, dilation_w")          # of the Functions
 
 
-def dcnv3(input, offset, mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256):
-    """DCNv3's sampling core: input [N, H, W, G Gc] sampled at kh kw learned positions per output pixel and group (offset
-    [N, Ho, Wo, G K 2], pairs (dx, dy)), the samples weighted by mask [N, Ho, Wo, G K] and summed: [N, Ho, Wo, G Gc]."""
-    kernel = _int_pair("kernel_size", kernel_size, 1)
-    stride, pad, dil = _int_pair("stride", stride, 1), _int_pair("padding", padding, 0), _int_pair("dilation", dilation, 1)
-    if not isinstance(group, int) or isinstance(group, bool):
-        raise TypeError("group must be an int, got %r" % (group,))
+def _dcn_pairs(names, kernel, stride, pad, dil):
+    """kernel, stride, pad and dil as pairs (h, w) of ints, under the caller's names for them."""
+    return _int_pair(names[0], kernel, 1), _int_pair(names[1], stride, 1), _int_pair(names[2], pad, 0), _int_pair(names[3], dil, 1)
+
+
+def _dcn_group_channels(input, group):
+    """The group rules of dcnv3() and dcnv4(), which have no group_channels argument: it follows from input."""
+    _check_int("group", group)
     if group < 1:
         raise ValueError("group must be at least 1, got %d" % group)
     if isinstance(input, torch.Tensor) and input.dim() == 4 and input.shape[3] % group != 0:
         raise ValueError("input's %d channels must be divisible by group, got %d" % (input.shape[3], group))
-    gc = input.shape[3] // group if isinstance(input, torch.Tensor) and input.dim() == 4 else 1
-    _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, gc, offset_scale, im2col_step)
-    return _dcnv3(input, offset, mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, gc,
-                  float(offset_scale), im2col_step)
+    return input.shape[3] // group if isinstance(input, torch.Tensor) and input.dim() == 4 else 1
 
 
-def dcnv3_core_pytorch(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
-                       group_channels, offset_scale):
-    """InternImage's dcnv3_core_pytorch: the same operator composed from F.pad and one F.grid_sample, on any device.  It materialises an
-    [N G, Gc, Ho Wo, K] tensor."""
-    F = torch.nn.functional
-    x = F.pad(input, [0, 0, pad_w, pad_w, pad_h, pad_h])
-    n, hp, wp, _ = x.shape
-    ho, wo = offset.shape[1], offset.shape[2]
-    k = kernel_h * kernel_w
-    bx, by = (dilation_w * (kernel_w - 1)) // 2, (dilation_h * (kernel_h - 1)) // 2
-    new = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device)     # noqa: E731
-    steps = lambda count: torch.arange(count, dtype=x.dtype, device=x.device)   # noqa: E731
-    ref = torch.stack(torch.broadcast_tensors(((steps(wo) * stride_w + bx + 0.5) / wp).view(1, wo),
-                                              ((steps(ho) * stride_h + by + 0.5) / hp).view(ho, 1)), -1)           # [Ho, Wo, 2] (x, y)
-    grid = torch.stack([((steps(kernel_w) * dilation_w - bx) / wp).repeat_interleave(kernel_h),                     # x: the outer index
-                        ((steps(kernel_h) * dilation_h - by) / hp).repeat(kernel_w)], -1) * offset_scale            # [K, 2]
-    loc = (ref.view(1, ho, wo, 1, 1, 2) + grid.view(1, 1, 1, 1, k, 2)
-           + offset.view(n, ho, wo, group, k, 2) * offset_scale / new([wp, hp]))
-    maps = x.reshape(n, hp * wp, group, group_channels).permute(0, 2, 3, 1).reshape(n * group, group_channels, hp, wp)
-    grids = (2 * loc - 1).view(n, ho * wo, group, k, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, K, 2]
-    sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, K]
-    weights = mask.view(n, ho * wo, group, k).transpose(1, 2).reshape(n * group, 1, ho * wo, k)
-    out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
-    return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
-
-
-def _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step, remove_center):
-    """The argument rules of dcnv4 / DCNv4Function: kernel, stride, pad and dil pairs (h, w) of ints."""
+def _dcn_args(op, input, learned, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step, remove_center=False):
+    """The argument rules of op "dcnv3" (dcnv3 / DCNv3Function, learned = (offset, mask)) or "dcnv4" (dcnv4 / DCNv4Function, learned =
+    (offset_mask,), with its remove_center), kernel, stride, pad and dil pairs (h, w) of ints; returns what the custom op takes after
+    its tensors."""
+    v4 = op == "dcnv4"
+    names = ("offset_mask",) if v4 else ("offset", "mask")
     _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT)
     dtypes, what = _box_dtypes(input)
-    _check_tensor("offset_mask", offset_mask, dtypes, what)
-    _check_same_device(input, offset_mask, "input", "offset_mask")
+    for name, t in zip(names, learned):
+        _check_tensor(name, t, dtypes, what)
+    for name, t in zip(names, learned):
+        _check_same_device(input, t, "input", name)
     if input.dim() != 4:
         raise ValueError("input must be [N, H, W, C] (channels last), got shape %s" % (tuple(input.shape),))
     for name, v in (("group", group), ("group_channels", group_channels), ("im2col_step", im2col_step)):
-        if not isinstance(v, int) or isinstance(v, bool):
-            raise TypeError("%s must be an int, got %r" % (name, v))
-    if not isinstance(remove_center, (bool, int)):
+        _check_int(name, v)
+    if v4 and not isinstance(remove_center, (bool, int)):
         raise TypeError("remove_center must be a bool, got %r" % (remove_center,))
-    if remove_center not in (0, 1):
+    if v4 and remove_center not in (0, 1):
         raise ValueError("remove_center must be False or True (0 or 1), got %r" % (remove_center,))
     if isinstance(offset_scale, bool) or not isinstance(offset_scale, (int, float)):
         raise TypeError("offset_scale must be a float, got %r" % (offset_scale,))
@@ -2157,27 +2016,80 @@ def _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, group_chan
         raise ValueError("group_channels must lie in [1, MAX_DCNV3_CHANNELS = %d], got %d" % (MAX_DCNV3_CHANNELS, group_channels))
     if not (1 <= kernel[0] <= MAX_DCNV3_KERNEL and 1 <= kernel[1] <= MAX_DCNV3_KERNEL):
         raise ValueError("kernel_size must lie in [1, MAX_DCNV3_KERNEL = %d], got %r" % (MAX_DCNV3_KERNEL, tuple(kernel)))
-    if remove_center and (kernel[0] != kernel[1] or kernel[0] % 2 == 0 or kernel[0] < 3):
+    if v4 and remove_center and (kernel[0] != kernel[1] or kernel[0] % 2 == 0 or kernel[0] < 3):
         raise ValueError("remove_center requires a square kernel of odd size >= 3, got %r" % (tuple(kernel),))
     for name, v, low in (("stride", stride, 1), ("padding", pad, 0), ("dilation", dil, 1)):
         if not (low <= v[0] <= MAX_DCNV3_STEP and low <= v[1] <= MAX_DCNV3_STEP):
             raise ValueError("%s must lie in [%d, MAX_DCNV3_STEP = %d], got %r" % (name, low, MAX_DCNV3_STEP, tuple(v)))
     if h > MAX_DCNV3_SIDE or w > MAX_DCNV3_SIDE:
         raise ValueError("input must have H and W of at most MAX_DCNV3_SIDE = %d, got shape %s" % (MAX_DCNV3_SIDE, tuple(input.shape)))
-    p = _dcnv4_points(kernel[0], kernel[1], remove_center)
-    rec = _dcnv4_record(group, p)
+    p = _dcnv4_points(kernel[0], kernel[1], v4 and remove_center)
     ho, wo = _dcnv3_out_size(h, kernel[0], stride[0], pad[0], dil[0]), _dcnv3_out_size(w, kernel[1], stride[1], pad[1], dil[1])
-    if tuple(offset_mask.shape) != (n, ho, wo, rec):
-        raise ValueError("offset_mask must be [N, Ho, Wo, L] = [%d, %d, %d, %d] with L = ceil(G P 3 / 8) 8 for G = %d groups of P = %d "
-                         "points (2 P offsets, then P masks; the record padded to a multiple of 8), got shape %s"
-                         % (n, ho, wo, rec, group, p, tuple(offset_mask.shape)))
+    if v4:
+        rec = _dcnv4_record(group, p)
+        if tuple(learned[0].shape) != (n, ho, wo, rec):
+            raise ValueError("offset_mask must be [N, Ho, Wo, L] = [%d, %d, %d, %d] with L = ceil(G P 3 / 8) 8 for G = %d groups of P = %d "
+                             "points (2 P offsets, then P masks; the record padded to a multiple of 8), got shape %s"
+                             % (n, ho, wo, rec, group, p, tuple(learned[0].shape)))
+    else:
+        for name, t, what, last in zip(names, learned, ("G K 2", "G K"), (group * p * 2, group * p)):
+            if tuple(t.shape) != (n, ho, wo, last):
+                raise ValueError("%s must be [N, Ho, Wo, %s] = [%d, %d, %d, %d], got shape %s" % (name, what, n, ho, wo, last, tuple(t.shape)))
     nb = min(n, im2col_step)
     if nb * h * w * group > MAX_MSDA_INDEX:
         raise ValueError("input is too large for the kernels' 32-bit cell indices: %d images x H x W x G = %d > MAX_MSDA_INDEX = %d "
                          "(lower im2col_step)" % (nb, nb * h * w * group, MAX_MSDA_INDEX))
     if nb * ho * wo * group * p * 4 > MAX_MSDA_INDEX:
-        raise ValueError("offset_mask is too large for the kernels' 32-bit plan indices: %d images x Ho x Wo x G x P x 4 = %d > "
-                         "MAX_MSDA_INDEX = %d (lower im2col_step)" % (nb, nb * ho * wo * group * p * 4, MAX_MSDA_INDEX))
+        raise ValueError("%s is too large for the kernels' 32-bit plan indices: %d images x Ho x Wo x G x %s x 4 = %d > MAX_MSDA_INDEX = "
+                         "%d (lower im2col_step)" % (names[0], nb, "P" if v4 else "K", nb * ho * wo * group * p * 4, MAX_MSDA_INDEX))
+    return (kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, group_channels, float(offset_scale),
+            im2col_step) + ((bool(remove_center),) if v4 else ())
+
+
+def dcnv3(input, offset, mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256):
+    """DCNv3's sampling core: input [N, H, W, G Gc] sampled at kh kw learned positions per output pixel and group (offset
+    [N, Ho, Wo, G K 2], pairs (dx, dy)), the samples weighted by mask [N, Ho, Wo, G K] and summed: [N, Ho, Wo, G Gc]."""
+    pairs = _dcn_pairs(_DCN_NAMES, kernel_size, stride, padding, dilation)
+    return _dcnv3(input, offset, mask, *_dcn_args("dcnv3", input, (offset, mask), *pairs, group, _dcn_group_channels(input, group),
+                                                  offset_scale, im2col_step))
+
+
+def dcnv3_core_pytorch(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                       group_channels, offset_scale):
+    """InternImage's dcnv3_core_pytorch: the same operator composed from F.pad and one F.grid_sample, on any device.  It materialises an
+    [N G, Gc, Ho Wo, K] tensor."""
+    n, ho, wo, k = input.shape[0], offset.shape[1], offset.shape[2], kernel_h * kernel_w
+    return _dcn_core_pytorch(input, offset.view(n, ho, wo, group, k, 2), mask.view(n, ho * wo, group, k), None, kernel_h, kernel_w,
+                             stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels, offset_scale)
+
+
+def _dcn_core_pytorch(input, offset, mask, points, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                      group_channels, offset_scale):
+    """The composition behind dcnv3_core_pytorch and dcnv4_core_pytorch: offset [N, Ho, Wo, G, P, 2] and mask [N, Ho Wo, G, P], views of
+    the callers' tensors.  points: None for all kh kw grid points, laid out on the device as dcnv3_core_pytorch always has; dcnv4's list
+    of the (i, j) it keeps, whose P integer parts come from the host as dcnv4_core_pytorch's always have."""
+    F = torch.nn.functional
+    x = F.pad(input, [0, 0, pad_w, pad_w, pad_h, pad_h])
+    n, hp, wp, _ = x.shape
+    ho, wo, p = offset.shape[1], offset.shape[2], offset.shape[4]
+    bx, by = (dilation_w * (kernel_w - 1)) // 2, (dilation_h * (kernel_h - 1)) // 2
+    new = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device)     # noqa: E731
+    steps = lambda count: torch.arange(count, dtype=x.dtype, device=x.device)   # noqa: E731
+    ref = torch.stack(torch.broadcast_tensors(((steps(wo) * stride_w + bx + 0.5) / wp).view(1, wo),
+                                              ((steps(ho) * stride_h + by + 0.5) / hp).view(ho, 1)), -1)           # [Ho, Wo, 2] (x, y)
+    if points is None:
+        grid = torch.stack([((steps(kernel_w) * dilation_w - bx) / wp).repeat_interleave(kernel_h),                 # x: the outer index
+                            ((steps(kernel_h) * dilation_h - by) / hp).repeat(kernel_w)], -1) * offset_scale        # [K, 2]
+    else:
+        grid = torch.stack([new([float(i * dilation_w - bx) for i, j in points]) / wp,
+                            new([float(j * dilation_h - by) for i, j in points]) / hp], -1) * offset_scale          # [P, 2]
+    loc = ref.view(1, ho, wo, 1, 1, 2) + grid.view(1, 1, 1, 1, p, 2) + offset * offset_scale / new([wp, hp])
+    maps = x.reshape(n, hp * wp, group, group_channels).permute(0, 2, 3, 1).reshape(n * group, group_channels, hp, wp)
+    grids = (2 * loc - 1).view(n, ho * wo, group, p, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, P, 2]
+    sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, P]
+    weights = mask.transpose(1, 2).reshape(n * group, 1, ho * wo, p)
+    out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
+    return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
 
 
 def dcnv4(input, offset_mask, kernel_size, stride=1, padding=0, dilation=1, group=1, offset_scale=1.0, im2col_step=256,
@@ -2185,48 +2097,24 @@ def dcnv4(input, offset_mask, kernel_size, stride=1, padding=0, dilation=1, grou
     """DCNv4's sampling core: input [N, H, W, G Gc] sampled at P learned positions per output pixel and group, the samples weighted by
     unnormalised masks and summed: [N, Ho, Wo, G Gc].  offset_mask [N, Ho, Wo, L] holds, per pixel and group, the 2 P offsets (pairs
     (dx, dy)) and then the P masks, the record padded to L = ceil(G P 3 / 8) 8; P = kh kw, less the centre point with remove_center."""
-    kernel = _int_pair("kernel_size", kernel_size, 1)
-    stride, pad, dil = _int_pair("stride", stride, 1), _int_pair("padding", padding, 0), _int_pair("dilation", dilation, 1)
-    if not isinstance(group, int) or isinstance(group, bool):
-        raise TypeError("group must be an int, got %r" % (group,))
-    if group < 1:
-        raise ValueError("group must be at least 1, got %d" % group)
-    if isinstance(input, torch.Tensor) and input.dim() == 4 and input.shape[3] % group != 0:
-        raise ValueError("input's %d channels must be divisible by group, got %d" % (input.shape[3], group))
-    gc = input.shape[3] // group if isinstance(input, torch.Tensor) and input.dim() == 4 else 1
-    _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, gc, offset_scale, im2col_step, remove_center)
-    return _dcnv4(input, offset_mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, gc,
-                  float(offset_scale), im2col_step, bool(remove_center))
+    pairs = _dcn_pairs(_DCN_NAMES, kernel_size, stride, padding, dilation)
+    return _dcnv4(input, offset_mask, *_dcn_args("dcnv4", input, (offset_mask,), *pairs, group, _dcn_group_channels(input, group),
+                                                 offset_scale, im2col_step, remove_center))
 
 
 def dcnv4_core_pytorch(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
                        group_channels, offset_scale, remove_center):
     """The same operator composed from F.pad and one F.grid_sample, on any device, differentiable to input and offset_mask: it unpacks
     the record, drops the centre location when asked and applies no softmax.  It materialises an [N G, Gc, Ho Wo, P] tensor."""
-    F = torch.nn.functional
-    x = F.pad(input, [0, 0, pad_w, pad_w, pad_h, pad_h])
-    n, hp, wp, _ = x.shape
-    ho, wo = offset_mask.shape[1], offset_mask.shape[2]
+    n, ho, wo = input.shape[0], offset_mask.shape[1], offset_mask.shape[2]
     points = [(i, j) for i in range(kernel_w) for j in range(kernel_h)]                                             # x: the outer index
     if remove_center:
         points.remove((kernel_w // 2, kernel_h // 2))
     p = len(points)
     rec = offset_mask[..., :group * p * 3].reshape(n, ho, wo, group, p * 3)
-    offset, mask = rec[..., :2 * p].reshape(n, ho, wo, group, p, 2), rec[..., 2 * p:]
-    bx, by = (dilation_w * (kernel_w - 1)) // 2, (dilation_h * (kernel_h - 1)) // 2
-    new = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device)     # noqa: E731
-    steps = lambda count: torch.arange(count, dtype=x.dtype, device=x.device)   # noqa: E731
-    ref = torch.stack(torch.broadcast_tensors(((steps(wo) * stride_w + bx + 0.5) / wp).view(1, wo),
-                                              ((steps(ho) * stride_h + by + 0.5) / hp).view(ho, 1)), -1)           # [Ho, Wo, 2] (x, y)
-    grid = torch.stack([new([float(i * dilation_w - bx) for i, j in points]) / wp,
-                        new([float(j * dilation_h - by) for i, j in points]) / hp], -1) * offset_scale              # [P, 2]
-    loc = ref.view(1, ho, wo, 1, 1, 2) + grid.view(1, 1, 1, 1, p, 2) + offset * offset_scale / new([wp, hp])
-    maps = x.reshape(n, hp * wp, group, group_channels).permute(0, 2, 3, 1).reshape(n * group, group_channels, hp, wp)
-    grids = (2 * loc - 1).view(n, ho * wo, group, p, 2).transpose(1, 2).flatten(0, 1)                               # [N G, Q, P, 2]
-    sampled = F.grid_sample(maps, grids, mode="bilinear", padding_mode="zeros", align_corners=False)                # [N G, Gc, Q, P]
-    weights = mask.reshape(n, ho * wo, group, p).transpose(1, 2).reshape(n * group, 1, ho * wo, p)
-    out = (sampled * weights).sum(-1).view(n, group * group_channels, ho * wo)
-    return out.transpose(1, 2).reshape(n, ho, wo, group * group_channels).contiguous()
+    return _dcn_core_pytorch(input, rec[..., :2 * p].reshape(n, ho, wo, group, p, 2), rec[..., 2 * p:].reshape(n, ho * wo, group, p),
+                             points, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
+                             offset_scale)
 
 
 def _ms_features(features):
@@ -2695,11 +2583,9 @@ class DCNv3Function:
     @staticmethod
     def apply(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
               offset_scale, im2col_step):
-        kernel, stride = _int_pair("kernel_h, kernel_w", (kernel_h, kernel_w), 1), _int_pair("stride_h, stride_w", (stride_h, stride_w), 1)
-        pad, dil = _int_pair("pad_h, pad_w", (pad_h, pad_w), 0), _int_pair("dilation_h, dilation_w", (dilation_h, dilation_w), 1)
-        _dcnv3_check(input, offset, mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step)
-        return _dcnv3(input, offset, mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group,
-                      group_channels, float(offset_scale), im2col_step)
+        pairs = _dcn_pairs(_DCN_APPLY_NAMES, (kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w), (dilation_h, dilation_w))
+        return _dcnv3(input, offset, mask, *_dcn_args("dcnv3", input, (offset, mask), *pairs, group, group_channels, offset_scale,
+                                                      im2col_step))
 
 
 class _ToChannelsLast(torch.nn.Module):
@@ -2772,11 +2658,9 @@ class DCNv4Function:
     @staticmethod
     def apply(input, offset_mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, group_channels,
               offset_scale, im2col_step, remove_center):
-        kernel, stride = _int_pair("kernel_h, kernel_w", (kernel_h, kernel_w), 1), _int_pair("stride_h, stride_w", (stride_h, stride_w), 1)
-        pad, dil = _int_pair("pad_h, pad_w", (pad_h, pad_w), 0), _int_pair("dilation_h, dilation_w", (dilation_h, dilation_w), 1)
-        _dcnv4_check(input, offset_mask, kernel, stride, pad, dil, group, group_channels, offset_scale, im2col_step, remove_center)
-        return _dcnv4(input, offset_mask, kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group,
-                      group_channels, float(offset_scale), im2col_step, bool(remove_center))
+        pairs = _dcn_pairs(_DCN_APPLY_NAMES, (kernel_h, kernel_w), (stride_h, stride_w), (pad_h, pad_w), (dilation_h, dilation_w))
+        return _dcnv4(input, offset_mask, *_dcn_args("dcnv4", input, (offset_mask,), *pairs, group, group_channels, offset_scale,
+                                                     im2col_step, remove_center))
 
 
 class DCNv4(torch.nn.Module):
