@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include <new>
@@ -18,6 +19,28 @@ void set_hip_error(hipError_t e) { g_hip_error = hipGetErrorString(e); }
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct EventRec { int cls; hipEvent_t start, stop; };
+
+// A device buffer of the context that is not part of the slab: allocated by the first call that needs it, replaced by a larger one when a
+// later call needs more.  What size to ask for, whether the buffer starts zeroed and whether it may grow at all is each site's own policy.
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    // At least `want` bytes.  A buffer that is too small is freed first, after everything enqueued on `s` (which may still use it) has
+    // finished; the allocation synchronises the device, so only the first image of a shape pays for it.
+    int reserve(size_t want, hipStream_t s, bool zero)
+    {
+        if (want <= bytes) return FRCNN_OK;
+        if (p) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); release(); }
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) { set_hip_error(e); p = nullptr; return FRCNN_ENOMEM; }
+        // zeroed ON THE CALLER'S STREAM: the slots of in-flight images run on non-blocking streams, which a null-stream hipMemset is not
+        // ordered with (it could still be clearing the buffer while the first layer writes its records)
+        if (zero && (e = hipMemsetAsync(p, 0, want, s)) != hipSuccess) { set_hip_error(e); release(); return FRCNN_EHIP; }
+        bytes = want;
+        return FRCNN_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
 
 }  // namespace frcnn
 
@@ -39,23 +62,24 @@ struct frcnn_ctx {
     float *roi_out = nullptr;                      // [max_rois][7][7][512]
     float *fc1_out = nullptr, *fc2_out = nullptr;  // [max_rois][4096]
     void *roi_rec = nullptr, *fc1_rec = nullptr;   // x6t / x3t records of roi_out ([rec_rows][25088]) and fc1_out (FRCNN_FC_F32X6T / _F32X3T):
-    int rec_rows = 0;                              // one allocation, made by the first forward that runs fc1 / fc2 in a record mode
+    int rec_rows = 0;                              // one allocation (fc_recs), made by the first forward that runs fc1 / fc2 in a record mode
+    Scratch fc_recs;                               // ... which the two record arrays and the three float arrays of the next line are carved from
     float *roi_inv = nullptr, *fc1_inv = nullptr, *fm_cmax = nullptr;   // FRCNN_FC_F32X3T: row scales of the two record arrays, channel maximum of the feature map
     float *head_logits = nullptr;                  // [max_rois][128]
     void* lin_ws = nullptr; size_t lin_ws_bytes = 0;
     void* conv_ws = nullptr; size_t conv_ws_bytes = 0;   // split-K partials of under-filled conv layers
-    void* wino_ws = nullptr; size_t wino_ws_bytes = 0;   // V and M of the Winograd layers; allocated by the first forward that needs it
-    void* wx_ws = nullptr; size_t wx_ws_bytes = 0;       // V records, M and split-K partials of the x6 Winograd layers; allocated on first use
+    Scratch wino_ws;            // V and M of the Winograd layers; allocated by the first forward that needs it
+    Scratch wx_ws;              // V records, M and split-K partials of the x6 Winograd layers; allocated on first use
     int max_head_rois = 0;      // frcnn_ctx_create_head: pooled RoIs a call of frcnn_resnet_head may bring
-    float* x3f_cmax = nullptr; size_t x3f_cmax_bytes = 0;   // channel maxima of a one-launch f32x3 Winograd layer's input (csrc/wino_x3f.hip); first use
-    void* rx_rec = nullptr; size_t rx_rec_bytes = 0;     // activation records of the x6 1x1 convolutions (ResNet bottlenecks); on first use
-    void* rx_ws = nullptr; size_t rx_ws_bytes = 0;       // their split-K partials
-    float* rx_aux = nullptr; size_t rx_aux_floats = 0;   // f32x3 form: row scales of the record array + channel maxima of the layer input
+    Scratch x3f_cmax;           // channel maxima of a one-launch f32x3 Winograd layer's input (csrc/wino_x3f.hip): three equal buffers; first use
+    Scratch rx_rec;             // activation records of the x6 1x1 convolutions (ResNet bottlenecks); on first use
+    Scratch rx_ws;              // their split-K partials
+    Scratch rx_aux;             // f32x3 form: row scales of the record array + channel maxima of the layer input (floats)
     // g3 bottlenecks (frcnn_bottleneck_weights.g3): the tensor maxima handed from one convolution's epilogue to the next one's scale.  One
     // zeroed float per convolution output of a forward (gx_next counts them; one memset per stage), gx_x = the slot bounding the CURRENT
     // block input (null: unknown, the next g3 block measures it)
-    float* gx_max = nullptr; int gx_next = 0; const float* gx_x = nullptr;
-    unsigned* gx_cnt = nullptr;                  // GX_TILE_COUNTERS tile tickets of the in-kernel split reductions (conv_gather_x3_kernel), zero between launches
+    Scratch gx_max; int gx_next = 0; const float* gx_x = nullptr;
+    Scratch gx_cnt;             // GX_TILE_COUNTERS tile tickets (unsigned) of the in-kernel split reductions (conv_gather_x3_kernel), zero between launches
     float* res_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // ResNet bottleneck rotation
     size_t res_buf_floats = 0;
     int last_c = 512, last_vec = 4096, last_head_ld = 128;
@@ -101,6 +125,32 @@ struct Scope {
 };
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// One launch of a fused forward, timed as class `cls`; the first failure ends the forward.  (Needs c, s and rc in scope.)
+#define STEP(cls, call) do { Scope _sc(c, cls, s); rc = (call); } while (0); if (rc) return rc
+
+// The slab of a context: ONE allocation that every item gets a 256-byte aligned piece of, in the order given.
+struct SlabItem { void** p; size_t bytes; };
+int carve_slab(frcnn_ctx* c, std::initializer_list<SlabItem> items)
+{
+    size_t total = 0;
+    for (auto& it : items) total += align_up(it.bytes, 256);
+    hipError_t e = hipMalloc(&c->slab, total);
+    if (e != hipSuccess) { set_hip_error(e); return FRCNN_ENOMEM; }
+    c->slab_bytes = total;
+    unsigned char* q = static_cast<unsigned char*>(c->slab);
+    for (auto& it : items) { *it.p = q; q += align_up(it.bytes, 256); }
+    return FRCNN_OK;
+}
+
+// The largest image of a context that runs proposals, and what follows from it: the largest feature map and the anchor / pre-NMS capacities.
+void ctx_set_image_limits(frcnn_ctx* c, int max_image_h, int max_image_w)
+{
+    c->max_h = max_image_h; c->max_w = max_image_w;
+    c->max_fh = cdiv(max_image_h, 16); c->max_fw = cdiv(max_image_w, 16);   // ceil covers ResNet maps too
+    c->a_cap = std::max(c->max_fh * c->max_fw * 9, 16384);      // the stand-alone NMS entry borrows this scratch
+    c->pre_cap = 16384;
+}
 
 }  // namespace
 
@@ -945,34 +995,21 @@ int frcnn_ctx_create(frcnn_ctx** out, int max_image_h, int max_image_w, int max_
     if (!out || max_image_h < 16 || max_image_w < 16 || max_rois < 1 || max_rois > 512) return FRCNN_EINVAL;
     frcnn_ctx* c = new (std::nothrow) frcnn_ctx();
     if (!c) return FRCNN_ENOMEM;
-    c->max_h = max_image_h; c->max_w = max_image_w; c->max_rois = max_rois;
-    c->max_fh = cdiv(max_image_h, 16); c->max_fw = cdiv(max_image_w, 16);   // ceil covers ResNet maps too
-    c->a_cap = c->max_fh * c->max_fw * 9;
-    if (c->a_cap < 16384) c->a_cap = 16384;      // the stand-alone NMS entry borrows this scratch
-    c->pre_cap = 16384;
+    ctx_set_image_limits(c, max_image_h, max_image_w);
+    c->max_rois = max_rois;
 
     const size_t act = (size_t)max_image_h * max_image_w * 64 * sizeof(float);
     const size_t fmb = (size_t)c->max_fh * c->max_fw * 1024 * sizeof(float);   // 1024 channels for the ResNet maps
     const size_t headb = (size_t)c->max_fh * c->max_fw * 128 * sizeof(float);
-    size_t lin = 0;
-    {
-        const size_t w1 = linear_workspace_bytes(max_rois, 4096, 512 * 49);
-        const size_t w2 = linear_workspace_bytes(max_rois, 4096, 4096);
-        const size_t w3 = linear_workspace_bytes(max_rois, FRCNN_HEAD_LD_MAX, 4096);
-        const size_t w4 = linear_workspace_bytes(c->max_fh * c->max_fw, 45, 512);
-        const size_t w5 = linear_workspace_bytes(c->max_fh * c->max_fw, 45, 1024);
-        const size_t w6 = linear_workspace_bytes(max_rois, FRCNN_HEAD_LD_MAX, 2048);
-        lin = w1; if (w2 > lin) lin = w2; if (w3 > lin) lin = w3; if (w4 > lin) lin = w4; if (w5 > lin) lin = w5; if (w6 > lin) lin = w6;
-        const size_t t1 = gemm_x6t_workspace_bytes(max_rois, 4096, 512 * 49, 1), t2 = gemm_x6t_workspace_bytes(max_rois, 4096, 4096, 1);
-        if (t1 > lin) lin = t1;
-        if (t2 > lin) lin = t2;
-        const size_t h1 = gemm_x3t_workspace_bytes(max_rois, 4096, 512 * 49, 1), h2 = gemm_x3t_workspace_bytes(max_rois, 4096, 4096, 1);
-        if (h1 > lin) lin = h1;
-        if (h2 > lin) lin = h2;
-    }
+    // the GEMM scratch: fc1, fc2 and the heads (VGG-16, ResNet) over max_rois rows, the RPN heads over the largest map, fc1 / fc2 on records
+    const size_t lin = std::max({
+        linear_workspace_bytes(max_rois, 4096, 512 * 49), linear_workspace_bytes(max_rois, 4096, 4096),
+        linear_workspace_bytes(max_rois, FRCNN_HEAD_LD_MAX, 4096), linear_workspace_bytes(max_rois, FRCNN_HEAD_LD_MAX, 2048),
+        linear_workspace_bytes(c->max_fh * c->max_fw, 45, 512), linear_workspace_bytes(c->max_fh * c->max_fw, 45, 1024),
+        gemm_x6t_workspace_bytes(max_rois, 4096, 512 * 49, 1), gemm_x6t_workspace_bytes(max_rois, 4096, 4096, 1),
+        gemm_x3t_workspace_bytes(max_rois, 4096, 512 * 49, 1), gemm_x3t_workspace_bytes(max_rois, 4096, 4096, 1)});
     // row count of the activation record arrays: the x6t GEMM's 320-row tiles over max_rois
-    const int rec_rows = cdiv(max_rois, gemm_x6t_row_tile(max_rois)) * gemm_x6t_row_tile(max_rois);
-    c->rec_rows = rec_rows;
+    c->rec_rows = cdiv(max_rois, gemm_x6t_row_tile(max_rois)) * gemm_x6t_row_tile(max_rois);
     size_t cws = 0;
     {
         // the layers that may split: every VGG-16 shape at the largest image this ctx accepts
@@ -981,29 +1018,20 @@ int frcnn_ctx_create(frcnn_ctx** out, int max_image_h, int max_image_w, int max_
                                 {max_image_h / 16, max_image_w / 16}};
         const int chans[5][2] = {{64, 64}, {128, 128}, {256, 256}, {512, 512}, {512, 512}};
         for (int i = 0; i < 5; ++i) {
-            size_t b = conv3x3_workspace_bytes(dims[i][0], dims[i][1], chans[i][0], chans[i][1]);
-            if (i > 0) {
-                const size_t b2 = conv3x3_workspace_bytes(dims[i][0], dims[i][1], chans[i - 1][1], chans[i][1]);
-                if (b2 > b) b = b2;
-            }
-            if (b > cws) cws = b;
+            cws = std::max(cws, conv3x3_workspace_bytes(dims[i][0], dims[i][1], chans[i][0], chans[i][1]));
+            if (i > 0) cws = std::max(cws, conv3x3_workspace_bytes(dims[i][0], dims[i][1], chans[i - 1][1], chans[i][1]));
         }
         // smaller images of the same ctx can pick a larger split factor: size for the worst case
-        const size_t generous = (size_t)16 * c->max_fh * c->max_fw * 512 * sizeof(float);
-        if (generous > cws) cws = generous;
+        cws = std::max(cws, (size_t)16 * c->max_fh * c->max_fw * 512 * sizeof(float));
     }
     {
         // ResNet: stem output ((H+1)/2 x (W+1)/2 x 64) == layer1 output size; per-RoI head tensors
         const size_t stem = (size_t)((max_image_h + 1) / 2) * ((max_image_w + 1) / 2) * 64;
-        const size_t head = (size_t)max_rois * 49 * 512;
-        const size_t head2 = (size_t)max_rois * 16 * 2048;
-        size_t m = stem; if (head > m) m = head; if (head2 > m) m = head2;
-        c->res_buf_floats = m;
-        if (cws < ((size_t)160 << 20)) cws = (size_t)160 << 20;
+        c->res_buf_floats = std::max({stem, (size_t)max_rois * 49 * 512, (size_t)max_rois * 16 * 2048});
+        cws = std::max(cws, (size_t)160 << 20);
     }
-    struct Item { void** p; size_t bytes; };
     void* ps_base = nullptr;
-    Item items[] = {
+    const int rc = carve_slab(c, {
         {(void**)&c->act_a, act}, {(void**)&c->act_b, act / 2},
         {(void**)&c->fm, fmb}, {(void**)&c->rpn_trunk, fmb}, {(void**)&c->rpn_head, headb},
         {(void**)&c->scores, (size_t)c->a_cap * 4}, {(void**)&c->sorted_idx, (size_t)c->pre_cap * 4},
@@ -1016,14 +1044,8 @@ int frcnn_ctx_create(frcnn_ctx** out, int max_image_h, int max_image_w, int max_
         {(void**)&c->res_buf[2], c->res_buf_floats * 4}, {(void**)&c->res_buf[3], c->res_buf_floats * 4},
         {(void**)&c->res_buf[4], c->res_buf_floats * 4},
         {&ps_base, proposal_scratch_bytes(c->a_cap, c->pre_cap, 2048)},
-    };
-    size_t total = 0;
-    for (auto& it : items) total += align_up(it.bytes, 256);
-    hipError_t e = hipMalloc(&c->slab, total);
-    if (e != hipSuccess) { set_hip_error(e); delete c; return FRCNN_ENOMEM; }
-    c->slab_bytes = total;
-    unsigned char* p = static_cast<unsigned char*>(c->slab);
-    for (auto& it : items) { *it.p = p; p += align_up(it.bytes, 256); }
+    });
+    if (rc) { delete c; return rc; }
     c->lin_ws_bytes = lin;
     c->conv_ws_bytes = cws;
     proposal_scratch_carve(c->ps, ps_base, c->a_cap, c->pre_cap, 2048);
@@ -1038,16 +1060,12 @@ int frcnn_ctx_create_proposals(frcnn_ctx** out, int max_image_h, int max_image_w
     if (!out || max_image_h < 16 || max_image_w < 16) return FRCNN_EINVAL;
     frcnn_ctx* c = new (std::nothrow) frcnn_ctx();
     if (!c) return FRCNN_ENOMEM;
-    c->max_h = max_image_h; c->max_w = max_image_w; c->max_rois = 0;
-    c->max_fh = cdiv(max_image_h, 16); c->max_fw = cdiv(max_image_w, 16);
-    c->a_cap = c->max_fh * c->max_fw * 9;
-    if (c->a_cap < 16384) c->a_cap = 16384;
-    c->pre_cap = 16384;
-    const size_t total = align_up(proposal_scratch_bytes(c->a_cap, c->pre_cap, 2048), 256);
-    hipError_t e = hipMalloc(&c->slab, total);
-    if (e != hipSuccess) { set_hip_error(e); delete c; return FRCNN_ENOMEM; }
-    c->slab_bytes = total;
-    proposal_scratch_carve(c->ps, c->slab, c->a_cap, c->pre_cap, 2048);
+    ctx_set_image_limits(c, max_image_h, max_image_w);
+    c->max_rois = 0;
+    void* ps_base = nullptr;
+    const int rc = carve_slab(c, {{&ps_base, proposal_scratch_bytes(c->a_cap, c->pre_cap, 2048)}});
+    if (rc) { delete c; return rc; }
+    proposal_scratch_carve(c->ps, ps_base, c->a_cap, c->pre_cap, 2048);
     *out = c;
     return FRCNN_OK;
 }
@@ -1059,19 +1077,19 @@ void frcnn_ctx_destroy(frcnn_ctx* ctx)
     for (auto e : ctx->free_events) (void)hipEventDestroy(e);
     for (auto e : ctx->dep_ring) if (e) (void)hipEventDestroy(e);
     if (ctx->slab) (void)hipFree(ctx->slab);
-    if (ctx->wino_ws) (void)hipFree(ctx->wino_ws);
-    if (ctx->wx_ws) (void)hipFree(ctx->wx_ws);
-    if (ctx->x3f_cmax) (void)hipFree(ctx->x3f_cmax);
-    if (ctx->roi_rec) (void)hipFree(ctx->roi_rec);
-    if (ctx->rx_rec) (void)hipFree(ctx->rx_rec);
-    if (ctx->rx_ws) (void)hipFree(ctx->rx_ws);
-    if (ctx->rx_aux) (void)hipFree(ctx->rx_aux);
-    if (ctx->gx_max) (void)hipFree(ctx->gx_max);
-    if (ctx->gx_cnt) (void)hipFree(ctx->gx_cnt);
+    for (Scratch* b : {&ctx->wino_ws, &ctx->wx_ws, &ctx->x3f_cmax, &ctx->fc_recs, &ctx->rx_rec, &ctx->rx_ws, &ctx->rx_aux, &ctx->gx_max, &ctx->gx_cnt})
+        b->release();
     delete ctx;
 }
 
-size_t frcnn_ctx_bytes(const frcnn_ctx* ctx) { return ctx ? ctx->slab_bytes + ctx->wino_ws_bytes + ctx->wx_ws_bytes + ctx->rx_rec_bytes + ctx->rx_ws_bytes + (ctx->roi_rec ? (size_t)ctx->rec_rows * (49 * 512 + 4096) * 6 : 0) : 0; }
+// The slab, the two Winograd scratches, the records and partials of the 1x1 convolutions and the two fc record arrays.  NOT counted: the
+// float arrays that share the fc records' allocation, x3f_cmax, rx_aux and the gx buffers (callers have been reading this sum as it is).
+size_t frcnn_ctx_bytes(const frcnn_ctx* ctx)
+{
+    if (!ctx) return 0;
+    return ctx->slab_bytes + ctx->wino_ws.bytes + ctx->wx_ws.bytes + ctx->rx_rec.bytes + ctx->rx_ws.bytes +
+           (ctx->roi_rec ? (size_t)ctx->rec_rows * (49 * 512 + 4096) * 6 : 0);
+}
 
 int frcnn_ctx_timing_enable(frcnn_ctx* ctx, int enable)
 {
@@ -1120,27 +1138,20 @@ int frcnn_ctx_tensor(frcnn_ctx* c, int which, void** d_ptr, size_t* bytes)
 namespace {
 // Winograd scratch (V and M of the largest eligible layer up to the ctx's largest image), allocated once, on first use:
 // contexts that never run the mode do not pay the 16*T*(cin+cout) floats.
-int ensure_wino_ws(frcnn_ctx* c)
+int ensure_wino_ws(frcnn_ctx* c, hipStream_t s)
 {
-    if (c->wino_ws) return FRCNN_OK;
+    if (c->wino_ws.p) return FRCNN_OK;           // sized for the ctx's largest image: never grows
     size_t need = 0;
     // VGG-16 layer shapes (image / 4, / 8, / 16)
     const int shapes[5][3] = {{4, 128, 256}, {4, 256, 256}, {8, 256, 512}, {8, 512, 512}, {16, 512, 512}};
-    for (auto& sh : shapes) {
-        const size_t b = c->max_h > 0 ? conv3x3_winograd_workspace_bytes(1, c->max_h / sh[0], c->max_w / sh[0], sh[1], sh[2]) : 0;
-        if (b > need) need = b;
-    }
+    for (auto& sh : shapes)
+        if (c->max_h > 0) need = std::max(need, conv3x3_winograd_workspace_bytes(1, c->max_h / sh[0], c->max_w / sh[0], sh[1], sh[2]));
     // ResNet: the RPN trunk on the 1024-channel map, layer4's 512-wide 3x3 on max_rois 4x4 maps (a head ctx: max_head_rois)
-    const int rois = c->max_rois > c->max_head_rois ? c->max_rois : c->max_head_rois;
-    const size_t b1 = c->max_fh > 0 ? conv3x3_winograd_workspace_bytes(1, c->max_fh, c->max_fw, 1024, 1024) : 0;
-    const size_t b2 = rois > 0 ? conv3x3_winograd_workspace_bytes(rois, 4, 4, 512, 512) : 0;
-    if (b1 > need) need = b1;
-    if (b2 > need) need = b2;
+    const int rois = std::max(c->max_rois, c->max_head_rois);
+    if (c->max_fh > 0) need = std::max(need, conv3x3_winograd_workspace_bytes(1, c->max_fh, c->max_fw, 1024, 1024));
+    if (rois > 0) need = std::max(need, conv3x3_winograd_workspace_bytes(rois, 4, 4, 512, 512));
     if (need == 0) return FRCNN_EINVAL;
-    hipError_t e = hipMalloc(&c->wino_ws, need);
-    if (e != hipSuccess) { set_hip_error(e); c->wino_ws = nullptr; return FRCNN_ENOMEM; }
-    c->wino_ws_bytes = need;
-    return FRCNN_OK;
+    return c->wino_ws.reserve(need, s, false);
 }
 
 // One Winograd layer inside a fused forward, its three launches timed as classes 6 (transforms) and 7 (GEMM).
@@ -1148,7 +1159,7 @@ int run_winograd_layer(frcnn_ctx* c, const float* x, const float* u, const float
                        unsigned flags, hipStream_t s)
 {
     float *V = nullptr, *M = nullptr;
-    int r = winograd_plan(N, h, w, ci, co, flags, c->wino_ws, c->wino_ws_bytes, &V, &M);
+    int r = winograd_plan(N, h, w, ci, co, flags, c->wino_ws.p, c->wino_ws.bytes, &V, &M);
     if (r) return r;
     { Scope _t(c, 6, s); r = launch_winograd_input(x, V, N, h, w, ci, s); }
     if (r) return r;
@@ -1160,32 +1171,17 @@ int run_winograd_layer(frcnn_ctx* c, const float* x, const float* u, const float
 
 // Scratch of the x6 Winograd layers (V records + M + split-K partials).  Sized on first use for the largest layer of the DEFAULT table
 // up to the ctx's largest image (conv4_x on image / 8, conv5_x / RPN trunk on image / 16, ResNet's 1024-channel trunk); a layer that
-// needs more (a larger map put on the table by the caller) grows it once (hipMalloc synchronises: first image only).  Zeroed, so the
+// needs more (a larger map put on the table by the caller) grows it once (the allocation synchronises: first image only).  Zeroed, so the
 // padding row blocks of V are zero for ever: nobody writes them.
 int ensure_wx_ws(frcnn_ctx* c, size_t layer_need, hipStream_t s)
 {
-    if (c->wx_ws && layer_need <= c->wx_ws_bytes) return FRCNN_OK;
+    if (c->wx_ws.p && layer_need <= c->wx_ws.bytes) return FRCNN_OK;
     size_t need = layer_need;
     const int shapes[4][4] = {{c->max_h / 8, c->max_w / 8, 256, 512}, {c->max_h / 8, c->max_w / 8, 512, 512},
                               {c->max_fh, c->max_fw, 512, 512}, {c->max_fh, c->max_fw, 1024, 1024}};
-    for (auto& sh : shapes) {
-        const size_t b = conv3x3_winograd_x6_workspace_bytes(1, sh[0], sh[1], sh[2], sh[3]);
-        if (b > need) need = b;
-    }
+    for (auto& sh : shapes) need = std::max(need, conv3x3_winograd_x6_workspace_bytes(1, sh[0], sh[1], sh[2], sh[3]));
     if (need == 0) return FRCNN_EINVAL;
-    if (c->wx_ws) {
-        FRCNN_HIP_TRY(hipStreamSynchronize(s));
-        (void)hipFree(c->wx_ws);
-        c->wx_ws = nullptr; c->wx_ws_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&c->wx_ws, need);
-    if (e != hipSuccess) { set_hip_error(e); c->wx_ws = nullptr; return FRCNN_ENOMEM; }
-    // zeroed ON THE CALLER'S STREAM: the slots of in-flight images run on non-blocking streams, which a null-stream hipMemset is not
-    // ordered with (it could still be clearing the buffer while the first layer writes its records)
-    e = hipMemsetAsync(c->wx_ws, 0, need, s);
-    if (e != hipSuccess) { set_hip_error(e); (void)hipFree(c->wx_ws); c->wx_ws = nullptr; return FRCNN_EHIP; }
-    c->wx_ws_bytes = need;
-    return FRCNN_OK;
+    return c->wx_ws.reserve(need, s, true);
 }
 
 // The activation record arrays of fc1 / fc2 (x6t / x3t modes of the VGG-16 detector): 53 MB at 320 rows, allocated and zeroed by the first
@@ -1196,16 +1192,14 @@ int ensure_fc_records(frcnn_ctx* c, hipStream_t s)
     // (sized for the x6t records, 6 bytes per value; the x3t records of FRCNN_FC_F32X3T need 4)
     const size_t b1 = (size_t)c->rec_rows * 49 * 512 * 6, b2 = (size_t)c->rec_rows * 4096 * 6;
     const size_t b3 = align_up((size_t)c->rec_rows * sizeof(float), 256), b4 = align_up((size_t)c->max_fh * c->max_fw * sizeof(float), 256);
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, b1 + b2 + 2 * b3 + b4);
-    if (e != hipSuccess) { set_hip_error(e); return FRCNN_ENOMEM; }
-    e = hipMemsetAsync(p, 0, b1 + b2 + 2 * b3 + b4, s);     // on the caller's stream (see ensure_wx_ws)
-    if (e != hipSuccess) { set_hip_error(e); (void)hipFree(p); return FRCNN_EHIP; }
+    const int rc = c->fc_recs.reserve(b1 + b2 + 2 * b3 + b4, s, true);
+    if (rc) return rc;
+    unsigned char* p = static_cast<unsigned char*>(c->fc_recs.p);
     c->roi_rec = p;
-    c->fc1_rec = static_cast<unsigned char*>(p) + b1;
-    c->roi_inv = reinterpret_cast<float*>(static_cast<unsigned char*>(p) + b1 + b2);
-    c->fc1_inv = reinterpret_cast<float*>(static_cast<unsigned char*>(p) + b1 + b2 + b3);
-    c->fm_cmax = reinterpret_cast<float*>(static_cast<unsigned char*>(p) + b1 + b2 + 2 * b3);
+    c->fc1_rec = p + b1;
+    c->roi_inv = reinterpret_cast<float*>(p + b1 + b2);
+    c->fc1_inv = reinterpret_cast<float*>(p + b1 + b2 + b3);
+    c->fm_cmax = reinterpret_cast<float*>(p + b1 + b2 + 2 * b3);
     return FRCNN_OK;
 }
 
@@ -1219,7 +1213,7 @@ int run_wino_x6_layer(frcnn_ctx* c, const float* x, const void* urec, const floa
     void *V = nullptr, *G = nullptr;
     float* M = nullptr;
     size_t gb = 0;
-    r = winograd_x6_plan(N, h, w, ci, co, flags, c->wx_ws, c->wx_ws_bytes, &V, &M, &G, &gb);
+    r = winograd_x6_plan(N, h, w, ci, co, flags, c->wx_ws.p, c->wx_ws.bytes, &V, &M, &G, &gb);
     if (r) return r;
     { Scope _t(c, 8, s); r = launch_winograd_x6_input(x, V, N, h, w, ci, s); }
     if (r) return r;
@@ -1242,7 +1236,7 @@ int run_wino_x3_layer(frcnn_ctx* c, const float* x, const void* ublob, const flo
     void *V = nullptr, *G = nullptr;
     float *M = nullptr, *vinv = nullptr, *cmax = nullptr;
     size_t gb = 0;
-    r = winograd_x3_plan(N, h, w, ci, co, flags, c->wx_ws, c->wx_ws_bytes, &V, &vinv, &cmax, &M, &G, &gb);
+    r = winograd_x3_plan(N, h, w, ci, co, flags, c->wx_ws.p, c->wx_ws.bytes, &V, &vinv, &cmax, &M, &G, &gb);
     if (r) return r;
     { Scope _t(c, 8, s); r = launch_winograd_x3_input(x, cmax, V, vinv, N, h, w, ci, s, cmax_ready); }
     if (r) return r;
@@ -1254,17 +1248,13 @@ int run_wino_x3_layer(frcnn_ctx* c, const float* x, const void* ublob, const flo
 
 // The three channel-maximum buffers of a ctx (max_h x max_w floats each): [0] scratch of a layer that has to compute its input's maxima
 // itself, [1] / [2] the ping-pong pair the f32x3 layers hand the maxima of their OUTPUT to the next layer in.
+// One allocation of three times max(need, max_h x max_w floats), not zeroed (a forward clears what it accumulates into).
 int ensure_x3f_cmax(frcnn_ctx* c, size_t need, hipStream_t s)
 {
-    if (c->x3f_cmax && c->x3f_cmax_bytes >= need) return FRCNN_OK;
-    if (c->x3f_cmax) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->x3f_cmax); c->x3f_cmax = nullptr; c->x3f_cmax_bytes = 0; }
-    const size_t cap = std::max(need, (size_t)c->max_h * c->max_w * sizeof(float));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->x3f_cmax), 3 * cap);
-    if (e != hipSuccess) { set_hip_error(e); c->x3f_cmax = nullptr; return FRCNN_ENOMEM; }
-    c->x3f_cmax_bytes = cap;
-    return FRCNN_OK;
+    return c->x3f_cmax.reserve(3 * std::max(need, (size_t)c->max_h * c->max_w * sizeof(float)), s, false);
 }
-float* x3f_cmax_buffer(frcnn_ctx* c, int which) { return reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(c->x3f_cmax) + (size_t)which * c->x3f_cmax_bytes); }
+size_t x3f_cmax_bytes(const frcnn_ctx* c) { return c->x3f_cmax.bytes / 3; }      // of ONE of the three
+float* x3f_cmax_buffer(frcnn_ctx* c, int which) { return reinterpret_cast<float*>(static_cast<unsigned char*>(c->x3f_cmax.p) + (size_t)which * x3f_cmax_bytes(c)); }
 
 // A ONE-LAUNCH f32x3 Winograd layer inside a fused forward (csrc/wino_x3f.hip; a bit of frcnn_forward_params.winograd_x3f_mask; timing class 10,
 // which includes the channel-maximum pass over the layer input).  ublob = frcnn_pack_conv3x3_winograd_x3's blob.
@@ -1274,7 +1264,7 @@ int run_wino_x3f_layer(frcnn_ctx* c, const float* x, const void* ublob, const fl
     int r = ensure_x3f_cmax(c, conv3x3_winograd_x3_fused_workspace_bytes(1, h, w), s);
     if (r) return r;
     Scope _w(c, 10, s);
-    return launch_conv3x3_winograd_x3_fused(x, ublob, b, y, 1, h, w, ci, co, flags, x3f_cmax_buffer(c, 0), c->x3f_cmax_bytes, s, cmax_ready, cmax_out);
+    return launch_conv3x3_winograd_x3_fused(x, ublob, b, y, 1, h, w, ci, co, flags, x3f_cmax_buffer(c, 0), x3f_cmax_bytes(c), s, cmax_ready, cmax_out);
 }
 
 // One one-launch Winograd layer inside a fused forward (timed as class 7).
@@ -1292,6 +1282,66 @@ struct BlocksTargetScope {
     explicit BlocksTargetScope(int t, int wino_rows = 0, int x6_tiles = 0) { conv3x3_set_blocks_target(t); linear_batched_set_tile(wino_rows); gemm_x6t_set_tiles(x6_tiles); }
     ~BlocksTargetScope() { conv3x3_set_blocks_target(0); linear_batched_set_tile(0); gemm_x6t_set_tiles(0); }
 };
+
+// The parameter rules the two forwards share.  `bad_math_mode`: what a math mode outside the two float32 ones is to the caller
+// (FRCNN_EINVAL for VGG-16; FRCNN_EUNSUPPORTED for ResNet, which has no f32x6 path).
+int check_forward_params(const frcnn_forward_params* p, int bad_math_mode)
+{
+    if ((p->winograd_x3_mask & ~p->winograd_x6_mask) != 0) return FRCNN_EINVAL;     // a subset of the x6 table (ResNet: only the RPN trunk bit exists)
+    if (p->math_mode != FRCNN_MATH_F32 && p->math_mode != FRCNN_MATH_F32_WINOGRAD) return bad_math_mode;
+    if ((p->roi_op != FRCNN_ROI_POOL && p->roi_op != FRCNN_ROI_ALIGN) || p->roi_sampling_ratio > 2) return FRCNN_EINVAL;
+    if (p->conv_blocks_target < 0) return FRCNN_EINVAL;
+    if (p->winograd_tile_rows != 0 && p->winograd_tile_rows != 64 && p->winograd_tile_rows != 128) return FRCNN_EINVAL;
+    if (p->x6_gemm_tiles < 0 || p->x6_gemm_tiles > 2) return FRCNN_EINVAL;
+    return FRCNN_OK;
+}
+
+// The RPN after its trunk convolution (models/rpn.py:88-153): the stacked objectness / box heads over the [fh][fw][C] trunk output, the
+// anchors of this image shape (cached in the ctx unless the caller brings maps), and the proposals into d_props / d_counts.
+int run_rpn_after_trunk(frcnn_ctx* c, const float* head_w, const float* head_b, const frcnn_forward_params* p, int H, int W, int fh, int fw,
+                        int C, const float* d_anchor_map, const float* d_valid_map, float* d_props, int32_t* d_counts, hipStream_t s)
+{
+    int rc;
+    STEP(2, launch_linear(c->rpn_trunk, C, head_w, head_b, c->rpn_head, 128, fh * fw, 45, C, 0u, c->lin_ws, c->lin_ws_bytes, s));
+    const float* amap = d_anchor_map;
+    const float* vmap = d_valid_map;
+    if (!amap || !vmap) {
+        if (c->anc_h != H || c->anc_w != W || c->anc_fh != fh || c->anc_fw != fw) {
+            STEP(5, launch_anchors(H, W, fh, fw, 16, c->anchor_map, c->valid_map, s));
+            c->anc_h = H; c->anc_w = W; c->anc_fh = fh; c->anc_fw = fw;
+        }
+        amap = c->anchor_map; vmap = c->valid_map;
+    }
+    FRCNN_HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), s));
+    STEP(3, launch_rpn_proposals(c->ps, c->rpn_head, 128, amap, p->allow_edge_proposals ? nullptr : vmap, fh, fw,
+                                 H, W, p->pre_nms, p->post_nms, p->rpn_nms_threshold, p->min_side, c->scores,
+                                 c->sorted_idx, d_props, d_counts, s));
+    return FRCNN_OK;
+}
+
+// RoI pooling of the image's proposals from c->fm into a float32 buffer [post_nms][7][7][C], by the operator the parameters name.
+int run_roi_f32(frcnn_ctx* c, const frcnn_forward_params* p, int fh, int fw, int C, const float* d_props, const int32_t* d_counts,
+                float* dst, hipStream_t s)
+{
+    Scope _sc(c, 4, s);
+    if (p->roi_op == FRCNN_ROI_ALIGN)
+        return launch_roi_align(c->fm, fh, fw, C, d_props, d_counts + 2, p->post_nms, 7, 1.0f / 16.0f, p->roi_sampling_ratio, 0, dst, s);
+    return launch_roi_pool(c->fm, fh, fw, C, d_props, d_counts + 2, p->post_nms, 7, 1.0f / 16.0f, dst, s);
+}
+
+// The detector's last two launches: the stacked classifier + regressor over the n_rois vectors of V floats in c->fc2_out, then softmax
+// and the split into d_classes / d_deltas.
+int run_detector_heads(frcnn_ctx* c, const float* head_w, const float* head_b, int ncls, int V, int n_rois, float* d_classes,
+                       float* d_deltas, hipStream_t s)
+{
+    int rc;
+    const int nd = (ncls - 1) * 4;
+    const int hld = cdiv(ncls + nd, 128) * 128;                  // row count of the stacked classifier + regressor operand (zero padded)
+    c->last_head_ld = hld;
+    STEP(2, launch_linear(c->fc2_out, V, head_w, head_b, c->head_logits, hld, n_rois, ncls + nd, V, 0u, c->lin_ws, c->lin_ws_bytes, s));
+    STEP(5, launch_head_finish(c->head_logits, hld, n_rois, ncls, nd, d_classes, d_deltas, s));
+    return FRCNN_OK;
+}
 }  // namespace
 
 // ---- fused forward ---------------------------------------------------------------------------
@@ -1310,14 +1360,9 @@ int frcnn_vgg16_forward(frcnn_ctx* c, const frcnn_vgg16_weights* w, const frcnn_
         return FRCNN_EINVAL;
     hipStream_t s = as_stream(stream);
     const unsigned R = FRCNN_RELU, RP = FRCNN_RELU | FRCNN_POOL2;
-    int rc;
-    if (p->math_mode != FRCNN_MATH_F32 && p->math_mode != FRCNN_MATH_F32_WINOGRAD) return FRCNN_EINVAL;
-    if (p->conv_blocks_target < 0) return FRCNN_EINVAL;
+    int rc = check_forward_params(p, FRCNN_EINVAL);
+    if (rc) return rc;
     if (p->fc_math_mode != FRCNN_FC_F32 && p->fc_math_mode != FRCNN_FC_F32X6T && p->fc_math_mode != FRCNN_FC_F32X3T) return FRCNN_EINVAL;
-    if ((p->roi_op != FRCNN_ROI_POOL && p->roi_op != FRCNN_ROI_ALIGN) || p->roi_sampling_ratio > 2) return FRCNN_EINVAL;
-    if (p->winograd_tile_rows != 0 && p->winograd_tile_rows != 64 && p->winograd_tile_rows != 128) return FRCNN_EINVAL;
-    if (p->x6_gemm_tiles < 0 || p->x6_gemm_tiles > 2) return FRCNN_EINVAL;
-    if ((p->winograd_x3_mask & ~p->winograd_x6_mask) != 0) return FRCNN_EINVAL;     // a subset of the x6 table
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
     const bool wino = p->math_mode == FRCNN_MATH_F32_WINOGRAD;
     if (p->winograd_x6_mask != 0 && (!wino || (p->winograd_x6_mask & ~0x3FFE) != 0)) return FRCNN_EINVAL;
@@ -1345,7 +1390,7 @@ int frcnn_vgg16_forward(frcnn_ctx* c, const frcnn_vgg16_weights* w, const frcnn_
             if (pool_of[li]) { eh /= 2; ew /= 2; }
             if ((f3 || t3) && (f3 || winograd_output_emits_cmax(co_of[li], efl))) want += ((size_t)eh * ew + 63) & ~(size_t)63;
         }
-        if (want > 2 * c->x3f_cmax_bytes / sizeof(float)) return FRCNN_EINVAL;      // (< 0.75 H W floats for any table: cannot happen)
+        if (want > 2 * x3f_cmax_bytes(c) / sizeof(float)) return FRCNN_EINVAL;     // (< 0.75 H W floats for any table: cannot happen)
         cmax_cleared = want;
         if (want) FRCNN_HIP_TRY(hipMemsetAsync(x3f_cmax_buffer(c, 1), 0, cmax_cleared * sizeof(float), s));
     }
@@ -1386,7 +1431,6 @@ int frcnn_vgg16_forward(frcnn_ctx* c, const frcnn_vgg16_weights* w, const frcnn_
         Scope _d(c, 0, s);
         return launch_conv3x3_nhwc(xin, wgt, bs, yout, hh, ww, ci, co, fl, c->conv_ws, c->conv_ws_bytes, s);
     };
-#define STEP(cls, call) do { Scope _sc(c, cls, s); rc = (call); } while (0); if (rc) return rc
 #define CONV(call) do { rc = (call); } while (0); if (rc) return rc
 
     // stage 1: feature extractor (models/vgg16.py:76-96)
@@ -1415,21 +1459,7 @@ int frcnn_vgg16_forward(frcnn_ctx* c, const frcnn_vgg16_weights* w, const frcnn_
 
     // stage 2: RPN (models/rpn.py:88-153)
     CONV(conv3(c->fm, w->rpn_conv_w, w->rpn_conv_b, c->rpn_trunk, fh, fw, 512, 512, R));
-    STEP(2, launch_linear(c->rpn_trunk, 512, w->rpn_head_w, w->rpn_head_b, c->rpn_head, 128, fh * fw, 45, 512,
-                          0u, c->lin_ws, c->lin_ws_bytes, s));
-    const float* amap = d_anchor_map;
-    const float* vmap = d_valid_map;
-    if (!amap || !vmap) {
-        if (c->anc_h != H || c->anc_w != W || c->anc_fh != fh || c->anc_fw != fw) {
-            STEP(5, launch_anchors(H, W, fh, fw, 16, c->anchor_map, c->valid_map, s));
-            c->anc_h = H; c->anc_w = W; c->anc_fh = fh; c->anc_fw = fw;
-        }
-        amap = c->anchor_map; vmap = c->valid_map;
-    }
-    FRCNN_HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), s));
-    STEP(3, launch_rpn_proposals(c->ps, c->rpn_head, 128, amap, p->allow_edge_proposals ? nullptr : vmap, fh, fw,
-                                 H, W, p->pre_nms, p->post_nms, p->rpn_nms_threshold, p->min_side, c->scores,
-                                 c->sorted_idx, d_props, d_counts, s));
+    CONV(run_rpn_after_trunk(c, w->rpn_head_w, w->rpn_head_b, p, H, W, fh, fw, 512, d_anchor_map, d_valid_map, d_props, d_counts, s));
 
     // stage 3: detector (models/detector.py:65-80, models/vgg16.py:129-133)
     const int R_ = p->post_nms;
@@ -1482,34 +1512,24 @@ int frcnn_vgg16_forward(frcnn_ctx* c, const frcnn_vgg16_weights* w, const frcnn_
                                 c->lin_ws, c->lin_ws_bytes, s, fc_tiles));
     } else
     {
-        if (p->roi_op == FRCNN_ROI_ALIGN) {
-            STEP(4, launch_roi_align(c->fm, fh, fw, 512, d_props, d_counts + 2, R_, 7, 1.0f / 16.0f, p->roi_sampling_ratio, 0, c->roi_out, s));
-        } else {
-            STEP(4, launch_roi_pool(c->fm, fh, fw, 512, d_props, d_counts + 2, R_, 7, 1.0f / 16.0f, c->roi_out, s));
-        }
+        CONV(run_roi_f32(c, p, fh, fw, 512, d_props, d_counts, c->roi_out, s));
         STEP(2, launch_linear(c->roi_out, 49 * 512, w->fc1_w, w->fc1_b, c->fc1_out, 4096, R_, 4096, 49 * 512, R,
                               c->lin_ws, c->lin_ws_bytes, s));
         STEP(2, launch_linear(c->fc1_out, 4096, w->fc2_w, w->fc2_b, c->fc2_out, 4096, R_, 4096, 4096, R,
                               c->lin_ws, c->lin_ws_bytes, s));
     }
-    const int ncls = w->num_classes, nd = (ncls - 1) * 4;
-    const int hld = cdiv(ncls + nd, 128) * 128;                  // row count of the stacked classifier + regressor operand (zero padded)
-    c->last_head_ld = hld;
-    STEP(2, launch_linear(c->fc2_out, 4096, w->head_w, w->head_b, c->head_logits, hld, R_, ncls + nd, 4096, 0u,
-                          c->lin_ws, c->lin_ws_bytes, s));
-    STEP(5, launch_head_finish(c->head_logits, hld, R_, ncls, nd, d_classes, d_deltas, s));
-#undef STEP
 #undef CONV
-    return FRCNN_OK;
+    return run_detector_heads(c, w->head_w, w->head_b, w->num_classes, 4096, R_, d_classes, d_deltas, s);
 }
 
 // ---- fused ResNet forward ----------------------------------------------------------------------
 namespace {
-// One 1x1 convolution (stride 1 or 2) of a bottleneck as an f32x6 GEMM: y[N Ho Wo][cout] = act(bias + residual + x_pixels . w^T).
-// The activation records live in the ctx's rx_rec scratch (grown on demand: hipMalloc synchronises, first image of a shape only).
-// (ksize 3: the 3x3 / padding-1 form over im2col records, K = 9 cin -- layer4.0.conv2's stride-2 convolution)
-int run_conv1x1_x6(frcnn_ctx* c, const float* x, const void* wrec, const float* bias, const float* residual, float* y, int N, int h,
-                   int w, int cin, int cout, int stride, unsigned flags, int cls, hipStream_t s, int ksize = 1)
+// The front the two split-operand convolutions below share: the argument check, the GEMM's shape -- M output pixels (Mp: padded to whole
+// row tiles) by cout (Np: padded to whole column tiles) over K -- and the record and split-K scratch of that shape in the arithmetic
+// whose two size functions the caller passes (grown on demand: the allocation synchronises, first image of a shape only).
+struct Conv1x1Gemm { int M, Mp, Np, K; };
+int conv1x1_front(frcnn_ctx* c, int N, int h, int w, int cin, int cout, int stride, int ksize, size_t (*record_bytes)(int, int),
+                  size_t (*workspace_bytes)(int, int, int, int), hipStream_t s, Conv1x1Gemm* g)
 {
     if (cin % 16 != 0 || cout % 4 != 0 || (ksize != 1 && ksize != 3)) return FRCNN_EINVAL;
     const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
@@ -1517,26 +1537,25 @@ int run_conv1x1_x6(frcnn_ctx* c, const float* x, const void* wrec, const float* 
     const long long rows = (long long)N * ho * wo;
     if (rows > 0x7fffffffLL / 8) return FRCNN_EINVAL;
     const int M = (int)rows;
-    const int Mp = cdiv(M, gemm_x6t_row_tile(M)) * gemm_x6t_row_tile(M), Np = cdiv(cout, gemm_x6t_col_tile(cout)) * gemm_x6t_col_tile(cout);
-    const size_t need = x6t_record_bytes(Mp, K), gneed = gemm_x6t_workspace_bytes(M, cout, K, 1);
-    if (need > c->rx_rec_bytes) {
-        if (c->rx_rec) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->rx_rec); c->rx_rec = nullptr; c->rx_rec_bytes = 0; }
-        hipError_t e = hipMalloc(&c->rx_rec, need);
-        if (e != hipSuccess) { set_hip_error(e); c->rx_rec = nullptr; return FRCNN_ENOMEM; }
-        c->rx_rec_bytes = need;
-    }
-    if (gneed > c->rx_ws_bytes) {
-        if (c->rx_ws) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->rx_ws); c->rx_ws = nullptr; c->rx_ws_bytes = 0; }
-        hipError_t e = hipMalloc(&c->rx_ws, gneed);
-        if (e != hipSuccess) { set_hip_error(e); c->rx_ws = nullptr; return FRCNN_ENOMEM; }
-        c->rx_ws_bytes = gneed;
-    }
-    int rc;
-    { Scope _t(c, 8, s); rc = ksize == 3 ? launch_split_patches3x3_x6t(x, c->rx_rec, N, h, w, cin, stride, Mp, s)
-                                        : launch_split_pixels_x6t(x, c->rx_rec, N, h, w, cin, stride, Mp, s); }
+    *g = {M, cdiv(M, gemm_x6t_row_tile(M)) * gemm_x6t_row_tile(M), cdiv(cout, gemm_x6t_col_tile(cout)) * gemm_x6t_col_tile(cout), K};
+    const int rc = c->rx_rec.reserve(record_bytes(g->Mp, K), s, false);
+    return rc ? rc : c->rx_ws.reserve(workspace_bytes(M, cout, K, 1), s, false);
+}
+
+// One 1x1 convolution (stride 1 or 2) of a bottleneck as an f32x6 GEMM: y[N Ho Wo][cout] = act(bias + residual + x_pixels . w^T).
+// The activation records live in the ctx's rx_rec scratch.
+// (ksize 3: the 3x3 / padding-1 form over im2col records, K = 9 cin -- layer4.0.conv2's stride-2 convolution)
+int run_conv1x1_x6(frcnn_ctx* c, const float* x, const void* wrec, const float* bias, const float* residual, float* y, int N, int h,
+                   int w, int cin, int cout, int stride, unsigned flags, int cls, hipStream_t s, int ksize = 1)
+{
+    Conv1x1Gemm g;
+    int rc = conv1x1_front(c, N, h, w, cin, cout, stride, ksize, x6t_record_bytes, gemm_x6t_workspace_bytes, s, &g);
+    if (rc) return rc;
+    { Scope _t(c, 8, s); rc = ksize == 3 ? launch_split_patches3x3_x6t(x, c->rx_rec.p, N, h, w, cin, stride, g.Mp, s)
+                                        : launch_split_pixels_x6t(x, c->rx_rec.p, N, h, w, cin, stride, g.Mp, s); }
     if (rc) return rc;
     Scope _g(c, cls, s);
-    return launch_gemm_x6t(c->rx_rec, Mp, 0, wrec, Np, 0, bias, residual, y, cout, 0, M, cout, K, 1, flags, c->rx_ws, c->rx_ws_bytes, s);
+    return launch_gemm_x6t(c->rx_rec.p, g.Mp, 0, wrec, g.Np, 0, bias, residual, y, cout, 0, g.M, cout, g.K, 1, flags, c->rx_ws.p, c->rx_ws.bytes, s);
 }
 
 // The same convolution in the f32x3 arithmetic (csrc/gemm_x3t.hip): wblob = frcnn_pack_rows_x3t of the [cout][K] matrix (records, then
@@ -1544,74 +1563,45 @@ int run_conv1x1_x6(frcnn_ctx* c, const float* x, const void* wrec, const float* 
 int run_conv1x1_x3(frcnn_ctx* c, const float* x, const void* wblob, const float* bias, const float* residual, float* y, int N, int h,
                    int w, int cin, int cout, int stride, unsigned flags, int cls, hipStream_t s, int ksize = 1)
 {
-    if (cin % 16 != 0 || cout % 4 != 0 || (ksize != 1 && ksize != 3)) return FRCNN_EINVAL;
-    const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
-    const int K = ksize == 3 ? 9 * cin : cin;
-    const long long rows = (long long)N * ho * wo;
-    if (rows > 0x7fffffffLL / 8) return FRCNN_EINVAL;
-    const int M = (int)rows;
-    const int Mp = cdiv(M, gemm_x6t_row_tile(M)) * gemm_x6t_row_tile(M), Np = cdiv(cout, gemm_x6t_col_tile(cout)) * gemm_x6t_col_tile(cout);
-    const size_t need = x3t_record_bytes(Mp, K), gneed = gemm_x3t_workspace_bytes(M, cout, K, 1);
-    const size_t aneed = (size_t)Mp + (size_t)N * h * w;
-    if (need > c->rx_rec_bytes) {
-        if (c->rx_rec) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->rx_rec); c->rx_rec = nullptr; c->rx_rec_bytes = 0; }
-        hipError_t e = hipMalloc(&c->rx_rec, need);
-        if (e != hipSuccess) { set_hip_error(e); c->rx_rec = nullptr; return FRCNN_ENOMEM; }
-        c->rx_rec_bytes = need;
-    }
-    if (gneed > c->rx_ws_bytes) {
-        if (c->rx_ws) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->rx_ws); c->rx_ws = nullptr; c->rx_ws_bytes = 0; }
-        hipError_t e = hipMalloc(&c->rx_ws, gneed);
-        if (e != hipSuccess) { set_hip_error(e); c->rx_ws = nullptr; return FRCNN_ENOMEM; }
-        c->rx_ws_bytes = gneed;
-    }
-    if (aneed > c->rx_aux_floats) {
-        if (c->rx_aux) { FRCNN_HIP_TRY(hipStreamSynchronize(s)); (void)hipFree(c->rx_aux); c->rx_aux = nullptr; c->rx_aux_floats = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->rx_aux), aneed * sizeof(float));
-        if (e != hipSuccess) { set_hip_error(e); c->rx_aux = nullptr; return FRCNN_ENOMEM; }
-        c->rx_aux_floats = aneed;
-    }
-    float* ainv = c->rx_aux;
-    float* cmax = c->rx_aux + Mp;
-    int rc;
+    Conv1x1Gemm g;
+    int rc = conv1x1_front(c, N, h, w, cin, cout, stride, ksize, x3t_record_bytes, gemm_x3t_workspace_bytes, s, &g);
+    if (!rc) rc = c->rx_aux.reserve(((size_t)g.Mp + (size_t)N * h * w) * sizeof(float), s, false);      // a scale per record row, a maximum per input pixel
+    if (rc) return rc;
+    const int M = g.M, Mp = g.Mp, Np = g.Np, K = g.K;
+    float* ainv = static_cast<float*>(c->rx_aux.p);
+    float* cmax = ainv + Mp;
     {
         Scope _t(c, 8, s);
         // (1x1: one launch that reduces the row maxima itself; the 3x3 patches take their scale from nine pixels' maxima: two launches)
         static const bool two_pass = frcnn_knob("FRCNN_SPLIT_TWO_PASS") != nullptr;      // experiments / the bit-identity test
         rc = (ksize == 3 || two_pass) ? launch_pixel_absmax(x, cmax, (long long)N * h * w, cin, s) : FRCNN_OK;
-        if (!rc) rc = ksize == 3 ? launch_split_patches3x3_x3t(x, cmax, c->rx_rec, ainv, N, h, w, cin, stride, Mp, s)
-                                 : launch_split_pixels_x3t(x, two_pass ? cmax : nullptr, c->rx_rec, ainv, N, h, w, cin, stride, Mp, s);
+        if (!rc) rc = ksize == 3 ? launch_split_patches3x3_x3t(x, cmax, c->rx_rec.p, ainv, N, h, w, cin, stride, Mp, s)
+                                 : launch_split_pixels_x3t(x, two_pass ? cmax : nullptr, c->rx_rec.p, ainv, N, h, w, cin, stride, Mp, s);
     }
     if (rc) return rc;
     const float* winv = reinterpret_cast<const float*>(static_cast<const unsigned char*>(wblob) + x3t_record_bytes(Np, K));
     Scope _g(c, cls, s);
-    return launch_gemm_x3t(c->rx_rec, ainv, Mp, 0, 0, wblob, winv, Np, 0, 0, bias, residual, y, cout, 0, M, cout, K, 1, flags, c->rx_ws,
-                           c->rx_ws_bytes, s);
+    return launch_gemm_x3t(c->rx_rec.p, ainv, Mp, 0, 0, wblob, winv, Np, 0, 0, bias, residual, y, cout, 0, M, cout, K, 1, flags, c->rx_ws.p,
+                           c->rx_ws.bytes, s);
 }
 
 // the next zeroed maximum slot of this context's current pass (GX_SLOTS floats, zeroed by gx_begin)
 static constexpr int GX_SLOTS = 512;
 int gx_begin(frcnn_ctx* c, hipStream_t s)
 {
-    if (!c->gx_max) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->gx_max), GX_SLOTS * sizeof(float));
-        if (e != hipSuccess) { set_hip_error(e); c->gx_max = nullptr; return FRCNN_ENOMEM; }
-    }
-    if (!c->gx_cnt) {                                              // zeroed ONCE: the last block of a tile leaves its counter at zero again
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->gx_cnt), GX_TILE_COUNTERS * sizeof(unsigned));
-        if (e != hipSuccess) { set_hip_error(e); c->gx_cnt = nullptr; return FRCNN_ENOMEM; }
-        FRCNN_HIP_TRY(hipMemsetAsync(c->gx_cnt, 0, GX_TILE_COUNTERS * sizeof(unsigned), s));
-    }
-    FRCNN_HIP_TRY(hipMemsetAsync(c->gx_max, 0, GX_SLOTS * sizeof(float), s));
+    int rc = c->gx_max.reserve(GX_SLOTS * sizeof(float), s, false);
+    // zeroed ONCE, when it is created: the last block of a tile leaves its counter at zero again
+    if (!rc) rc = c->gx_cnt.reserve(GX_TILE_COUNTERS * sizeof(unsigned), s, true);
+    if (rc) return rc;
+    FRCNN_HIP_TRY(hipMemsetAsync(c->gx_max.p, 0, GX_SLOTS * sizeof(float), s));
     c->gx_next = 0;
     c->gx_x = nullptr;
     return FRCNN_OK;
 }
-int gx_slot(frcnn_ctx* c, hipStream_t s, float** out)
+int gx_slot(frcnn_ctx* c, float** out)
 {
-    if (!c->gx_max || c->gx_next >= GX_SLOTS) return FRCNN_EINVAL;
-    (void)s;
-    *out = c->gx_max + c->gx_next++;
+    if (!c->gx_max.p || c->gx_next >= GX_SLOTS) return FRCNN_EINVAL;
+    *out = static_cast<float*>(c->gx_max.p) + c->gx_next++;
     return FRCNN_OK;
 }
 
@@ -1636,31 +1626,31 @@ int run_bottleneck(frcnn_ctx* c, const frcnn_bottleneck_weights& b, int N, int& 
     const int ho = (h + 2 - 3) / b.stride + 1, wo = (w + 2 - 3) / b.stride + 1;
     const size_t need1 = (size_t)N * h * w * b.width, need2 = (size_t)N * ho * wo * b.cout;
     if (need1 > c->res_buf_floats || need2 > c->res_buf_floats) return FRCNN_EINVAL;
-#define RSTEP(call) do { Scope _sc(c, cls_conv, s); rc = (call); } while (0); if (rc) return rc
     if (b.g3 != 0) {
         // (a split-operand block belongs to the f32_winograd table: math mode "f32" is the strict exact-f32 mode -- ADVICE r4)
         if (b.x6_mask != 0 || !b.wmax || !wino) return FRCNN_EINVAL;
         float *m1, *m2, *m3;
         if (!c->gx_x) {                                          // the block input came from a kernel that leaves no maximum behind
             float* mx;
-            if ((rc = gx_slot(c, s, &mx))) return rc;
-            RSTEP(launch_tensor_absmax(X, (long long)N * h * w * b.cin, mx, s));
+            if ((rc = gx_slot(c, &mx))) return rc;
+            STEP(cls_conv, launch_tensor_absmax(X, (long long)N * h * w * b.cin, mx, s));
             c->gx_x = mx;
         }
-        if ((rc = gx_slot(c, s, &m1)) || (rc = gx_slot(c, s, &m2)) || (rc = gx_slot(c, s, &m3))) return rc;
+        if ((rc = gx_slot(c, &m1)) || (rc = gx_slot(c, &m2)) || (rc = gx_slot(c, &m3))) return rc;
         const bool ws_ = b.g3 == 2;                              // the packs are pre-split images (frcnn_pack_conv_x3g_weights)
-        const GatherX3 g1{c->gx_x, b.wmax + 0, m1, c->gx_cnt, ws_, ws_}, g2{m1, b.wmax + 1, m2, c->gx_cnt, ws_, ws_}, g3{m2, b.wmax + 2, m3, c->gx_cnt, ws_, ws_}, gd{c->gx_x, b.wmax + 3, nullptr, c->gx_cnt, ws_, ws_};      // (trusted: every maximum of this chain is a producer's or tensor_absmax_kernel's)
+        unsigned* const cnt = static_cast<unsigned*>(c->gx_cnt.p);
+        const GatherX3 g1{c->gx_x, b.wmax + 0, m1, cnt, ws_, ws_}, g2{m1, b.wmax + 1, m2, cnt, ws_, ws_}, g3{m2, b.wmax + 2, m3, cnt, ws_, ws_}, gd{c->gx_x, b.wmax + 3, nullptr, cnt, ws_, ws_};      // (trusted: every maximum of this chain is a producer's or tensor_absmax_kernel's)
         const int X3 = FRCNN_CONV_F32X3G;
-        RSTEP(launch_conv_gather(X, b.w1, b.b1, nullptr, T1, N, h, w, b.cin, b.width, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g1));
-        RSTEP(launch_conv_gather(T1, b.w2, b.b2, nullptr, T2, N, h, w, b.width, b.width, 3, b.stride, 1, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g2));
+        STEP(cls_conv, launch_conv_gather(X, b.w1, b.b1, nullptr, T1, N, h, w, b.cin, b.width, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g1));
+        STEP(cls_conv, launch_conv_gather(T1, b.w2, b.b2, nullptr, T2, N, h, w, b.width, b.width, 3, b.stride, 1, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g2));
         const float* identity = X;
         if (b.wd) {
-            RSTEP(launch_conv_gather(X, b.wd, b.bd, nullptr, ID, N, h, w, b.cin, b.cout, 1, b.stride, 0, 0u, c->conv_ws, c->conv_ws_bytes, s, X3, &gd));
+            STEP(cls_conv, launch_conv_gather(X, b.wd, b.bd, nullptr, ID, N, h, w, b.cin, b.cout, 1, b.stride, 0, 0u, c->conv_ws, c->conv_ws_bytes, s, X3, &gd));
             identity = ID;
         } else if (b.cin != b.cout || b.stride != 1) {
             return FRCNN_EINVAL;
         }
-        RSTEP(launch_conv_gather(T2, b.w3, b.b3, identity, OUT, N, ho, wo, b.width, b.cout, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g3));
+        STEP(cls_conv, launch_conv_gather(T2, b.w3, b.b3, identity, OUT, N, ho, wo, b.width, b.cout, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s, X3, &g3));
         c->gx_x = m3;
         h = ho; w = wo;
         *out_idx = f[3];
@@ -1674,7 +1664,7 @@ int run_bottleneck(frcnn_ctx* c, const frcnn_bottleneck_weights& b, int N, int& 
                                           : run_conv1x1_x6(c, X, b.w1, b.b1, nullptr, T1, N, h, w, b.cin, b.width, 1, R, 9, s);
         if (rc) return rc;
     } else {
-        RSTEP(launch_conv_gather(X, b.w1, b.b1, nullptr, T1, N, h, w, b.cin, b.width, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s));
+        STEP(cls_conv, launch_conv_gather(X, b.w1, b.b1, nullptr, T1, N, h, w, b.cin, b.width, 1, 1, 0, R, c->conv_ws, c->conv_ws_bytes, s));
     }
     if (b.x6_mask & FRCNN_X6_CONV2) {
         // the 3x3 on the bf16 pipe: stride 1 = an x6 Winograd layer over the block's N maps, stride 2 = an im2col GEMM (K = 9 width)
@@ -1694,12 +1684,12 @@ int run_bottleneck(frcnn_ctx* c, const frcnn_bottleneck_weights& b, int N, int& 
     } else if (b.stride == 1 && pack_maps == 1 && b.width % 64 == 0) {
         // direct exact-f32 3x3 (math mode "f32"): one launch per image of the batch
         for (int i = 0; i < N; ++i) {
-            RSTEP(launch_conv3x3_nhwc(T1 + (size_t)i * h * w * b.width, b.w2, b.b2, T2 + (size_t)i * h * w * b.width, h, w, b.width, b.width, R,
-                                      c->conv_ws, c->conv_ws_bytes, s));
+            STEP(cls_conv, launch_conv3x3_nhwc(T1 + (size_t)i * h * w * b.width, b.w2, b.b2, T2 + (size_t)i * h * w * b.width, h, w, b.width, b.width, R,
+                                               c->conv_ws, c->conv_ws_bytes, s));
         }
     } else {
-        RSTEP(launch_conv_gather(T1, b.w2, b.b2, nullptr, T2, N, h, w, b.width, b.width, 3, b.stride, 1, R,
-                                 c->conv_ws, c->conv_ws_bytes, s));
+        STEP(cls_conv, launch_conv_gather(T1, b.w2, b.b2, nullptr, T2, N, h, w, b.width, b.width, 3, b.stride, 1, R,
+                                          c->conv_ws, c->conv_ws_bytes, s));
     }
     const float* identity = X;
     if (b.wd) {
@@ -1708,8 +1698,8 @@ int run_bottleneck(frcnn_ctx* c, const frcnn_bottleneck_weights& b, int N, int& 
                                              : run_conv1x1_x6(c, X, b.wd, b.bd, nullptr, ID, N, h, w, b.cin, b.cout, b.stride, 0u, 9, s);
             if (rc) return rc;
         } else {
-            RSTEP(launch_conv_gather(X, b.wd, b.bd, nullptr, ID, N, h, w, b.cin, b.cout, 1, b.stride, 0, 0u,
-                                     c->conv_ws, c->conv_ws_bytes, s));
+            STEP(cls_conv, launch_conv_gather(X, b.wd, b.bd, nullptr, ID, N, h, w, b.cin, b.cout, 1, b.stride, 0, 0u,
+                                              c->conv_ws, c->conv_ws_bytes, s));
         }
         identity = ID;
     } else if (b.cin != b.cout || b.stride != 1) {
@@ -1720,10 +1710,9 @@ int run_bottleneck(frcnn_ctx* c, const frcnn_bottleneck_weights& b, int N, int& 
                                           : run_conv1x1_x6(c, T2, b.w3, b.b3, identity, OUT, N, ho, wo, b.width, b.cout, 1, R, 9, s);
         if (rc) return rc;
     } else {
-        RSTEP(launch_conv_gather(T2, b.w3, b.b3, identity, OUT, N, ho, wo, b.width, b.cout, 1, 1, 0, R,
-                                 c->conv_ws, c->conv_ws_bytes, s));
+        STEP(cls_conv, launch_conv_gather(T2, b.w3, b.b3, identity, OUT, N, ho, wo, b.width, b.cout, 1, 1, 0, R,
+                                          c->conv_ws, c->conv_ws_bytes, s));
     }
-#undef RSTEP
     h = ho; w = wo;
     *out_idx = f[3];
     return FRCNN_OK;
@@ -1746,14 +1735,34 @@ int resnet_check_weights(const frcnn_resnet_weights* w, bool with_heads)
     return FRCNN_OK;
 }
 
-int resnet_check_params(const frcnn_forward_params* p)
+// What the five ResNet entry points check after their own pointers, in this order, and the Winograd scratch.  `needs`: what the entry
+// point uses -- an image of H x W, the proposal limits, the class count, the RPN / detector head weights, the three-launch Winograd layers.
+enum : unsigned { RN_IMAGE = 1, RN_LIMITS = 2, RN_CLASSES = 4, RN_HEADS = 8, RN_WINO = 16 };
+int resnet_prologue(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forward_params* p, int H, int W, unsigned needs, hipStream_t s)
 {
-    if ((p->winograd_x3_mask & ~p->winograd_x6_mask) != 0) return FRCNN_EINVAL;    // (only the RPN trunk bit exists for ResNet)
-    if (p->math_mode != FRCNN_MATH_F32 && p->math_mode != FRCNN_MATH_F32_WINOGRAD) return FRCNN_EUNSUPPORTED;   // no f32x6 ResNet path
-    if ((p->roi_op != FRCNN_ROI_POOL && p->roi_op != FRCNN_ROI_ALIGN) || p->roi_sampling_ratio > 2) return FRCNN_EINVAL;
-    if (p->conv_blocks_target < 0) return FRCNN_EINVAL;
-    if (p->winograd_tile_rows != 0 && p->winograd_tile_rows != 64 && p->winograd_tile_rows != 128) return FRCNN_EINVAL;
-    if (p->x6_gemm_tiles < 0 || p->x6_gemm_tiles > 2) return FRCNN_EINVAL;
+    if ((needs & RN_IMAGE) && (H < 32 || W < 32 || H > c->max_h || W > c->max_w)) return FRCNN_EINVAL;
+    if ((needs & RN_LIMITS) && (p->post_nms < 1 || p->post_nms > c->max_rois || p->pre_nms < 1 || p->pre_nms > c->pre_cap)) return FRCNN_EINVAL;
+    if ((needs & RN_CLASSES) && (w->num_classes < 2 || w->num_classes > FRCNN_MAX_NUM_CLASSES)) return FRCNN_EUNSUPPORTED;
+    int rc = check_forward_params(p, FRCNN_EUNSUPPORTED);
+    if (!rc) rc = resnet_check_weights(w, (needs & RN_HEADS) != 0);
+    if (!rc && (needs & RN_WINO) && p->math_mode == FRCNN_MATH_F32_WINOGRAD) rc = ensure_wino_ws(c, s);
+    return rc;
+}
+
+// The feature map of an H x W image handed in by the caller: its shape follows from the image's (conv1 7x7/2 pad 3, maxpool 3x3/2 pad 1,
+// layer2 and layer3 stride 2) and its channels from layer3's last block; checked against the ctx and staged into c->fm.
+int resnet_stage_features(frcnn_ctx* c, const frcnn_resnet_weights* w, const float* d_feature_map, int H, int W, int* fh_out, int* fw_out,
+                          int* c_out, hipStream_t s)
+{
+    int fh = (H + 6 - 7) / 2 + 1, fw = (W + 6 - 7) / 2 + 1;
+    fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1;
+    for (int i = 0; i < 2; ++i) { fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1; }
+    const int nb3 = w->n_blocks[0] + w->n_blocks[1] + w->n_blocks[2];
+    const int C = w->blocks[nb3 - 1].cout;
+    if (fh > c->max_fh || fw > c->max_fw || C > 1024 || C % 64) return FRCNN_EINVAL;
+    if (d_feature_map != c->fm)
+        FRCNN_HIP_TRY(hipMemcpyAsync(c->fm, d_feature_map, (size_t)fh * fw * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    *fh_out = fh; *fw_out = fw; *c_out = C;
     return FRCNN_OK;
 }
 
@@ -1801,7 +1810,6 @@ int resnet_rpn_roi(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forw
 {
     const bool wino = p->math_mode == FRCNN_MATH_F32_WINOGRAD;
     int rc;
-#define STEP(cls, call) do { Scope _sc(c, cls, s); rc = (call); } while (0); if (rc) return rc
     c->last_fh = fh; c->last_fw = fw; c->last_pre = p->pre_nms; c->last_post = p->post_nms; c->last_c = C;
     if (p->winograd_x6_mask != 0 && (!wino || p->winograd_x6_mask != (1 << FRCNN_X6_RPN_TRUNK_BIT))) return FRCNN_EINVAL;
     if (wino && p->winograd_x6_mask) {
@@ -1815,30 +1823,9 @@ int resnet_rpn_roi(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forw
         STEP(0, launch_conv3x3_nhwc(c->fm, w->rpn_conv_w, w->rpn_conv_b, c->rpn_trunk, fh, fw, C, C, FRCNN_RELU,
                                     c->conv_ws, c->conv_ws_bytes, s));
     }
-    STEP(2, launch_linear(c->rpn_trunk, C, w->rpn_head_w, w->rpn_head_b, c->rpn_head, 128, fh * fw, 45, C, 0u,
-                          c->lin_ws, c->lin_ws_bytes, s));
-    const float* amap = d_anchor_map;
-    const float* vmap = d_valid_map;
-    if (!amap || !vmap) {
-        if (c->anc_h != H || c->anc_w != W || c->anc_fh != fh || c->anc_fw != fw) {
-            STEP(5, launch_anchors(H, W, fh, fw, 16, c->anchor_map, c->valid_map, s));
-            c->anc_h = H; c->anc_w = W; c->anc_fh = fh; c->anc_fw = fw;
-        }
-        amap = c->anchor_map; vmap = c->valid_map;
-    }
-    FRCNN_HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(int32_t), s));
-    STEP(3, launch_rpn_proposals(c->ps, c->rpn_head, 128, amap, p->allow_edge_proposals ? nullptr : vmap, fh, fw,
-                                 H, W, p->pre_nms, p->post_nms, p->rpn_nms_threshold, p->min_side, c->scores,
-                                 c->sorted_idx, d_props, d_counts, s));
-
-    const int R_ = p->post_nms;
-    if (p->roi_op == FRCNN_ROI_ALIGN) {
-        STEP(4, launch_roi_align(c->fm, fh, fw, C, d_props, d_counts + 2, R_, 7, 1.0f / 16.0f, p->roi_sampling_ratio, 0, roi_dst, s));
-    } else {
-        STEP(4, launch_roi_pool(c->fm, fh, fw, C, d_props, d_counts + 2, R_, 7, 1.0f / 16.0f, roi_dst, s));
-    }
-#undef STEP
-    return FRCNN_OK;
+    rc = run_rpn_after_trunk(c, w->rpn_head_w, w->rpn_head_b, p, H, W, fh, fw, C, d_anchor_map, d_valid_map, d_props, d_counts, s);
+    if (rc) return rc;
+    return run_roi_f32(c, p, fh, fw, C, d_props, d_counts, roi_dst, s);
 }
 
 int resnet_head(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forward_params* p, float* roi_in, int n_rois, float* d_classes,
@@ -1848,7 +1835,6 @@ int resnet_head(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forward
     int rc;
     int bi = w->n_blocks[0] + w->n_blocks[1] + w->n_blocks[2];
     const int R_ = n_rois;
-#define STEP(cls, call) do { Scope _sc(c, cls, s); rc = (call); } while (0); if (rc) return rc
     // layer4 reads its input from the pooled RoIs: staged as res_buf "cur" by pointer swap
     float* saved = c->res_buf[0];
     c->res_buf[0] = roi_in;
@@ -1870,14 +1856,7 @@ int resnet_head(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forward
     if (V > 4096) return FRCNN_EINVAL;
     c->last_vec = V;
     STEP(5, launch_spatial_mean(head_in, c->fc2_out, R_, h, wd, V, s));
-    const int ncls = w->num_classes, nd = (ncls - 1) * 4;
-    const int hld = cdiv(ncls + nd, 128) * 128;
-    c->last_head_ld = hld;
-    STEP(2, launch_linear(c->fc2_out, V, w->head_w, w->head_b, c->head_logits, hld, R_, ncls + nd, V, 0u,
-                          c->lin_ws, c->lin_ws_bytes, s));
-    STEP(5, launch_head_finish(c->head_logits, hld, R_, ncls, nd, d_classes, d_deltas, s));
-#undef STEP
-    return FRCNN_OK;
+    return run_detector_heads(c, w->head_w, w->head_b, w->num_classes, V, R_, d_classes, d_deltas, s);
 }
 
 int resnet_tail(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_forward_params* p, int H, int W, int fh, int fw, int C,
@@ -1896,16 +1875,10 @@ int frcnn_resnet_forward(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcn
                          int32_t* d_counts, void* stream)
 {
     if (!c || !w || !p || !d_image || !d_props || !d_classes || !d_deltas || !d_counts) return FRCNN_EINVAL;
-    if (H < 32 || W < 32 || H > c->max_h || W > c->max_w) return FRCNN_EINVAL;
-    if (p->post_nms < 1 || p->post_nms > c->max_rois || p->pre_nms < 1 || p->pre_nms > c->pre_cap) return FRCNN_EINVAL;
-    if (w->num_classes < 2 || w->num_classes > FRCNN_MAX_NUM_CLASSES) return FRCNN_EUNSUPPORTED;
-    int rc = resnet_check_params(p);
-    if (rc) return rc;
-    rc = resnet_check_weights(w, true);
-    if (rc) return rc;
     hipStream_t s = as_stream(stream);
+    int rc = resnet_prologue(c, w, p, H, W, RN_IMAGE | RN_LIMITS | RN_CLASSES | RN_HEADS | RN_WINO, s);
+    if (rc) return rc;
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
-    if (p->math_mode == FRCNN_MATH_F32_WINOGRAD) { rc = ensure_wino_ws(c); if (rc) return rc; }
     int cur = 0, fh = 0, fw = 0, C = 0;
     rc = resnet_stage1(c, w, p, d_image, 1, H, W, &cur, &fh, &fw, &C, s);
     if (rc) return rc;
@@ -2032,13 +2005,11 @@ int frcnn_ctx_create_backbone(frcnn_ctx** out, int max_image_h, int max_image_w,
     const size_t stem = (size_t)((max_image_h + 1) / 2) * ((max_image_w + 1) / 2) * 64;
     c->res_buf_floats = stem * max_images;
     const size_t cws = (size_t)160 << 20;
-    const size_t total = 5 * align_up(c->res_buf_floats * 4, 256) + align_up(cws, 256);
-    hipError_t e = hipMalloc(&c->slab, total);
-    if (e != hipSuccess) { set_hip_error(e); delete c; return FRCNN_ENOMEM; }
-    c->slab_bytes = total;
-    unsigned char* q = static_cast<unsigned char*>(c->slab);
-    for (int i = 0; i < 5; ++i) { c->res_buf[i] = reinterpret_cast<float*>(q); q += align_up(c->res_buf_floats * 4, 256); }
-    c->conv_ws = q; c->conv_ws_bytes = cws;
+    const size_t rb = c->res_buf_floats * 4;
+    const int rc = carve_slab(c, {{(void**)&c->res_buf[0], rb}, {(void**)&c->res_buf[1], rb}, {(void**)&c->res_buf[2], rb}, {(void**)&c->res_buf[3], rb},
+                                  {(void**)&c->res_buf[4], rb}, {&c->conv_ws, cws}});
+    if (rc) { delete c; return rc; }
+    c->conv_ws_bytes = cws;
     *out = c;
     return FRCNN_OK;
 }
@@ -2047,12 +2018,10 @@ int frcnn_resnet_backbone(frcnn_ctx* c, const frcnn_resnet_weights* w, const frc
                           int n_images, int H, int W, float* d_features, void* stream)
 {
     if (!c || !w || !p || !d_images || !d_features || n_images < 1) return FRCNN_EINVAL;
-    if (H < 32 || W < 32 || H > c->max_h || W > c->max_w || n_images > (c->max_images > 0 ? c->max_images : 1)) return FRCNN_EINVAL;
-    int rc = resnet_check_params(p);
-    if (rc) return rc;
-    rc = resnet_check_weights(w, false);
-    if (rc) return rc;
+    if (n_images > (c->max_images > 0 ? c->max_images : 1)) return FRCNN_EINVAL;
     hipStream_t s = as_stream(stream);
+    int rc = resnet_prologue(c, w, p, H, W, RN_IMAGE, s);
+    if (rc) return rc;
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
     int cur = 0, fh = 0, fw = 0, C = 0;
     rc = resnet_stage1(c, w, p, d_images, n_images, H, W, &cur, &fh, &fw, &C, s);
@@ -2067,25 +2036,13 @@ int frcnn_resnet_forward_features(frcnn_ctx* c, const frcnn_resnet_weights* w, c
                                   int32_t* d_counts, void* stream)
 {
     if (!c || !w || !p || !d_feature_map || !d_props || !d_classes || !d_deltas || !d_counts) return FRCNN_EINVAL;
-    if (H < 32 || W < 32 || H > c->max_h || W > c->max_w) return FRCNN_EINVAL;
-    if (p->post_nms < 1 || p->post_nms > c->max_rois || p->pre_nms < 1 || p->pre_nms > c->pre_cap) return FRCNN_EINVAL;
-    if (w->num_classes < 2 || w->num_classes > FRCNN_MAX_NUM_CLASSES) return FRCNN_EUNSUPPORTED;
-    int rc = resnet_check_params(p);
-    if (rc) return rc;
-    rc = resnet_check_weights(w, true);
-    if (rc) return rc;
     hipStream_t s = as_stream(stream);
+    int rc = resnet_prologue(c, w, p, H, W, RN_IMAGE | RN_LIMITS | RN_CLASSES | RN_HEADS | RN_WINO, s);
+    if (rc) return rc;
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
-    if (p->math_mode == FRCNN_MATH_F32_WINOGRAD) { rc = ensure_wino_ws(c); if (rc) return rc; }
-    // the map's shape follows from the image's (conv1 7x7/2 pad 3, maxpool 3x3/2 pad 1, layer2 and layer3 stride 2)
-    int fh = (H + 6 - 7) / 2 + 1, fw = (W + 6 - 7) / 2 + 1;
-    fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1;
-    for (int i = 0; i < 2; ++i) { fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1; }
-    const int nb3 = w->n_blocks[0] + w->n_blocks[1] + w->n_blocks[2];
-    const int C = w->blocks[nb3 - 1].cout;
-    if (fh > c->max_fh || fw > c->max_fw || C > 1024 || C % 64) return FRCNN_EINVAL;
-    if (d_feature_map != c->fm)
-        FRCNN_HIP_TRY(hipMemcpyAsync(c->fm, d_feature_map, (size_t)fh * fw * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    int fh = 0, fw = 0, C = 0;
+    rc = resnet_stage_features(c, w, d_feature_map, H, W, &fh, &fw, &C, s);
+    if (rc) return rc;
     return resnet_tail(c, w, p, H, W, fh, fw, C, d_anchor_map, d_valid_map, d_props, d_classes, d_deltas, d_counts, s);
 }
 
@@ -2099,23 +2056,13 @@ int frcnn_resnet_rpn_roipool(frcnn_ctx* c, const frcnn_resnet_weights* w, const 
                              void* stream)
 {
     if (!c || !w || !p || !d_feature_map || !d_props || !d_counts || !d_roi_out) return FRCNN_EINVAL;
-    if (H < 32 || W < 32 || H > c->max_h || W > c->max_w) return FRCNN_EINVAL;
-    if (p->post_nms < 1 || p->post_nms > c->max_rois || p->pre_nms < 1 || p->pre_nms > c->pre_cap) return FRCNN_EINVAL;
-    int rc = resnet_check_params(p);
-    if (rc) return rc;
-    rc = resnet_check_weights(w, true);
-    if (rc) return rc;
     hipStream_t s = as_stream(stream);
+    int rc = resnet_prologue(c, w, p, H, W, RN_IMAGE | RN_LIMITS | RN_HEADS | RN_WINO, s);
+    if (rc) return rc;
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
-    if (p->math_mode == FRCNN_MATH_F32_WINOGRAD) { rc = ensure_wino_ws(c); if (rc) return rc; }
-    int fh = (H + 6 - 7) / 2 + 1, fw = (W + 6 - 7) / 2 + 1;
-    fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1;
-    for (int i = 0; i < 2; ++i) { fh = (fh + 2 - 3) / 2 + 1; fw = (fw + 2 - 3) / 2 + 1; }
-    const int nb3 = w->n_blocks[0] + w->n_blocks[1] + w->n_blocks[2];
-    const int C = w->blocks[nb3 - 1].cout;
-    if (fh > c->max_fh || fw > c->max_fw || C > 1024 || C % 64) return FRCNN_EINVAL;
-    if (d_feature_map != c->fm)
-        FRCNN_HIP_TRY(hipMemcpyAsync(c->fm, d_feature_map, (size_t)fh * fw * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    int fh = 0, fw = 0, C = 0;
+    rc = resnet_stage_features(c, w, d_feature_map, H, W, &fh, &fw, &C, s);
+    if (rc) return rc;
     return resnet_rpn_roi(c, w, p, H, W, fh, fw, C, d_anchor_map, d_valid_map, d_props, d_counts, d_roi_out, s);
 }
 
@@ -2129,22 +2076,14 @@ int frcnn_ctx_create_head(frcnn_ctx** out, int max_rois_total)
     if (!c) return FRCNN_ENOMEM;
     c->max_h = 0; c->max_w = 0; c->max_rois = 0; c->max_images = 0; c->max_head_rois = max_rois_total;
     const size_t n = (size_t)max_rois_total;
-    c->res_buf_floats = n * 49 * 512 > n * 16 * 2048 ? n * 49 * 512 : n * 16 * 2048;
+    c->res_buf_floats = std::max(n * 49 * 512, n * 16 * 2048);
     const size_t lin = linear_workspace_bytes(max_rois_total, FRCNN_HEAD_LD_MAX, 2048);
-    const size_t cws = (size_t)160 << 20;
-    struct Item { void** p; size_t bytes; };
-    Item items[] = {
+    const size_t cws = (size_t)160 << 20, rb = c->res_buf_floats * 4;
+    const int rc = carve_slab(c, {
         {(void**)&c->fc2_out, n * 4096 * 4}, {(void**)&c->head_logits, n * FRCNN_HEAD_LD_MAX * 4}, {(void**)&c->lin_ws, lin}, {(void**)&c->conv_ws, cws},
-        {(void**)&c->res_buf[0], c->res_buf_floats * 4}, {(void**)&c->res_buf[1], c->res_buf_floats * 4}, {(void**)&c->res_buf[2], c->res_buf_floats * 4},
-        {(void**)&c->res_buf[3], c->res_buf_floats * 4}, {(void**)&c->res_buf[4], c->res_buf_floats * 4},
-    };
-    size_t total = 0;
-    for (auto& it : items) total += align_up(it.bytes, 256);
-    hipError_t e = hipMalloc(&c->slab, total);
-    if (e != hipSuccess) { set_hip_error(e); delete c; return FRCNN_ENOMEM; }
-    c->slab_bytes = total;
-    unsigned char* q = static_cast<unsigned char*>(c->slab);
-    for (auto& it : items) { *it.p = q; q += align_up(it.bytes, 256); }
+        {(void**)&c->res_buf[0], rb}, {(void**)&c->res_buf[1], rb}, {(void**)&c->res_buf[2], rb}, {(void**)&c->res_buf[3], rb}, {(void**)&c->res_buf[4], rb},
+    });
+    if (rc) { delete c; return rc; }
     c->lin_ws_bytes = lin;
     c->conv_ws_bytes = cws;
     *out = c;
@@ -2156,15 +2095,12 @@ int frcnn_resnet_head(frcnn_ctx* c, const frcnn_resnet_weights* w, const frcnn_f
 {
     if (!c || !w || !p || !d_rois || !d_classes || !d_deltas) return FRCNN_EINVAL;
     if (n_rois < 1 || n_rois > c->max_head_rois) return FRCNN_EINVAL;
-    if (w->num_classes < 2 || w->num_classes > FRCNN_MAX_NUM_CLASSES) return FRCNN_EUNSUPPORTED;
-    int rc = resnet_check_params(p);
-    if (rc) return rc;
-    rc = resnet_check_weights(w, true);
-    if (rc) return rc;
     hipStream_t s = as_stream(stream);
+    const int rc = resnet_prologue(c, w, p, 0, 0, RN_CLASSES | RN_HEADS | RN_WINO, s);
+    if (rc) return rc;
     BlocksTargetScope target_scope(p->conv_blocks_target, p->winograd_tile_rows, p->x6_gemm_tiles);
-    if (p->math_mode == FRCNN_MATH_F32_WINOGRAD) { rc = ensure_wino_ws(c); if (rc) return rc; }
     return resnet_head(c, w, p, d_rois, n_rois, d_classes, d_deltas, s);
 }
 
 }  // extern "C"
+#undef STEP

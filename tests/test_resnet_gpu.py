@@ -400,6 +400,48 @@ def test_resnet50_x6_modes(r50, golden_dir):
         model.bottleneck_g3 = "some"
 
 
+@pytest.mark.parametrize("arith", ["f32x6", "f32x3"])
+def test_resnet50_context_scratch_grows_and_is_reused(r50, arith):
+    """The on-demand scratch of a live context.  With x6_conv1x1 = "all" and bottleneck_g3 = "off" (the g3 blocks would take layer1..3
+    back) the 1x1 convolutions of layer2, layer3 (layer1's 64-wide ones stay on the float32 kernel: x6_mask 0) and of the head size the
+    record, split-K and (f32x3) scale buffers of its ctx, which
+    grows them -- synchronise, free, allocate again -- whenever a layer needs more than every layer before it.  A new context does that
+    several times inside its first forward, layer by layer up to the head, whose 300 x 49 rows over K = 1024 are far more than the
+    backbone's 32 x 48 = 1536 rows over K = 256 at the larger image here: after the first forward the buffers do not change (asserted),
+    so the backbone of the later images runs in buffers much larger than the ones a new context gives it.  One context that sees
+    64 x 96, then 128 x 192, then 64 x 96 again must give each image the bits of a context that has only ever seen that image size."""
+    model, _ = r50
+    small = synthetic.image_rgb(71, 64, 96).unsqueeze(0).cuda()
+    large = synthetic.image_rgb(72, 128, 192).unsqueeze(0).cuda()
+    try:
+        _set_modes(model, **dict(R50_DEFAULTS, x6_conv1x1="all", x6_conv1x1_arith=arith, bottleneck_g3="off", winograd_x6_layers=("rpn_trunk",),
+                                 winograd_x3_layers=("rpn_trunk",) if arith == "f32x3" else ()))      # test_resnet50_x6_modes' all_x6 / all_x3
+        blocks = model._weights().blocks
+        masks = [blocks[i].x6_mask for i in range(16)]
+        print("%s: x6_mask of the 13 + 3 blocks: %s" % (arith, masks))
+        assert all(blocks[i].g3 == 0 for i in range(16)) and any(masks[:13]) and all(masks[13:])      # backbone blocks on the split-operand GEMMs too
+        fresh = []
+        for img in (small, large):
+            model._slots.clear()                                          # slot 0 anew: a context without a history
+            fresh.append([v.clone() for v in model(image_data=img)])
+        model._slots.clear()
+        ctx, sizes = None, []
+        for img, ref in ((small, fresh[0]), (large, fresh[1]), (small, fresh[0])):
+            out = model(image_data=img)
+            torch.cuda.synchronize()
+            assert ctx is None or model.context(0) is ctx                  # one slot, one context
+            ctx = model.context(0)
+            sizes.append(ctx.nbytes)
+            assert len(out) == len(ref) == 3
+            for u, v in zip(out, ref):                                     # proposals, classes, deltas
+                assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(u, v)
+        print("%s: ctx bytes after 64x96, 128x192, 64x96: %s" % (arith, sizes))
+        assert sizes[0] == sizes[1] == sizes[2]                            # sized by the head in the first forward
+    finally:
+        _set_modes(model, **R50_DEFAULTS)
+        model._slots.clear()
+
+
 @pytest.mark.parametrize("n,h,w,cin,width,cout,stride", [(3, 7, 7, 1024, 512, 2048, 2), (2, 4, 4, 2048, 512, 2048, 1), (1, 19, 31, 512, 256, 1024, 2),
                                                          (1, 10, 12, 1024, 256, 1024, 1)])
 def test_bottleneck_x6_1x1_against_the_float32_block(n, h, w, cin, width, cout, stride):

@@ -277,3 +277,41 @@ def test_model_layer_table_x6_vs_float32_winograd(gpu_model):
         assert rel <= 1e-5 and (d <= 1e-3).mean() >= 0.99
     with pytest.raises(ValueError):
         gpu_model.winograd_x6_layers = ("conv1_2",)
+
+
+def test_model_x6_scratch_grows_in_a_live_context(gpu_model):
+    """The scratch of the three-launch Winograd layers is sized, by the first forward that runs one, for the default table's layers
+    (image / 8 and smaller maps).  A table that then puts conv3_2 (an image / 4 map: about twice the records) on the x6 kernels makes
+    the live context synchronise, free the buffer, allocate a larger one and zero it again.  Each table's forward in that context must
+    give the bits of a context that has only ever run that table, before and after the buffer grew."""
+    from fasterrcnn_amd import synthetic
+    model = gpu_model
+    attrs = ("winograd_x6_layers", "winograd_x3_layers", "winograd_x3f_layers", "inflight_winograd_x3f_layers", "alone_winograd_x3f_layers")
+    saved = {a: getattr(model, a) for a in attrs}
+    table_a = dict(model.layer_forms(0), **{n: "f32x3" for n in nv.DEFAULT_X6_LAYERS_VGG16})     # the 512-channel layers in three launches
+    table_b = dict(table_a, conv3_2="f32x6")
+    img = synthetic.image(0).unsqueeze(0).cuda()
+    try:
+        fresh = {}
+        for name, table in (("a", table_a), ("b", table_b)):
+            model.set_layer_forms(table)
+            assert model.layer_forms(0) == table
+            model._slots.clear()                                          # slot 0 anew: a context without a history
+            fresh[name] = [v.clone() for v in model(image_data=img)]
+        model._slots.clear()
+        ctx, sizes = None, []
+        for name, table in (("a", table_a), ("b", table_b), ("a", table_a)):
+            model.set_layer_forms(table)
+            out = model(image_data=img)
+            torch.cuda.synchronize()
+            assert ctx is None or model.context(0) is ctx                  # one slot, one context
+            ctx = model.context(0)
+            sizes.append(ctx.nbytes)
+            for u, v in zip(out, fresh[name]):                             # proposals, classes, deltas
+                assert u.shape == v.shape and u.dtype == v.dtype and torch.equal(u, v)
+        print("ctx bytes after the default-sized table, conv3_2 on x6, the first table again: %s" % sizes)
+        assert sizes[1] > sizes[0] and sizes[2] == sizes[1]                # it grew for conv3_2 and never shrinks
+    finally:
+        for a, v in saved.items():
+            setattr(model, a, v)
+        model._slots.clear()
