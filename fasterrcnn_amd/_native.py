@@ -72,6 +72,7 @@ SYMBOLS = (
     "frcnn_ops_deform_roi_pool_backward", "frcnn_ops_deform_roi_pool_16", "frcnn_ops_deform_roi_pool_backward_16",
     "frcnn_ops_box_iou_rotated", "frcnn_ops_nms_rotated", "frcnn_ops_roi_align_rotated_cull_list", "frcnn_ops_roi_align_rotated",
     "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
+    "frcnn_ops_diff_iou_rotated", "frcnn_ops_diff_iou_rotated_backward",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
     "frcnn_ops_carafe", "frcnn_ops_carafe_backward", "frcnn_ops_carafe_16", "frcnn_ops_carafe_backward_16",
     "frcnn_ops_msda_max_levels", "frcnn_ops_msda_max_points", "frcnn_ops_msda_max_channels", "frcnn_ops_msda_block_items",
@@ -319,6 +320,8 @@ _SIGNATURES = {
     "frcnn_ops_roi_align_rotated_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_roi_align_rotated_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "frcnn_ops_roi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_diff_iou_rotated": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "frcnn_ops_diff_iou_rotated_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     # CARAFE upsampling (csrc/ops_carafe.hip); the _16 forms take the element-type code first
     "frcnn_ops_carafe_max_kernel": (C.c_int, []),
     "frcnn_ops_carafe_channel_chunk": (C.c_int, []),

@@ -15,6 +15,10 @@
 // +-1, so that a box clips to itself exactly and IoU(b, b) == 1.  The vertex lists live in LDS, one column per lane (a runtime-indexed
 // register array would go to scratch).  A pair is exactly 0 when either box has a non-finite component, a negative side or w h < 1e-14.
 //
+// Differentiable IoU of aligned pairs (frcnn_ops_diff_iou_rotated*; mmcv's diff_iou_rotated_2d restated): the forward is rot_iou handing
+// back the intersection area too; the backward is one launch that clips again with a tag per vertex and sums the closed-form gradient
+// over the edges of the final polygon (ops_rot_diff_iou_backward_kernel).
+//
 // NMS: ops_rot_nms_mask_kernel writes ops_nms_mask_kernel's 64 x 64 bit tiles (ops.hip) with the same diagonal and category skipping,
 // bit j of row i = rot_iou(sorted i, sorted j) > thr; ops_nms_reduce_kernel then runs the greedy pass unchanged.
 //
@@ -54,38 +58,53 @@ __device__ __forceinline__ RotBox rot_box(const float* p)
 
 // One Sutherland-Hodgman pass: keeps the part of the polygon `in` (n vertices) with SIGN * coordinate[AXIS] <= bound.  in / out point
 // at the lane's column: vertex i is (in[(2 i) * 64], in[(2 i + 1) * 64]).  A vertex on the boundary is inside.
-template <int AXIS, int SIGN>
-__device__ __forceinline__ int rot_clip(const float* in, float* out, int n, float bound)
+// TAGGED (the differentiable IoU's backward): vertex i carries in bits [3 i, 3 i + 3) of tin / tout the tag of the boundary piece that
+// leaves it -- 0..3 an edge of box A, 4 + AXIS + (SIGN < 0 ? 2 : 0) this pass's line.  A kept vertex keeps its tag; a crossing where the
+// polygon leaves the half-plane starts a piece of the clip line; one where it enters continues the edge that left p.
+template <int AXIS, int SIGN, bool TAGGED = false>
+__device__ __forceinline__ int rot_clip(const float* in, float* out, int n, float bound, unsigned tin = 0u, unsigned* tout = nullptr)
 {
+    constexpr unsigned LINE = 4 + AXIS + (SIGN < 0 ? 2 : 0);
+    unsigned tags = 0u;
+    if (TAGGED) *tout = 0u;
     if (n == 0) return 0;
     int m = 0;
     float px = in[(2 * (n - 1)) * 64], py = in[(2 * (n - 1) + 1) * 64];
     float pd = (float)SIGN * (AXIS ? py : px);
     bool pin = pd <= bound;
+    unsigned ptag = TAGGED ? (tin >> (3 * (n - 1))) & 7u : 0u;
     for (int i = 0; i < n; ++i) {
         const float qx = in[(2 * i) * 64], qy = in[(2 * i + 1) * 64];
         const float qd = (float)SIGN * (AXIS ? qy : qx);
         const bool qin = qd <= bound;
+        const unsigned qtag = TAGGED ? (tin >> (3 * i)) & 7u : 0u;
         if (pin != qin && m < ROT_MAX_VERTS) {
             const float t = (bound - pd) / (qd - pd);
             out[(2 * m) * 64] = AXIS ? px + t * (qx - px) : (float)SIGN * bound;
             out[(2 * m + 1) * 64] = AXIS ? (float)SIGN * bound : py + t * (qy - py);
+            if (TAGGED) tags |= (pin ? LINE : ptag) << (3 * m);
             ++m;
         }
         if (qin && m < ROT_MAX_VERTS) {
             out[(2 * m) * 64] = qx;
             out[(2 * m + 1) * 64] = qy;
+            if (TAGGED) tags |= qtag << (3 * m);
             ++m;
         }
-        px = qx; py = qy; pd = qd; pin = qin;
+        px = qx; py = qy; pd = qd; pin = qin; ptag = qtag;
     }
+    if (TAGGED) *tout = tags;
     return m;
 }
 
-// iof == 0: inter / (area a + area b - inter); else inter / area a.  poly: the lane's column of the block's ROT_POLY_FLOATS.
-__device__ __forceinline__ float rot_iou(const RotBox& a, const RotBox& b, int iof, float* poly)
+// Box a in box b's frame (both ok): its centre, the rotation from a's frame to b's, and its quadrilateral clipped against b's four
+// half-planes, left in the first vertex list of the lane's column `poly` of the block's ROT_POLY_FLOATS; returns the vertex count.  The
+// four start vertices carry a's edge numbers 0..3: edge 0 is the local +h/2 side, 1 is -w/2, 2 is -h/2, 3 is +w/2.
+struct RotFrame { float ox, oy, cd, sd; };
+
+template <bool TAGGED = false>
+__device__ __forceinline__ int rot_polygon(const RotBox& a, const RotBox& b, float* poly, RotFrame& f, unsigned* tags = nullptr)
 {
-    if (!a.ok || !b.ok) return 0.f;
     const float dx = a.cx - b.cx, dy = a.cy - b.cy;
     const float ox = dx * b.c + dy * b.s, oy = dy * b.c - dx * b.s;       // a's centre in b's frame
     float cd = a.c * b.c + a.s * b.s, sd = a.s * b.c - a.c * b.s;        // the rotation from a's frame to b's
@@ -98,10 +117,19 @@ __device__ __forceinline__ float rot_iou(const RotBox& a, const RotBox& b, int i
     p0[2 * 64] = (ox - ux) + vx; p0[3 * 64] = (oy - uy) + vy;
     p0[4 * 64] = (ox - ux) - vx; p0[5 * 64] = (oy - uy) - vy;
     p0[6 * 64] = (ox + ux) - vx; p0[7 * 64] = (oy + uy) - vy;
-    int n = rot_clip<0, 1>(p0, p1, 4, b.hw);
-    n = rot_clip<1, 1>(p1, p0, n, b.hh);
-    n = rot_clip<0, -1>(p0, p1, n, b.hw);
-    n = rot_clip<1, -1>(p1, p0, n, b.hh);
+    f.ox = ox; f.oy = oy; f.cd = cd; f.sd = sd;
+    unsigned t = 0u | 1u << 3 | 2u << 6 | 3u << 9;
+    int n = rot_clip<0, 1, TAGGED>(p0, p1, 4, b.hw, t, &t);
+    n = rot_clip<1, 1, TAGGED>(p1, p0, n, b.hh, t, &t);
+    n = rot_clip<0, -1, TAGGED>(p0, p1, n, b.hw, t, &t);
+    n = rot_clip<1, -1, TAGGED>(p1, p0, n, b.hh, t, &t);
+    if (TAGGED) *tags = t;
+    return n;
+}
+
+// the area of the polygon rot_polygon left (n vertices): the fan of triangles from the first vertex
+__device__ __forceinline__ float rot_area(const float* p0, int n)
+{
     float sum = 0.f;
     if (n >= 3) {
         const float x0 = p0[0], y0 = p0[64];
@@ -112,7 +140,19 @@ __device__ __forceinline__ float rot_iou(const RotBox& a, const RotBox& b, int i
             ex = fx; ey = fy;
         }
     }
-    const float inter = 0.5f * fabsf(sum);
+    return 0.5f * fabsf(sum);
+}
+
+// iof == 0: inter / (area a + area b - inter); else inter / area a.  poly: the lane's column of the block's ROT_POLY_FLOATS.
+// inter_out, when given, receives inter (0 under the zero rule).
+__device__ __forceinline__ float rot_iou(const RotBox& a, const RotBox& b, int iof, float* poly, float* inter_out = nullptr)
+{
+    if (inter_out) *inter_out = 0.f;
+    if (!a.ok || !b.ok) return 0.f;
+    RotFrame f;
+    const int n = rot_polygon(a, b, poly, f);
+    const float inter = rot_area(poly, n);
+    if (inter_out) *inter_out = inter;
     return iof ? inter / a.area : inter / ((a.area + b.area) - inter);
 }
 
@@ -139,6 +179,88 @@ void ops_rot_iou_aligned_kernel(const float* __restrict__ boxes1, const float* _
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     out[i] = rot_iou(rot_box(boxes1 + (size_t)i * 5), rot_box(boxes2 + (size_t)i * 5), iof, s_poly + threadIdx.x);
+}
+
+// ---- the differentiable IoU of aligned pairs (diff_iou_rotated) ---------------------------------------------------------------------
+// iou[i] = rot_iou(boxes1[i], boxes2[i]), bit for bit ops_rot_iou_aligned_kernel's value, and inter[i] the intersection area it divides
+__global__ __launch_bounds__(64)
+void ops_rot_diff_iou_kernel(const float* __restrict__ boxes1, const float* __restrict__ boxes2, int n, float* __restrict__ iou,
+                             float* __restrict__ inter)
+{
+    __shared__ float s_poly[ROT_POLY_FLOATS];
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float area;
+    iou[i] = rot_iou(rot_box(boxes1 + (size_t)i * 5), rot_box(boxes2 + (size_t)i * 5), 0, s_poly + threadIdx.x, &area);
+    inter[i] = area;
+}
+
+__device__ __forceinline__ void rot_store_box(float* __restrict__ d, int i, float v0, float v1, float v2, float v3, float v4)
+{
+    if (!d) return;
+    d += (size_t)i * 5;
+    d[0] = v0; d[1] = v1; d[2] = v2; d[3] = v3; d[4] = v4;
+}
+
+// The gradients of sum_i (grad_iou[i] iou[i] + grad_inter[i] inter[i]) for the ten parameters of pair i: one lane per pair, no atomics,
+// every element of a wanted gradient written once.  The lane clips again, with tags, and sums over the edges of the final polygon: moving
+// a boundary line outward at unit speed adds the length L of the polygon's edges that lie on it.  In b's frame, with o a's centre, d the
+// relative angle and n_k the outward normal of a's edge k ((-sd, cd), (-cd, -sd), (sd, -cd), (cd, sd)):
+//   dI/d(b.hw) = sum of L on x = +-b.hw, dI/d(b.hh) likewise; dI/d(a.hw) = L on edges 1, 3; dI/d(a.hh) = L on edges 0, 2;
+//   dI/do = sum over a's edges of L n_k; dI/dd = sum over a's edges of L (n_k . perp(mid - o)), perp(x, y) = (-y, x);
+// chained by o = R(-angle_b)(centre_a - centre_b) (so do/d angle_b = (oy, -ox)), d = angle_a - angle_b, w = 2 hw.  With U = Sa + Sb - I the
+// adjoint of I is grad_inter + grad_iou (U + I) / U^2 and that of each area S = w h is -grad_iou I / U^2.  A pair under the zero rule, or
+// whose polygon has fewer than 3 vertices, gets exact zeros.  grad_iou / grad_inter may be null (zeros), d1 / d2 null (skipped).
+__global__ __launch_bounds__(64)
+void ops_rot_diff_iou_backward_kernel(const float* __restrict__ boxes1, const float* __restrict__ boxes2, const float* __restrict__ grad_iou,
+                                      const float* __restrict__ grad_inter, int n, float* __restrict__ d1, float* __restrict__ d2)
+{
+    __shared__ float s_poly[ROT_POLY_FLOATS];
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const float* pa = boxes1 + (size_t)i * 5;
+    const float* pb = boxes2 + (size_t)i * 5;
+    const RotBox a = rot_box(pa), b = rot_box(pb);
+    const float* p0 = s_poly + threadIdx.x;
+    RotFrame f;
+    unsigned tags = 0u;
+    const int nv = a.ok && b.ok ? rot_polygon<true>(a, b, s_poly + threadIdx.x, f, &tags) : 0;
+    if (nv < 3) {
+        rot_store_box(d1, i, 0.f, 0.f, 0.f, 0.f, 0.f);
+        rot_store_box(d2, i, 0.f, 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float inter = rot_area(p0, nv);
+    float l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f, lbw = 0.f, lbh = 0.f, gd = 0.f;     // lengths per tag; dI/dd
+    float px = p0[(2 * (nv - 1)) * 64], py = p0[(2 * (nv - 1) + 1) * 64];
+    unsigned tag = (tags >> (3 * (nv - 1))) & 7u;                                    // of the edge p -> q
+    for (int v = 0; v < nv; ++v) {
+        const float qx = p0[(2 * v) * 64], qy = p0[(2 * v + 1) * 64];
+        const float ex = qx - px, ey = qy - py;
+        const float len = sqrtf(ex * ex + ey * ey);
+        if (tag < 4u) {
+            const float nx = tag == 0u ? -f.sd : tag == 1u ? -f.cd : tag == 2u ? f.sd : f.cd;
+            const float ny = tag == 0u ? f.cd : tag == 1u ? -f.sd : tag == 2u ? -f.cd : f.sd;
+            const float mx = 0.5f * (px + qx) - f.ox, my = 0.5f * (py + qy) - f.oy;
+            gd += len * (ny * mx - nx * my);
+            l0 += tag == 0u ? len : 0.f; l1 += tag == 1u ? len : 0.f; l2 += tag == 2u ? len : 0.f; l3 += tag == 3u ? len : 0.f;
+        } else {
+            lbw += (tag & 1u) ? 0.f : len;
+            lbh += (tag & 1u) ? len : 0.f;
+        }
+        px = qx; py = qy;
+        tag = (tags >> (3 * v)) & 7u;
+    }
+    const float gox = f.sd * (l2 - l0) + f.cd * (l3 - l1), goy = f.cd * (l0 - l2) + f.sd * (l3 - l1);     // dI/do
+    const float u = (a.area + b.area) - inter;
+    const float gi = grad_iou ? grad_iou[i] : 0.f;
+    const float g_inter = (grad_inter ? grad_inter[i] : 0.f) + gi * ((u + inter) / (u * u));
+    const float g_area = -gi * (inter / (u * u));
+    const float gx = g_inter * (gox * b.c - goy * b.s), gy = g_inter * (gox * b.s + goy * b.c);         // to a's centre; b's gets the negative
+    rot_store_box(d1, i, gx, gy, g_inter * (0.5f * (l1 + l3)) + g_area * pa[3], g_inter * (0.5f * (l0 + l2)) + g_area * pa[2],
+                  g_inter * gd);
+    rot_store_box(d2, i, -gx, -gy, g_inter * (0.5f * lbw) + g_area * pb[3], g_inter * (0.5f * lbh) + g_area * pb[2],
+                  g_inter * ((gox * f.oy - goy * f.ox) - gd));
 }
 
 // ops_nms_mask_kernel (ops.hip) on rotated boxes: the same grid, tiles, skipping and bit layout
@@ -419,6 +541,26 @@ int frcnn_ops_box_iou_rotated(const float* d_boxes1, int n, const float* d_boxes
     else
         hipLaunchKernelGGL(ops_rot_iou_kernel, dim3(cdiv(m, 64), cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, d_boxes1, n, d_boxes2, m,
                            mode, d_out);
+    return check_launch();
+}
+
+int frcnn_ops_diff_iou_rotated(const float* d_boxes1, const float* d_boxes2, int n, float* d_iou, float* d_inter, void* stream)
+{
+    if (n < 0 || cdiv(n, 64) > 65535) return FRCNN_EINVAL;
+    if (n == 0) return FRCNN_OK;
+    if (!d_boxes1 || !d_boxes2 || !d_iou || !d_inter) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_rot_diff_iou_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, d_boxes1, d_boxes2, n, d_iou, d_inter);
+    return check_launch();
+}
+
+int frcnn_ops_diff_iou_rotated_backward(const float* d_boxes1, const float* d_boxes2, const float* d_grad_iou, const float* d_grad_inter,
+                                        int n, float* d_dboxes1, float* d_dboxes2, void* stream)
+{
+    if (n < 0 || cdiv(n, 64) > 65535) return FRCNN_EINVAL;
+    if (n == 0) return FRCNN_OK;
+    if (!d_boxes1 || !d_boxes2 || !(d_grad_iou || d_grad_inter) || !(d_dboxes1 || d_dboxes2)) return FRCNN_EINVAL;
+    hipLaunchKernelGGL(ops_rot_diff_iou_backward_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, d_boxes1, d_boxes2,
+                       d_grad_iou, d_grad_inter, n, d_dboxes1, d_dboxes2);
     return check_launch();
 }
 

@@ -6,6 +6,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import deform_conv2d, DeformConv2d
     from fasterrcnn_amd.ops import deform_roi_pool, DeformRoIPool, DeformRoIPoolPack, ModulatedDeformRoIPoolPack
     from fasterrcnn_amd.ops import box_iou_rotated, nms_rotated, roi_align_rotated, RoIAlignRotated
+    from fasterrcnn_amd.ops import diff_iou_rotated_2d, diff_iou_rotated_3d, diff_iou_rotated_2d_pytorch
     from fasterrcnn_amd.ops import carafe, CARAFE, CARAFEPack
     from fasterrcnn_amd.ops import multi_scale_deformable_attn, MultiScaleDeformableAttnFunction, MultiScaleDeformableAttention
     from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
@@ -105,6 +106,29 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       Limits, layouts ([K, C, oh, ow] channels_last), channel padding and the batch-index rule are roi_align's; 16-bit maps run under
       the contract below, forward and backward, with RoIs in float32.  The gradient goes to input only; it is a deterministic gather
       without atomics (RoIs ascending, ROI_ALIGN_ROTATED_CULL_LIST per pass, then bins in (ph, pw) order).  Double backward raises.
+  diff_iou_rotated_2d(box1, box2) -> float32 [B, N] or [N]
+  diff_iou_rotated_3d(box3d1, box3d2) -> float32 [B, N] or [N]
+  diff_iou_rotated_2d_pytorch(box1, box2)
+      The differentiable IoU of aligned pairs of rotated boxes, what mmrotate's RotatedIoULoss and mmdet3d's 3-D IoU losses are built on
+      (csrc/ops_rot.hip; mmcv's diff_iou_rotated_2d / _3d, signatures kept).  box1 and box2 are float32, of one shape [B, N, 5] or
+      [N, 5], rows (cx, cy, w, h, angle in radians); there is no clockwise flag: the IoU of a pair does not depend on the convention as
+      long as both boxes use one.  The value is box_iou_rotated(box1.view(-1, 5), box2.view(-1, 5), aligned=True) bit for bit -- the
+      same device function -- so the zero rule holds (exactly 0 for a non-finite component, a negative side or w h < 1e-14) and
+      identical boxes give exactly 1.  This is where it differs from mmcv, which intersects the edges pairwise into 24 candidate points,
+      sorts them around their mean and takes the hull's area, with epsilons, in dozens of small launches differentiated by autograd:
+      here the forward is one launch and the whole backward is one launch with the closed-form gradient of the clipped polygon
+      (include/frcnn_hip.h states it: the length of the polygon's edges on each boundary line, chained to the ten box parameters).
+      Where edges of the two boxes coincide the IoU has a kink, and the gradient is the one-sided value of the polygon the clip
+      produced (a vertex on a line counts as inside: identical boxes get the gradient of box1 inside box2).  A pair under the zero
+      rule, or one that does not overlap, gets exact zeros in all ten slots, whatever NaNs it holds.  Deterministic, no atomics; each
+      gradient is skipped when its argument needs none; double backward raises.  3d: rows (x, y, z, w, h, l, alpha), [B, N, 7] or
+      [N, 7], mmcv's definition: inter2d of the columns (0, 1, 3, 4, 6), z_overlap = clamp_min(min(z1 + l1 / 2, z2 + l2 / 2) -
+      max(z1 - l1 / 2, z2 - l2 / 2), 0), inter3d = inter2d z_overlap, vol = w h l, inter3d / (vol1 + vol2 - inter3d); inter2d and
+      its gradient come from the kernels, the rest is torch's.  float64 or 16-bit boxes are a TypeError (pass .float()), differing
+      shapes or devices, CPU tensors and more than MAX_ROTATED_IOU_ROWS pairs a ValueError; no pairs give empty results and zero
+      gradients without a launch.  diff_iou_rotated_2d_pytorch is the same clip from torch operations (8 vertex slots per pair, four
+      passes, the fan area), differentiable by autograd, on any device and in float64 too: the fallback, with finite gradients for
+      every input (each division sees a safe denominator before torch.where selects).
   carafe(features, masks, kernel_size, group_size, scale_factor) -> Tensor [N, C, s H, s W]
   CARAFE(kernel_size, group_size, scale_factor).forward(features, masks)
   CARAFEPack(channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1, compressed_channels=64).forward(x)
@@ -262,7 +286,7 @@ a zero-padded copy; input gradients come back in the input's dtype and memory fo
 """
 import ctypes as C
 import math
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -272,6 +296,7 @@ from . import _native as nv
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
+           "diff_iou_rotated_2d", "diff_iou_rotated_3d", "diff_iou_rotated_2d_pytorch",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
            "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4"]
@@ -303,13 +328,15 @@ CARAFE_RUN = 4                            # channels a thread of carafe's d_feat
 
 
 # ---- argument checks (the public functions; the custom ops assume them) -----------------------------------------------------------
-def _check_tensor(name, t, dtypes, what):
+def _check_tensor(name, t, dtypes, what, fallback=None):
+    """fallback: the name of the torch composition that serves other devices, for the message."""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
     if t.dtype not in dtypes:
         raise TypeError("%s must be %s, got %s" % (name, what, t.dtype))
     if t.device.type not in ("cuda", "meta"):
-        raise ValueError("%s must be a tensor on the GPU, got device %s: fasterrcnn_amd.ops has no CPU implementation" % (name, t.device))
+        raise ValueError("%s must be a tensor on the GPU, got device %s: fasterrcnn_amd.ops has no CPU implementation%s"
+                         % (name, t.device, " (%s runs on any device)" % fallback if fallback else ""))
 
 
 def _check_same_device(a, b, na, nb):
@@ -1172,6 +1199,59 @@ def _(boxes1, boxes2, mode, aligned):
     return boxes1.new_empty((n,) if aligned else (n, m), dtype=torch.float32)
 
 
+@torch.library.custom_op("frcnn::diff_iou_rotated", mutates_args=())
+def _diff_iou_rotated(boxes1: Tensor, boxes2: Tensor) -> Tuple[Tensor, Tensor]:
+    """(iou [n], inter [n]) of the aligned pairs boxes1[i], boxes2[i] ([n, 5] each, the kernels' convention)."""
+    n = boxes1.shape[0]
+    iou, inter = boxes1.new_empty((n,)), boxes1.new_empty((n,))
+    if n == 0:
+        return iou, inter
+    with torch.cuda.device(boxes1.device):
+        a, b = boxes1.contiguous(), boxes2.contiguous()
+        nv.check(nv.lib().frcnn_ops_diff_iou_rotated(a.data_ptr(), b.data_ptr(), n, iou.data_ptr(), inter.data_ptr(), _stream(boxes1)),
+                 "frcnn_ops_diff_iou_rotated")
+    return iou, inter
+
+
+@_diff_iou_rotated.register_fake
+def _(boxes1, boxes2):
+    n = boxes1.shape[0]
+    return boxes1.new_empty((n,)), boxes1.new_empty((n,))
+
+
+@torch.library.custom_op("frcnn::diff_iou_rotated_backward", mutates_args=())
+def _diff_iou_rotated_backward(grad_iou: Tensor, grad_inter: Tensor, boxes1: Tensor, boxes2: Tensor, needs: List[bool]) -> List[Tensor]:
+    """[d_boxes1, d_boxes2] of sum(grad_iou * iou + grad_inter * inter); needs: which of them are wanted (the other comes back as an
+    empty placeholder and is not written)."""
+    n = boxes1.shape[0]
+    if n == 0:
+        return [torch.zeros_like(t, memory_format=torch.contiguous_format) if need else _placeholder(grad_iou)
+                for t, need in zip((boxes1, boxes2), needs)]
+    if not any(needs):
+        return [_placeholder(grad_iou), _placeholder(grad_iou)]
+    with torch.cuda.device(boxes1.device):
+        a, b, gi, gn = boxes1.contiguous(), boxes2.contiguous(), grad_iou.contiguous(), grad_inter.contiguous()
+        d1 = torch.empty_like(a) if needs[0] else None
+        d2 = torch.empty_like(b) if needs[1] else None
+        nv.check(nv.lib().frcnn_ops_diff_iou_rotated_backward(a.data_ptr(), b.data_ptr(), gi.data_ptr(), gn.data_ptr(), n, _opt_ptr(d1),
+                                                              _opt_ptr(d2), _stream(boxes1)), "frcnn_ops_diff_iou_rotated_backward")
+    return [_placeholder(grad_iou) if d is None else d for d in (d1, d2)]
+
+
+@_diff_iou_rotated_backward.register_fake
+def _(grad_iou, grad_inter, boxes1, boxes2, needs):
+    return _needs_fake(grad_iou, (boxes1, boxes2), needs)
+
+
+def _diff_iou_rotated_bwd(ctx, grad_iou, grad_inter):
+    needs = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+    d1, d2 = _diff_iou_rotated_backward(grad_iou, grad_inter, *ctx.saved_tensors, needs)
+    return (d1 if needs[0] else None, d2 if needs[1] else None)
+
+
+_register_autograd("diff_iou_rotated", _diff_iou_rotated_bwd, lambda ctx, inputs, output: ctx.save_for_backward(*inputs))
+
+
 @torch.library.custom_op("frcnn::nms_rotated", mutates_args=())
 def _nms_rotated_op(boxes: Tensor, scores: Tensor, labels: Optional[Tensor], iou_threshold: float) -> Tensor:
     """The kept indices; boxes in the kernels' (clockwise) convention."""
@@ -1812,6 +1892,115 @@ def box_iou_rotated(boxes1, boxes2, mode="iou", aligned=False, clockwise=True):
     if b1.shape[0] > MAX_ROTATED_IOU_ROWS:
         raise ValueError("boxes1 holds at most %d boxes, got %d" % (MAX_ROTATED_IOU_ROWS, b1.shape[0]))
     return _box_iou_rotated(b1.detach(), b2.detach(), int(mode == "iof"), bool(aligned))
+
+
+def _diff_iou_input(names, boxes, last, row, fallback=None):
+    """Checks the two box tensors of a differentiable IoU: float32, one shape [B, N, last] or [N, last], one device, at most
+    MAX_ROTATED_IOU_ROWS pairs."""
+    for name, b in zip(names, boxes):
+        _check_tensor(name, b, (torch.float32,), "float32 (rotated boxes are float32 only: pass .float())", fallback)
+        if b.dim() not in (2, 3) or b.shape[-1] != last:
+            raise ValueError("%s must be [B, N, %d] or [N, %d] %s, got shape %s" % (name, last, last, row, tuple(b.shape)))
+    if boxes[0].shape != boxes[1].shape:
+        raise ValueError("%s and %s must have one shape, got %s and %s" % (names + (tuple(boxes[0].shape), tuple(boxes[1].shape))))
+    _check_same_device(boxes[0], boxes[1], *names)
+    n = boxes[0].numel() // last
+    if n > MAX_ROTATED_IOU_ROWS:
+        raise ValueError("%s and %s hold at most MAX_ROTATED_IOU_ROWS = %d pairs, got %d" % (names + (MAX_ROTATED_IOU_ROWS, n)))
+
+
+def diff_iou_rotated_2d(box1, box2):
+    """mmcv.ops.diff_iou_rotated_2d: the IoU of the aligned pairs of rotated boxes (cx, cy, w, h, angle in radians), [B, N, 5] or [N, 5]
+    -> [B, N] or [N], with gradients for both: box_iou_rotated(aligned=True)'s value bit for bit, a closed-form backward in one launch."""
+    _diff_iou_input(("box1", "box2"), (box1, box2), 5, "(cx, cy, w, h, angle)", "diff_iou_rotated_2d_pytorch")
+    return _diff_iou_rotated(box1.reshape(-1, 5), box2.reshape(-1, 5))[0].view(box1.shape[:-1])
+
+
+def diff_iou_rotated_3d(box3d1, box3d2):
+    """mmcv.ops.diff_iou_rotated_3d: the IoU of the aligned pairs of 3-D boxes (x, y, z, w, h, l, alpha), rotated by alpha about z,
+    [B, N, 7] or [N, 7] -> [B, N] or [N]: the 2-D intersection of (x, y, w, h, alpha) times the overlap along z, over the union volume."""
+    _diff_iou_input(("box3d1", "box3d2"), (box3d1, box3d2), 7, "(x, y, z, w, h, l, alpha)")
+    a, b = box3d1.reshape(-1, 7), box3d2.reshape(-1, 7)
+    bev = lambda t: torch.cat([t[:, 0:2], t[:, 3:5], t[:, 6:7]], dim=1)     # noqa: E731
+    inter2d = _diff_iou_rotated(bev(a), bev(b))[1]
+    z_overlap = (torch.min(a[:, 2] + a[:, 5] * 0.5, b[:, 2] + b[:, 5] * 0.5)
+                 - torch.max(a[:, 2] - a[:, 5] * 0.5, b[:, 2] - b[:, 5] * 0.5)).clamp_min(0.0)
+    inter3d = inter2d * z_overlap
+    vol1, vol2 = a[:, 3] * a[:, 4] * a[:, 5], b[:, 3] * b[:, 4] * b[:, 5]
+    return (inter3d / (vol1 + vol2 - inter3d)).view(box3d1.shape[:-1])
+
+
+def _diff_iou_clip(v, n, axis, sign, bound):
+    """One Sutherland-Hodgman pass over polygons v [P, 8, 2] with n [P] vertices, keeping sign * coordinate[axis] <= bound [P]: out of
+    place and free of host syncs; the division sees a denominator of 1 wherever the edge does not cross."""
+    slots = torch.arange(8, device=v.device)
+    out, m = torch.zeros_like(v), torch.zeros_like(n)
+    prev = v.gather(1, (n - 1).clamp(min=0)[:, None, None].expand(-1, 1, 2))[:, 0]
+    for i in range(8):
+        q = v[:, i]
+        act = i < n
+        pd, qd = sign * prev[:, axis], sign * q[:, axis]
+        pin, qin = pd <= bound, qd <= bound
+        cross = act & (pin != qin) & (m < 8)
+        t = (bound - pd) / torch.where(cross, qd - pd, torch.ones_like(qd))
+        other = prev[:, 1 - axis] + t * (q[:, 1 - axis] - prev[:, 1 - axis])
+        pt = torch.stack([sign * bound, other] if axis == 0 else [other, sign * bound], 1)
+        out = torch.where(((slots == m[:, None]) & cross[:, None])[:, :, None], pt[:, None], out)
+        m = m + cross
+        keep = act & qin & (m < 8)
+        out = torch.where(((slots == m[:, None]) & keep[:, None])[:, :, None], q[:, None], out)
+        m = m + keep
+        prev = torch.where(act[:, None], q, prev)
+    return out, m
+
+
+def diff_iou_rotated_2d_pytorch(box1, box2):
+    """diff_iou_rotated_2d from torch operations, differentiable by autograd, on any device, in float32 or float64: box 1's corners in
+    box 2's frame, four Sutherland-Hodgman passes over a fixed list of 8 vertices per pair, the fan area.  Every gradient is finite
+    whatever the boxes hold (a pair under the zero rule gets zeros)."""
+    for name, b in (("box1", box1), ("box2", box2)):
+        if not isinstance(b, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(b).__name__))
+        if b.dtype not in (torch.float32, torch.float64):
+            raise TypeError("%s must be float32 or float64, got %s" % (name, b.dtype))
+        if b.dim() not in (2, 3) or b.shape[-1] != 5:
+            raise ValueError("%s must be [B, N, 5] or [N, 5] (cx, cy, w, h, angle), got shape %s" % (name, tuple(b.shape)))
+    if box1.shape != box2.shape or box1.dtype != box2.dtype:
+        raise ValueError("box1 and box2 must have one shape and dtype, got %s %s and %s %s"
+                         % (tuple(box1.shape), box1.dtype, tuple(box2.shape), box2.dtype))
+    _check_same_device(box1, box2, "box1", "box2")
+    a, b = box1.reshape(-1, 5), box2.reshape(-1, 5)
+    ok = lambda t: torch.isfinite(t).all(1) & (t[:, 2] >= 0) & (t[:, 3] >= 0) & (t[:, 2] * t[:, 3] >= 1e-14)     # noqa: E731
+    valid = ok(a) & ok(b)
+    unit = a.new_tensor([0.0, 0.0, 1.0, 1.0, 0.0])
+    a, b = torch.where(valid[:, None], a, unit), torch.where(valid[:, None], b, unit)      # a NaN never meets a gradient
+    ca, sa, cb, sb = torch.cos(a[:, 4]), torch.sin(a[:, 4]), torch.cos(b[:, 4]), torch.sin(b[:, 4])
+    dx, dy = a[:, 0] - b[:, 0], a[:, 1] - b[:, 1]
+    ox, oy = dx * cb + dy * sb, dy * cb - dx * sb
+    cd, sd = ca * cb + sa * sb, sa * cb - ca * sb
+    one = torch.ones_like(cd)
+    cd = torch.where(sd == 0, torch.where(cd < 0, -one, one), cd)
+    sd = torch.where(cd == 0, torch.where(sd < 0, -one, one), sd)
+    hw, hh = 0.5 * a[:, 2], 0.5 * a[:, 3]
+    ux, uy, vx, vy = hw * cd, hw * sd, -hh * sd, hh * cd
+    zero = torch.zeros_like(ox)
+    corners = [((ox + ux) + vx, (oy + uy) + vy), ((ox - ux) + vx, (oy - uy) + vy), ((ox - ux) - vx, (oy - uy) - vy),
+               ((ox + ux) - vx, (oy + uy) - vy)] + [(zero, zero)] * 4
+    v = torch.stack([torch.stack(c, 1) for c in corners], 1)
+    n = torch.full_like(valid, 4, dtype=torch.int64)
+    bw, bh = 0.5 * b[:, 2], 0.5 * b[:, 3]
+    for axis, sign, bound in ((0, 1.0, bw), (1, 1.0, bh), (0, -1.0, bw), (1, -1.0, bh)):
+        v, n = _diff_iou_clip(v, n, axis, sign, bound)
+    total = zero
+    e = v[:, 1] - v[:, 0]
+    for i in range(2, 8):
+        f = v[:, i] - v[:, 0]
+        act = (i < n) & (n >= 3)
+        total = total + torch.where(act, e[:, 0] * f[:, 1] - f[:, 0] * e[:, 1], zero)
+        e = torch.where(act[:, None], f, e)
+    inter = 0.5 * total.abs()
+    iou = inter / ((a[:, 2] * a[:, 3] + b[:, 2] * b[:, 3]) - inter)
+    return torch.where(valid, iou, zero).view(box1.shape[:-1])
 
 
 def nms_rotated(boxes, scores, iou_threshold, labels=None, clockwise=True):

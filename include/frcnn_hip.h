@@ -80,7 +80,9 @@ extern "C" {
                                  convolution v3);
                                  still 21 (additions only): frcnn_ops_dcnv4_forward, _backward_offset_mask, _plan, _backward_input, _workspace_bytes,
                                  the _16 forms and the frcnn_ops_dcnv4_block_items / _record getters (DCNv4: FlashInternImage's deformable
-                                 convolution v4, one packed offset_mask tensor, optionally without the centre point) */
+                                 convolution v4, one packed offset_mask tensor, optionally without the centre point);
+                                 still 21 (additions only): frcnn_ops_diff_iou_rotated and its _backward (the differentiable IoU of aligned
+                                 rotated boxes: mmcv's diff_iou_rotated_2d / _3d) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -747,9 +749,33 @@ int frcnn_ops_prroi_pool_backward_16(int elem_type, const void* d_x, const float
  *   in (iy, ix) order) / count; it stays in registers and is stored once.
  * Arguments are validated before the GPU is touched (FRCNN_EINVAL): frcnn_ops_roi_align's limits, fh <= 131070, NULL pointers, mode
  *   outside {0, 1}, aligned with n != m, n beyond the limits, a small workspace.
- * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; RoIs stay float32. */
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; RoIs stay float32.
+ * frcnn_ops_diff_iou_rotated: the differentiable IoU of n aligned pairs (mmcv's diff_iou_rotated_2d; mmcv builds it from 24 candidate
+ *   points and a sorted hull with epsilons, this is the clipped polygon above).  d_iou [n] = IoU(d_boxes1[i], d_boxes2[i]), the bits of
+ *   frcnn_ops_box_iou_rotated(mode 0, aligned) from the same device function, and d_inter [n] = the intersection area it divides (0 under
+ *   the zero rule).  n == 0 returns FRCNN_OK; n <= 4194240.
+ * frcnn_ops_diff_iou_rotated_backward: d_dboxes1 / d_dboxes2 [n][5] = the gradient of sum_i (grad_iou[i] iou[i] + grad_inter[i] inter[i])
+ *   in the boxes.  d_grad_iou or d_grad_inter may be NULL (zeros), not both; d_dboxes1 or d_dboxes2 may be NULL (skipped), not both.  One
+ *   launch, one lane per pair, no atomics, no workspace, every element of a wanted gradient written once; deterministic.  The lane
+ *   repeats the clip and carries, per vertex, the tag of the boundary piece that leaves it: box 1's edges 0..3 in the order the corners
+ *   are laid down (edge 0 the local +h/2 side, 1 the -w/2 side, 2 the -h/2 side, 3 the +w/2 side) or one of box 2's four lines; a kept
+ *   vertex keeps its tag, a crossing where the polygon leaves the half-plane takes the clip line's, one where it enters takes that of
+ *   the vertex it comes from.  With L_e the length of edge e of the final polygon, o box 1's centre in box 2's frame, d = angle1 - angle2,
+ *   (cd, sd) its cosine and sine as the forward forms them, and n_k the outward normal of box 1's edge k -- (-sd, cd), (-cd, -sd),
+ *   (sd, -cd), (cd, sd) --
+ *     d inter / d (w2 / 2) = the sum of L_e over the edges on x = +-w2 / 2, d inter / d (h2 / 2) likewise,
+ *     d inter / d (w1 / 2) = the sum over the edges tagged 1 or 3, d inter / d (h1 / 2) over those tagged 0 or 2,
+ *     d inter / d o = the sum over box 1's edges of L_e n_k, d inter / d d = the sum over box 1's edges of L_e (n_k . perp(mid_e - o)),
+ *   perp(x, y) = (-y, x), mid_e the edge's midpoint; chained by o = R(-angle2)(centre1 - centre2), so d o / d angle2 = (o_y, -o_x), and
+ *   d d / d angle1 = 1, d d / d angle2 = -1.  With U = w1 h1 + w2 h2 - inter the adjoint of inter is grad_inter + grad_iou (U + inter) /
+ *   U^2 and that of each area w h is -grad_iou inter / U^2.  Where edges of the two boxes coincide the function has a kink; the result
+ *   is the one-sided derivative of the polygon the clip produced (a vertex on a line counts as inside).  A pair under the zero rule, or
+ *   whose polygon has fewer than 3 vertices, gets exact zeros in all ten slots, whatever NaNs the boxes hold. */
 int frcnn_ops_box_iou_rotated(const float* d_boxes1, int n, const float* d_boxes2, int m, int mode, int aligned, float* d_out,
                               void* stream);
+int frcnn_ops_diff_iou_rotated(const float* d_boxes1, const float* d_boxes2, int n, float* d_iou, float* d_inter, void* stream);
+int frcnn_ops_diff_iou_rotated_backward(const float* d_boxes1, const float* d_boxes2, const float* d_grad_iou, const float* d_grad_inter,
+                                        int n, float* d_dboxes1, float* d_dboxes2, void* stream);
 int frcnn_ops_nms_rotated(const float* d_boxes, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
                           uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
 int frcnn_ops_roi_align_rotated_cull_list(void);

@@ -62,6 +62,11 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     unpacked tensors, with the two unpacking copies (and, backward, autograd's re-packing of the gradients) inside the timed region;
     forward and forward + backward of both gradients, in alternating windows.  Informational: no speed bound is set.
 
+  * diffiou: the differentiable rotated IoU of 2^20 aligned pairs (boxes of 8 to 30 px against jittered copies of themselves, every
+    pair overlapping): ops.diff_iou_rotated_2d beside ops.diff_iou_rotated_2d_pytorch (the clip from torch operations, autograd's
+    backward), forward and forward + backward of both gradients, in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only diffiou         # just the differentiable-IoU leg
     python tools/ops_bench.py --only dcnv4           # just the DCNv4 leg
     python tools/ops_bench.py --only dcnv3           # just the DCNv3 leg
     python tools/ops_bench.py --only prroi           # just the Precise-RoI-Pooling leg
@@ -516,6 +521,24 @@ def prroi_leg(rng, reps, warmup):
     return res
 
 
+def diffiou_leg(rng, reps, warmup):
+    n = 1 << 20
+    u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
+    b1 = torch.cat([u(0, 1000, 2), u(8, 30, 2), u(-np.pi, np.pi, 1)], 1)
+    b2 = torch.cat([b1[:, :2] + u(-3, 3, 2), b1[:, 2:4] * u(0.8, 1.25, 2), b1[:, 4:] + u(-0.3, 0.3, 1)], 1)
+    b1, b2, g = b1.to(DEV), b2.to(DEV), u(-1, 1).to(DEV)
+    leaves = (b1.clone().requires_grad_(True), b2.clone().requires_grad_(True))
+    y, yc = ops.diff_iou_rotated_2d(b1, b2), ops.diff_iou_rotated_2d_pytorch(b1, b2)
+    r = {"max |diff_iou_rotated_2d - composition|": float((y - yc).abs().max()), "mean IoU": float(y.mean())}
+    for name, fns in (("fwd", (lambda: ops.diff_iou_rotated_2d(b1, b2), lambda: ops.diff_iou_rotated_2d_pytorch(b1, b2))),
+                      ("fwd+bwd (both boxes)", (lambda: ops.diff_iou_rotated_2d(*leaves).backward(g),
+                                                lambda: ops.diff_iou_rotated_2d_pytorch(*leaves).backward(g)))):
+        t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+        r[name] = {"ops.diff_iou_rotated_2d": round(t_native, 1), "ops.diff_iou_rotated_2d_pytorch": round(t_comp, 1),
+                   "composition / diff_iou_rotated_2d": round(t_comp / t_native, 2)}
+    return {"diffiou float32, %d aligned pairs" % n: r}
+
+
 def proposals(rng, k, H, W):
     y1 = rng.uniform(0, H - 64, k); x1 = rng.uniform(0, W - 64, k)
     return np.stack([y1, x1, np.minimum(y1 + rng.uniform(32, 400, k), H), np.minimum(x1 + rng.uniform(32, 600, k), W)], 1).astype(np.float32)
@@ -525,7 +548,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -561,6 +584,9 @@ def main():
         return
     if a.only == "dcnv3":
         print(json.dumps(dcnv3_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "diffiou":
+        print(json.dumps(diffiou_leg(rng, 5, 2), indent=1))
         return
     if a.only == "dcnv4":
         print(json.dumps(dcnv4_leg(rng, 5, 2), indent=1))
