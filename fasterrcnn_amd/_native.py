@@ -73,6 +73,8 @@ SYMBOLS = (
     "frcnn_ops_box_iou_rotated", "frcnn_ops_nms_rotated", "frcnn_ops_roi_align_rotated_cull_list", "frcnn_ops_roi_align_rotated",
     "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
     "frcnn_ops_diff_iou_rotated", "frcnn_ops_diff_iou_rotated_backward",
+    "frcnn_ops_soft_nms_block_threads", "frcnn_ops_soft_nms_lds_boxes", "frcnn_ops_soft_nms_max_boxes", "frcnn_ops_soft_nms_workspace_bytes",
+    "frcnn_ops_soft_nms",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
     "frcnn_ops_carafe", "frcnn_ops_carafe_backward", "frcnn_ops_carafe_16", "frcnn_ops_carafe_backward_16",
     "frcnn_ops_msda_max_levels", "frcnn_ops_msda_max_points", "frcnn_ops_msda_max_channels", "frcnn_ops_msda_block_items",
@@ -322,6 +324,12 @@ _SIGNATURES = {
     "frcnn_ops_roi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
+    "frcnn_ops_soft_nms_block_threads": (C.c_int, []),
+    "frcnn_ops_soft_nms_lds_boxes": (C.c_int, []),
+    "frcnn_ops_soft_nms_max_boxes": (C.c_int, []),
+    "frcnn_ops_soft_nms_workspace_bytes": (C.c_size_t, [_i]),
+    "frcnn_ops_soft_nms": (C.c_int, [_vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     # CARAFE upsampling (csrc/ops_carafe.hip); the _16 forms take the element-type code first
     "frcnn_ops_carafe_max_kernel": (C.c_int, []),
     "frcnn_ops_carafe_channel_chunk": (C.c_int, []),

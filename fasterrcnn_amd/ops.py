@@ -7,6 +7,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import deform_roi_pool, DeformRoIPool, DeformRoIPoolPack, ModulatedDeformRoIPoolPack
     from fasterrcnn_amd.ops import box_iou_rotated, nms_rotated, roi_align_rotated, RoIAlignRotated
     from fasterrcnn_amd.ops import diff_iou_rotated_2d, diff_iou_rotated_3d, diff_iou_rotated_2d_pytorch
+    from fasterrcnn_amd.ops import soft_nms, soft_nms_pytorch
     from fasterrcnn_amd.ops import carafe, CARAFE, CARAFEPack
     from fasterrcnn_amd.ops import multi_scale_deformable_attn, MultiScaleDeformableAttnFunction, MultiScaleDeformableAttention
     from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
@@ -129,6 +130,35 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       gradients without a launch.  diff_iou_rotated_2d_pytorch is the same clip from torch operations (8 vertex slots per pair, four
       passes, the fan area), differentiable by autograd, on any device and in float64 too: the fallback, with finite gradients for
       every input (each division sees a safe denominator before torch.where selects).
+  soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method="linear", offset=0, labels=None)
+      -> (dets [K, 5] float32, inds int64 [K])
+  soft_nms_pytorch(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method="linear", offset=0, labels=None)
+      Soft-NMS (Bodla et al., 2017), what mmdetection reaches with nms=dict(type='soft_nms', ...) (csrc/ops_softnms.hip; mmcv's soft_nms,
+      which runs on the CPU only, restated, unpinned: where the two differ include/frcnn_hip.h holds; the signature is mmcv's plus
+      `labels`, as nms_rotated has it).  boxes float32 [N, 4] rows (x1, y1, x2, y2); scores float32 [N]; method "naive", "linear" or
+      "gaussian"; offset 0 or 1; sigma > 0; labels None or an integer tensor [N] of any int64 values.  The contract: all arithmetic is
+      float32, every operation rounded on its own, the division IEEE; iou_threshold (thr), sigma and min_score are first rounded to
+      float32; min / max ignore a NaN operand (fmin / fmax).  Each label is an independent problem (no labels: one problem).  Every box
+      has a working score s_j = scores[j]; the live set starts as all of the problem's boxes; while it is not empty: (1) pick the live
+      box i with the largest s, ties to the smaller index, NaN scores after every number and in index order (as nms orders its
+      visits); i leaves the live set and is kept with its current s_i whatever that is -- the first pick of a problem is kept even
+      below min_score; (2) for every live j: area = (x2 - x1 + offset) * (y2 - y1 + offset), w = max(0, min(x2_i, x2_j) -
+      max(x1_i, x1_j) + offset), h likewise, inter = w * h, ovr = inter / ((area_i + area_j) - inter), a NaN ovr (0 / 0) counting as 0;
+      (3) weight = naive: 0 if ovr >= thr else 1; linear: 1 - ovr if ovr >= thr else 1; gaussian: expf(-(ovr * ovr) / sigma);
+      (4) s_j = s_j * weight, and j is dropped from the live set if s_j < min_score (a NaN s_j never is).  inds: the kept boxes of all
+      problems by descending final score, ties by ascending index, NaN last, as batched_nms merges -- within one problem of
+      non-negative scores that is exactly the pick order (the header proves it), so the kernel emits no rank; dets =
+      cat(boxes[inds], final_scores[inds, None]).  No autograd (mmcv has none): the results are detached.  It differs from upstream in
+      three places: the tie rule (mmcv's depends on its in-place swaps), a NaN ovr (0 here), and labels -- mmdetection's
+      coordinate-offset trick lets a pick of one class drop a box of another class that is already below min_score, here a box is only
+      ever touched by picks of its own label.  One launch: one workgroup owns one problem from its first pick to its last (the picks
+      are a dependent chain), labels run side by side; the state of a problem lives in LDS up to 4096 boxes, in registers up to 64.
+      N == 0 gives ([0, 5], [0]) without a launch; N <= MAX_SOFT_NMS_BOXES = 65536, else a ValueError naming N (one label may hold every
+      box; one workgroup then runs N dependent picks).  float64 or 16-bit boxes or scores and non-integer labels are a TypeError (pass
+      .float(), or use soft_nms_pytorch); wrong shapes, an unknown method, an offset outside {0, 1}, sigma <= 0 or not finite, a NaN
+      iou_threshold or min_score, differing devices and CPU tensors a ValueError.  soft_nms_pytorch is the same contract from torch
+      operations, one vectorised rescoring per pick, on any device, in float32 and in float64 (the boxes' dtype): the fallback, and the
+      CPU reference users can read.
   carafe(features, masks, kernel_size, group_size, scale_factor) -> Tensor [N, C, s H, s W]
   CARAFE(kernel_size, group_size, scale_factor).forward(features, masks)
   CARAFEPack(channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1, compressed_channels=64).forward(x)
@@ -296,7 +326,7 @@ from . import _native as nv
 __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign", "multi_scale_roi_align", "MultiScaleRoIAlign",
            "ps_roi_pool", "ps_roi_align", "PSRoIPool", "PSRoIAlign", "deform_conv2d", "DeformConv2d", "deform_roi_pool", "DeformRoIPool",
            "DeformRoIPoolPack", "ModulatedDeformRoIPoolPack", "box_iou_rotated", "nms_rotated", "roi_align_rotated", "RoIAlignRotated",
-           "diff_iou_rotated_2d", "diff_iou_rotated_3d", "diff_iou_rotated_2d_pytorch",
+           "diff_iou_rotated_2d", "diff_iou_rotated_3d", "diff_iou_rotated_2d_pytorch", "soft_nms", "soft_nms_pytorch",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
            "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4"]
@@ -309,6 +339,11 @@ PRROI_CULL_LIST = 1024                    # RoIs that prroi_pool's input-gradien
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
 MAX_ROTATED_IOU_ROWS = 65535 * 64         # rows of box_iou_rotated's matrix (the tile rows of its launch grid)
+MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
+                                          # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
+                                          # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
+                                          # 65536 boxes are picked one after the other (16384 boxes: 157 ms, 4096: 14 ms)
+SOFT_NMS_METHODS = {"naive": 0, "linear": 1, "gaussian": 2}     # mmcv's method codes
 MAX_LEVELS = 8
 DEFORM_CHUNK_IMAGES = 32                  # images per chunk of deform_conv2d's column workspace (torchvision processes 32 at a time too)
 MAX_DEFORM_INDEX = 2 ** 31 - 1 - 1024     # what the 32-bit indices of csrc/ops_deform.hip hold: columns, cells and plan entries of a chunk
@@ -1263,6 +1298,43 @@ def _(boxes, scores, labels, iou_threshold):
     return _nms_fake_result(boxes)
 
 
+# ---- frcnn::soft_nms (csrc/ops_softnms.hip) ------------------------------------------------------------------------------------------
+@torch.library.custom_op("frcnn::soft_nms", mutates_args=())
+def _soft_nms_op(boxes: Tensor, scores: Tensor, labels: Optional[Tensor], iou_threshold: float, sigma: float, min_score: float,
+                 method: int, offset: int) -> Tuple[Tensor, Tensor]:
+    """(the final scores of the kept boxes [K], their indices int64 [K]): by descending final score, ties by ascending index, NaN last."""
+    n = boxes.shape[0]
+    if n == 0:
+        return scores.new_empty((0,)), torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        cats = None
+        if labels is not None:
+            cats = labels.to(torch.int64).contiguous()
+            order = torch.sort(cats, stable=True).indices                     # each label one run, ascending in the index inside it
+        else:
+            order = torch.arange(n, dtype=torch.int64, device=boxes.device)
+        ws = _workspace("soft_nms", boxes, n)
+        keep = torch.empty((n,), dtype=torch.uint8, device=boxes.device)
+        out = torch.empty((n,), dtype=torch.float32, device=boxes.device)
+        b, s = boxes.contiguous(), scores.contiguous()
+        nv.check(nv.lib().frcnn_ops_soft_nms(b.data_ptr(), s.data_ptr(), order.data_ptr(), _opt_ptr(cats), n, iou_threshold, sigma,
+                                             min_score, method, offset, out.data_ptr(), keep.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _stream(boxes)), "frcnn_ops_soft_nms")
+        kept = keep.bool()
+        inds, final = order[kept], out[kept]
+        if cats is not None:                                                   # merge the labels: ascending index first
+            inds, by_index = torch.sort(inds)
+            final = final[by_index]
+        rank = _score_order(final)                                             # a problem's picks already are in this order
+        return final[rank], inds[rank]
+
+
+@_soft_nms_op.register_fake
+def _(boxes, scores, labels, iou_threshold, sigma, min_score, method, offset):
+    k = torch.library.get_ctx().new_dynamic_size()
+    return scores.new_empty((k,), dtype=torch.float32), boxes.new_empty((k,), dtype=torch.int64)
+
+
 @torch.library.custom_op("frcnn::roi_align_rotated", mutates_args=())
 def _roi_align_rotated(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, sampling_ratio: int,
                        aligned: bool, clockwise: bool) -> Tensor:
@@ -2020,6 +2092,122 @@ def nms_rotated(boxes, scores, iou_threshold, labels=None, clockwise=True):
             raise ValueError("labels must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(labels.shape)))
     keep = _nms_rotated_op(b.detach(), scores.detach(), labels, float(iou_threshold))
     return torch.cat([boxes[keep], scores[keep, None]], dim=1), keep
+
+
+def _f32(v):
+    """v rounded to float32, as the kernels receive it."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _soft_nms_args(boxes, scores, iou_threshold, sigma, min_score, method, offset, labels):
+    """The checks soft_nms and soft_nms_pytorch share (dtypes and devices are each one's own); returns (thr, sigma, min_score) rounded
+    to float32, the method's code and the offset."""
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be [N, 4] (x1, y1, x2, y2), got shape %s" % (tuple(boxes.shape),))
+    if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise ValueError("scores must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(scores.shape)))
+    _check_same_device(boxes, scores, "boxes", "scores")
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor):
+            raise TypeError("labels must be a torch.Tensor, got %s" % type(labels).__name__)
+        if labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise TypeError("labels must be an integer tensor, got %s" % labels.dtype)
+        _check_same_device(boxes, labels, "boxes", "labels")
+        if labels.dim() != 1 or labels.shape[0] != boxes.shape[0]:
+            raise ValueError("labels must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(labels.shape)))
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError("method must be 'naive', 'linear' or 'gaussian', got %r" % (method,))
+    if isinstance(offset, bool) or offset not in (0, 1):
+        raise ValueError("offset must be 0 or 1, got %r" % (offset,))
+    thr, sig, low = _f32(iou_threshold), _f32(sigma), _f32(min_score)
+    if not (sig > 0 and math.isfinite(sig)):
+        raise ValueError("sigma must be positive and finite, got %r" % (sigma,))
+    if math.isnan(thr):
+        raise ValueError("iou_threshold must not be NaN, got %r" % (iou_threshold,))
+    if math.isnan(low):
+        raise ValueError("min_score must not be NaN, got %r" % (min_score,))
+    return thr, sig, low, SOFT_NMS_METHODS[method], int(offset)
+
+
+def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method="linear", offset=0, labels=None):
+    """mmcv.ops.soft_nms on the GPU, within each label when labels are given: Soft-NMS with naive, linear or gaussian rescoring under the
+    contract of the module docstring (float32, ties to the smaller index, a box only ever touched by picks of its own label).  Returns
+    (dets [K, 5] = cat(boxes[inds], final_scores[inds, None]), inds int64 [K]), by descending final score, ties by ascending index,
+    NaN last.  No autograd."""
+    what = "float32 (soft_nms is float32 only: pass .float(), or use soft_nms_pytorch)"
+    _check_tensor("boxes", boxes, (torch.float32,), what, "soft_nms_pytorch")
+    _check_tensor("scores", scores, (torch.float32,), what, "soft_nms_pytorch")
+    thr, sig, low, code, off = _soft_nms_args(boxes, scores, iou_threshold, sigma, min_score, method, offset, labels)
+    if boxes.shape[0] > MAX_SOFT_NMS_BOXES:
+        raise ValueError("soft_nms takes at most MAX_SOFT_NMS_BOXES = %d boxes, got N = %d" % (MAX_SOFT_NMS_BOXES, boxes.shape[0]))
+    final, inds = _soft_nms_op(boxes.detach(), scores.detach(), labels, thr, sig, low, code, off)
+    return torch.cat([boxes.detach()[inds], final[:, None]], dim=1), inds
+
+
+def _soft_nms_problem(boxes, scores, thr, sig, low, code, off):
+    """One problem of soft_nms_pytorch: (the final scores, live-or-kept mask) of its boxes."""
+    m = boxes.shape[0]
+    x1, y1, x2, y2 = boxes.unbind(1)
+    area = (x2 - x1 + off) * (y2 - y1 + off)
+    s = scores.clone()
+    live = torch.ones((m,), dtype=torch.bool, device=boxes.device)
+    kept = torch.zeros_like(live)
+    index = torch.arange(m, device=boxes.device)
+    for _ in range(m):
+        if not bool(live.any()):
+            break
+        number = live & ~torch.isnan(s)
+        if bool(number.any()):
+            cand = number & (s == s[number].max())
+        else:
+            cand = live                                                        # NaN scores only: in index order
+        i = int(torch.where(cand, index, m).min())
+        live[i] = False
+        kept[i] = True
+        zero = torch.zeros_like(s)
+        w = torch.fmax(zero, torch.fmin(x2[i], x2) - torch.fmax(x1[i], x1) + off)
+        h = torch.fmax(zero, torch.fmin(y2[i], y2) - torch.fmax(y1[i], y1) + off)
+        inter = w * h
+        ovr = inter / ((area[i] + area) - inter)
+        ovr = torch.where(torch.isnan(ovr), zero, ovr)
+        if code == 2:
+            weight = torch.exp(-(ovr * ovr) / sig)
+        elif code == 1:
+            weight = torch.where(ovr >= thr, 1 - ovr, torch.ones_like(ovr))
+        else:
+            weight = torch.where(ovr >= thr, torch.zeros_like(ovr), torch.ones_like(ovr))
+        s = torch.where(live, s * weight, s)
+        live = live & ~(s < low)
+    return s, kept
+
+
+def soft_nms_pytorch(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method="linear", offset=0, labels=None):
+    """soft_nms from torch operations under the same contract, one vectorised rescoring per pick (and a few host syncs): the fallback
+    and the reference users can read, on any device, in float32 or float64 (the boxes' dtype; iou_threshold, sigma and min_score are
+    rounded to float32 first either way).  Returns (dets [K, 5] in the boxes' dtype, inds int64 [K])."""
+    for name, t in (("boxes", boxes), ("scores", scores)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError("%s must be float32 or float64, got %s" % (name, t.dtype))
+    if boxes.dtype != scores.dtype:
+        raise TypeError("boxes and scores must have one dtype, got %s and %s" % (boxes.dtype, scores.dtype))
+    thr, sig, low, code, off = _soft_nms_args(boxes, scores, iou_threshold, sigma, min_score, method, offset, labels)
+    boxes, scores = boxes.detach(), scores.detach()
+    n = boxes.shape[0]
+    final = scores.clone()
+    kept = torch.zeros((n,), dtype=torch.bool, device=boxes.device)
+    if labels is None:
+        problems = [torch.arange(n, device=boxes.device)] if n else []
+    else:
+        problems = [(labels == v).nonzero()[:, 0] for v in torch.unique(labels)]
+    for rows in problems:
+        s, k = _soft_nms_problem(boxes[rows], scores[rows], thr, sig, low, code, off)
+        final[rows] = s
+        kept[rows] = k
+    inds = kept.nonzero()[:, 0]
+    inds = inds[_score_order(final[inds])]
+    return torch.cat([boxes[inds], final[inds, None]], dim=1), inds
 
 
 def roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True, clockwise=False):

@@ -82,7 +82,9 @@ extern "C" {
                                  the _16 forms and the frcnn_ops_dcnv4_block_items / _record getters (DCNv4: FlashInternImage's deformable
                                  convolution v4, one packed offset_mask tensor, optionally without the centre point);
                                  still 21 (additions only): frcnn_ops_diff_iou_rotated and its _backward (the differentiable IoU of aligned
-                                 rotated boxes: mmcv's diff_iou_rotated_2d / _3d) */
+                                 rotated boxes: mmcv's diff_iou_rotated_2d / _3d);
+                                 still 21 (additions only): frcnn_ops_soft_nms, its _workspace_bytes and the frcnn_ops_soft_nms_block_threads /
+                                 _lds_boxes / _max_boxes getters (Soft-NMS, per label: mmcv's CPU-only soft_nms) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -790,6 +792,49 @@ int frcnn_ops_roi_align_rotated_16(int elem_type, const void* d_x, int n_img, in
 int frcnn_ops_roi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h,
                                             int out_w, float spatial_scale, int sampling_ratio, int aligned, int clockwise,
                                             const void* d_dout, void* d_dx, void* stream);
+
+/* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
+ *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).
+ * The contract.  All arithmetic is float32, every operation rounded on its own (no contraction), the division IEEE; min and max are
+ *   fminf / fmaxf (a NaN operand gives the other one).  thr = iou_threshold, sigma and min_score arrive as float32; off = (float)offset.
+ *   Each label (d_categories) is an independent problem; without labels there is one problem.  Within a problem every box j has a
+ *   working score s_j = d_scores[j] and area_j = (x2_j - x1_j + off) * (y2_j - y1_j + off); the live set starts as all of the
+ *   problem's boxes.  While the live set is not empty:
+ *     1. pick the live box i with the largest s; ties (-0 == +0 is one) go to the smaller box index; NaN scores rank after every
+ *        number, among themselves by index.  Box i leaves the live set and is KEPT with its current s_i, whatever that is: the first
+ *        pick of a problem is kept even when its score is below min_score;
+ *     2. for every live j: w = max(0, min(x2_i, x2_j) - max(x1_i, x1_j) + off), h likewise in y, inter = w * h,
+ *        ovr = inter / ((area_i + area_j) - inter), and a NaN ovr (0 / 0) counts as 0;
+ *     3. weight = method 0 (naive): ovr >= thr ? 0 : 1;  1 (linear): ovr >= thr ? 1 - ovr : 1;  2 (gaussian): expf(-(ovr * ovr) / sigma);
+ *     4. s_j = s_j * weight; if s_j < min_score, j leaves the live set and is DROPPED (a NaN s_j never is).
+ *   The final score of a kept box is the s it was picked with.
+ *   The output order is (final score descending, ties by ascending index, NaN last) over the kept boxes of all problems.  Within one
+ *   problem of non-negative scores and proper boxes that is exactly the pick order, so this entry point returns no rank and the
+ *   caller sorts by that key, which also merges the problems.  Proof: picks are non-increasing -- pick t is the maximum of the live
+ *   set, every live s_j <= s_t, and for ovr in [0, 1] all three weights lie in [0, 1], so s_j * weight <= s_j <= s_t when s_j >= 0:
+ *   the maximum of the next live set is no larger; a NaN is picked only when no number is live, and no number becomes live later.
+ *   And two picks t < u with equal final scores: u was live at pick t with s_u(then) >= s_u(final) = s_t, and s_u(then) <= s_t, so
+ *   it tied with t there and t won by the smaller index.  (Negative scores, which a weight below 1 raises, or inverted boxes, whose
+ *   ovr can leave [0, 1], can break the chain; the sort key is the definition of the output order either way.)
+ * frcnn_ops_soft_nms: d_boxes float32 [n][4] rows (x1, y1, x2, y2), d_scores float32 [n].  d_order int64 [n]: a permutation of the box
+ *   indices in which each label is one run, as frcnn_ops_nms expects, and ASCENDING in the index inside a run (the tie rule reads the
+ *   position); d_categories int64 [n] by box index, any values, or NULL: one problem, d_order then ascending.  Outputs by POSITION s in
+ *   d_order: d_keep[s] = 1 iff box d_order[s] is kept, d_scores_out[s] = the score it was picked with, or, for a dropped box, the
+ *   rescored value that dropped it; every element of both is written.  0 <= n <= frcnn_ops_soft_nms_max_boxes() = 65536: one label may
+ *   hold every box, and one workgroup then runs n dependent picks.  d_ws of frcnn_ops_soft_nms_workspace_bytes(n) bytes holds the state
+ *   of problems longer than frcnn_ops_soft_nms_lds_boxes() = 4096 (shorter ones live in LDS, those of at most 64 boxes in the registers
+ *   of one wave); a workgroup has frcnn_ops_soft_nms_block_threads() = 512 threads, thread i owning positions i, i + 512, ... of its
+ *   problem.  One launch; deterministic (no atomics, and the argmax key is a total order).
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): n outside the range, method outside {0, 1, 2}, offset outside
+ *   {0, 1}, sigma not positive and finite, a NaN iou_threshold or min_score, and for n > 0 NULL pointers (d_categories excepted) or a
+ *   small workspace.  n == 0 returns FRCNN_OK. */
+int frcnn_ops_soft_nms_block_threads(void);
+int frcnn_ops_soft_nms_lds_boxes(void);
+int frcnn_ops_soft_nms_max_boxes(void);
+size_t frcnn_ops_soft_nms_workspace_bytes(int n);
+int frcnn_ops_soft_nms(const float* d_boxes, const float* d_scores, const int64_t* d_order, const int64_t* d_categories, int n,
+                       float iou_threshold, float sigma, float min_score, int method, int offset, float* d_scores_out, uint8_t* d_keep,
+                       void* d_ws, size_t ws_bytes, void* stream);
 
 /* CARAFE, content-aware reassembly of features (the learned upsampler of FPN_CARAFE necks; csrc/ops_carafe.hip): mmcv's carafe, restated
  *   from its published definition (third party, absent here: restated, unpinned; where the two differ this text holds).
