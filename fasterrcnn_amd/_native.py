@@ -88,6 +88,8 @@ SYMBOLS = (
     "frcnn_ops_dcnv4_record", "frcnn_ops_dcnv4_block_items", "frcnn_ops_dcnv4_workspace_bytes",
     "frcnn_ops_dcnv4_forward", "frcnn_ops_dcnv4_backward_offset_mask", "frcnn_ops_dcnv4_plan", "frcnn_ops_dcnv4_backward_input",
     "frcnn_ops_dcnv4_forward_16", "frcnn_ops_dcnv4_backward_offset_mask_16", "frcnn_ops_dcnv4_backward_input_16",
+    "frcnn_ops_border_align_cull_list", "frcnn_ops_border_align", "frcnn_ops_border_align_backward", "frcnn_ops_border_align_16",
+    "frcnn_ops_border_align_backward_16",
 )
 
 
@@ -360,6 +362,12 @@ _SIGNATURES = {
     "frcnn_ops_prroi_pool_backward": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_ops_prroi_pool_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     "frcnn_ops_prroi_pool_backward_16": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # BorderAlign (csrc/ops_border.hip); c is the channels of one edge group; the _16 forms take the element-type code first
+    "frcnn_ops_border_align_cull_list": (C.c_int, []),
+    "frcnn_ops_border_align": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_border_align_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_border_align_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_border_align_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # DCNv3 (csrc/ops_dcnv3.hip): n, h, w, g, gc, kernel, stride, padding and dilation (h, w each), offset_scale; the _16 forms take the
     # element-type code first
     "frcnn_ops_dcnv3_max_kernel": (C.c_int, []),

@@ -13,6 +13,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import prroi_pool, PrRoIPool, prroi_pool_pytorch
     from fasterrcnn_amd.ops import dcnv3, DCNv3Function, dcnv3_core_pytorch, DCNv3
     from fasterrcnn_amd.ops import dcnv4, DCNv4Function, dcnv4_core_pytorch, DCNv4
+    from fasterrcnn_amd.ops import border_align, BorderAlign, border_align_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -299,6 +300,30 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       parameter names (offset_mask, and value_proj / output_proj unless without_pointwise; offset_mask_dw, a depthwise Conv2d, only with
       dw_kernel_size) and init (zeros on offset_mask, Xavier-uniform with zero bias on the projections), so checkpoints load strict; any
       Gc in [1, 256] works (upstream's Gc % 16 == 0 is not required); center_feature_scale is not implemented (NotImplementedError).
+  border_align(input, boxes, pool_size) -> Tensor [N, C, K, 4]
+  BorderAlign(pool_size).forward(input, boxes)
+  border_align_pytorch(input, boxes, pool_size)
+      BorderAlign, the border pooling of BorderDet's heads (csrc/ops_border.hip; mmcv's border_align restated, unpinned: where the two
+      differ include/frcnn_hip.h holds).  input [N, 4 C, H, W], channels [0, C) for the top edge, [C, 2 C) left, [2 C, 3 C) bottom,
+      [3 C, 4 C) right; boxes [N, K, 4] as (x1, y1, x2, y2) in map coordinates, float32 or the input's own 16-bit dtype, any strides; K
+      need not be H W.  The result is [N, C, K, 4] (channels_last memory), last axis top, left, bottom, right, in the input's dtype.  All
+      arithmetic is float32.  Edge e starts at (x1, y1) (top, left) or (x2, y2) (bottom, right) and steps by s = (x2 - x1) / pool_size
+      along x (top: +s, bottom: -s) or (y2 - y1) / pool_size along y (left: +s, right: -s); sample i = 0 .. pool_size lies at
+      (x0 + (float)i dx, y0 + (float)i dy), the product first, in both directions (mmcv accumulates x += stride forwards and multiplies
+      backwards).  A sample counts iff -1 <= y <= H and -1 <= x <= W, with roi_align's bilinear value (coordinates <= 0 go to 0, a low
+      index >= size - 1 collapses to the last cell); otherwise, NaN included, it is exactly 0 and receives nothing.  No box is rejected
+      as a whole: inverted, empty and non-finite boxes are sampled by that rule.  out[n, c, k, e] is the maximum over i under
+      val > best from i = 0: ties go to the smallest i, a NaN sample never replaces the running value, a NaN at i = 0 stays.  The int32
+      argmax is saved and the backward sends dout[n, c, k, e] to the four cells of that sample: roi_align's 2 x 2 tile gather with one
+      wave per edge group, which tests BORDER_ALIGN_CULL_LIST = 64 boxes at once and walks the ballot's bits, each lane re-deriving its
+      channels' samples from their argmax; ascending box order, no atomics (two runs agree bit for bit; mmcv's is an atomic scatter).
+      boxes get no gradient (None), as in mmcv; double backward raises.  16-bit maps under the contract below (output and d_input; the
+      argmax is the widened map's).  Limits:
+      pool_size in [1, MAX_BORDER_POOL = 64], H, W <= MAX_BORDER_SIDE = 2 ** 24, and the flat launch grids N K 4 ceil(C / 4) and
+      N ceil(C / 256) ceil(H / 2) ceil(W / 2) <= MAX_BORDER_INDEX.  N == 0, K == 0 or C == 0 give empty results and a zero d_input
+      without a launch.  border_align_pytorch is the same contract from torch operations (index gathers and torch.max), on any device,
+      differentiable by autograd, in float64 for a float64 map and float32 otherwise: the CPU route, and what tools/ops_bench.py
+      measures the kernels against.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -329,7 +354,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "diff_iou_rotated_2d", "diff_iou_rotated_3d", "diff_iou_rotated_2d_pytorch", "soft_nms", "soft_nms_pytorch",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
-           "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4"]
+           "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4",
+           "border_align", "BorderAlign", "border_align_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -359,6 +385,11 @@ MAX_DCNV3_KERNEL = 7                      # dcnv3: kh and kw (frcnn_ops_dcnv3_ma
 MAX_DCNV3_CHANNELS = 256                  # dcnv3: channels of one group (frcnn_ops_dcnv3_max_channels())
 MAX_DCNV3_STEP = 65536                    # dcnv3: stride, dilation and padding (the integer part of a coordinate stays far inside 32 bits)
 MAX_DCNV3_SIDE = 2 ** 24                  # dcnv3: H and W, exact in float32
+MAX_BORDER_POOL = 64                      # border_align: pool_size (BorderDet uses 10)
+MAX_BORDER_SIDE = 2 ** 24                 # border_align: H and W, exact in float32
+MAX_BORDER_INDEX = 2 ** 31 - 1 - 1024     # border_align's flat launch grids (csrc/ops_border.hip): the forward's lanes N K 4 ceil(C / 4) and the
+                                          # backward's blocks N ceil(C / 256) ceil(H / 2) ceil(W / 2)
+BORDER_ALIGN_CULL_LIST = 64               # boxes a wave of border_align's input-gradient gather tests at once (BORDER_GROUP of csrc/ops_border.hip)
 CARAFE_RUN = 4                            # channels a thread of carafe's d_features gather owns: G ceil(C / G / 4) blocks along the grid's y
 
 
@@ -1138,6 +1169,88 @@ def _prroi_pool_bwd(ctx, grad):
 
 
 _register_autograd("prroi_pool", _prroi_pool_bwd, _prroi_pool_setup)
+
+
+# ---- frcnn::border_align (the map NHWC with each edge group padded to whole runs; csrc/ops_border.hip) ------------------------------
+def _border_groups(x, cp, fill=0):
+    """x [A, 4 c, B, D] as a channels_last [A, 4 cp, B, D] tensor, each of the four edge groups padded to cp channels; no copy when x
+    already is one."""
+    c = x.shape[1] // 4
+    if cp == c:
+        return x.contiguous(memory_format=_CL)
+    xp = torch.full((x.shape[0], 4 * cp) + tuple(x.shape[2:]), fill, dtype=x.dtype, device=x.device).contiguous(memory_format=_CL)
+    xp.unflatten(1, (4, cp))[:, :, :c].copy_(x.unflatten(1, (4, c)))
+    return xp
+
+
+@torch.library.custom_op("frcnn::border_align", mutates_args=())
+def _border_align(input: Tensor, boxes: Tensor, pool_size: int) -> tuple[Tensor, Tensor]:
+    """(output, int32 argmax), both [N, C, K, 4] in channels_last memory ([N, K, 4, C])."""
+    n, c4, h, w = input.shape
+    c, k = c4 // 4, boxes.shape[1]
+    out = _empty_cl((n, c, k, 4), input)
+    argmax = _empty_cl((n, c, k, 4), input, torch.int32)
+    if n * c * k == 0:
+        return out, argmax
+    if h * w == 0:
+        return out.zero_(), argmax.zero_()
+    with torch.cuda.device(input.device):
+        cp = _padded_channels(c, input.dtype)
+        x = _border_groups(input, cp)
+        b = boxes.contiguous()
+        padded = cp != c
+        dst = _empty_cl((n, cp, k, 4), input) if padded else out
+        am = _empty_cl((n, cp, k, 4), input, torch.int32) if padded else argmax
+        _call("border_align", input, x.data_ptr(), n, h, w, cp, b.data_ptr(), k, pool_size, dst.data_ptr(), am.data_ptr(), _stream(input))
+        if padded:
+            out.copy_(dst[:, :c])
+            argmax.copy_(am[:, :c])
+    return out, argmax
+
+
+@_border_align.register_fake
+def _(input, boxes, pool_size):
+    shape = (input.shape[0], input.shape[1] // 4, boxes.shape[1], 4)
+    return _empty_cl(shape, input), _empty_cl(shape, input, torch.int32)
+
+
+@torch.library.custom_op("frcnn::border_align_backward", mutates_args=())
+def _border_align_backward(grad: Tensor, boxes: Tensor, argmax: Tensor, pool_size: int, height: int, width: int,
+                           channels_last: bool) -> Tensor:
+    n, c, k, _ = grad.shape
+    if n * c * height * width == 0:
+        return _format(grad.new_zeros((n, 4 * c, height, width)), channels_last)
+    with torch.cuda.device(grad.device):
+        cp = _padded_channels(c, grad.dtype)
+        g = _nhwc(grad)
+        am = _nhwc(argmax, like=grad)
+        b = boxes.contiguous()
+        dx = _empty_cl((n, 4 * cp, height, width), grad)
+        _call("border_align_backward", grad, b.data_ptr() if k else None, k, n, height, width, cp, pool_size, am.data_ptr() if k else None,
+              g.data_ptr() if k else None, dx.data_ptr(), _stream(grad))
+        if cp != c:
+            dx = dx.unflatten(1, (4, cp))[:, :, :c].flatten(1, 2)
+        return _format(dx, channels_last)
+
+
+@_border_align_backward.register_fake
+def _(grad, boxes, argmax, pool_size, height, width, channels_last):
+    return _grad_empty((grad.shape[0], 4 * grad.shape[1], height, width), grad, channels_last)
+
+
+def _border_align_setup(ctx, inputs, output):
+    input, boxes, pool_size = inputs
+    ctx.save_for_backward(boxes, output[1])
+    ctx.args = (pool_size, input.shape[2], input.shape[3])
+    ctx.channels_last = _input_is_channels_last(input)
+
+
+def _border_align_bwd(ctx, grad, grad_argmax):
+    boxes, argmax = ctx.saved_tensors
+    return _border_align_backward(grad, boxes, argmax, *ctx.args, ctx.channels_last), None, None
+
+
+_register_autograd("border_align", _border_align_bwd, _border_align_setup)
 
 
 # ---- frcnn::nms, frcnn::batched_nms -----------------------------------------------------------------------------------------------
@@ -1942,6 +2055,103 @@ def prroi_pool_pytorch(input, rois, output_size, spatial_scale=1.0):
     return out.to(input.dtype)
 
 
+def _border_pool_size(pool_size):
+    _check_int("pool_size", pool_size)
+    if not 1 <= pool_size <= MAX_BORDER_POOL:
+        raise ValueError("pool_size must lie in [1, %d], got %d" % (MAX_BORDER_POOL, pool_size))
+    return pool_size
+
+
+def _border_shapes(input, boxes):
+    """The shape rules border_align and border_align_pytorch share."""
+    if input.dim() != 4:
+        raise ValueError("input must be [N, 4 C, H, W], got shape %s" % (tuple(input.shape),))
+    if input.shape[1] % 4 != 0:
+        raise ValueError("input must have 4 C channels (top, left, bottom, right groups of C), got %d" % input.shape[1])
+    if boxes.dim() != 3 or boxes.shape[0] != input.shape[0] or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [N, K, 4] (x1, y1, x2, y2) with N = %d, got shape %s" % (input.shape[0], tuple(boxes.shape)))
+
+
+def border_align(input, boxes, pool_size):
+    """BorderAlign (BorderDet's border pooling; mmcv's border_align, restated, unpinned): [N, C, K, 4] (channels_last memory), per box
+    and edge (top, left, bottom, right) the per-channel maximum of pool_size + 1 bilinear samples along the edge, taken from that
+    edge's group of the 4 C channels; differentiable in input."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT, "border_align_pytorch")
+    dtypes, what = _box_dtypes(input)
+    _check_tensor("boxes", boxes, dtypes, what, "border_align_pytorch")
+    _check_same_device(input, boxes, "input", "boxes")
+    _border_shapes(input, boxes)
+    pool_size = _border_pool_size(pool_size)
+    n, c4, h, w = input.shape
+    c, k = c4 // 4, boxes.shape[1]
+    if h > MAX_BORDER_SIDE or w > MAX_BORDER_SIDE:
+        raise ValueError("input: H and W must be <= %d, got %d x %d" % (MAX_BORDER_SIDE, h, w))
+    lanes = n * k * 4 * ((c + 3) // 4)
+    blocks = n * ((c + 255) // 256) * ((h + 1) // 2) * ((w + 1) // 2)
+    if lanes > MAX_BORDER_INDEX:
+        raise ValueError("N K 4 ceil(C / 4) = %d exceeds %d (the forward's launch grid)" % (lanes, MAX_BORDER_INDEX))
+    if blocks > MAX_BORDER_INDEX:
+        raise ValueError("N ceil(C / 256) ceil(H / 2) ceil(W / 2) = %d exceeds %d (the backward's launch grid)" % (blocks, MAX_BORDER_INDEX))
+    return _border_align(input, boxes.float(), pool_size)[0]
+
+
+def _border_axis_pytorch(v, size):
+    """roi_align's rule for one coordinate already known to lie in [-1, size]: (low index, high index, weight of low, weight of high)."""
+    v = v.clamp(min=0)
+    low = v.long()
+    last = low >= size - 1
+    low = torch.where(last, torch.full_like(low, size - 1), low)
+    high = torch.where(last, low, low + 1)
+    v = torch.where(last, low.to(v.dtype), v)
+    wh = v - low.to(v.dtype)
+    return low, high, 1 - wh, wh
+
+
+def border_align_pytorch(input, boxes, pool_size):
+    """border_align from torch operations, on any device, with autograd to input: the fallback, and what tools/ops_bench.py measures the
+    kernels against.  input [N, 4 C, H, W] of any floating dtype (16-bit maps compute in float32, float64 in float64), boxes a
+    floating-point [N, K, 4].  Returns [N, C, K, 4] in the input's dtype.  One edge at a time it gathers the four cells of every sample
+    ([N, C, K, pool_size + 1] each) and takes torch.max over the samples, which keeps the first maximum; a NaN sample at i > 0 is
+    replaced by -inf first, so that it never wins."""
+    for name, t in (("input", input), ("boxes", boxes)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError("%s must be a floating-point torch.Tensor, got %s" % (name, t.dtype if isinstance(t, torch.Tensor)
+                                                                                   else type(t).__name__))
+    _check_same_device(input, boxes, "input", "boxes")
+    _border_shapes(input, boxes)
+    pool_size = _border_pool_size(pool_size)
+    dtype = torch.float64 if input.dtype == torch.float64 else torch.float32
+    n, c4, h, w = input.shape
+    c, k = c4 // 4, boxes.shape[1]
+    if n * c * k == 0 or h * w == 0:
+        return input.new_zeros((n, c, k, 4)) + input.sum() * 0
+    b = boxes.detach().to(dtype)
+    x1, y1, x2, y2 = (b[..., j, None] for j in range(4))                    # [N, K, 1]
+    i = torch.arange(pool_size + 1, dtype=dtype, device=input.device)      # [P + 1]
+    sx, sy = (x2 - x1) / pool_size, (y2 - y1) / pool_size
+    zero = torch.zeros_like(i)
+    edges = ((x1, y1, i * sx, zero), (x1, y1, zero, i * sy), (x2, y2, i * -sx, zero), (x2, y2, zero, i * -sy))
+    maps = input.to(dtype).reshape(n, 4, c, h * w)
+    outs = []
+    for e, (x0, y0, dx, dy) in enumerate(edges):
+        x, y = x0 + dx, y0 + dy                                             # [N, K, P + 1]
+        valid = (y >= -1) & (y <= h) & (x >= -1) & (x <= w)                 # a NaN fails
+        yl, yh, wyl, wyh = _border_axis_pytorch(torch.where(valid, y, zero), h)
+        xl, xh, wxl, wxh = _border_axis_pytorch(torch.where(valid, x, zero), w)
+
+        def cells(row, col):
+            index = (row * w + col).reshape(n, 1, -1).expand(n, c, -1)
+            return maps[:, e].gather(2, index).reshape(n, c, k, pool_size + 1)
+
+        w1, w2, w3, w4 = ((a * b)[:, None] for a, b in ((wyl, wxl), (wyl, wxh), (wyh, wxl), (wyh, wxh)))
+        vals = ((cells(yl, xl) * w1 + cells(yl, xh) * w2) + cells(yh, xl) * w3) + cells(yh, xh) * w4
+        vals = torch.where(valid[:, None], vals, torch.zeros_like(vals))
+        late_nan = torch.isnan(vals) & (i > 0)
+        vals = torch.where(late_nan, torch.full_like(vals, float("-inf")), vals)
+        outs.append(vals.max(dim=3).values)
+    return torch.stack(outs, dim=3).to(input.dtype)
+
+
 def _rotated_boxes(name, boxes, clockwise):
     """Checks a Tensor[N, 5] of rotated boxes; returns it in the kernels' convention (angles negated for clockwise=False)."""
     _check_tensor(name, boxes, (torch.float32,), "float32 (rotated boxes are float32 only: pass .float())")
@@ -2741,6 +2951,20 @@ class PrRoIPool(torch.nn.Module):
 
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s" % (self.output_size, self.spatial_scale)
+
+
+class BorderAlign(torch.nn.Module):
+    """mmcv.ops.BorderAlign: BorderDet's border pooling, input [N, 4 C, H, W] and boxes [N, K, 4] to [N, C, K, 4]."""
+
+    def __init__(self, pool_size):
+        super().__init__()
+        self.pool_size = _border_pool_size(pool_size)
+
+    def forward(self, input, boxes):
+        return border_align(input, boxes, self.pool_size)
+
+    def __repr__(self):
+        return "%s(pool_size=%d)" % (self.__class__.__name__, self.pool_size)
 
 
 def _zero_last(stack, index):

@@ -84,7 +84,9 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_diff_iou_rotated and its _backward (the differentiable IoU of aligned
                                  rotated boxes: mmcv's diff_iou_rotated_2d / _3d);
                                  still 21 (additions only): frcnn_ops_soft_nms, its _workspace_bytes and the frcnn_ops_soft_nms_block_threads /
-                                 _lds_boxes / _max_boxes getters (Soft-NMS, per label: mmcv's CPU-only soft_nms) */
+                                 _lds_boxes / _max_boxes getters (Soft-NMS, per label: mmcv's CPU-only soft_nms);
+                                 still 21 (additions only): frcnn_ops_border_align, its _backward, _16 and _cull_list forms (BorderAlign, the
+                                 border pooling of BorderDet: mmcv's border_align) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -719,6 +721,51 @@ int frcnn_ops_prroi_pool_16(int elem_type, const void* d_x, int n_img, int fh, i
 int frcnn_ops_prroi_pool_backward_16(int elem_type, const void* d_x, const float* d_rois, int k, int n_img, int fh, int fw, int c,
                                      int out_h, int out_w, float spatial_scale, const void* d_dout, void* d_dx, float* d_drois, void* d_ws,
                                      size_t ws_bytes, void* stream);
+
+/* BorderAlign, the border pooling of BorderDet (csrc/ops_border.hip): mmcv's border_align in both directions, restated from the published
+ *   definition (third party, absent here: restated, unpinned; where the two differ this text holds).
+ *   Layouts (element types as frcnn_ops_roi_align above; c = the channels of ONE edge group, c % 4 == 0, the _16 forms c % 8 == 0):
+ *     d_x      : [n_img][fh][fw][4 c], group e in channels [e c, (e + 1) c): e = 0 top, 1 left, 2 bottom, 3 right
+ *     d_boxes  : float32 [n_img][k][4] rows (x1, y1, x2, y2) in map coordinates; box r of image b pools image b
+ *     d_out    : [n_img][k][4][c];  d_argmax : int32 [n_img][k][4][c];  d_dout as d_out, d_dx as d_x
+ *   The contract.  All arithmetic is float32, every operation rounded on its own.  With P = pool_size, edge e of a box starts at
+ *   (x0, y0) and steps by (dx, dy):
+ *     e = 0 top    : (x1, y1), s = (x2 - x1) / P, ( s, 0)        e = 1 left  : (x1, y1), s = (y2 - y1) / P, (0,  s)
+ *     e = 2 bottom : (x2, y2), s = (x2 - x1) / P, (-s, 0)        e = 3 right : (x2, y2), s = (y2 - y1) / P, (0, -s)
+ *   Sample i = 0 .. P lies at (x0 + (float)i * dx, y0 + (float)i * dy): the product is formed first, then one add, in the forward and in
+ *   the backward, so the backward lands on the forward's sample exactly (mmcv accumulates x += stride forwards and multiplies backwards).
+ *   A sample counts iff -1 <= y <= fh and -1 <= x <= fw; its value is then the bilinear one of frcnn_ops_roi_align: a coordinate <= 0
+ *   goes to 0, low = (int)v, a low index >= size - 1 collapses to the last cell (low = high = size - 1, v = low), weights 1 - (v - low)
+ *   and v - low, and value = ((w1 v1 + w2 v2) + w3 v3) + w4 v4 over (y low, x low), (y low, x high), (y high, x low), (y high, x high)
+ *   with w = wy * wx.  Any other sample, a NaN coordinate included, is exactly 0 and receives no gradient.  No box is rejected as a
+ *   whole: inverted and empty boxes are simply sampled (a zero stride makes every sample the same point) and non-finite coordinates
+ *   fall under the sample rule.  No coordinate is converted to int before it has passed the range test.
+ *   d_out[b][r][e][ch] = the maximum over i of the samples of channel e c + ch, found as best = sample 0, then for i = 1 .. P:
+ *   if (val > best) take val and i.  So ties go to the smallest i, a NaN sample never replaces the running value, and a NaN at i = 0
+ *   stays.  d_argmax holds the winning i.  Every element of both is written.
+ * frcnn_ops_border_align_backward: d_dx (every element overwritten) gets, for every (b, r, e, ch), d_dout times the four bilinear weights
+ *   of sample d_argmax[b][r][e][ch] on its four cells (a collapsed pair adds both weights to the one cell); a sample outside the range
+ *   sends nothing, whatever the argmax holds.  A gather per 2 x 2 tile and 64 channel runs, one wave per edge group: the wave tests the
+ *   boxes of its image frcnn_ops_border_align_cull_list() = 64 at a time, one per lane (a box is taken for edge e when that edge's
+ *   segment, sample 0 to sample P, grown by one cell and rounded outwards, meets the tile) and walks the ballot's bits from the lowest;
+ *   each lane re-derives its channels' samples from their argmax and adds, in ascending box order over all groups, into the registers of
+ *   the tile's four cells, one store each.  Deterministic, no atomics.  k == 0 returns FRCNN_OK after
+ *   zero-filling d_dx.  d_boxes gets no gradient.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): pool_size outside [1, 64], k < 0, sizes < 1, fh or fw > 2^24
+ *   (coordinates up to the map's size are exact in float32), c not in whole runs, fh * fw beyond 32 bits, the flat launch grids
+ *   n_img k 4 (c / run) lanes (forward) or n_img ceil(c / run / 64) ceil(fh / 2) ceil(fw / 2) blocks (backward) above 2^31 - 1 - 1024,
+ *   NULL pointers.
+ * The _16 forms take float16 / bfloat16 d_x / d_out / d_dout / d_dx under the contract of the 16-bit operators above; the boxes stay
+ *   float32 and the argmax is that of the widened map. */
+int frcnn_ops_border_align_cull_list(void);
+int frcnn_ops_border_align(const float* d_x, int n_img, int fh, int fw, int c, const float* d_boxes, int k, int pool_size, float* d_out,
+                           int* d_argmax, void* stream);
+int frcnn_ops_border_align_backward(const float* d_boxes, int k, int n_img, int fh, int fw, int c, int pool_size, const int* d_argmax,
+                                    const float* d_dout, float* d_dx, void* stream);
+int frcnn_ops_border_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_boxes, int k,
+                              int pool_size, void* d_out, int* d_argmax, void* stream);
+int frcnn_ops_border_align_backward_16(int elem_type, const float* d_boxes, int k, int n_img, int fh, int fw, int c, int pool_size,
+                                       const int* d_argmax, const void* d_dout, void* d_dx, void* stream);
 
 /* Rotated boxes (oriented detection; csrc/ops_rot.hip): mmcv's box_iou_rotated, nms_rotated and roi_align_rotated, restated from their
  *   published definitions (third party, absent here: restated, unpinned; where the two differ this text holds).

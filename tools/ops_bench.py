@@ -78,6 +78,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
       80 labels x 250 boxes, linear        kept  3852   ops.soft_nms  0.405   soft_nms_pytorch on the GPU  1082.4 ( 2673x)   copies + soft_nms_pytorch on the CPU  191.0 ( 472x)
       80 labels x 250 boxes, gaussian      kept  4410   ops.soft_nms  0.392   soft_nms_pytorch on the GPU  1216.9 ( 3104x)   copies + soft_nms_pytorch on the CPU  211.2 ( 539x)
 
+  * border: BorderAlign in a BorderDet head (2 x (4 x 256) x 100 x 152, the P3 map of an 800 x 1216 image; one box per location,
+    K = H W = 15200, its four sides log-uniform in 1 to 24 cells from the location; pool_size 10), float32 and float16:
+    ops.border_align beside ops.border_align_pytorch (index gathers and torch.max, autograd's backward), forward and forward + backward,
+    in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only border          # just the BorderAlign leg
     python tools/ops_bench.py --only softnms         # just the Soft-NMS leg
     python tools/ops_bench.py --only diffiou         # just the differentiable-IoU leg
     python tools/ops_bench.py --only dcnv4           # just the DCNv4 leg
@@ -534,6 +540,35 @@ def prroi_leg(rng, reps, warmup):
     return res
 
 
+def border_leg(rng, reps, warmup):
+    n, c, h, w, pool = 2, 256, 100, 152, 10
+    gen = torch.Generator().manual_seed(0)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    sides = torch.exp(torch.rand((n, h * w, 4), generator=gen) * float(np.log(24.0)))            # left, top, right, bottom
+    centre = torch.stack([xs.reshape(-1), ys.reshape(-1)], 1)[None]
+    boxes = torch.cat([centre - sides[..., :2], centre + sides[..., 2:]], 2).to(DEV)
+    res = {}
+    for dtype in (torch.float32, torch.float16):
+        x = torch.randn((n, 4 * c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((n, c, h * w, 4), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        leaf = x.clone().requires_grad_(True)
+
+        def native(a=x):
+            return ops.border_align(a, boxes, pool)
+
+        def composed(a=x):
+            return ops.border_align_pytorch(a, boxes, pool)
+        y, yc = native().float(), composed().float()
+        r = {"max |border_align - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        for name, fns in (("fwd", (native, composed)),
+                          ("fwd+bwd", (lambda: native(leaf).backward(g), lambda: composed(leaf).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.border_align": round(t_native, 1), "ops.border_align_pytorch": round(t_comp, 1),
+                       "composition / border_align": round(t_comp / t_native, 2)}
+        res["border %s 2 x (4 x 256) x 100 x 152, K 15200, pool_size 10" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -617,7 +652,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -662,6 +697,9 @@ def main():
         return
     if a.only == "dcnv4":
         print(json.dumps(dcnv4_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "border":
+        print(json.dumps(border_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -733,6 +771,7 @@ def main():
     res.update(prroi_leg(rng, 5, 2))
     res.update(dcnv3_leg(rng, 5, 2))
     res.update(dcnv4_leg(rng, 5, 2))
+    res.update(border_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
