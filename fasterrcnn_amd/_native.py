@@ -90,6 +90,10 @@ SYMBOLS = (
     "frcnn_ops_dcnv4_forward_16", "frcnn_ops_dcnv4_backward_offset_mask_16", "frcnn_ops_dcnv4_backward_input_16",
     "frcnn_ops_border_align_cull_list", "frcnn_ops_border_align", "frcnn_ops_border_align_backward", "frcnn_ops_border_align_16",
     "frcnn_ops_border_align_backward_16",
+    "frcnn_ops_riroi_align_rotated_max_orientations", "frcnn_ops_riroi_align_rotated", "frcnn_ops_riroi_align_rotated_backward",
+    "frcnn_ops_riroi_align_rotated_16", "frcnn_ops_riroi_align_rotated_backward_16",
+    "frcnn_ops_rotated_feature_align", "frcnn_ops_rotated_feature_align_plan", "frcnn_ops_rotated_feature_align_backward",
+    "frcnn_ops_rotated_feature_align_16", "frcnn_ops_rotated_feature_align_backward_16",
 )
 
 
@@ -324,6 +328,12 @@ _SIGNATURES = {
     "frcnn_ops_roi_align_rotated_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_roi_align_rotated_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "frcnn_ops_roi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
+    # riroi_align_rotated: c (the channels in memory) then c_real (those in orientation groups); num_samples, num_orientations, clockwise
+    "frcnn_ops_riroi_align_rotated_max_orientations": (C.c_int, []),
+    "frcnn_ops_riroi_align_rotated": (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_riroi_align_rotated_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
+    "frcnn_ops_riroi_align_rotated_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_riroi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
@@ -368,6 +378,12 @@ _SIGNATURES = {
     "frcnn_ops_border_align_backward": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "frcnn_ops_border_align_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_border_align_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # rotated_feature_align (csrc/ops_rfa.hip): map, boxes, n, h, w, c, scale, points; the backward takes the sorted plan first
+    "frcnn_ops_rotated_feature_align": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+    "frcnn_ops_rotated_feature_align_plan": (C.c_int, [_vp, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "frcnn_ops_rotated_feature_align_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_rotated_feature_align_16": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+    "frcnn_ops_rotated_feature_align_backward_16": (C.c_int, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     # DCNv3 (csrc/ops_dcnv3.hip): n, h, w, g, gc, kernel, stride, padding and dilation (h, w each), offset_scale; the _16 forms take the
     # element-type code first
     "frcnn_ops_dcnv3_max_kernel": (C.c_int, []),

@@ -29,6 +29,10 @@
 // only if its local coordinates lie within sqrt(2) of the cell's on both local axes, which bounds the candidate sample rows and columns
 // analytically (rot_sample_range); every candidate is then tested exactly with the forward's own expressions.  Per RoI the bins are
 // visited in (ph, pw) order and a bin sends dout (sum of its samples' weights, in (iy, ix) order) / count.
+//
+// riroi_align_rotated (frcnn_ops_riroi_align_rotated*; mmcv's riroi_align_rotated restated): roi_align_rotated's pooling of C n channels,
+// then each group's n orientation channels rotated by the RoI's angle and blended between the two nearest.  The forward pools and blends
+// in one launch through LDS (ops_riroi_align_kernel); the backward is the gather above with the blend where it loads a bin's gradient.
 #include "ops_run.h"
 #include <cfloat>
 
@@ -385,6 +389,149 @@ void ops_rot_roi_align_kernel(const E* __restrict__ x, int n_img, int fh, int fw
     }
 }
 
+// ---- riroi_align_rotated (ReDet's rotation-invariant RoI pooling) --------------------------------------------------------------------
+// Channel c n + o of the map is orientation o of group c (n = num_orientations).  The operator is roi_align_rotated's pooled S (aligned
+// off, the opposite clockwise flag) with each group's orientations rotated by the RoI's angle: with f = angle n / (2 pi) formed in
+// double and rounded once, ind = floor(f), l = f - ind, r = 1 - l, k = ind mod n >= 0,
+//   out[c n + o] = r S[c n + (o - k) mod n] + l S[c n + (o - k + 1) mod n].
+static constexpr int RIROI_MAX_ORIENTATIONS = 64;    // a group, wherever it starts in its run, lies inside the 64 runs of one wave
+
+struct RiBlend { float l, r; int k; };
+
+// false: the RoI pools to zeros and sends no gradient (a non-finite angle, |f| >= 2^24)
+__device__ __forceinline__ bool riroi_blend(float angle, int n, RiBlend& b)
+{
+    if (!rot_finite(angle)) return false;
+    const float f = (float)((double)angle * (double)n / 6.283185307179586);
+    if (!(fabsf(f) < 16777216.f)) return false;
+    const float ind = floorf(f);
+    b.l = f - ind;
+    b.r = 1.0f - b.l;
+    const int k = (int)ind % n;
+    b.k = k < 0 ? k + n : k;
+    return true;
+}
+
+// Forward: roi_align_rotated's loop, one block per (RoI, ph), but a wave owns whole (pw, channel chunk) pieces: `cl` lanes hold the
+// pooled runs of one piece, 64 / cl pieces share a wave when the channels are few.  chunk_runs is a multiple of lcm(n, V) / V, so a
+// chunk starts on a group's first channel and no group leaves its piece: the pooled runs go to the wave's LDS row, each lane blends its
+// run's channels from there and stores once.  Channels from c_real on belong to no group and are written as zeros.
+template <typename E>
+__global__ __launch_bounds__(256)
+void ops_riroi_align_kernel(const E* __restrict__ x, int n_img, int fh, int fw, int C, int c_real, const float* __restrict__ rois,
+                            int out_h, int out_w, float scale, int sampling_ratio, int clockwise, int n_orient, int chunk_runs,
+                            E* __restrict__ out)
+{
+    typedef Run<E> R;
+    typedef typename R::vec vec;
+    constexpr int V = R::V;
+    __shared__ float s_pool[4][64 * V];
+    const int r = blockIdx.x, ph = blockIdx.y, C4 = C / V;
+    const float* roi = rois + (size_t)r * 6;
+    E* orow = out + ((size_t)r * out_h + ph) * out_w * C;
+    int b;
+    RiBlend bl;
+    if (!roi_image(roi[0], n_img, b) || !riroi_blend(roi[5], n_orient, bl)) {
+        zero_row(orow, out_w * C4);
+        return;
+    }
+    const RotGeom g = rot_geom(roi, scale, out_h, out_w, sampling_ratio, 0, !clockwise);
+    const E* fm = x + (size_t)b * fh * fw * C;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_chunks = (C4 + chunk_runs - 1) / chunk_runs;
+    const int cl = n_chunks == 1 ? C4 : chunk_runs;                // <= 64
+    const int ppw = 64 / cl;                                       // pieces (bins pw) of a wave
+    const int sub = lane / cl, li = lane - sub * cl;
+    const int total = ((out_w + ppw - 1) / ppw) * n_chunks;
+    float* pool = s_pool[wave] + (sub < ppw ? sub * cl * V : 0);
+    for (int it0 = 0; it0 < total; it0 += 4) {                     // uniform over the block: the barriers below
+        const int item = it0 + wave;
+        const int pwg = item / n_chunks, ck = item - pwg * n_chunks;
+        const int pw = pwg * ppw + sub, r0 = ck * chunk_runs, c4 = r0 + li;
+        const bool act = item < total && sub < ppw && pw < out_w && c4 < C4;
+        if (act) {
+            vec acc = 0.f;
+            for (int iy = 0; iy < g.grid_h; ++iy) {
+                const float yy = sample_coord(g.start_h, g.bin_h, g.grid_h, ph, iy);
+                for (int ix = 0; ix < g.grid_w; ++ix) {
+                    const float xx = sample_coord(g.start_w, g.bin_w, g.grid_w, pw, ix);
+                    float y, xs;
+                    rot_sample(g, yy, xx, y, xs);
+                    int yl, yh, xl, xh; float hy, ly, hx, lx;
+                    if (!rot_axis(y, fh, yl, yh, hy, ly) || !rot_axis(xs, fw, xl, xh, hx, lx)) continue;
+                    const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+                    const vec v1 = R::load(fm + ((size_t)yl * fw + xl) * C, c4);
+                    const vec v2 = R::load(fm + ((size_t)yl * fw + xh) * C, c4);
+                    const vec v3 = R::load(fm + ((size_t)yh * fw + xl) * C, c4);
+                    const vec v4 = R::load(fm + ((size_t)yh * fw + xh) * C, c4);
+                    acc = acc + (((v1 * w1 + v2 * w2) + v3 * w3) + v4 * w4);
+                }
+            }
+            acc = acc / g.count;
+#pragma unroll
+            for (int j = 0; j < V; ++j) pool[li * V + j] = acc[j];
+        }
+        __syncthreads();
+        if (act) {
+            vec o;
+            int base = c4 * V / n_orient * n_orient, ori = c4 * V - base;        // of the run's first channel; one division per run
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float v = 0.f;
+                if (c4 * V + j < c_real) {
+                    int s1 = ori - bl.k;
+                    s1 = s1 < 0 ? s1 + n_orient : s1;
+                    const int s2 = s1 + 1 == n_orient ? 0 : s1 + 1;
+                    const float* grp = pool + (base - r0 * V);
+                    v = bl.r * grp[s1] + bl.l * grp[s2];
+                }
+                o[j] = v;
+                if (++ori == n_orient) { ori = 0; base += n_orient; }
+            }
+            R::store(orow, (size_t)pw * C4 + c4, o);
+        }
+        __syncthreads();                                           // the next piece overwrites the row
+    }
+}
+
+// Backward: what a lane of the gather knows of its run's V channels -- per channel the first channel of its group (-1: no group) and its
+// orientation -- and the pooled gradient blended from the gradient row of one bin (gp [C]):
+//   dS[c n + j] = r dout[c n + (j + k) mod n] + l dout[c n + (j + k - 1) mod n].
+template <int V> struct RiLane { int base[V], o[V]; };
+
+template <int V>
+__device__ __forceinline__ RiLane<V> riroi_lane(int c4, int n, int c_real)
+{
+    RiLane<V> rl;
+    int base = c4 * V / n * n, o = c4 * V - base;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const bool real = c4 * V + j < c_real;
+        rl.base[j] = real ? base : -1;
+        rl.o[j] = real ? o : 0;
+        if (++o == n) { o = 0; base += n; }
+    }
+    return rl;
+}
+
+template <typename E>
+__device__ __forceinline__ typename Run<E>::vec riroi_grad(const E* __restrict__ gp, const RiLane<Run<E>::V>& rl, const RiBlend& bl, int n)
+{
+    typename Run<E>::vec v;
+#pragma unroll
+    for (int j = 0; j < Run<E>::V; ++j) {
+        float d = 0.f;
+        if (rl.base[j] >= 0) {
+            int a = rl.o[j] + bl.k;
+            a = a >= n ? a - n : a;
+            const int p = a == 0 ? n - 1 : a - 1;
+            d = bl.r * Run<E>::at(gp, rl.base[j] + a) + bl.l * Run<E>::at(gp, rl.base[j] + p);
+        }
+        v[j] = d;
+    }
+    return v;
+}
+
 // The sample positions s = p * grid + i (0 <= s < n_out * grid) whose local coordinate can lie within `radius` of loc: the linear model
 // of the positions (start + (s + 0.5) bin / grid), widened by one sample and a relative margin for rounding; the caller evaluates every
 // candidate exactly.  ops.hip's sample_range around a local coordinate.
@@ -411,10 +558,11 @@ __device__ __forceinline__ bool rot_touches_tile(const RotGeom& g, int ty0, int 
     return (g.cx + ex) + m >= (float)tx0 && (g.cx - ex) - m <= (float)tx1 && (g.cy + ey) + m >= (float)ty0 && (g.cy - ey) - m <= (float)ty1;
 }
 
-// Adds to acc the gradient that one RoI (plan g, output gradient rows dr [out_h][out_w][C4] runs) sends to cell (cy, cx), channel run c4
-template <typename E>
-__device__ __forceinline__ void rot_cell_grad(const RotGeom& g, const E* __restrict__ dr, int fh, int fw, int cy, int cx, int out_h,
-                                              int out_w, int C4, int c4, bool act, typename Run<E>::vec& acc)
+// Adds to acc the gradient that one RoI (plan g) sends to cell (cy, cx) for the lane's channel run: load(bin) is the RoI's output gradient
+// of that run at bin ph * out_w + pw, as float32
+template <typename E, typename Load>
+__device__ __forceinline__ void rot_cell_grad(const RotGeom& g, Load load, int fh, int fw, int cy, int cx, int out_h, int out_w, bool act,
+                                              typename Run<E>::vec& acc)
 {
     // the cell in the RoI's local frame (the inverse of rot_sample); a touching sample is within sqrt(2) of it on both local axes
     const float dx = (float)cx - g.cx, dy = (float)cy - g.cy;
@@ -443,18 +591,20 @@ __device__ __forceinline__ void rot_cell_grad(const RotGeom& g, const E* __restr
                     }
                 }
             }
-            if (hit && act) acc = acc + (Run<E>::load(dr, ((size_t)ph * out_w + pw) * C4 + c4) * w_sum) / g.count;
+            if (hit && act) acc = acc + (load((size_t)ph * out_w + pw) * w_sum) / g.count;
             sx = x_end + 1;
         }
         sy = y_end + 1;
     }
 }
 
-template <typename E>
+// RIROI (riroi_align_rotated's backward, below): dout is the gradient of the blended output; the pooled gradient dS a bin sends is blended
+// from it on the fly (riroi_grad), a RoI that riroi_blend refuses is never listed, and the channels from c_real on belong to no group.
+template <typename E, bool RIROI>
 __global__ __launch_bounds__(256)
 void ops_rot_roi_align_backward_kernel(const float* __restrict__ rois, int k, int n_img, int fh, int fw, int C, int out_h, int out_w,
-                                       float scale, int sampling_ratio, int aligned, int clockwise, const E* __restrict__ dout,
-                                       E* __restrict__ dx)
+                                       float scale, int sampling_ratio, int aligned, int clockwise, int n_orient, int c_real,
+                                       const E* __restrict__ dout, E* __restrict__ dx)
 {
     __shared__ int s_list[OPS_LIST];
     __shared__ int s_cnt[4];
@@ -473,9 +623,13 @@ void ops_rot_roi_align_backward_kernel(const float* __restrict__ rois, int k, in
         const float* roi = rois + (size_t)r * 6;
         int b;
         if (!roi_image(roi[0], n_img, b) || b != img) return false;
+        RiBlend bl;
+        if (RIROI && !riroi_blend(roi[5], n_orient, bl)) return false;
         return rot_touches_tile(rot_geom(roi, scale, out_h, out_w, sampling_ratio, aligned, clockwise), ty0, ty1, tx0, tx1);
     };
 
+    RiLane<Run<E>::V> rl;
+    if constexpr (RIROI) rl = riroi_lane<Run<E>::V>(c4, n_orient, c_real);
     typename Run<E>::vec acc = 0.f;
     int r_next = 0;
     do {
@@ -484,8 +638,17 @@ void ops_rot_roi_align_backward_kernel(const float* __restrict__ rois, int k, in
         if (cell_ok)
             for (int li = 0; li < n_list; ++li) {
                 const int r = s_list[li];
-                rot_cell_grad<E>(rot_geom(rois + (size_t)r * 6, scale, out_h, out_w, sampling_ratio, aligned, clockwise),
-                                 dout + (size_t)r * out_h * out_w * C, fh, fw, cy, cx, out_h, out_w, C4, c4, act, acc);
+                const float* roi = rois + (size_t)r * 6;
+                const E* dr = dout + (size_t)r * out_h * out_w * C;
+                const RotGeom g = rot_geom(roi, scale, out_h, out_w, sampling_ratio, aligned, clockwise);
+                if constexpr (RIROI) {
+                    RiBlend bl;
+                    riroi_blend(roi[5], n_orient, bl);                 // a listed RoI passed it
+                    rot_cell_grad<E>(g, [&](size_t bin) { return riroi_grad<E>(dr + bin * C, rl, bl, n_orient); }, fh, fw, cy, cx, out_h,
+                                     out_w, act, acc);
+                } else {
+                    rot_cell_grad<E>(g, [&](size_t bin) { return Run<E>::load(dr, bin * C4 + c4); }, fh, fw, cy, cx, out_h, out_w, act, acc);
+                }
             }
     } while (r_next < k);
     if (cell_ok && act) Run<E>::store(dx + (size_t)img * fh * fw * C, ((size_t)cy * fw + cx) * C4 + c4, acc);
@@ -518,9 +681,48 @@ static int rot_roi_align_backward_impl(const float* d_rois, int k, int n_img, in
 {
     if (!rot_args_ok(n_img, fh, fw, c, k, out_h, out_w, sampling_ratio, Run<E>::V)) return FRCNN_EINVAL;
     if (!d_dx || (k > 0 && (!d_rois || !d_dout))) return FRCNN_EINVAL;
-    hipLaunchKernelGGL(ops_rot_roi_align_backward_kernel<E>, dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / Run<E>::V, 64)),
-                       dim3(256), 0, (hipStream_t)stream, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio,
-                       aligned ? 1 : 0, clockwise ? 1 : 0, static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
+    hipLaunchKernelGGL((ops_rot_roi_align_backward_kernel<E, false>),
+                       dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / Run<E>::V, 64)), dim3(256), 0, (hipStream_t)stream, d_rois,
+                       k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, aligned ? 1 : 0, clockwise ? 1 : 0, 1, c,
+                       static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
+    return check_launch();
+}
+
+// c: the channels in memory (whole runs); c_real <= c of them form groups of n_orient
+static bool riroi_args_ok(int n_img, int fh, int fw, int c, int c_real, int k, int out_h, int out_w, int num_samples, int n_orient, int v)
+{
+    return rot_args_ok(n_img, fh, fw, c, k, out_h, out_w, num_samples, v) && n_orient >= 1 && n_orient <= RIROI_MAX_ORIENTATIONS &&
+           c_real >= n_orient && c_real <= c && c_real % n_orient == 0;
+}
+
+static int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+template <typename E>
+static int riroi_align_impl(const void* d_x, int n_img, int fh, int fw, int c, int c_real, const float* d_rois, int k, int out_h, int out_w,
+                            float spatial_scale, int num_samples, int n_orient, int clockwise, void* d_out, void* stream)
+{
+    constexpr int V = Run<E>::V;
+    if (!riroi_args_ok(n_img, fh, fw, c, c_real, k, out_h, out_w, num_samples, n_orient, V)) return FRCNN_EINVAL;
+    if (k == 0) return FRCNN_OK;
+    if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
+    const int period = n_orient / gcd_int(n_orient, V);            // runs after which groups and runs line up again: <= 64
+    hipLaunchKernelGGL(ops_riroi_align_kernel<E>, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, static_cast<const E*>(d_x), n_img, fh,
+                       fw, c, c_real, d_rois, out_h, out_w, spatial_scale, num_samples, clockwise ? 1 : 0, n_orient, 64 / period * period,
+                       static_cast<E*>(d_out));
+    return check_launch();
+}
+
+template <typename E>
+static int riroi_align_backward_impl(const float* d_rois, int k, int n_img, int fh, int fw, int c, int c_real, int out_h, int out_w,
+                                     float spatial_scale, int num_samples, int n_orient, int clockwise, const void* d_dout, void* d_dx,
+                                     void* stream)
+{
+    if (!riroi_args_ok(n_img, fh, fw, c, c_real, k, out_h, out_w, num_samples, n_orient, Run<E>::V)) return FRCNN_EINVAL;
+    if (!d_dx || (k > 0 && (!d_rois || !d_dout))) return FRCNN_EINVAL;
+    hipLaunchKernelGGL((ops_rot_roi_align_backward_kernel<E, true>),
+                       dim3(cdiv(fw, OPS_TILE), cdiv(fh, OPS_TILE), n_img * cdiv(c / Run<E>::V, 64)), dim3(256), 0, (hipStream_t)stream, d_rois,
+                       k, n_img, fh, fw, c, out_h, out_w, spatial_scale, num_samples, 0, clockwise ? 0 : 1, n_orient, c_real,
+                       static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
     return check_launch();
 }
 
@@ -610,6 +812,40 @@ int frcnn_ops_roi_align_rotated_backward_16(int elem_type, const float* d_rois, 
 {
     OPS_DISPATCH_16(elem_type, c, backward_run(c), rot_roi_align_backward_impl, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale,
                     sampling_ratio, aligned, clockwise, d_dout, d_dx, stream);
+}
+
+int frcnn_ops_riroi_align_rotated_max_orientations(void) { return RIROI_MAX_ORIENTATIONS; }
+
+int frcnn_ops_riroi_align_rotated(const float* d_x, int n_img, int fh, int fw, int c, int c_real, const float* d_rois, int k, int out_h,
+                                  int out_w, float spatial_scale, int num_samples, int num_orientations, int clockwise, float* d_out,
+                                  void* stream)
+{
+    return riroi_align_impl<float>(d_x, n_img, fh, fw, c, c_real, d_rois, k, out_h, out_w, spatial_scale, num_samples, num_orientations,
+                                   clockwise, d_out, stream);
+}
+
+int frcnn_ops_riroi_align_rotated_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int c_real, int out_h, int out_w,
+                                           float spatial_scale, int num_samples, int num_orientations, int clockwise, const float* d_dout,
+                                           float* d_dx, void* stream)
+{
+    return riroi_align_backward_impl<float>(d_rois, k, n_img, fh, fw, c, c_real, out_h, out_w, spatial_scale, num_samples,
+                                            num_orientations, clockwise, d_dout, d_dx, stream);
+}
+
+int frcnn_ops_riroi_align_rotated_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, int c_real, const float* d_rois,
+                                     int k, int out_h, int out_w, float spatial_scale, int num_samples, int num_orientations,
+                                     int clockwise, void* d_out, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, OPS_HALF_RUN, riroi_align_impl, d_x, n_img, fh, fw, c, c_real, d_rois, k, out_h, out_w, spatial_scale,
+                    num_samples, num_orientations, clockwise, d_out, stream);
+}
+
+int frcnn_ops_riroi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int c_real,
+                                              int out_h, int out_w, float spatial_scale, int num_samples, int num_orientations,
+                                              int clockwise, const void* d_dout, void* d_dx, void* stream)
+{
+    OPS_DISPATCH_16(elem_type, c, backward_run(c), riroi_align_backward_impl, d_rois, k, n_img, fh, fw, c, c_real, out_h, out_w,
+                    spatial_scale, num_samples, num_orientations, clockwise, d_dout, d_dx, stream);
 }
 
 }  // extern "C"

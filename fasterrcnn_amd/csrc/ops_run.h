@@ -36,6 +36,7 @@ template <> struct Run<float> {
     typedef int ivec __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ vec load(const float* p, size_t i) { return reinterpret_cast<const vec*>(p)[i]; }
     static __device__ __forceinline__ void store(float* p, size_t i, vec v) { reinterpret_cast<vec*>(p)[i] = v; }
+    static __device__ __forceinline__ float at(const float* p, size_t i) { return p[i]; }      // one element, widened
 };
 template <int N> struct Run<f16_t<N>> {
     static constexpr int V = N;
@@ -50,6 +51,7 @@ template <int N> struct Run<f16_t<N>> {
     {
         reinterpret_cast<raw*>(p)[i] = __builtin_convertvector(v, raw);
     }
+    static __device__ __forceinline__ float at(const f16_t<N>* p, size_t i) { return (float)p[i].v; }
 };
 template <int N> struct Run<bf16_t<N>> {
     static constexpr int V = N;
@@ -74,6 +76,7 @@ template <int N> struct Run<bf16_t<N>> {
         }
         reinterpret_cast<raw*>(p)[i] = u;
     }
+    static __device__ __forceinline__ float at(const bf16_t<N>* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
 };
 
 template <typename E> __device__ __forceinline__ void zero_row(E* orow, int n)
@@ -111,7 +114,7 @@ __device__ int cull_rois(int r_begin, int k, Touches touches, int* s_list, int* 
 }
 
 // v: the channels of a lane's run (Run<E>::V)
-static bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w, int v)
+static inline bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w, int v)
 {
     return n_img >= 1 && fh >= 1 && fw >= 1 && c >= v && c % v == 0 && k >= 0 && out_h >= 1 && out_h <= OPS_MAX_OUT && out_w >= 1 &&
            out_w <= OPS_MAX_OUT && (size_t)fh * fw <= (size_t)INT32_MAX && (size_t)n_img * cdiv(c / v, 64) <= 65535;   // backward grid z

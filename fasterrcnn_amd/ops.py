@@ -14,6 +14,8 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import dcnv3, DCNv3Function, dcnv3_core_pytorch, DCNv3
     from fasterrcnn_amd.ops import dcnv4, DCNv4Function, dcnv4_core_pytorch, DCNv4
     from fasterrcnn_amd.ops import border_align, BorderAlign, border_align_pytorch
+    from fasterrcnn_amd.ops import riroi_align_rotated, RiRoIAlignRotated, riroi_align_rotated_pytorch
+    from fasterrcnn_amd.ops import rotated_feature_align, RotatedFeatureAlign, rotated_feature_align_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -324,6 +326,38 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       without a launch.  border_align_pytorch is the same contract from torch operations (index gathers and torch.max), on any device,
       differentiable by autograd, in float64 for a float64 map and float32 otherwise: the CPU route, and what tools/ops_bench.py
       measures the kernels against.
+  riroi_align_rotated(input, rois, output_size, spatial_scale=1.0, num_samples=0, num_orientations=8, clockwise=False)
+  RiRoIAlignRotated(out_size, spatial_scale, num_samples=0, num_orientations=8, clockwise=False).forward(input, rois)
+  riroi_align_rotated_pytorch(pooled, rois, num_orientations=8)
+      ReDet's rotation-invariant RoI pooling (csrc/ops_rot.hip; mmcv's riroi_align_rotated restated, unpinned: where the two differ
+      include/frcnn_hip.h holds).  input [N, C n, H, W], n = num_orientations in [1, MAX_RIROI_ORIENTATIONS = 64] dividing the channel
+      count (else ValueError), channel c n + o being orientation o of group c; rois [K, 6] (batch index, cx, cy, w, h, angle), float32 or
+      the input's own 16-bit dtype; the other limits are roi_align_rotated's, num_samples playing sampling_ratio's part.  The result is
+      [K, C n, oh, ow] (channels_last memory).  Pool, then blend: S = roi_align_rotated(input, rois, output_size, spatial_scale,
+      num_samples, aligned=False, clockwise=not clockwise) in float32, then per RoI f = float32(float64(angle) n / (2 pi)), ind = floor(f),
+      l = f - ind, r = 1 - l, k = ind mod n >= 0 and out[c n + o] = r S[c n + (o - k) mod n] + l S[c n + (o - k + 1) mod n], two products
+      and a sum, each rounded.  mmcv blends per sample; pooling each source channel once and blending the pooled values is the same sum
+      in another order at half the loads, and makes the result bit-identical to riroi_align_rotated_pytorch(S, rois, n).  One launch each
+      way: the forward exchanges the pooled runs through LDS, the backward is roi_align_rotated's culled tile gather that blends dS where it
+      loads a bin's gradient (deterministic, no atomics; mmcv's is an atomic scatter).  A RoI with a batch index outside (-1, N), a
+      non-finite angle or |f| >= 2 ** 24 pools to zeros and sends no gradient.  rois get no gradient; double backward raises.  16-bit
+      maps: S and the blend stay float32, one rounding (op(x) == op(x.float()).to(x.dtype)).  riroi_align_rotated_pytorch is the blend
+      alone, from torch operations around any pooled S, on any device, differentiable by autograd in S.
+  rotated_feature_align(features, best_bboxes, spatial_scale=1 / 8, points=1)
+  RotatedFeatureAlign(spatial_scale=1 / 8, points=1).forward(features, best_bboxes)
+  rotated_feature_align_pytorch(features, best_bboxes, spatial_scale=1 / 8, points=1)
+      R3Det's feature refinement module (csrc/ops_rfa.hip; mmcv's rotated_feature_align restated, unpinned).  features [N, C, H, W];
+      best_bboxes [N, H, W, 5], one row per pixel, float32 (or the map's 16-bit dtype), any strides.  COMPONENT 0 OF A ROW IS THE ROW
+      (y) COORDINATE: the row is (y, x, w, h, angle) in input coordinates, although mmcv's docstring names it (x, y, w, h, a); swap the
+      first two columns of (x, y, ...) boxes.  y0 = b0 s, x0 = b1 s, w2 = b2 s / 2, h2 = b3 s / 2, (wx, wy) = (cos a, sin a) w2,
+      (hx, hy) = (-sin a, cos a) h2; the sample points are the centre (x0, y0) and, for points = 5, the corners (x0 + wx + hx, y0 + wy +
+      hy), (x0 - wx + hx, y0 - wy + hy), (x0 - wx - hx, y0 - wy - hy), (x0 + wx - hx, y0 + wy - hy).  out[n, :, h, w] = features[n, :, h, w]
+      + the bilinear samples of features[n] at the pixel's points, added in that order in float32, by roi_align's rule (nothing outside
+      [-1, size] or at a non-finite coordinate).  points is 1 or 5 (else ValueError); with points = 1 components 2..4 are never read.  The
+      result has the input's dtype and memory format.  Backward for features only: d_features[cell] = dout[cell], then + weight *
+      dout[pixel] over the sample corners that land on the cell in ascending (pixel, point, corner) order, through the sorted plan of
+      multi_scale_deformable_attn (one plan and one stable sort, 64 channel runs per block): deterministic, no atomics.  N H W points 4
+      <= MAX_RFA_INDEX.  rotated_feature_align_pytorch is the same contract from index gathers, on any device, float64 for a float64 map.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -355,7 +389,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "carafe", "CARAFE", "CARAFEPack", "multi_scale_deformable_attn", "multi_scale_deformable_attn_pytorch",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
            "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4",
-           "border_align", "BorderAlign", "border_align_pytorch"]
+           "border_align", "BorderAlign", "border_align_pytorch", "riroi_align_rotated", "RiRoIAlignRotated",
+           "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -390,6 +425,10 @@ MAX_BORDER_SIDE = 2 ** 24                 # border_align: H and W, exact in floa
 MAX_BORDER_INDEX = 2 ** 31 - 1 - 1024     # border_align's flat launch grids (csrc/ops_border.hip): the forward's lanes N K 4 ceil(C / 4) and the
                                           # backward's blocks N ceil(C / 256) ceil(H / 2) ceil(W / 2)
 BORDER_ALIGN_CULL_LIST = 64               # boxes a wave of border_align's input-gradient gather tests at once (BORDER_GROUP of csrc/ops_border.hip)
+MAX_RIROI_ORIENTATIONS = 64               # riroi_align_rotated: num_orientations (frcnn_ops_riroi_align_rotated_max_orientations(): a group lies
+                                          # inside the 64 channel runs of one wave)
+RFA_POINTS = (1, 5)                       # rotated_feature_align: the centre, or the centre and the four corners
+MAX_RFA_INDEX = 2 ** 31 - 1 - 1024        # rotated_feature_align: the plan entries N H W points 4 of one call (csrc/ops_rfa.hip)
 CARAFE_RUN = 4                            # channels a thread of carafe's d_features gather owns: G ceil(C / G / 4) blocks along the grid's y
 
 
@@ -1507,6 +1546,129 @@ def _roi_align_rotated_bwd(ctx, grad):
 _register_autograd("roi_align_rotated", _roi_align_rotated_bwd, _roi_setup)
 
 
+# ---- frcnn::riroi_align_rotated (csrc/ops_rot.hip: the kernels get the padded channel count and the real one) -----------------------
+@torch.library.custom_op("frcnn::riroi_align_rotated", mutates_args=())
+def _riroi_align_rotated(input: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int, num_samples: int,
+                         num_orientations: int, clockwise: bool) -> Tensor:
+    n, c, h, w = input.shape
+    k = rois.shape[0]
+    out = _empty_cl((k, c, pooled_height, pooled_width), input)
+    if k == 0 or c == 0:
+        return out
+    if n * h * w == 0:
+        return out.zero_()
+    with torch.cuda.device(input.device):
+        x = _nhwc(input)
+        r = rois.contiguous()
+        cp = x.shape[1]
+        dst = out if cp == c else _empty_cl((k, cp, pooled_height, pooled_width), input)
+        _call("riroi_align_rotated", input, x.data_ptr(), n, h, w, cp, c, r.data_ptr(), k, pooled_height, pooled_width, spatial_scale,
+              num_samples, num_orientations, int(clockwise), dst.data_ptr(), _stream(input))
+        if dst is not out:
+            out.copy_(dst[:, :c])
+    return out
+
+
+@_riroi_align_rotated.register_fake
+def _(input, rois, spatial_scale, pooled_height, pooled_width, num_samples, num_orientations, clockwise):
+    return _empty_cl((rois.shape[0], input.shape[1], pooled_height, pooled_width), input)
+
+
+@torch.library.custom_op("frcnn::riroi_align_rotated_backward", mutates_args=())
+def _riroi_align_rotated_backward(grad: Tensor, rois: Tensor, spatial_scale: float, pooled_height: int, pooled_width: int,
+                                  num_samples: int, num_orientations: int, clockwise: bool, batch_size: int, channels: int, height: int,
+                                  width: int, channels_last: bool) -> Tensor:
+    k = rois.shape[0]
+    if channels == 0 or batch_size * height * width == 0:
+        return _grad_layout(grad.new_zeros((batch_size, channels, height, width)), channels, channels_last)
+    with torch.cuda.device(grad.device):
+        cp = _padded_channels(channels, grad.dtype)
+        g = _nhwc(grad)
+        r = rois.contiguous()
+        dx = _empty_cl((batch_size, cp, height, width), grad)
+        _call("riroi_align_rotated_backward", grad, r.data_ptr() if k else None, k, batch_size, height, width, cp, channels, pooled_height,
+              pooled_width, spatial_scale, num_samples, num_orientations, int(clockwise), g.data_ptr() if k else None, dx.data_ptr(),
+              _stream(grad))
+        return _grad_layout(dx, channels, channels_last)
+
+
+@_riroi_align_rotated_backward.register_fake
+def _(grad, rois, spatial_scale, pooled_height, pooled_width, num_samples, num_orientations, clockwise, batch_size, channels, height, width,
+      channels_last):
+    return _grad_empty((batch_size, channels, height, width), grad, channels_last)
+
+
+def _riroi_align_rotated_bwd(ctx, grad):
+    rois, = ctx.saved_tensors
+    return (_riroi_align_rotated_backward(grad, rois, *ctx.args, *ctx.shape, ctx.channels_last),) + (None,) * 7
+
+
+_register_autograd("riroi_align_rotated", _riroi_align_rotated_bwd, _roi_setup)
+
+
+# ---- frcnn::rotated_feature_align (csrc/ops_rfa.hip) ---------------------------------------------------------------------------------
+@torch.library.custom_op("frcnn::rotated_feature_align", mutates_args=())
+def _rotated_feature_align(features: Tensor, best_bboxes: Tensor, spatial_scale: float, points: int) -> Tensor:
+    n, c, h, w = features.shape
+    channels_last = _input_is_channels_last(features)
+    if features.numel() == 0:
+        return _grad_empty((n, c, h, w), features, channels_last)
+    with torch.cuda.device(features.device):
+        x = _nhwc(features)
+        b = best_bboxes.contiguous()
+        out = _empty_cl(tuple(x.shape), features)
+        _call("rotated_feature_align", features, x.data_ptr(), b.data_ptr(), n, h, w, x.shape[1], spatial_scale, points, out.data_ptr(),
+              _stream(features))
+        return _grad_layout(out, c, channels_last)
+
+
+@_rotated_feature_align.register_fake
+def _(features, best_bboxes, spatial_scale, points):
+    return _grad_empty(tuple(features.shape), features, _input_is_channels_last(features))
+
+
+@torch.library.custom_op("frcnn::rotated_feature_align_backward", mutates_args=())
+def _rotated_feature_align_backward(grad: Tensor, best_bboxes: Tensor, spatial_scale: float, points: int, channels_last: bool) -> Tensor:
+    n, c, h, w = grad.shape
+    if grad.numel() == 0:
+        return _grad_empty((n, c, h, w), grad, channels_last)
+    with torch.cuda.device(grad.device):
+        g = _nhwc(grad)
+        b = best_bboxes.contiguous()
+        cp = g.shape[1]
+        dx = _empty_cl((n, cp, h, w), grad)
+        stream, lib = _stream(grad), nv.lib()
+
+        def plan(keys, wts):
+            nv.check(lib.frcnn_ops_rotated_feature_align_plan(b.data_ptr(), n, h, w, spatial_scale, points, keys, wts, stream),
+                     "frcnn_ops_rotated_feature_align_plan")
+
+        def gather(keys, order, wts):
+            _call("rotated_feature_align_backward", grad, keys, order, wts, g.data_ptr(), n, h, w, cp, points, dx.data_ptr(), stream)
+        held = _sorted_gather(plan, gather, n * h * w * points * 4, grad.device)       # noqa: F841 (kept alive)
+        return _grad_layout(dx, c, channels_last)
+
+
+@_rotated_feature_align_backward.register_fake
+def _(grad, best_bboxes, spatial_scale, points, channels_last):
+    return _grad_empty(tuple(grad.shape), grad, channels_last)
+
+
+def _rotated_feature_align_setup(ctx, inputs, output):
+    features, best_bboxes, spatial_scale, points = inputs
+    ctx.save_for_backward(best_bboxes)
+    ctx.args = (spatial_scale, points)
+    ctx.channels_last = _input_is_channels_last(features)
+
+
+def _rotated_feature_align_bwd(ctx, grad):
+    best_bboxes, = ctx.saved_tensors
+    return _rotated_feature_align_backward(grad, best_bboxes, *ctx.args, ctx.channels_last), None, None, None
+
+
+_register_autograd("rotated_feature_align", _rotated_feature_align_bwd, _rotated_feature_align_setup)
+
+
 # ---- frcnn::carafe (plain NCHW; csrc/ops_carafe.hip) --------------------------------------------------------------------------------
 @torch.library.custom_op("frcnn::carafe", mutates_args=())
 def _carafe(features: Tensor, masks: Tensor, kernel_size: int, group_size: int, scale_factor: int) -> Tensor:
@@ -2437,6 +2599,151 @@ def roi_align_rotated(input, rois, output_size, spatial_scale=1.0, sampling_rati
     return _roi_align_rotated(input, rois.float(), float(spatial_scale), oh, ow, int(sampling_ratio), bool(aligned), bool(clockwise))
 
 
+def _riroi_orientations(num_orientations, channels):
+    _check_int("num_orientations", num_orientations)
+    if not 1 <= num_orientations <= MAX_RIROI_ORIENTATIONS:
+        raise ValueError("num_orientations must lie in [1, %d], got %d" % (MAX_RIROI_ORIENTATIONS, num_orientations))
+    if channels % num_orientations != 0:
+        raise ValueError("num_orientations = %d must divide the channel count, got %d channels" % (num_orientations, channels))
+    return num_orientations
+
+
+def _riroi_rois(rois):
+    if rois.dim() != 2 or rois.shape[1] != 6:
+        raise ValueError("rois must be a Tensor[K, 6] (batch index, cx, cy, w, h, angle), got shape %s" % (tuple(rois.shape),))
+
+
+def riroi_align_rotated(input, rois, output_size, spatial_scale=1.0, num_samples=0, num_orientations=8, clockwise=False):
+    """mmcv.ops.riroi_align_rotated (ReDet's rotation-invariant RoI pooling): roi_align_rotated's pooled values of input [N, C n, H, W]
+    (aligned off) with the n = num_orientations channels of every group rotated by the RoI's angle and blended between the two nearest
+    orientations: [K, C n, oh, ow] (channels_last memory); differentiable in input."""
+    _check_tensor("input", input, _MAP_DTYPES, _MAP_WHAT, "riroi_align_rotated_pytorch around a pooled tensor")
+    if input.dim() != 4:
+        raise ValueError("input must be [N, C * num_orientations, H, W], got shape %s" % (tuple(input.shape),))
+    dtypes, what = _box_dtypes(input)
+    _check_tensor("rois", rois, dtypes, what, "riroi_align_rotated_pytorch around a pooled tensor")
+    _check_same_device(input, rois, "input", "rois")
+    _riroi_rois(rois)
+    oh, ow = _output_size(output_size)
+    _check_int("num_samples", num_samples)
+    if num_samples > MAX_SAMPLING_RATIO:
+        raise ValueError("num_samples must be <= %d, got %d" % (MAX_SAMPLING_RATIO, num_samples))
+    n = _riroi_orientations(num_orientations, input.shape[1])
+    return _riroi_align_rotated(input, rois.float(), float(spatial_scale), oh, ow, num_samples, n, bool(clockwise))
+
+
+def riroi_align_rotated_pytorch(pooled, rois, num_orientations=8):
+    """riroi_align_rotated's blend from torch operations, on any device: pooled is S [K, C n, oh, ow], the result of roi_align_rotated
+    (aligned=False, the opposite clockwise flag) or of any other pooling, rois [K, 6] the rows it was pooled with.  Per RoI
+    f = float32(float64(angle) n / (2 pi)), ind = floor(f), l = f - ind, r = 1 - l, k = ind mod n, and out[c n + o] =
+    r S[c n + (o - k) mod n] + l S[c n + (o - k + 1) mod n]; a RoI whose angle is not finite or whose |f| >= 2 ** 24 gives zeros.  Computed
+    in float32 (float64 for a float64 S), returned in S's dtype; differentiable by autograd in S."""
+    for name, t in (("pooled", pooled), ("rois", rois)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError("%s must be a floating-point torch.Tensor, got %s" % (name, t.dtype if isinstance(t, torch.Tensor)
+                                                                                   else type(t).__name__))
+    _check_same_device(pooled, rois, "pooled", "rois")
+    if pooled.dim() != 4:
+        raise ValueError("pooled must be [K, C * num_orientations, oh, ow], got shape %s" % (tuple(pooled.shape),))
+    _riroi_rois(rois)
+    if rois.shape[0] != pooled.shape[0]:
+        raise ValueError("pooled and rois must hold the same K RoIs, got %d and %d" % (pooled.shape[0], rois.shape[0]))
+    n = _riroi_orientations(num_orientations, pooled.shape[1])
+    dtype = torch.float64 if pooled.dtype == torch.float64 else torch.float32
+    k_rois, channels = pooled.shape[:2]
+    if pooled.numel() == 0:
+        return pooled.new_zeros(tuple(pooled.shape)) + pooled.sum() * 0
+    angle = rois.detach()[:, 5].double()
+    f = (angle * n / (2 * math.pi)).float()
+    ok = torch.isfinite(angle) & (f.abs() < 2.0 ** 24)
+    f = torch.where(ok, f, torch.zeros_like(f))
+    ind = torch.floor(f)
+    left = (f - ind).to(dtype)
+    right = 1 - left
+    k = torch.remainder(ind.long(), n)                                               # non-negative
+    ch = torch.arange(channels, device=pooled.device)
+    base, o = ch // n * n, ch % n
+    first = base[None] + torch.remainder(o[None] - k[:, None], n)                    # [K, C n]
+    second = base[None] + torch.remainder(o[None] - k[:, None] + 1, n)
+    s = pooled.to(dtype)
+    shape = (k_rois, channels) + tuple(pooled.shape[2:])
+    a = s.gather(1, first[:, :, None, None].expand(shape)) * right[:, None, None, None]
+    b = s.gather(1, second[:, :, None, None].expand(shape)) * left[:, None, None, None]
+    out = torch.where(ok[:, None, None, None], a + b, torch.zeros_like(a))
+    return out.to(pooled.dtype)
+
+
+def _rfa_args(features, best_bboxes, points):
+    """The shape rules rotated_feature_align and rotated_feature_align_pytorch share."""
+    if features.dim() != 4:
+        raise ValueError("features must be [N, C, H, W], got shape %s" % (tuple(features.shape),))
+    n, _, h, w = features.shape
+    if tuple(best_bboxes.shape) != (n, h, w, 5):
+        raise ValueError("best_bboxes must be [N, H, W, 5] = %s (one (y, x, w, h, angle) row per pixel), got shape %s"
+                         % ((n, h, w, 5), tuple(best_bboxes.shape)))
+    _check_int("points", points)
+    if points not in RFA_POINTS:
+        raise ValueError("points must be 1 or 5, got %d" % points)
+    if n * h * w * points * 4 > MAX_RFA_INDEX:
+        raise ValueError("N H W points 4 = %d exceeds %d (the plan entries of the backward)" % (n * h * w * points * 4, MAX_RFA_INDEX))
+
+
+def rotated_feature_align(features, best_bboxes, spatial_scale=1 / 8, points=1):
+    """mmcv.ops.rotated_feature_align (R3Det's feature refinement module): every pixel adds to its own value the bilinear samples of its
+    image at the centre (points=1) or the centre and the four corners (points=5) of its box row best_bboxes[n, h, w] =
+    (y, x, w, h, angle): component 0 is the ROW coordinate.  [N, C, H, W] in the input's memory format; differentiable in features."""
+    _check_tensor("features", features, _MAP_DTYPES, _MAP_WHAT, "rotated_feature_align_pytorch")
+    dtypes, what = _box_dtypes(features)
+    _check_tensor("best_bboxes", best_bboxes, dtypes, what, "rotated_feature_align_pytorch")
+    _check_same_device(features, best_bboxes, "features", "best_bboxes")
+    _rfa_args(features, best_bboxes, points)
+    return _rotated_feature_align(features, best_bboxes.float(), float(spatial_scale), points)
+
+
+def rotated_feature_align_pytorch(features, best_bboxes, spatial_scale=1 / 8, points=1):
+    """rotated_feature_align from torch operations (index gathers), on any device, with autograd to features: the fallback, and what
+    tools/ops_bench.py measures the kernels against.  features [N, C, H, W] of any floating dtype (16-bit maps compute in float32,
+    float64 in float64), best_bboxes a floating-point [N, H, W, 5] of (y, x, w, h, angle) rows.  Returns [N, C, H, W] in the input's
+    dtype."""
+    for name, t in (("features", features), ("best_bboxes", best_bboxes)):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError("%s must be a floating-point torch.Tensor, got %s" % (name, t.dtype if isinstance(t, torch.Tensor)
+                                                                                   else type(t).__name__))
+    _check_same_device(features, best_bboxes, "features", "best_bboxes")
+    _rfa_args(features, best_bboxes, points)
+    dtype = torch.float64 if features.dtype == torch.float64 else torch.float32
+    n, c, h, w = features.shape
+    if features.numel() == 0:
+        return features.new_zeros((n, c, h, w)) + features.sum() * 0
+    b = best_bboxes.detach().to(dtype)
+    scale = float(spatial_scale)
+    y0, x0 = b[..., 0] * scale, b[..., 1] * scale                          # [N, H, W]
+    pts = [(x0, y0)]
+    if points == 5:
+        w2, h2, a = b[..., 2] * scale / 2, b[..., 3] * scale / 2, b[..., 4]
+        ca, sa = torch.cos(a), torch.sin(a)
+        wx, wy, hx, hy = ca * w2, sa * w2, -sa * h2, ca * h2
+        pts += [((x0 + wx) + hx, (y0 + wy) + hy), ((x0 - wx) + hx, (y0 - wy) + hy), ((x0 - wx) - hx, (y0 - wy) - hy),
+                ((x0 + wx) - hx, (y0 + wy) - hy)]
+    x = features.to(dtype)
+    flat = x.reshape(n, c, h * w)
+    out = x
+    zero = torch.zeros_like(y0)
+    for px, py in pts:
+        valid = (py >= -1) & (py <= h) & (px >= -1) & (px <= w)             # a NaN fails
+        yl, yh, wyl, wyh = _border_axis_pytorch(torch.where(valid, py, zero), h)
+        xl, xh, wxl, wxh = _border_axis_pytorch(torch.where(valid, px, zero), w)
+
+        def cells(row, col):
+            index = (row * w + col).reshape(n, 1, -1).expand(n, c, -1)
+            return flat.gather(2, index).reshape(n, c, h, w)
+
+        w1, w2_, w3, w4 = ((p * q)[:, None] for p, q in ((wyl, wxl), (wyl, wxh), (wyh, wxl), (wyh, wxh)))
+        val = ((cells(yl, xl) * w1 + cells(yl, xh) * w2_) + cells(yh, xl) * w3) + cells(yh, xh) * w4
+        out = out + torch.where(valid[:, None], val, torch.zeros_like(val))
+    return out.to(features.dtype)
+
+
 def _carafe_int(name, v, low, high, what=""):
     _check_int(name, v)
     if not low <= v <= high:
@@ -2828,6 +3135,43 @@ class RoIAlignRotated(torch.nn.Module):
     def extra_repr(self):
         return "output_size=%s, spatial_scale=%s, sampling_ratio=%s, aligned=%s, clockwise=%s" % (
             self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned, self.clockwise)
+
+
+class RiRoIAlignRotated(torch.nn.Module):
+    """mmcv.ops.RiRoIAlignRotated (ReDet): its argument names; input [N, C * num_orientations, H, W] and rois [K, 6]."""
+
+    def __init__(self, out_size, spatial_scale, num_samples=0, num_orientations=8, clockwise=False):
+        super().__init__()
+        self.out_size = _output_size(out_size)
+        self.spatial_scale = float(spatial_scale)
+        self.num_samples = int(num_samples)
+        self.num_orientations = int(num_orientations)
+        self.clockwise = bool(clockwise)
+
+    def forward(self, features, rois):
+        return riroi_align_rotated(features, rois, self.out_size, self.spatial_scale, self.num_samples, self.num_orientations,
+                                   self.clockwise)
+
+    def extra_repr(self):
+        return "out_size=%s, spatial_scale=%s, num_samples=%s, num_orientations=%s, clockwise=%s" % (
+            self.out_size, self.spatial_scale, self.num_samples, self.num_orientations, self.clockwise)
+
+
+class RotatedFeatureAlign(torch.nn.Module):
+    """rotated_feature_align as a module: features [N, C, H, W] and best_bboxes [N, H, W, 5] of (y, x, w, h, angle) rows."""
+
+    def __init__(self, spatial_scale=1 / 8, points=1):
+        super().__init__()
+        if points not in RFA_POINTS:
+            raise ValueError("points must be 1 or 5, got %r" % (points,))
+        self.spatial_scale = float(spatial_scale)
+        self.points = points
+
+    def forward(self, features, best_bboxes):
+        return rotated_feature_align(features, best_bboxes, self.spatial_scale, self.points)
+
+    def extra_repr(self):
+        return "spatial_scale=%s, points=%d" % (self.spatial_scale, self.points)
 
 
 class RoIPool(torch.nn.Module):

@@ -86,7 +86,10 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_soft_nms, its _workspace_bytes and the frcnn_ops_soft_nms_block_threads /
                                  _lds_boxes / _max_boxes getters (Soft-NMS, per label: mmcv's CPU-only soft_nms);
                                  still 21 (additions only): frcnn_ops_border_align, its _backward, _16 and _cull_list forms (BorderAlign, the
-                                 border pooling of BorderDet: mmcv's border_align) */
+                                 border pooling of BorderDet: mmcv's border_align);
+                                 still 21 (additions only): frcnn_ops_riroi_align_rotated, its _backward, _16 and _max_orientations forms
+                                 (ReDet's rotation-invariant RoI pooling: mmcv's riroi_align_rotated) and frcnn_ops_rotated_feature_align, its
+                                 _plan, _backward and _16 forms (R3Det's feature refinement: mmcv's rotated_feature_align) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -839,6 +842,85 @@ int frcnn_ops_roi_align_rotated_16(int elem_type, const void* d_x, int n_img, in
 int frcnn_ops_roi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h,
                                             int out_w, float spatial_scale, int sampling_ratio, int aligned, int clockwise,
                                             const void* d_dout, void* d_dx, void* stream);
+
+/* RiRoIAlignRotated, the rotation-invariant RoI pooling of ReDet (csrc/ops_rot.hip): mmcv's riroi_align_rotated in both directions,
+ *   restated from the published kernels (third party, absent here: restated, unpinned; where the two differ this text holds).
+ *   Layouts and element types as frcnn_ops_roi_align_rotated: d_x [n_img][fh][fw][c], d_out [k][out_h][out_w][c], d_rois float32 [k][6]
+ *   rows (b, cx, cy, w, h, angle).  The first c_real channels form c_real / n groups of n = num_orientations channels, channel g n + o
+ *   being orientation o of group g; the channels from c_real to c (padding up to whole runs) belong to no group: the forward writes zeros
+ *   there and the backward ignores them.
+ *   The contract: pool, then blend.  Let S = frcnn_ops_roi_align_rotated(d_x, d_rois, spatial_scale, sampling_ratio = num_samples,
+ *   aligned = 0, clockwise = !clockwise), in float32.  (mmcv's RiRoI grid is x = xx cos t - yy sin t + cx, y = xx sin t + yy cos t + cy
+ *   with t = clockwise ? -angle : angle, which is the grid above under the opposite flag; sinf(-t) == -sinf(t) exactly.)  Per RoI
+ *     f = (float)((double)angle * n / (2 pi)),  ind = floor(f),  l = f - ind,  r = 1 - l,  k = ind mod n taken non-negative,
+ *     out[g n + o] = r * S[g n + (o - k) mod n] + l * S[g n + (o - k + 1) mod n]
+ *   as two products and one sum, each rounded in float32 (no fma).  The second term is computed even when l == 0, so a NaN in the
+ *   neighbouring orientation propagates, as in mmcv.  A RoI pools to zeros and sends no gradient if its batch index is outside
+ *   (-1, n_img), its angle is not finite, or |f| >= 2^24.
+ *   mmcv blends per sample: every sample's bilinear value is split between two output channels.  Here every source channel is pooled
+ *   once and the pooled values are blended: the same sum in another order at half the loads, and the output is, bit for bit, the blend
+ *   above applied to frcnn_ops_roi_align_rotated's own output.  One launch: a wave pools whole groups' runs, exchanges them through LDS
+ *   and stores the blended runs once; S never reaches memory.
+ * frcnn_ops_riroi_align_rotated_backward: d_dx [n_img][fh][fw][c], every element overwritten (k == 0: zeros), for d_x only.
+ *     dS[g n + j] = r * dout[g n + (j + k) mod n] + l * dout[g n + (j + k - 1) mod n]     (rounded the same way)
+ *   and then exactly frcnn_ops_roi_align_rotated_backward on dS -- the same launch grid, RoI order, bin order, w_sum / count and cull
+ *   list (frcnn_ops_roi_align_rotated_cull_list()) -- in one launch: dS is blended where that gather loads a bin's gradient, is never
+ *   rounded to 16 bits and never written to memory.  Deterministic, no atomics.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): frcnn_ops_roi_align_rotated's limits (num_samples as
+ *   sampling_ratio), num_orientations outside [1, frcnn_ops_riroi_align_rotated_max_orientations() = 64] (a group must fit the 64
+ *   channel runs of one wave wherever it starts in its run), c_real not a positive multiple of num_orientations or above c, NULL pointers.
+ * The _16 forms take float16 / bfloat16 maps under the contract of the 16-bit operators above: S and the blend stay float32 and the
+ *   result is rounded once. */
+int frcnn_ops_riroi_align_rotated_max_orientations(void);
+int frcnn_ops_riroi_align_rotated(const float* d_x, int n_img, int fh, int fw, int c, int c_real, const float* d_rois, int k, int out_h,
+                                  int out_w, float spatial_scale, int num_samples, int num_orientations, int clockwise, float* d_out,
+                                  void* stream);
+int frcnn_ops_riroi_align_rotated_backward(const float* d_rois, int k, int n_img, int fh, int fw, int c, int c_real, int out_h, int out_w,
+                                           float spatial_scale, int num_samples, int num_orientations, int clockwise, const float* d_dout,
+                                           float* d_dx, void* stream);
+int frcnn_ops_riroi_align_rotated_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, int c_real, const float* d_rois,
+                                     int k, int out_h, int out_w, float spatial_scale, int num_samples, int num_orientations,
+                                     int clockwise, void* d_out, void* stream);
+int frcnn_ops_riroi_align_rotated_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int c_real,
+                                              int out_h, int out_w, float spatial_scale, int num_samples, int num_orientations,
+                                              int clockwise, const void* d_dout, void* d_dx, void* stream);
+
+/* rotated_feature_align, the feature refinement module of R3Det (csrc/ops_rfa.hip): mmcv's rotated_feature_align in both directions,
+ *   restated from the published kernels (third party, absent here: restated, unpinned; where the two differ this text holds).
+ *   Layouts (element types as frcnn_ops_roi_align above; c % 4 == 0, the _16 forms c % 8 == 0):
+ *     d_x, d_out, d_dout, d_dx : [n_img][fh][fw][c];   d_boxes : float32 [n_img][fh][fw][5], one row b per pixel
+ *   The box row.  COMPONENT 0 IS THE ROW (y) COORDINATE, component 1 the column (x): (y, x, w, h, angle), in input coordinates; a caller
+ *   holding (x, y, w, h, a) rows swaps the first two columns.  With s = spatial_scale, all in float32, each operation rounded on its own:
+ *     y0 = b[0] s,  x0 = b[1] s,  w2 = b[2] s / 2,  h2 = b[3] s / 2,  a = b[4],
+ *     wx = cos a * w2,  wy = sin a * w2,  hx = -sin a * h2,  hy = cos a * h2,
+ *     p0 = (x0, y0),  p1 = ((x0 + wx) + hx, (y0 + wy) + hy),  p2 = ((x0 - wx) + hx, (y0 - wy) + hy),
+ *     p3 = ((x0 - wx) - hx, (y0 - wy) - hy),  p4 = ((x0 + wx) - hx, (y0 + wy) - hy)       as (x, y).
+ *   d_out[n][h][w][:] = d_x[n][h][w][:] + sum over i < points of bilinear(d_x[n], p_i), the terms added to the pixel's own value in order
+ *   i, in float32.  bilinear is frcnn_ops_roi_align's rule: value = ((w1 v1 + w2 v2) + w3 v3) + w4 v4 over (y low, x low), (y low, x high),
+ *   (y high, x low), (y high, x high); nothing outside [-1, size] on either axis and nothing at a NaN or infinite coordinate; a
+ *   coordinate <= 0 goes to 0 and a low index >= size - 1 collapses to the last cell.  points is 1 or 5; with points == 1 components
+ *   2..4 are never read.  One launch, lanes along channels; a pixel's positions and weights are formed once per lane, not per channel.
+ * The backward (for d_x only; the boxes get no gradient) is the sorted-plan gather of frcnn_ops_msda_plan / _backward_value for rows of
+ *   any length, deterministic and free of atomics:
+ *   frcnn_ops_rotated_feature_align_plan writes, for entry e = (pixel * points + i) * 4 + corner (pixel = (n fh + h) fw + w), the key
+ *     n fh fw + cell of the cell that corner lands on and its weight; all four corners of a sample that counts nothing carry the
+ *     sentinel key n_img fh fw and weight 0.  The caller sorts the keys stably and passes the sorted keys and the permutation.
+ *   frcnn_ops_rotated_feature_align_backward: d_dx[cell] = d_dout[cell] FIRST (the identity term), then + weight[e] * d_dout[pixel of e]
+ *     over the cell's entries in ascending e, each product and sum rounded in float32.  One group of lanes per cell and chunk of 64
+ *     channel runs (256 float32 channels), all chunks over the one plan and sort; a cell's segment is found by bisection and summed by
+ *     its group however long it is.  Every element of d_dx is written.
+ * Arguments are validated before the GPU is touched (FRCNN_EINVAL): points other than 1 or 5, fh or fw < 1, n_img < 0, c not in whole
+ *   runs, n_img fh fw points 4 (the plan's entries) above 2^31 - 1 - 1024, NULL pointers.  n_img == 0 returns FRCNN_OK. */
+int frcnn_ops_rotated_feature_align(const float* d_x, const float* d_boxes, int n_img, int fh, int fw, int c, float spatial_scale,
+                                    int points, float* d_out, void* stream);
+int frcnn_ops_rotated_feature_align_plan(const float* d_boxes, int n_img, int fh, int fw, float spatial_scale, int points, int64_t* d_keys,
+                                         float* d_weights, void* stream);
+int frcnn_ops_rotated_feature_align_backward(const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
+                                             const float* d_dout, int n_img, int fh, int fw, int c, int points, float* d_dx, void* stream);
+int frcnn_ops_rotated_feature_align_16(int elem_type, const void* d_x, const float* d_boxes, int n_img, int fh, int fw, int c,
+                                       float spatial_scale, int points, void* d_out, void* stream);
+int frcnn_ops_rotated_feature_align_backward_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
+                                                const void* d_dout, int n_img, int fh, int fw, int c, int points, void* d_dx, void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

@@ -83,6 +83,17 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     ops.border_align beside ops.border_align_pytorch (index gathers and torch.max, autograd's backward), forward and forward + backward,
     in alternating windows.  Informational: no speed bound is set.
 
+  * riroi: RiRoIAlignRotated in a ReDet head (2 x (32 x 8) x 128 x 128, 512 RoIs, 7 x 7, num_samples 2), float32 and float16:
+    ops.riroi_align_rotated beside the two-step route (ops.roi_align_rotated, then ops.riroi_align_rotated_pytorch's torch blend) and
+    beside plain ops.roi_align_rotated on the same shapes (the fused forward does its loads plus one LDS exchange, so the ratio to it
+    is what the blend costs), forward and forward + backward, in alternating windows.  Informational: no speed bound is set.
+
+  * rfa: rotated_feature_align in an R3Det head (2 x 256 x 128 x 128, points 5, spatial_scale 1 / 8), float32 and float16:
+    ops.rotated_feature_align beside ops.rotated_feature_align_pytorch (index gathers, autograd's backward), forward and
+    forward + backward, in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only rfa             # just the rotated_feature_align leg
+    python tools/ops_bench.py --only riroi           # just the RiRoIAlignRotated leg
     python tools/ops_bench.py --only border          # just the BorderAlign leg
     python tools/ops_bench.py --only softnms         # just the Soft-NMS leg
     python tools/ops_bench.py --only diffiou         # just the differentiable-IoU leg
@@ -569,6 +580,68 @@ def border_leg(rng, reps, warmup):
     return res
 
 
+def riroi_leg(rng, reps, warmup):
+    n, groups, orient, h, w, k, out, ns, scale = 2, 32, 8, 128, 128, 512, (7, 7), 2, 0.25
+    c = groups * orient
+    gen = torch.Generator().manual_seed(0)
+    u = lambda lo, hi: torch.rand((k,), generator=gen) * (hi - lo) + lo     # noqa: E731
+    rois = torch.stack([(torch.arange(k) % n).float(), u(0, w / scale), u(0, h / scale), u(16, 160), u(16, 160), u(-np.pi, np.pi)], 1).to(DEV)
+    res = {}
+    for dtype in (torch.float32, torch.float16):
+        x = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((k, c) + out, generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        leaf = x.clone().requires_grad_(True)
+
+        def fused(a=x):
+            return ops.riroi_align_rotated(a, rois, out, scale, ns, orient, False)
+
+        def plain(a=x):
+            return ops.roi_align_rotated(a, rois, out, scale, ns, False, True)
+
+        def two_step(a=x):
+            return ops.riroi_align_rotated_pytorch(plain(a), rois, orient)
+        y, yc = fused().float(), two_step().float()
+        r = {"max |riroi_align_rotated - two-step| / max |two-step|": float((y - yc).abs().max() / yc.abs().max())}
+        for name, fns in (("fwd", (fused, two_step, plain)),
+                          ("fwd+bwd", (lambda: fused(leaf).backward(g), lambda: two_step(leaf).backward(g), lambda: plain(leaf).backward(g)))):
+            t_fused, t_two, t_plain = timed_group(fns, reps, warmup)
+            r[name] = {"ops.riroi_align_rotated": round(t_fused, 1), "roi_align_rotated + torch blend": round(t_two, 1),
+                       "plain ops.roi_align_rotated": round(t_plain, 1), "two-step / riroi_align_rotated": round(t_two / t_fused, 2),
+                       "riroi_align_rotated / plain roi_align_rotated": round(t_fused / t_plain, 2)}
+        res["riroi %s 2 x (32 x 8) x 128 x 128, 512 RoIs, 7 x 7, num_samples 2" % str(dtype).split(".")[-1]] = r
+    return res
+
+
+def rfa_leg(rng, reps, warmup):
+    n, c, h, w, points, scale = 2, 256, 128, 128, 5, 1 / 8
+    gen = torch.Generator().manual_seed(0)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    u = lambda lo, hi: torch.rand((n, h, w), generator=gen) * (hi - lo) + lo     # noqa: E731
+    # refined boxes around their own locations, in input coordinates: (y, x, w, h, angle) rows
+    boxes = torch.stack([(ys[None] + u(-2, 2)) / scale, (xs[None] + u(-2, 2)) / scale, u(2, 24) / scale, u(2, 24) / scale,
+                         u(-np.pi / 2, np.pi / 2)], 3).to(DEV)
+    res = {}
+    for dtype in (torch.float32, torch.float16):
+        x = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        g = torch.randn((n, c, h, w), generator=gen).to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+        leaf = x.clone().requires_grad_(True)
+
+        def native(a=x):
+            return ops.rotated_feature_align(a, boxes, scale, points)
+
+        def composed(a=x):
+            return ops.rotated_feature_align_pytorch(a, boxes, scale, points)
+        y, yc = native().float(), composed().float()
+        r = {"max |rotated_feature_align - composition| / max |composition|": float((y - yc).abs().max() / yc.abs().max())}
+        for name, fns in (("fwd", (native, composed)),
+                          ("fwd+bwd", (lambda: native(leaf).backward(g), lambda: composed(leaf).backward(g)))):
+            t_native, t_comp = timed_pair(fns[0], fns[1], reps, warmup)
+            r[name] = {"ops.rotated_feature_align": round(t_native, 1), "ops.rotated_feature_align_pytorch": round(t_comp, 1),
+                       "composition / rotated_feature_align": round(t_comp / t_native, 2)}
+        res["rfa %s 2 x 256 x 128 x 128, points 5, spatial_scale 1/8" % str(dtype).split(".")[-1]] = r
+    return res
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -652,7 +725,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -700,6 +773,12 @@ def main():
         return
     if a.only == "border":
         print(json.dumps(border_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "riroi":
+        print(json.dumps(riroi_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "rfa":
+        print(json.dumps(rfa_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -772,6 +851,8 @@ def main():
     res.update(dcnv3_leg(rng, 5, 2))
     res.update(dcnv4_leg(rng, 5, 2))
     res.update(border_leg(rng, 5, 2))
+    res.update(riroi_leg(rng, 5, 2))
+    res.update(rfa_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
