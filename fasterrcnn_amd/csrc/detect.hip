@@ -26,6 +26,7 @@ __device__ __forceinline__ unsigned ordered_bits32(float f)
 }
 
 static constexpr int DET_MAX = 512;
+static constexpr double DET_LIMIT_K = 8388.608;      // 1e-3 / (2 * 2^-24): the pre-filter's margin over twice its unit error bound
 
 __global__ __launch_bounds__(1024)
 void detections_kernel(const float* __restrict__ props, const float* __restrict__ classes,
@@ -134,9 +135,11 @@ void detections_kernel(const float* __restrict__ props, const float* __restrict_
     // row's bits in a register -- no ballot, no per-item index arithmetic (round 3's form dealt (row, word) items to the waves with lane =
     // column and a ballot per item: ~930 items of ~500 instructions per four for a 289-candidate class, 50 of the kernel's 76 us; round 2's
     // lane-per-row form walked the columns in float64 at ~450 cycles per pair).
-    // Each pair is first decided in float32 with a margin that covers the rounding of the boxes and of the float32 arithmetic
-    // (coordinates <= a few thousand pixels: 1e-3 px per box side is > 8 ulp); only lanes inside that band -- a handful of pairs per
-    // image -- evaluate the reference's float64 expression inter / (area_i + area_j - inter) > thr.  Same decisions, same bits.
+    // Each pair is first decided in float32 with a margin that covers the rounding of the boxes and of the float32 arithmetic; only lanes
+    // inside that band -- a handful of pairs per image -- evaluate the reference's float64 expression inter / (area_i + area_j - inter) > thr.
+    // Same decisions, same bits, for boxes clipped to an image with (max(H, W) - 1) * (1.25 + 5.25 thr) <= DET_LIMIT_K (launch_detections
+    // refuses larger ones): with L = max(H, W) - 1, s = ha + wa + hb + wb and u = 2^-24, |lhs - (it - thr * un)| <= u L s (1.25 + 5.25 thr)
+    // (derived operation by operation in tests/detection_cases.py), which the limit keeps at or below half the margin 1e-3 (s + 1).
     {
         const int nw = (m + 63) >> 6;
         const float thr_f = (float)nms_thr;
@@ -164,7 +167,8 @@ void detections_kernel(const float* __restrict__ props, const float* __restrict_
                 const float lhs = inter - thr_f * (ha * wa + hb * wb - inter);
                 const float margin = 1e-3f * (ha + wa + hb + wb + 1.0f);
                 // exact shortcuts that keep the float64 path rare: a box of exactly zero area intersects nothing (inter == 0 -> IoU 0 or NaN:
-                // never > thr), and boxes the float32 coordinates separate by more than 1e-3 px are separate in float64 too
+                // never > thr), and boxes the float32 coordinates separate at all are separate in float64 too (rounding is monotone: float64
+                // boxes that touch or overlap give oy, ox >= 0 exactly -- at every image size)
                 const bool never = (z != 0u) | (oy < -1e-3f) | (ox < -1e-3f);
                 const bool valid = row_ok && j > i;
                 bool sup = (lhs > margin) & !never;
@@ -260,6 +264,8 @@ int launch_detections(const float* props, const float* classes, const float* del
                       float score_thr, float nms_thr, double* out, int32_t* out_cnt, hipStream_t s)
 {
     if (max_rois < 1 || max_rois > DET_MAX || ncls < 2 || ncls > 128) return FRCNN_EINVAL;
+    // the domain in which the float32 pre-filter of the bit matrix is proven to agree with float64 (see detections_kernel)
+    if ((double)((image_h > image_w ? image_h : image_w) - 1) * (1.25 + 5.25 * (double)nms_thr) > DET_LIMIT_K) return FRCNN_EUNSUPPORTED;
     hipLaunchKernelGGL(detections_kernel, dim3(ncls - 1), dim3(1024), 0, s, props, classes, deltas, n_rois,
                        max_rois, ncls, (double)(image_h - 1), (double)(image_w - 1), score_thr,
                        (double)nms_thr, out, out_cnt);

@@ -89,7 +89,9 @@ extern "C" {
                                  border pooling of BorderDet: mmcv's border_align);
                                  still 21 (additions only): frcnn_ops_riroi_align_rotated, its _backward, _16 and _max_orientations forms
                                  (ReDet's rotation-invariant RoI pooling: mmcv's riroi_align_rotated) and frcnn_ops_rotated_feature_align, its
-                                 _plan, _backward and _16 forms (R3Det's feature refinement: mmcv's rotated_feature_align) */
+                                 _plan, _backward and _16 forms (R3Det's feature refinement: mmcv's rotated_feature_align);
+                                 still 21 (no prototype or struct changed): frcnn_detections returns the documented FRCNN_EUNSUPPORTED for images past
+                                 the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -1198,7 +1200,11 @@ int frcnn_ops_dcnv4_backward_input_16(int elem_type, const int64_t* d_sorted_key
  * Outputs:
  *   d_out    : float64 [(ncls-1)][max_rois][5]  rows (y1,x1,y2,x2,score) in NMS (score-desc) order
  *   d_out_cnt: int32   [(ncls-1)]               rows valid per class (class c -> index c-1)
- * max_rois <= 512.
+ * 1 <= max_rois <= 512 and 2 <= ncls <= 128, else FRCNN_EINVAL.  nms_threshold in [0, 1].
+ * Image limit: (max(image_h, image_w) - 1) * (1.25 + 5.25 * nms_threshold) <= 8388.608, else FRCNN_EUNSUPPORTED -- sides up to 2970 px
+ * at the reference's 0.3 (2165 at 0.5, 1704 at 0.7, 1291 at 1.0, 6711 at 0.0).  Inside it the kernel's float32 pre-filter of the IoU test
+ * is proven to agree with the float64 expression (csrc/detect.hip; the derivation is in tests/detection_cases.py); past it the float32
+ * rounding of a pair of image-sized boxes can exceed the pre-filter's margin.
  * ---------------------------------------------------------------------------------------- */
 int frcnn_detections(const float* d_props, const float* d_classes, const float* d_deltas,
                      const int32_t* d_n_rois, int max_rois, int ncls,

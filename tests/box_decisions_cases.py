@@ -227,15 +227,17 @@ def isolated_score_call(scores):
 
 
 # ---- 5. detection NMS ---------------------------------------------------------------------------------------------------------------
-def det_decode(props, clip_h=599.0, clip_w=999.0):
-    """Boxes frcnn_detections decodes from proposals with zero deltas: the oracle's float32 anchor then float64 arithmetic
-    (oracle/frcnn_oracle.py: detections / convert_deltas_to_boxes), clipped."""
+def det_decode(props, clip_h=599.0, clip_w=999.0, deltas=None):
+    """Boxes frcnn_detections decodes from proposals with zero deltas (or one class's float32 deltas (n, 4)): the oracle's float32 anchor
+    then float64 arithmetic (oracle/frcnn_oracle.py: detections / convert_deltas_to_boxes), clipped."""
     from oracle import frcnn_oracle as O
     p = np.asarray(props, F32)
     anchors = np.empty((p.shape[0], 4))
     anchors[:, 0:2] = 0.5 * (p[:, 0:2] + p[:, 2:4])
     anchors[:, 2:4] = p[:, 2:4] - p[:, 0:2]
-    boxes = O.convert_deltas_to_boxes(np.zeros((p.shape[0], 4)), anchors, np.zeros(4), np.array([0.1, 0.1, 0.2, 0.2]))
+    d = np.zeros((p.shape[0], 4)) if deltas is None else np.asarray(deltas, F32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        boxes = O.convert_deltas_to_boxes(d, anchors, np.zeros(4), np.array([0.1, 0.1, 0.2, 0.2]))
     boxes[:, 0::2] = np.clip(boxes[:, 0::2], 0, clip_h)
     boxes[:, 1::2] = np.clip(boxes[:, 1::2], 0, clip_w)
     return boxes
