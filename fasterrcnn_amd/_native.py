@@ -73,6 +73,7 @@ SYMBOLS = (
     "frcnn_ops_box_iou_rotated", "frcnn_ops_nms_rotated", "frcnn_ops_roi_align_rotated_cull_list", "frcnn_ops_roi_align_rotated",
     "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
     "frcnn_ops_diff_iou_rotated", "frcnn_ops_diff_iou_rotated_backward",
+    "frcnn_ops_convex_iou_tile_rows", "frcnn_ops_convex_iou", "frcnn_ops_convex_giou", "frcnn_ops_min_area_polygons",
     "frcnn_ops_soft_nms_block_threads", "frcnn_ops_soft_nms_lds_boxes", "frcnn_ops_soft_nms_max_boxes", "frcnn_ops_soft_nms_workspace_bytes",
     "frcnn_ops_soft_nms",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
@@ -336,6 +337,11 @@ _SIGNATURES = {
     "frcnn_ops_riroi_align_rotated_backward_16": (C.c_int, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frcnn_ops_diff_iou_rotated_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    # the point-set operators (csrc/ops_convex.hip)
+    "frcnn_ops_convex_iou_tile_rows": (C.c_int, []),
+    "frcnn_ops_convex_iou": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp]),
+    "frcnn_ops_convex_giou": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "frcnn_ops_min_area_polygons": (C.c_int, [_vp, _i, _vp, _vp]),
     # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
     "frcnn_ops_soft_nms_block_threads": (C.c_int, []),
     "frcnn_ops_soft_nms_lds_boxes": (C.c_int, []),

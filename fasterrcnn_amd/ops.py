@@ -16,6 +16,8 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import border_align, BorderAlign, border_align_pytorch
     from fasterrcnn_amd.ops import riroi_align_rotated, RiRoIAlignRotated, riroi_align_rotated_pytorch
     from fasterrcnn_amd.ops import rotated_feature_align, RotatedFeatureAlign, rotated_feature_align_pytorch
+    from fasterrcnn_amd.ops import convex_iou, convex_giou, min_area_polygons
+    from fasterrcnn_amd.ops import convex_iou_pytorch, convex_giou_pytorch, min_area_polygons_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -358,6 +360,37 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       dout[pixel] over the sample corners that land on the cell in ascending (pixel, point, corner) order, through the sorted plan of
       multi_scale_deformable_attn (one plan and one stable sort, 64 channel runs per block): deterministic, no atomics.  N H W points 4
       <= MAX_RFA_INDEX.  rotated_feature_align_pytorch is the same contract from index gathers, on any device, float64 for a float64 map.
+  convex_iou(pointsets, polygons) -> float32 [N, K]
+  convex_giou(pointsets, polygons) -> (giou float32 [N], grad float32 [N, 18])
+  min_area_polygons(pointsets) -> float32 [N, 8]
+  convex_iou_pytorch(pointsets, polygons), convex_giou_pytorch(pointsets, polygons), min_area_polygons_pytorch(pointsets)
+      The point-set operators of Oriented RepPoints, CFA and SASM (csrc/ops_convex.hip; mmcv has operators of these names and
+      signatures, but the contract is the mathematical one of include/frcnn_hip.h: mmcv's epsilons, hull tie-breaks and the scaling of
+      its gradient output are not followed).  Everything is float32.  pointsets [N, 18], rows (x1, y1, ..., x9, y9); polygons [K, 8]
+      (convex_giou: [N, 8], aligned pairs), four vertices in any order.  P is the convex hull of the nine points, Q of the four
+      vertices, H of all thirteen: strictly convex vertices, counter-clockwise from the smallest (x, y); a point inside a hull edge is
+      no vertex, of equal points the smallest index is.  Turns and crossings are decided on coordinates relative to an origin (a set's
+      own smallest point for its own hull, Q's smallest vertex for everything about a pair), so boxes near x = 4096 behave as boxes near
+      0, and the hull is a function of the set: permuting the nine points or the four vertices changes no bit of any result (grad is
+      permuted alike; the header names the one exception, three nearly collinear candidates whose rounded products tie).  A_P, A_Q and C = area(H) are shoelace sums, I = area(P n Q) (Sutherland-Hodgman) is clamped at 0, U = A_P +
+      A_Q - I.  A row is dead when a coordinate is not finite, a polygon also when A_Q < 1e-14; a pair when a row of it is, or U <
+      1e-14 or C < 1e-14.  A degenerate set (A_P = 0) is not dead: I = 0 and the gradient goes through C.  convex_iou is I / U, 0 for a
+      dead pair, not differentiable (detached); a workgroup forms each hull of its CONVEX_IOU_TILE_ROWS x 64 tile once.  convex_giou
+      is I / U + U / C - 1 and its closed-form derivative in the 18 coordinates (the header states it: N / 2 of each hull edge's
+      scaled normal to both ends for the areas, N (s1 - s2) and N s2 for the part of P's edge inside Q), from ONE launch; a dead pair
+      gives 0 and a zero row, points that are no vertices of P exactly 0.  giou is differentiable by autograd too -- its backward is
+      grad_out[:, None] * grad, so (1 - giou).mean().backward() works --, grad is not; polygons get no gradient.  min_area_polygons:
+      over P's edges in hull order, u the edge's unit direction and v its left normal, the extents [u_min, u_max] x [0, v_max] of the
+      hull's vertices relative to the edge's start; the smallest (u_max - u_min) v_max wins, ties to the first edge (exact ties are
+      structural -- every edge of an acute triangle gives twice its area -- so a later edge wins only with an area < (1 - 2^-18)
+      times the best so far: CONVEX_RECT_TIE); corners (u_min, 0),
+      (u_max, 0), (u_max, v_max), (u_min, v_max), counter-clockwise; two hull vertices a, b give (a, b, b, a), one gives it four
+      times, a non-finite row zeros; not differentiable.  N = 0 or K = 0 gives empty tensors without a launch; K <=
+      MAX_CONVEX_POLYGONS, N <= MAX_CONVEX_ROWS; coordinate differences below 2^60 (beyond, products overflow).  Other dtypes are a
+      TypeError, CPU tensors, other shapes and differing devices a ValueError.  The _pytorch
+      forms are the same contract from torch operations (hull edges by the all-pairs left-of test, areas by the boundary sum over the
+      clipped edge pieces), on any device, float32 or float64, convex_giou_pytorch's gradient from autograd; they serve point sets in
+      GENERAL POSITION only: no duplicate points, no three collinear hull points, no coincident edges.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -390,7 +423,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttention", "prroi_pool", "PrRoIPool", "prroi_pool_pytorch",
            "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4",
            "border_align", "BorderAlign", "border_align_pytorch", "riroi_align_rotated", "RiRoIAlignRotated",
-           "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch"]
+           "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch",
+           "convex_iou", "convex_giou", "min_area_polygons", "convex_iou_pytorch", "convex_giou_pytorch", "min_area_polygons_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -400,6 +434,11 @@ PRROI_CULL_LIST = 1024                    # RoIs that prroi_pool's input-gradien
 MAX_SAMPLING_RATIO = 16
 MAX_NMS_BOXES = 524288
 MAX_ROTATED_IOU_ROWS = 65535 * 64         # rows of box_iou_rotated's matrix (the tile rows of its launch grid)
+MAX_CONVEX_POLYGONS = 65535 * 64          # columns of convex_iou's matrix (the tile columns of its launch grid)
+MAX_CONVEX_ROWS = 2 ** 31 - 1 - 1024      # point sets of one call (CVX_MAX_ROWS of csrc/ops_convex.hip: the grids' ceilings are formed in int)
+CONVEX_IOU_TILE_ROWS = 32                 # rows of convex_iou's tile (CVX_TILE_ROWS of csrc/ops_convex.hip); its columns: 64
+CONVEX_MIN_AREA = 1e-14                   # below it a polygon, a union or an enclosing hull is dead (CVX_MIN_AREA)
+CONVEX_RECT_TIE = 1 - 2.0 ** -18          # min_area_polygons: a later edge wins only with an area below this times the best (CVX_RECT_TIE)
 MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
                                           # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
                                           # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
@@ -3682,3 +3721,299 @@ class DCNv4(torch.nn.Module):
                 "remove_center=%s, without_pointwise=%s" % (self.channels, self.kernel_size, self.stride, self.pad, self.dilation, self.group,
                                                            self.offset_scale, self.dw_kernel_size, self.remove_center,
                                                            self.without_pointwise))
+
+
+# ---- point-set operators: convex_iou, convex_giou, min_area_polygons (csrc/ops_convex.hip) --------------------------------------------
+@torch.library.custom_op("frcnn::convex_iou", mutates_args=())
+def _convex_iou(pointsets: Tensor, polygons: Tensor) -> Tensor:
+    n, k = pointsets.shape[0], polygons.shape[0]
+    out = pointsets.new_empty((n, k))
+    if n == 0 or k == 0:
+        return out
+    with torch.cuda.device(pointsets.device):
+        a, b = pointsets.contiguous(), polygons.contiguous()
+        nv.check(nv.lib().frcnn_ops_convex_iou(a.data_ptr(), n, b.data_ptr(), k, out.data_ptr(), _stream(pointsets)),
+                 "frcnn_ops_convex_iou")
+    return out
+
+
+@_convex_iou.register_fake
+def _(pointsets, polygons):
+    return pointsets.new_empty((pointsets.shape[0], polygons.shape[0]))
+
+
+@torch.library.custom_op("frcnn::convex_giou", mutates_args=())
+def _convex_giou(pointsets: Tensor, polygons: Tensor) -> Tuple[Tensor, Tensor]:
+    """(giou [n], its derivative in the point sets [n, 18]) of the aligned pairs, from one launch."""
+    n = pointsets.shape[0]
+    giou, grad = pointsets.new_empty((n,)), pointsets.new_empty((n, 18))
+    if n == 0:
+        return giou, grad
+    with torch.cuda.device(pointsets.device):
+        a, b = pointsets.contiguous(), polygons.contiguous()
+        nv.check(nv.lib().frcnn_ops_convex_giou(a.data_ptr(), b.data_ptr(), n, giou.data_ptr(), grad.data_ptr(), _stream(pointsets)),
+                 "frcnn_ops_convex_giou")
+    return giou, grad
+
+
+@_convex_giou.register_fake
+def _(pointsets, polygons):
+    n = pointsets.shape[0]
+    return pointsets.new_empty((n,)), pointsets.new_empty((n, 18))
+
+
+def _convex_giou_bwd(ctx, grad_giou, grad_grad):
+    (grad,) = ctx.saved_tensors
+    return (grad_giou[:, None] * grad if ctx.needs_input_grad[0] else None), None
+
+
+torch.library.register_autograd("frcnn::convex_giou", _convex_giou_bwd,
+                                setup_context=lambda ctx, inputs, output: ctx.save_for_backward(output[1].detach()))
+
+
+@torch.library.custom_op("frcnn::min_area_polygons", mutates_args=())
+def _min_area_polygons(pointsets: Tensor) -> Tensor:
+    n = pointsets.shape[0]
+    out = pointsets.new_empty((n, 8))
+    if n == 0:
+        return out
+    with torch.cuda.device(pointsets.device):
+        a = pointsets.contiguous()
+        nv.check(nv.lib().frcnn_ops_min_area_polygons(a.data_ptr(), n, out.data_ptr(), _stream(pointsets)), "frcnn_ops_min_area_polygons")
+    return out
+
+
+@_min_area_polygons.register_fake
+def _(pointsets):
+    return pointsets.new_empty((pointsets.shape[0], 8))
+
+
+def _convex_input(name, t, width, row, fallback):
+    _check_tensor(name, t, (torch.float32,), "float32 (the point-set operators are float32 only: pass .float())", fallback)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError("%s must be [N, %d] %s, got shape %s" % (name, width, row, tuple(t.shape)))
+    if t.shape[0] > MAX_CONVEX_ROWS:
+        raise ValueError("%s holds at most MAX_CONVEX_ROWS = %d rows, got %d" % (name, MAX_CONVEX_ROWS, t.shape[0]))
+
+
+_CONVEX_SET_ROW, _CONVEX_POLY_ROW = "(x1, y1, ..., x9, y9)", "(x1, y1, ..., x4, y4)"
+
+
+def convex_iou(pointsets, polygons):
+    """mmcv.ops.convex_iou: the IoU of the convex hull of every point set [N, 18] with every polygon [K, 8] -> [N, K] (the module
+    docstring states the contract).  Not differentiable."""
+    _convex_input("pointsets", pointsets, 18, _CONVEX_SET_ROW, "convex_iou_pytorch")
+    _convex_input("polygons", polygons, 8, _CONVEX_POLY_ROW, "convex_iou_pytorch")
+    _check_same_device(pointsets, polygons, "pointsets", "polygons")
+    if polygons.shape[0] > MAX_CONVEX_POLYGONS:
+        raise ValueError("polygons holds at most MAX_CONVEX_POLYGONS = %d rows, got %d" % (MAX_CONVEX_POLYGONS, polygons.shape[0]))
+    return _convex_iou(pointsets.detach(), polygons.detach())
+
+
+def convex_giou(pointsets, polygons):
+    """mmcv.ops.convex_giou: (giou [N], grad [N, 18]) of the aligned pairs of point sets [N, 18] and polygons [N, 8]: the generalised
+    IoU of the sets' hulls and its closed-form derivative in the sets' coordinates, from one launch.  giou also carries that
+    derivative through autograd (backward: grad_out[:, None] * grad); grad itself is not differentiable."""
+    _convex_input("pointsets", pointsets, 18, _CONVEX_SET_ROW, "convex_giou_pytorch")
+    _convex_input("polygons", polygons, 8, _CONVEX_POLY_ROW, "convex_giou_pytorch")
+    if pointsets.shape[0] != polygons.shape[0]:
+        raise ValueError("pointsets and polygons must hold one polygon per point set, got %d and %d rows"
+                         % (pointsets.shape[0], polygons.shape[0]))
+    _check_same_device(pointsets, polygons, "pointsets", "polygons")
+    giou, grad = _convex_giou(pointsets, polygons.detach())
+    return giou, grad.detach()
+
+
+def min_area_polygons(pointsets):
+    """mmcv.ops.min_area_polygons: the rectangle of the smallest area around each point set [N, 18] -> [N, 8], four corners
+    counter-clockwise, one side on a hull edge (the module docstring states the contract).  Not differentiable."""
+    _convex_input("pointsets", pointsets, 18, _CONVEX_SET_ROW, "min_area_polygons_pytorch")
+    return _min_area_polygons(pointsets.detach())
+
+
+def _convex_pytorch_input(name, t, width, row):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s must be float32 or float64, got %s" % (name, t.dtype))
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError("%s must be [N, %d] %s, got shape %s" % (name, width, row, tuple(t.shape)))
+
+
+def _cross2(a, b):
+    return a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+
+
+def _convex_hull_list(pts):
+    """pts [B, n, 2] in general position -> the hull's vertices [B, n, 2], counter-clockwise from the smallest (x, y), the start repeated
+    after the last one (a zero-length edge adds nothing to any sum below).  i -> j is a hull edge iff every other point lies strictly on
+    its left; the decisions carry no gradient, the gathered vertices do."""
+    n = pts.shape[1]
+    with torch.no_grad():
+        d = pts[:, None, :, :] - pts[:, :, None, :]                                  # d[b, i, j] = p_j - p_i
+        left = d[:, :, :, None, 0] * d[:, :, None, :, 1] - d[:, :, :, None, 1] * d[:, :, None, :, 0] > 0     # [b, i, j, k]
+        eye = torch.eye(n, dtype=torch.bool, device=pts.device)
+        edge = (left | eye[:, None, :] | eye[None, :, :]).all(-1) & ~eye              # k == i or k == j does not vote
+        vertex = edge.any(-1)
+        nxt = edge.to(torch.uint8).argmax(-1)
+        inf = torch.full_like(pts[..., 0], float("inf"))
+        xs = torch.where(vertex, pts[..., 0], inf)
+        first = vertex & (xs == xs.min(-1, keepdim=True).values)
+        start = torch.where(first, pts[..., 1], inf).argmin(-1, keepdim=True)
+        cur, done, order = start, torch.zeros_like(start, dtype=torch.bool), [start]
+        for _ in range(n - 1):
+            step = nxt.gather(1, cur)
+            done = done | (step == start)
+            cur = torch.where(done, start, step)
+            order.append(cur)
+        order = torch.cat(order, 1)
+    return pts.gather(1, order[..., None].expand(-1, -1, 2))
+
+
+def _convex_list_area(v):
+    """The shoelace area of vertex lists [..., n, 2]: the fan from the first vertex."""
+    r = v[..., 1:, :] - v[..., :1, :]
+    return 0.5 * _cross2(r[..., :-1, :], r[..., 1:, :]).sum(-1)
+
+
+def _convex_boundary_inside(a, w):
+    """Half the sum of cross(start, end) over the pieces of polygon a's edges ([..., m, 2]) that lie inside the convex polygon w
+    ([..., k, 2], counter-clockwise): Cyrus-Beck per edge, every division on a safe denominator."""
+    b = torch.roll(a, -1, -2)
+    wa = w[..., None, :, :]
+    e = torch.roll(w, -1, -2)[..., None, :, :] - wa                                    # [..., 1, k, 2]
+    da = _cross2(e, a[..., :, None, :] - wa)                                          # [..., m, k]
+    db = _cross2(e, b[..., :, None, :] - wa)
+    enter, leave = (da < 0) & (db >= 0), (da >= 0) & (db < 0)
+    t = da / torch.where(enter | leave, da - db, torch.ones_like(da))
+    t0 = torch.where(enter, t, torch.zeros_like(t)).max(-1).values
+    t1 = torch.where(leave, t, torch.ones_like(t)).min(-1).values
+    inside = ~((da < 0) & (db < 0)).any(-1) & (t1 > t0)
+    d = b - a
+    piece = _cross2(a + t0[..., None] * d, a + t1[..., None] * d)
+    return 0.5 * torch.where(inside, piece, torch.zeros_like(piece)).sum(-1)
+
+
+def _convex_inter(p, q):
+    """area(P n Q) of hull lists p [..., 9, 2] and q [..., 4, 2] on one origin: the boundary of the intersection is P's edges inside Q
+    and Q's edges inside P."""
+    return (_convex_boundary_inside(p, q) + _convex_boundary_inside(q, p)).clamp_min(0)
+
+
+def _convex_finite(t):
+    return torch.isfinite(t).all(-1)
+
+
+def convex_iou_pytorch(pointsets, polygons):
+    """convex_iou from torch operations, on any device, float32 or float64 -> [N, K].  The hull edges come from the all-pairs left-of
+    test and I from the boundary sum over the clipped edge pieces, so it serves point sets in GENERAL POSITION only: no duplicate
+    points, no three collinear hull points, no edge of P on an edge of Q.  Not fast: rows go through in chunks."""
+    _convex_pytorch_input("pointsets", pointsets, 18, _CONVEX_SET_ROW)
+    _convex_pytorch_input("polygons", polygons, 8, _CONVEX_POLY_ROW)
+    n, k = pointsets.shape[0], polygons.shape[0]
+    out = pointsets.new_zeros((n, k))
+    if n == 0 or k == 0:
+        return out
+    with torch.no_grad():
+        polygons = polygons.to(pointsets.dtype)
+        okq = _convex_finite(polygons)
+        q = _convex_hull_list(torch.where(okq[:, None], polygons, torch.zeros_like(polygons)).view(k, 4, 2))
+        origin = q[:, 0]
+        q = q - origin[:, None]
+        aq = _convex_list_area(q)
+        okq = okq & (aq >= CONVEX_MIN_AREA)
+        for i0 in range(0, n, 1024):
+            rows = pointsets[i0:i0 + 1024]
+            okp = _convex_finite(rows)
+            p = _convex_hull_list(torch.where(okp[:, None], rows, torch.zeros_like(rows)).view(-1, 9, 2))
+            ap = _convex_list_area(p - p[:, :1])
+            inter = _convex_inter(p[:, None] - origin[None, :, None], q[None])
+            union = ap[:, None] + aq[None] - inter
+            ok = okp[:, None] & okq[None] & (union >= CONVEX_MIN_AREA)
+            out[i0:i0 + 1024] = torch.where(ok, inter / torch.where(ok, union, torch.ones_like(union)), torch.zeros_like(union))
+    return out
+
+
+def _convex_giou_value(pointsets, polygons):
+    n = pointsets.shape[0]
+    ok = _convex_finite(pointsets) & _convex_finite(polygons)
+    sets = torch.where(ok[:, None], pointsets, torch.zeros_like(pointsets)).view(n, 9, 2)
+    quads = torch.where(ok[:, None], polygons, torch.zeros_like(polygons)).view(n, 4, 2)
+    q = _convex_hull_list(quads)
+    origin = q[:, :1]
+    q = q - origin
+    p = _convex_hull_list(sets)
+    ap, aq = _convex_list_area(p - p[:, :1]), _convex_list_area(q)
+    p = p - origin
+    inter = _convex_inter(p, q)
+    union = ap + aq - inter
+    hull = _convex_list_area(_convex_hull_list(torch.cat([sets, quads], 1) - origin))
+    ok = ok & (aq >= CONVEX_MIN_AREA) & (union >= CONVEX_MIN_AREA) & (hull >= CONVEX_MIN_AREA)
+    one = torch.ones_like(union)
+    union, hull = torch.where(ok, union, one), torch.where(ok, hull, one)
+    return torch.where(ok, inter / union + union / hull - 1, torch.zeros_like(union))
+
+
+class _ConvexGiouPytorch(torch.autograd.Function):
+    """Hands giou out with the gradient that autograd already formed: backward is grad_out[:, None] * grad."""
+
+    @staticmethod
+    def forward(ctx, pointsets, giou, grad):
+        ctx.save_for_backward(grad)
+        return giou.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return grad_out[:, None] * ctx.saved_tensors[0], None, None
+
+
+def convex_giou_pytorch(pointsets, polygons):
+    """convex_giou from torch operations, on any device, float32 or float64 -> (giou [N], grad [N, 18]); grad comes from autograd
+    through the composition, and giou carries it as convex_giou's does.  For point sets in GENERAL POSITION only: no duplicate points, no
+    three collinear hull points (of P, or of the thirteen points), no edge of P on an edge of Q."""
+    _convex_pytorch_input("pointsets", pointsets, 18, _CONVEX_SET_ROW)
+    _convex_pytorch_input("polygons", polygons, 8, _CONVEX_POLY_ROW)
+    if pointsets.shape[0] != polygons.shape[0]:
+        raise ValueError("pointsets and polygons must hold one polygon per point set, got %d and %d rows"
+                         % (pointsets.shape[0], polygons.shape[0]))
+    if pointsets.shape[0] == 0:
+        return pointsets.new_zeros((0,)) + 0 * pointsets.sum(), pointsets.new_zeros((0, 18))
+    with torch.enable_grad():
+        leaf = pointsets.detach().requires_grad_(True)
+        value = _convex_giou_value(leaf, polygons.detach().to(pointsets.dtype))
+        (grad,) = torch.autograd.grad(value.sum(), leaf)
+    return _ConvexGiouPytorch.apply(pointsets, value.detach(), grad), grad
+
+
+def min_area_polygons_pytorch(pointsets):
+    """min_area_polygons from torch operations, on any device, float32 or float64 -> [N, 8].  For point sets in GENERAL POSITION only: no
+    duplicate points, no three collinear hull points; of edges whose rectangles tie (areas within a relative 2^-18 of the smallest) the
+    first one wins."""
+    _convex_pytorch_input("pointsets", pointsets, 18, _CONVEX_SET_ROW)
+    n = pointsets.shape[0]
+    if n == 0:
+        return pointsets.new_zeros((0, 8))
+    with torch.no_grad():
+        ok = _convex_finite(pointsets)
+        hull = _convex_hull_list(torch.where(ok[:, None], pointsets, torch.zeros_like(pointsets)).view(n, 9, 2))
+        origin = hull[:, :1]
+        v = hull - origin
+        e = torch.roll(v, -1, 1) - v                                                  # [n, 9, 2]; zero for the repeated start
+        length = e.norm(dim=-1)
+        real = length > 0
+        u = e / torch.where(real, length, torch.ones_like(length))[..., None]
+        d = v[:, None, :, :] - v[:, :, None, :]                                      # d[b, k, w] = v_w - v_k
+        pu = (d * u[:, :, None, :]).sum(-1)
+        pv = d[..., 1] * u[:, :, None, 0] - d[..., 0] * u[:, :, None, 1]
+        u0, u1, v1 = pu.min(-1).values, pu.max(-1).values, pv.max(-1).values
+        area = torch.where(real, (u1 - u0) * v1, torch.full_like(length, float("inf")))
+        tied = area * CONVEX_RECT_TIE <= area.min(-1, keepdim=True).values
+        best = tied.to(torch.uint8).argmax(-1, keepdim=True)                          # the first of the tied
+        pick = lambda t: t.gather(1, best)[:, 0]                                       # noqa: E731
+        a = v.gather(1, best[..., None].expand(-1, -1, 2))[:, 0]
+        ub = u.gather(1, best[..., None].expand(-1, -1, 2))[:, 0]
+        u0, u1, v1 = pick(u0)[:, None], pick(u1)[:, None], pick(v1)[:, None]
+        left = torch.stack([-ub[:, 1], ub[:, 0]], 1)
+        c0, c1 = a + u0 * ub, a + u1 * ub
+        out = torch.stack([c0, c1, c1 + v1 * left, c0 + v1 * left], 1) + origin
+        return torch.where(ok[:, None], out.reshape(n, 8), torch.zeros_like(pointsets[:, :8]))

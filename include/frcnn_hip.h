@@ -90,6 +90,9 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_riroi_align_rotated, its _backward, _16 and _max_orientations forms
                                  (ReDet's rotation-invariant RoI pooling: mmcv's riroi_align_rotated) and frcnn_ops_rotated_feature_align, its
                                  _plan, _backward and _16 forms (R3Det's feature refinement: mmcv's rotated_feature_align);
+                                 still 21 (additions only): frcnn_ops_convex_iou, its _tile_rows getter, frcnn_ops_convex_giou and
+                                 frcnn_ops_min_area_polygons (the point-set operators of Oriented RepPoints, CFA and SASM: mmcv's convex_iou,
+                                 convex_giou and min_area_polygons);
                                  still 21 (no prototype or struct changed): frcnn_detections returns the documented FRCNN_EUNSUPPORTED for images past
                                  the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before) */
 
@@ -923,6 +926,60 @@ int frcnn_ops_rotated_feature_align_16(int elem_type, const void* d_x, const flo
                                        float spatial_scale, int points, void* d_out, void* stream);
 int frcnn_ops_rotated_feature_align_backward_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,
                                                 const void* d_dout, int n_img, int fh, int fw, int c, int points, void* d_dx, void* stream);
+
+/* convex_iou, convex_giou and min_area_polygons, the point-set operators of Oriented RepPoints, CFA and SASM (csrc/ops_convex.hip).
+ *   mmcv has operators of these names (third party, absent here); this text is the mathematical contract and holds where mmcv's
+ *   kernels deviate from it: their epsilons, their hull tie-breaks and the scaling of their gradient output are not followed.
+ *   Everything is float32.  A point set is a row of 18 floats (x1, y1, ..., x9, y9); a polygon a row of 8 floats, four vertices in ANY
+ *   order.
+ * Hulls.  P is the convex hull of the nine points, Q that of the polygon's four vertices, H that of all thirteen.  A hull is the list
+ *   of its strictly convex vertices, counter-clockwise, starting at the vertex with the smallest x, ties to the smaller y.  A point
+ *   in the interior of a hull edge is not a vertex; of exactly equal points only the one with the smallest index (a set's points
+ *   before the polygon's) is a vertex.  Every product that decides a turn or a crossing is formed on coordinates relative to an
+ *   origin: a set's or a polygon's own hull relative to its own smallest point, everything that involves a pair (the clip, H, the
+ *   normals of the gradient) relative to Q's smallest vertex; boxes near x = 4096 behave as boxes near 0.  The hull is a function
+ *   of the set, not of the order of its points: permuting the nine points, or the four vertices, changes no bit of any result
+ *   (the gradient's rows are permuted alike).  The one exception: a turn is decided by comparing the two rounded products of its cross
+ *   product, and where the products of points that are not truly collinear round to one value the farther point wins; among three
+ *   such nearly collinear candidates that rule is no total order, and the winner can depend on the order of the points.
+ * Range.  The results are specified for coordinates whose differences stay below 2^60 in magnitude: beyond, the products of the turns
+ *   and the areas overflow.  Inside it, scaling every coordinate by a power of two scales every result exactly (no area is squared:
+ *   I / U^2 and U / C^2 are two divisions each), as long as the areas stay above the 1e-14 of the dead rule, which is absolute.
+ *   min_area_polygons has no such rule: where the products of differences underflow (differences below 2^-60) its hull may come out
+ *   flat, but it scales an edge by its larger component before it takes the length, so its unit vectors are finite for any two
+ *   distinct vertices.
+ * Areas.  A_P, A_Q and C = area(H) are shoelace sums (the fan of triangles from the first hull vertex); I = area(P n Q) is the area of
+ *   P's hull clipped against Q's half-planes (Sutherland-Hodgman, at most 13 vertices), clamped at 0 from below; U = A_P + A_Q - I.
+ * Dead rows and pairs.  A row is dead when a coordinate is not finite, a polygon also when A_Q < 1e-14.  A pair is dead when either
+ *   of its rows is, or when U < 1e-14 or C < 1e-14.  A degenerate point set (A_P = 0: coincident or collinear points) is NOT dead:
+ *   it has I = 0 and a gradient through C.
+ * frcnn_ops_convex_iou: d_out[n][k] = I / U of set i and polygon j, 0 for a dead pair.  One launch; a workgroup owns
+ *   frcnn_ops_convex_iou_tile_rows() rows x 64 columns, forms the hull of each of its rows and columns once, in LDS, and sweeps
+ *   them; a pair whose axis-aligned bounding boxes are apart is 0 without a clip.  (C plays no part: C >= U.)
+ * frcnn_ops_convex_giou: aligned pairs, one launch writing both outputs.  d_giou[n] = I / U + U / C - 1;  d_grad[n][18] its derivative
+ *   in the set's coordinates (the polygon is a target), in closed form.  For a hull edge a -> b let N = (b_y - a_y, a_x - b_x), the
+ *   outward normal times the edge's length; clip the edge against Q's half-planes (Cyrus-Beck), [t0, t1] the parameter interval
+ *   inside Q, s1 = t1 - t0, s2 = (t1^2 - t0^2) / 2.  Then
+ *     dA_P: every edge of P adds N / 2 to a and to b;     dC: the same over H's edges, for those ends that are points of the set;
+ *     dI: every edge of P with t1 > t0 adds N (s1 - s2) to a and N s2 to b;     dU = dA_P - dI;
+ *     d giou = dI / U - I dU / U^2 + dU / C - U dC / C^2.
+ *   Points that are not vertices of P get exactly 0; a dead pair gives giou = 0 and a zero row.  Where hull membership changes or
+ *   edges coincide the function has a kink and the result is the one-sided derivative of the hulls that were formed.
+ * frcnn_ops_min_area_polygons: d_out[n][8].  For every edge k of P in hull order, with u the edge's unit direction and v its left
+ *   normal: the extents [u_min, u_max] x [0, v_max] of the hull's vertices relative to the edge's start vertex.  The result is the
+ *   rectangle of the smallest area (u_max - u_min) v_max, ties to the first k, as four corners counter-clockwise: (u_min, 0),
+ *   (u_max, 0), (u_max, v_max), (u_min, v_max).  A hull of two vertices a, b gives (a, b, b, a), one of a single vertex that vertex
+ *   four times, a row with a non-finite coordinate zeros.  One launch.  Exact ties are structural (all edges of an acute triangle
+ *   give twice its area; so does every hull whose rectangle rests on three vertices) and no float32 sum resolves them, so a tie
+ *   has a width: walking k upwards, edge k replaces the best so far only when its area < (1 - 2^-18) * best.
+ * No vertex list lives in scratch memory (LDS columns, one per lane); no atomics; every output element is written.  Arguments are
+ *   validated before the GPU is touched (FRCNN_EINVAL): negative counts, more than 2^31 - 1 - 1024 rows (the grids' ceilings are formed
+ *   in int), more than 65535 * 64 polygons in convex_iou, NULL pointers.
+ *   n == 0 (or k == 0) returns FRCNN_OK without a launch. */
+int frcnn_ops_convex_iou_tile_rows(void);
+int frcnn_ops_convex_iou(const float* d_pointsets, int n, const float* d_polygons, int k, float* d_out, void* stream);
+int frcnn_ops_convex_giou(const float* d_pointsets, const float* d_polygons, int n, float* d_giou, float* d_grad, void* stream);
+int frcnn_ops_min_area_polygons(const float* d_pointsets, int n, float* d_out, void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

@@ -92,6 +92,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     ops.rotated_feature_align beside ops.rotated_feature_align_pytorch (index gathers, autograd's backward), forward and
     forward + backward, in alternating windows.  Informational: no speed bound is set.
 
+  * convex: the point-set operators of Oriented RepPoints / CFA / SASM on a 1024 x 1024 image, float32: ops.convex_iou of 20000 point
+    sets against 64 polygons (the assigner: half of the sets lie around a polygon, half anywhere), ops.convex_giou of 4096 aligned
+    pairs, forward and forward + backward (the loss), and ops.min_area_polygons of the 20000 sets, each beside its _pytorch
+    composition on the same GPU, in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only convex          # just the point-set leg
     python tools/ops_bench.py --only rfa             # just the rotated_feature_align leg
     python tools/ops_bench.py --only riroi           # just the RiRoIAlignRotated leg
     python tools/ops_bench.py --only border          # just the BorderAlign leg
@@ -642,6 +648,50 @@ def rfa_leg(rng, reps, warmup):
     return res
 
 
+def convex_leg(rng, reps, warmup):
+    n, k, pairs = 20000, 64, 4096
+
+    def rot(a):
+        return np.stack([np.stack([np.cos(a), -np.sin(a)], -1), np.stack([np.sin(a), np.cos(a)], -1)], -2)
+
+    def boxes(m):
+        return rng.uniform(0, 1024, (m, 2)), np.exp(rng.uniform(np.log(16), np.log(256), (m, 2))), rng.uniform(-np.pi / 2, np.pi / 2, m)
+
+    def polygons(c, wh, a):
+        corners = np.array([[-.5, -.5], [.5, -.5], [.5, .5], [-.5, .5]])[None] * wh[:, None]
+        return (np.einsum("nij,nkj->nki", rot(a), corners) + c[:, None]).reshape(-1, 8)
+
+    def pointsets(c, wh, a):
+        m = c.shape[0]
+        p = rng.uniform(-0.7, 0.7, (m, 9, 2)) * wh[:, None]
+        return (np.einsum("nij,nkj->nki", rot(a + rng.uniform(-0.3, 0.3, m)), p) + (rng.uniform(-0.2, 0.2, (m, 2)) * wh + c)[:, None]).reshape(-1, 18)
+
+    to = lambda v: torch.from_numpy(v.astype(np.float32)).to(DEV)     # noqa: E731
+    c, wh, a = boxes(k)
+    polys = to(polygons(c, wh, a))
+    pick = np.arange(n) % k
+    cs = np.where((np.arange(n) % 2 == 0)[:, None], c[pick], rng.uniform(0, 1024, (n, 2)))
+    sets = to(pointsets(cs, wh[pick], a[pick]))
+    c, wh, a = boxes(pairs)
+    pair_sets, pair_polys, g = to(pointsets(c, wh, a)), to(polygons(c, wh, a)), to(rng.uniform(-1, 1, pairs))
+    leaf = pair_sets.clone().requires_grad_(True)
+    iou, iou_c = ops.convex_iou(sets, polys), ops.convex_iou_pytorch(sets, polys)
+    giou, giou_c = ops.convex_giou(pair_sets, pair_polys), ops.convex_giou_pytorch(pair_sets, pair_polys)
+    res = {"max |convex_iou - composition|": float((iou - iou_c).abs().max()), "share of pairs with IoU > 0": float((iou > 0).float().mean()),
+           "max |giou - composition|": float((giou[0] - giou_c[0]).abs().max()), "mean giou": float(giou[0].mean()),
+           "median |grad - composition| / max |grad|": float((giou[1] - giou_c[1]).abs().amax(1).median() / giou_c[1].abs().max()),
+           "median |min_area_polygons - composition|": float((ops.min_area_polygons(sets) - ops.min_area_polygons_pytorch(sets)).abs().amax(1).median())}
+    for name, native, comp in (
+            ("convex_iou %d x %d" % (n, k), lambda: ops.convex_iou(sets, polys), lambda: ops.convex_iou_pytorch(sets, polys)),
+            ("convex_giou %d fwd" % pairs, lambda: ops.convex_giou(pair_sets, pair_polys), lambda: ops.convex_giou_pytorch(pair_sets, pair_polys)),
+            ("convex_giou %d fwd+bwd" % pairs, lambda: ops.convex_giou(leaf, pair_polys)[0].backward(g),
+             lambda: ops.convex_giou_pytorch(leaf, pair_polys)[0].backward(g)),
+            ("min_area_polygons %d" % n, lambda: ops.min_area_polygons(sets), lambda: ops.min_area_polygons_pytorch(sets))):
+        t_native, t_comp = timed_pair(native, comp, reps, warmup)
+        res[name] = {"ops": round(t_native, 1), "_pytorch composition": round(t_comp, 1), "composition / ops": round(t_comp / t_native, 2)}
+    return {"convex float32 (microseconds)": res}
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -725,7 +775,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -779,6 +829,9 @@ def main():
         return
     if a.only == "rfa":
         print(json.dumps(rfa_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "convex":
+        print(json.dumps(convex_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -853,6 +906,7 @@ def main():
     res.update(border_leg(rng, 5, 2))
     res.update(riroi_leg(rng, 5, 2))
     res.update(rfa_leg(rng, 5, 2))
+    res.update(convex_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
