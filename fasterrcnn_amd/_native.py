@@ -68,6 +68,9 @@ SYMBOLS = (
     "frcnn_ops_ps_roi_pool_16", "frcnn_ops_ps_roi_pool_backward_16", "frcnn_ops_ps_roi_align_16", "frcnn_ops_ps_roi_align_backward_16",
     "frcnn_ops_deform_workspace_bytes", "frcnn_ops_deform_forward", "frcnn_ops_deform_backward_columns", "frcnn_ops_deform_backward_offset",
     "frcnn_ops_deform_input_plan", "frcnn_ops_deform_backward_input", "frcnn_ops_deform_backward_weight",
+    "frcnn_ops_deform_workspace_bytes_16", "frcnn_ops_deform_forward_16", "frcnn_ops_deform_backward_columns_16",
+    "frcnn_ops_deform_backward_offset_16", "frcnn_ops_deform_input_plan_16", "frcnn_ops_deform_backward_input_16",
+    "frcnn_ops_deform_backward_weight_16",
     "frcnn_ops_deform_roi_pool_cull_list", "frcnn_ops_deform_roi_pool_workspace_bytes", "frcnn_ops_deform_roi_pool",
     "frcnn_ops_deform_roi_pool_backward", "frcnn_ops_deform_roi_pool_16", "frcnn_ops_deform_roi_pool_backward_16",
     "frcnn_ops_box_iou_rotated", "frcnn_ops_nms_rotated", "frcnn_ops_roi_align_rotated_cull_list", "frcnn_ops_roi_align_rotated",
@@ -313,6 +316,14 @@ _SIGNATURES = {
     "frcnn_ops_deform_input_plan": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp]),
     "frcnn_ops_deform_backward_input": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "frcnn_ops_deform_backward_weight": (C.c_int, [C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    # the same on float16 / bfloat16 tensors: the element-type code first (dcol, the plan's weights and d_weight stay float32)
+    "frcnn_ops_deform_workspace_bytes_16": (C.c_size_t, [_i, C.POINTER(DeformGeom), _i, _i]),
+    "frcnn_ops_deform_forward_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_columns_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_offset_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_deform_input_plan_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp]),
+    "frcnn_ops_deform_backward_input_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_deform_backward_weight_16": (C.c_int, [_i, C.POINTER(DeformGeom), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     # deformable RoI pooling on NHWC maps (csrc/ops_droi.hip); the _16 forms take the element-type code first
     "frcnn_ops_deform_roi_pool_cull_list": (C.c_int, []),
     "frcnn_ops_deform_roi_pool_workspace_bytes": (C.c_size_t, [_i, _i, _i]),

@@ -278,6 +278,15 @@ int launch_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, i
                    void* ws, size_t ws_bytes, hipStream_t s, int math = FRCNN_GRAD_F32);
 int launch_conv3x3_wgrad(const float* x, const float* dz, float* dwp, int H, int W, int cin, int cout,
                          void* ws, size_t ws_bytes, hipStream_t s, int math = FRCNN_GRAD_F32);
+// gemm_nt16.hip: C[m][n] = sum_r A[m][r] B[n][r], operands float16 / bfloat16 in memory (elem_type: FRCNN_OPS_F16 / _BF16), 16-byte
+// aligned, lda, ldb and R multiples of 8 with the pad written as zeros; float32 accumulators
+int gemm_nt16_splits(int M, int N, int R);
+size_t gemm_nt16_workspace_bytes(int M, int N, int R);
+int launch_gemm_nt16(int elem_type, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int R, hipStream_t s);
+int launch_gemm_nt16_split(int elem_type, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int R,
+                           int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_gemm_nt16_nchw(int elem_type, const void* A, int lda, const void* B, int ldb, int M, int N, int R, const void* bias, void* out,
+                          int P, int c_total, int c_base, hipStream_t s);
 int launch_label_proposals(const float* props, const int32_t* n_props, int max_props, const float* gt,
                            const int32_t* gt_cls, int M, int ncls, float bg_thr, float obj_thr,
                            const float means[4], const float stds[4], float* out_props, int32_t* out_cls,

@@ -1,9 +1,36 @@
 // ops_deform.h -- the bilinear sample of deformable convolution, stated once for every kernel of ops_deform.hip (torchvision's
-// deform_conv2d_kernel.cu: bilinear_interpolate and get_coordinate_weight, restated, unpinned).
+// deform_conv2d_kernel.cu: bilinear_interpolate and get_coordinate_weight, restated, unpinned), over the storage type E of the maps:
+// float, or a 16-bit type that is widened exactly on load, so that the arithmetic is the float32 kernels' whatever E is.
 #pragma once
 #include "common.h"
 
 namespace frcnn {
+
+// Storage types of input, offset, mask and their gradients: float, or the 16-bit ones of the frcnn_ops_deform_*_16 entry points.
+// deform_load widens exactly; deform_store rounds to nearest even once, NaN and infinities as torch's Tensor.to() (float16 by the
+// hardware conversion, bfloat16 by the integer rounding of c10::BFloat16: every NaN becomes 0x7FC0).
+struct deform_f16 { _Float16 v; };
+struct deform_bf16 { unsigned short bits; };
+
+__device__ __forceinline__ float deform_load(const float* p, size_t i) { return p[i]; }
+__device__ __forceinline__ float deform_load(const deform_f16* p, size_t i) { return (float)p[i].v; }
+__device__ __forceinline__ float deform_load(const deform_bf16* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
+
+__device__ __forceinline__ void deform_round(float v, float& e) { e = v; }
+// The empty asm pins v as a float32 VALUE before the conversion.  Without it the compiler folds a preceding float32 multiply or add
+// into the conversion (v_fma_mixlo_f16), which rounds the exact product to float16 directly: where the float32 product is a float16
+// tie that skips the float32 rounding of the contract and lands on the other neighbour (seen on an MI355X: one column in 21384).
+__device__ __forceinline__ void deform_round(float v, deform_f16& e)
+{
+    asm volatile("" : "+v"(v));
+    e.v = (_Float16)v;
+}
+__device__ __forceinline__ void deform_round(float v, deform_bf16& e)
+{
+    const unsigned b = __float_as_uint(v);
+    e.bits = v != v ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+}
+template <typename E> __device__ __forceinline__ void deform_store(E* p, size_t i, float v) { deform_round(v, p[i]); }
 
 // sample coordinate of tap i at output index o along one axis: the integer position first, then the float displacement
 __device__ __forceinline__ float deform_coord(int o, int stride, int pad, int i, int dil, float off)
@@ -39,7 +66,8 @@ __device__ __forceinline__ void deform_corners(const DeformSample& s, int H, int
 }
 
 // bilinear_interpolate: 0 for a rejected sample, else w1 v1 + w2 v2 + w3 v3 + w4 v4 summed from the left
-__device__ __forceinline__ float deform_bilinear(const float* __restrict__ plane, int H, int W, float y, float x)
+template <typename E>
+__device__ __forceinline__ float deform_bilinear(const E* __restrict__ plane, int H, int W, float y, float x)
 {
     DeformSample s;
     if (!deform_sample(y, x, H, W, s)) return 0.f;
@@ -47,22 +75,23 @@ __device__ __forceinline__ float deform_bilinear(const float* __restrict__ plane
     deform_corners(s, H, W, w, cell);
     float v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = cell[k] >= 0 ? plane[cell[k]] : 0.f;
+    for (int k = 0; k < 4; ++k) v[k] = cell[k] >= 0 ? deform_load(plane, cell[k]) : 0.f;
     return ((w[0] * v[0] + w[1] * v[1]) + w[2] * v[2]) + w[3] * v[3];
 }
 
 // get_coordinate_weight: the derivative of the sample along y (y_direction) or x -- the difference of the validly indexed corner
 // values weighted by the other axis's fractions; the right-hand slope at an integer coordinate.  It has no early-out: at y == -1 the
 // corner row 0 still counts.  Outside [-1, H) x [-1, W) no corner is valid and the result is 0 (NaN coordinates included).
-__device__ __forceinline__ float deform_coordinate_weight(const float* __restrict__ plane, int H, int W, float y, float x,
+template <typename E>
+__device__ __forceinline__ float deform_coordinate_weight(const E* __restrict__ plane, int H, int W, float y, float x,
                                                           bool y_direction)
 {
     if (!(y >= -1.0f && y < (float)H && x >= -1.0f && x < (float)W)) return 0.f;
     const float yf = floorf(y), xf = floorf(x);
     const int yl = (int)yf, xl = (int)xf, yh = yl + 1, xh = xl + 1;
     const bool vyl = yl >= 0, vyh = yh < H, vxl = xl >= 0, vxh = xh < W;      // yl <= H - 1 and yh >= 0 hold in the accepted range
-    const float v_yx = (vyl && vxl) ? plane[yl * W + xl] : 0.f, v_yX = (vyl && vxh) ? plane[yl * W + xh] : 0.f;
-    const float v_Yx = (vyh && vxl) ? plane[yh * W + xl] : 0.f, v_YX = (vyh && vxh) ? plane[yh * W + xh] : 0.f;
+    const float v_yx = (vyl && vxl) ? deform_load(plane, yl * W + xl) : 0.f, v_yX = (vyl && vxh) ? deform_load(plane, yl * W + xh) : 0.f;
+    const float v_Yx = (vyh && vxl) ? deform_load(plane, yh * W + xl) : 0.f, v_YX = (vyh && vxh) ? deform_load(plane, yh * W + xh) : 0.f;
     const float dx = x - xf, dy = y - yf;
     return y_direction ? dx * (v_YX - v_yX) + (1.0f - dx) * (v_Yx - v_yx) : dy * (v_YX - v_Yx) + (1.0f - dy) * (v_yX - v_yx);
 }

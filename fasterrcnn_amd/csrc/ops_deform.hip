@@ -28,6 +28,10 @@
 //   weight:  dW[co][k] = sum over (b, p) of dout^T[(b, p)][co] col^T[(b, p)][k] per group: the columns are sampled again, both
 //            operands transposed to reduction-major form, deterministic split reduction through the workspace; chunks are added in
 //            ascending order by the caller's accumulate flag.
+//
+// float16 / bfloat16 (the frcnn_ops_deform_*_16 entry points): the same kernels, templates over the storage type E of the tensors
+// (ops_deform.h widens on load, rounds once on store; dcol and the plan's weights stay float32), around gemm_nt16.hip's product of
+// 16-bit operands; see "the 16-bit operator" below for the operand layouts and include/frcnn_hip.h for the arithmetic contract.
 #include "ops_deform.h"
 
 namespace frcnn {
@@ -42,9 +46,11 @@ struct DeformGeom {
 };
 
 static inline int round4(int v) { return (v + 3) & ~3; }
+static inline int round8(int v) { return (v + 7) & ~7; }
 
-// validates the public geometry and the sizes the 32-bit indices of the kernels and of gemm_tn can hold; fills the kernel form
-static bool deform_geom(const frcnn_deform_geom* g, int n_img, DeformGeom& d, int& c_out, int& groups)
+// validates the public geometry and the sizes the 32-bit indices of the kernels and of the products can hold; fills the kernel form.
+// pad: what P is rounded up to in the column rows (4 floats for gemm_tn, 8 elements for the 16-bit product)
+static bool deform_geom(const frcnn_deform_geom* g, int n_img, DeformGeom& d, int& c_out, int& groups, int pad = 4)
 {
     if (!g || n_img < 1) return false;
     if (g->c_in < 1 || g->c_out < 1 || g->height < 1 || g->width < 1 || g->kernel_h < 1 || g->kernel_w < 1) return false;
@@ -58,8 +64,8 @@ static bool deform_geom(const frcnn_deform_geom* g, int n_img, DeformGeom& d, in
     const long long kk = (long long)g->kernel_h * g->kernel_w, P = oh * ow;
     if (kk > lim || P > lim || (long long)g->height * g->width > lim) return false;
     if ((long long)g->height + g->pad_h + eh > lim || (long long)g->width + g->pad_w + ew > lim) return false;   // o stride - pad + i dil
-    const long long Pp = (P + 3) / 4 * 4;
-    if (n_img * Pp > lim || g->c_in * kk > lim || (long long)n_img * g->offset_groups * g->height * g->width > lim) return false;
+    const long long Pp = (P + pad - 1) / pad * pad;
+    if (n_img * Pp > lim || g->c_in * kk + (pad == 8 ? 8LL * g->groups : 0) > lim || (long long)n_img * g->offset_groups * g->height * g->width > lim) return false;
     if ((long long)n_img * g->offset_groups * kk > lim / 4 / P) return false;                                    // plan entries
     d.C = g->c_in; d.H = g->height; d.W = g->width; d.kh = g->kernel_h; d.kw = g->kernel_w; d.sh = g->stride_h; d.sw = g->stride_w;
     d.ph = g->pad_h; d.pw = g->pad_w; d.dh = g->dilation_h; d.dw = g->dilation_w; d.G = g->offset_groups;
@@ -75,19 +81,33 @@ static inline unsigned df_blocks(size_t total)
 }
 
 // offset and mask of sample t = (b G + g) kk + tap at output p
-__device__ __forceinline__ void deform_read(const DeformGeom& g, const float* __restrict__ offset, const float* __restrict__ mask,
+template <typename E>
+__device__ __forceinline__ void deform_read(const DeformGeom& g, const E* __restrict__ offset, const E* __restrict__ mask,
                                             size_t t, int p, int tap, float& y, float& x, float& m)
 {
     const int i = tap / g.kw, j = tap - i * g.kw, oy = p / g.ow, ox = p - oy * g.ow;
-    y = deform_coord(oy, g.sh, g.ph, i, g.dh, offset[(2 * t) * g.P + p]);
-    x = deform_coord(ox, g.sw, g.pw, j, g.dw, offset[(2 * t + 1) * g.P + p]);
-    m = mask ? mask[t * g.P + p] : 1.0f;
+    y = deform_coord(oy, g.sh, g.ph, i, g.dh, deform_load(offset, (2 * t) * g.P + p));
+    x = deform_coord(ox, g.sw, g.pw, j, g.dw, deform_load(offset, (2 * t + 1) * g.P + p));
+    m = mask ? deform_load(mask, t * g.P + p) : 1.0f;
+}
+
+// the column value of input channel c, tap `tap`, image b of the chunk, output p: mask * bilinear sample, in float32
+template <typename E>
+__device__ __forceinline__ float deform_column(const DeformGeom& g, const E* __restrict__ x, const E* __restrict__ offset,
+                                               const E* __restrict__ mask, int b, int c, int tap, int p)
+{
+    const size_t t = ((size_t)b * g.G + c / g.cpo) * g.kk + tap;
+    float sy, sx, m;
+    deform_read(g, offset, mask, t, p, tap, sy, sx, m);
+    return m * deform_bilinear(x + ((size_t)b * g.C + c) * g.H * g.W, g.H, g.W, sy, sx);
 }
 
 // ---- deformable im2col -----------------------------------------------------------------------------------------------------------
+// col[(c, tap)][b Pp + p], rounded once to E on the store (float: as it is)
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
-void deform_columns_kernel(const float* __restrict__ x, const float* __restrict__ offset, const float* __restrict__ mask, DeformGeom g,
-                           int n_img, size_t total, float* __restrict__ col)
+void deform_columns_kernel(const E* __restrict__ x, const E* __restrict__ offset, const E* __restrict__ mask, DeformGeom g,
+                           int n_img, size_t total, E* __restrict__ col)
 {
     const size_t ld = (size_t)n_img * g.Pp;
     for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
@@ -95,13 +115,42 @@ void deform_columns_kernel(const float* __restrict__ x, const float* __restrict_
         const int b = cn / g.Pp, p = cn - b * g.Pp;
         float v = 0.f;
         if (p < g.P) {
-            const int c = row / g.kk, tap = row - c * g.kk;
-            const size_t t = ((size_t)b * g.G + c / g.cpo) * g.kk + tap;
-            float sy, sx, m;
-            deform_read(g, offset, mask, t, p, tap, sy, sx, m);
-            v = m * deform_bilinear(x + ((size_t)b * g.C + c) * g.H * g.W, g.H, g.W, sy, sx);
+            const int c = row / g.kk;
+            v = deform_column(g, x, offset, mask, b, c, row - c * g.kk, p);
         }
-        col[idx] = v;
+        deform_store(col, idx, v);
+    }
+}
+
+// The same values in the forward product's layout (16-bit E only): col[b P + p][w Kp + kl], kl = (c - w cg) kk + tap the index inside
+// weight group w (cg = C / groups channels, K = cg kk, Kp = K rounded up to 8, the pad kl >= K written as zeros).  A thread owns eight
+// consecutive kl of one output, one 16-byte store; a wave owns 64 consecutive outputs (the offset and mask reads coalesce as in the
+// kernel above) and the waves that follow it take the next kl of the same outputs, so a row's cache lines fill while they are hot.
+template <typename E>
+__global__ __launch_bounds__(DF_BLOCK)
+void deform_columns_nk_kernel(const E* __restrict__ x, const E* __restrict__ offset, const E* __restrict__ mask, DeformGeom g, int n_img,
+                              int cg, int Kp, int groups, size_t total, E* __restrict__ col)
+{
+    static_assert(sizeof(E) == 2, "eight elements are one 16-byte store");
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const int K = cg * g.kk, runs = groups * (Kp / 8), N = n_img * g.P;
+    for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
+        const size_t q = idx >> 6;
+        const int run = (int)(q % runs), n = (int)(q / runs) * 64 + (int)(idx & 63);
+        if (n >= N) continue;
+        const int b = n / g.P, p = n - b * g.P, w = run / (Kp / 8), kl0 = (run - w * (Kp / 8)) * 8;
+        union { E e[8]; u32x4 v; } r;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int kl = kl0 + j;
+            float v = 0.f;
+            if (kl < K) {
+                const int cl = kl / g.kk;
+                v = deform_column(g, x, offset, mask, b, w * cg + cl, kl - cl * g.kk, p);
+            }
+            deform_round(v, r.e[j]);
+        }
+        *reinterpret_cast<u32x4*>(col + (size_t)n * groups * Kp + (size_t)run * 8) = r.v;
     }
 }
 
@@ -121,25 +170,57 @@ void deform_output_kernel(const float* __restrict__ tmp, const float* __restrict
 }
 
 // gt[co][b Pp + p] = dout[b][co][p], zero for p >= P
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
-void deform_pack_grad_kernel(const float* __restrict__ dout, int n_img, int c_out, int P, int Pp, size_t total, float* __restrict__ gt)
+void deform_pack_grad_kernel(const E* __restrict__ dout, int n_img, int c_out, int P, int Pp, size_t total, E* __restrict__ gt)
 {
     for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
         const int p = (int)(idx % Pp);
         const size_t cb = idx / Pp;
         const int b = (int)(cb % n_img), co = (int)(cb / n_img);
-        gt[idx] = p < P ? dout[((size_t)b * c_out + co) * P + p] : 0.f;
+        gt[idx] = p < P ? dout[((size_t)b * c_out + co) * P + p] : E{};
+    }
+}
+
+// gT[b Pp + p][w cogp + col] = dout[b][w cog + col][p], zero for p >= P and for col >= cog (cogp: cog rounded up to 8)
+template <typename E>
+__global__ __launch_bounds__(DF_BLOCK)
+void deform_pack_grad_t_kernel(const E* __restrict__ dout, int c_out, int cog, int cogp, int groups, int P, int Pp, size_t total,
+                               E* __restrict__ gT)
+{
+    const int ld = groups * cogp;
+    for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
+        const int j = (int)(idx % ld), w = j / cogp, col = j - w * cogp;
+        const size_t n = idx / ld;
+        const int p = (int)(n % Pp);
+        const size_t b = n / Pp;
+        gT[idx] = p < P && col < cog ? dout[(b * c_out + w * cog + col) * P + p] : E{};
+    }
+}
+
+// wt[w][k][col] (row stride cogp) = weight[w cog + col][k], zero for col >= cog
+template <typename E>
+__global__ __launch_bounds__(DF_BLOCK)
+void deform_pack_weight_t_kernel(const E* __restrict__ weight, int cog, int cogp, int K, size_t total, E* __restrict__ wt)
+{
+    for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
+        const int col = (int)(idx % cogp);
+        const size_t wk = idx / cogp;
+        const int k = (int)(wk % K);
+        const size_t w = wk / K;
+        wt[idx] = col < cog ? weight[(w * cog + col) * K + k] : E{};
     }
 }
 
 // dst[r][c] (row stride ldd, c < ldd) = src[r][c] for c < cols, else zero
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
-void deform_pad_rows_kernel(const float* __restrict__ src, int cols, float* __restrict__ dst, int ldd, size_t total)
+void deform_pad_rows_kernel(const E* __restrict__ src, int cols, E* __restrict__ dst, int ldd, size_t total)
 {
     for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
         const int c = (int)(idx % ldd);
         const size_t r = idx / ldd;
-        dst[idx] = c < cols ? src[r * cols + c] : 0.f;
+        dst[idx] = c < cols ? src[r * cols + c] : E{};
     }
 }
 
@@ -156,10 +237,11 @@ void deform_add_rows_kernel(const float* __restrict__ src, int lds, float* __res
 }
 
 // ---- offset and mask gradient ------------------------------------------------------------------------------------------------------
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
-void deform_offset_grad_kernel(const float* __restrict__ x, const float* __restrict__ offset, const float* __restrict__ mask,
-                               const float* __restrict__ dcol, DeformGeom g, int n_img, size_t total, float* __restrict__ doffset,
-                               float* __restrict__ dmask)
+void deform_offset_grad_kernel(const E* __restrict__ x, const E* __restrict__ offset, const E* __restrict__ mask,
+                               const float* __restrict__ dcol, DeformGeom g, int n_img, size_t total, E* __restrict__ doffset,
+                               E* __restrict__ dmask)
 {
     const size_t ld = (size_t)n_img * g.Pp;
     for (size_t idx = (size_t)blockIdx.x * DF_BLOCK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * DF_BLOCK) {
@@ -173,7 +255,7 @@ void deform_offset_grad_kernel(const float* __restrict__ x, const float* __restr
         float gy = 0.f, gx = 0.f, gm = 0.f;
         for (int cc = 0; cc < g.cpo; ++cc) {
             const int c = og * g.cpo + cc;
-            const float* plane = x + ((size_t)b * g.C + c) * g.H * g.W;
+            const E* plane = x + ((size_t)b * g.C + c) * g.H * g.W;
             const float dc = dcol[((size_t)c * g.kk + tap) * ld + (size_t)b * g.Pp + p];
             if (doffset) {
                 gy += (m * deform_coordinate_weight(plane, g.H, g.W, sy, sx, true)) * dc;
@@ -181,14 +263,15 @@ void deform_offset_grad_kernel(const float* __restrict__ x, const float* __restr
             }
             if (dmask) gm += dc * deform_bilinear(plane, g.H, g.W, sy, sx);
         }
-        if (doffset) { doffset[(2 * t) * g.P + p] = gy; doffset[(2 * t + 1) * g.P + p] = gx; }
-        if (dmask) dmask[idx] = gm;
+        if (doffset) { deform_store(doffset, (2 * t) * g.P + p, gy); deform_store(doffset, (2 * t + 1) * g.P + p, gx); }
+        if (dmask) deform_store(dmask, idx, gm);
     }
 }
 
 // ---- input gradient: plan, segment starts, gather ------------------------------------------------------------------------------------
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
-void deform_plan_kernel(const float* __restrict__ offset, const float* __restrict__ mask, DeformGeom g, int n_img, size_t total,
+void deform_plan_kernel(const E* __restrict__ offset, const E* __restrict__ mask, DeformGeom g, int n_img, size_t total,
                         long long* __restrict__ keys, float* __restrict__ wts)
 {
     const long long cells = (long long)g.H * g.W, sentinel = (long long)n_img * g.G * cells;
@@ -225,9 +308,10 @@ void deform_segments_kernel(const long long* __restrict__ sorted_keys, int n_ent
     }
 }
 
+template <typename E>
 __global__ __launch_bounds__(DF_BLOCK)
 void deform_input_grad_kernel(const int* __restrict__ start, const long long* __restrict__ order, const float* __restrict__ wts,
-                              const float* __restrict__ dcol, DeformGeom g, int n_img, size_t total, float* __restrict__ dx)
+                              const float* __restrict__ dcol, DeformGeom g, int n_img, size_t total, E* __restrict__ dx)
 {
     const size_t ld = (size_t)n_img * g.Pp;
     const int cells = g.H * g.W;
@@ -245,7 +329,7 @@ void deform_input_grad_kernel(const int* __restrict__ start, const long long* __
             const int p = (int)(smp % g.P), tap = (int)((smp / g.P) % g.kk);
             acc += wts[e] * rows[(size_t)tap * ld + p];
         }
-        dx[idx] = acc;
+        deform_store(dx, idx, acc);
     }
 }
 
@@ -269,40 +353,187 @@ static DeformSizes deform_sizes(const DeformGeom& d, int c_out, int groups, int 
     return z;
 }
 
+static size_t deform_input_workspace(const DeformGeom& d, int n_img)
+{
+    return align256(((size_t)n_img * d.G * d.H * d.W + 1) * sizeof(int));
+}
+
 static size_t deform_workspace(const DeformGeom& d, const DeformSizes& z, int n_img, int stage)
 {
     switch (stage) {
     case FRCNN_DEFORM_WS_FORWARD: return z.col + z.gt + z.wt;
     case FRCNN_DEFORM_WS_BACKWARD_COLUMNS: return z.wp + z.gt;
-    case FRCNN_DEFORM_WS_BACKWARD_INPUT: return align256(((size_t)n_img * d.G * d.H * d.W + 1) * sizeof(int));
+    case FRCNN_DEFORM_WS_BACKWARD_INPUT: return deform_input_workspace(d, n_img);
     case FRCNN_DEFORM_WS_BACKWARD_WEIGHT: return z.col + z.gt + z.gtT + z.colT + z.tmpw + z.gemm;
     case FRCNN_DEFORM_WS_COLUMNS: return (size_t)d.C * d.kk * z.ld * sizeof(float);
     default: return 0;
     }
 }
 
-static int deform_launch_columns(const DeformGeom& d, int n_img, const float* x, const float* offset, const float* mask, float* col,
-                                 hipStream_t s)
+template <typename E>
+static int deform_launch_columns(const DeformGeom& d, int n_img, const E* x, const E* offset, const E* mask, E* col, hipStream_t s)
 {
     const size_t total = (size_t)d.C * d.kk * n_img * d.Pp;
-    hipLaunchKernelGGL(deform_columns_kernel, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, x, offset, mask, d, n_img, total, col);
+    hipLaunchKernelGGL(deform_columns_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, x, offset, mask, d, n_img, total, col);
     return check_launch();
 }
 
-static int deform_launch_pack_grad(int n_img, int c_out, const DeformGeom& d, const float* dout, float* gt, hipStream_t s)
+template <typename E>
+static int deform_launch_pack_grad(int n_img, int c_out, const DeformGeom& d, const E* dout, E* gt, hipStream_t s)
 {
     const size_t total = (size_t)c_out * n_img * d.Pp;
-    hipLaunchKernelGGL(deform_pack_grad_kernel, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, dout, n_img, c_out, d.P, d.Pp, total, gt);
+    hipLaunchKernelGGL(deform_pack_grad_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, dout, n_img, c_out, d.P, d.Pp, total, gt);
     return check_launch();
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+#define DF_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// ---- the gathers' entry points, for every element type (pad: deform_geom's) ---------------------------------------------------------
+template <typename E>
+static int deform_backward_offset_impl(const frcnn_deform_geom* g, int n_img, int pad, const E* d_x, const E* d_offset, const E* d_mask,
+                                       const float* d_dcol, E* d_doffset, E* d_dmask, void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform_geom(g, n_img, d, c_out, groups, pad)) return FRCNN_EINVAL;
+    if (!d_x || !d_offset || !d_dcol || (!d_doffset && !d_dmask)) return FRCNN_EINVAL;
+    const size_t total = (size_t)n_img * d.G * d.kk * d.P;
+    hipLaunchKernelGGL(deform_offset_grad_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, (hipStream_t)stream, d_x, d_offset, d_mask,
+                       d_dcol, d, n_img, total, d_doffset, d_dmask);
+    return check_launch();
+}
+
+template <typename E>
+static int deform_input_plan_impl(const frcnn_deform_geom* g, int n_img, int pad, const E* d_offset, const E* d_mask, int64_t* d_keys,
+                                  float* d_weights, void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform_geom(g, n_img, d, c_out, groups, pad)) return FRCNN_EINVAL;
+    if (!d_offset || !d_keys || !d_weights) return FRCNN_EINVAL;
+    const size_t total = (size_t)n_img * d.G * d.kk * d.P;
+    hipLaunchKernelGGL(deform_plan_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, (hipStream_t)stream, d_offset, d_mask, d, n_img,
+                       total, reinterpret_cast<long long*>(d_keys), d_weights);
+    return check_launch();
+}
+
+template <typename E>
+static int deform_backward_input_impl(const frcnn_deform_geom* g, int n_img, int pad, const int64_t* d_sorted_keys, const int64_t* d_order,
+                                      const float* d_weights, const float* d_dcol, E* d_dx, void* d_ws, size_t ws_bytes, void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform_geom(g, n_img, d, c_out, groups, pad)) return FRCNN_EINVAL;
+    if (!d_sorted_keys || !d_order || !d_weights || !d_dcol || !d_dx || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
+    if (ws_bytes < deform_input_workspace(d, n_img)) return FRCNN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    int* start = static_cast<int*>(d_ws);
+    const int n_cells = n_img * d.G * d.H * d.W, n_entries = n_img * d.G * d.kk * d.P * 4;
+    hipLaunchKernelGGL(deform_segments_kernel, dim3(df_blocks((size_t)n_cells + 1)), dim3(DF_BLOCK), 0, s,
+                       reinterpret_cast<const long long*>(d_sorted_keys), n_entries, n_cells, start);
+    DF_TRY(check_launch());
+    const size_t total = (size_t)n_img * d.C * d.H * d.W;
+    hipLaunchKernelGGL(deform_input_grad_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, start,
+                       reinterpret_cast<const long long*>(d_order), d_weights, d_dcol, d, n_img, total, d_dx);
+    return check_launch();
+}
+
+// ---- the 16-bit operator (frcnn_ops_deform_*_16): the same sampling kernels on 16-bit tensors around gemm_nt16.hip's product ----------
+// Every operand of that product is reduction-contiguous with a row stride that is a multiple of 8 elements and zeros in the pad:
+//   forward   out[co][n]  = sum_k  wp[co][k] colNK[n][k]        wp: the weights with rows padded to Kp; colNK: deform_columns_nk_kernel
+//   dcol      dcol[k][n]  = sum_co wt[k][co] gT[n][co]          wt, gT: deform_pack_weight_t_kernel, deform_pack_grad_t_kernel
+//   d_weight  dW[co][k]   = sum_n  gt[co][n] col[k][n]          gt: deform_pack_grad_kernel; col: deform_columns_kernel, Pp = P up to 8
+struct Deform16Sizes { int K, Kp, cog, cogp, ld, N; size_t colnk, wp, wt, gT, col, gt, part; };
+
+static Deform16Sizes deform16_sizes(const DeformGeom& d, int c_out, int groups, int n_img)
+{
+    Deform16Sizes z;
+    z.K = d.C / groups * d.kk; z.Kp = round8(z.K); z.cog = c_out / groups; z.cogp = round8(z.cog); z.ld = n_img * d.Pp; z.N = n_img * d.P;
+    z.colnk = align256((size_t)z.N * groups * z.Kp * 2);
+    z.wp = align256((size_t)c_out * z.Kp * 2);
+    z.wt = align256((size_t)groups * z.K * z.cogp * 2);
+    z.gT = align256((size_t)z.ld * groups * z.cogp * 2);
+    z.col = align256((size_t)d.C * d.kk * z.ld * 2);
+    z.gt = align256((size_t)c_out * z.ld * 2);
+    z.part = align256(gemm_nt16_workspace_bytes(z.cog, z.K, z.ld));
+    return z;
+}
+
+static size_t deform16_workspace(const DeformGeom& d, const Deform16Sizes& z, int n_img, int stage)
+{
+    switch (stage) {
+    case FRCNN_DEFORM_WS_FORWARD: return z.colnk + z.wp;
+    case FRCNN_DEFORM_WS_BACKWARD_COLUMNS: return z.wt + z.gT;
+    case FRCNN_DEFORM_WS_BACKWARD_INPUT: return deform_input_workspace(d, n_img);
+    case FRCNN_DEFORM_WS_BACKWARD_WEIGHT: return z.col + z.gt + z.part;
+    case FRCNN_DEFORM_WS_COLUMNS: return (size_t)d.C * d.kk * z.ld * sizeof(float);
+    default: return 0;
+    }
+}
+
+template <typename E>
+static int deform16_forward(int elem_type, const DeformGeom& d, const Deform16Sizes& z, int c_out, int groups, int n_img, const E* x,
+                            const E* offset, const E* mask, const E* weight, const E* bias, E* out, char* ws, hipStream_t s)
+{
+    E* col = reinterpret_cast<E*>(ws);
+    E* wp = reinterpret_cast<E*>(ws + z.colnk);
+    const size_t total = (size_t)cdiv(z.N, 64) * 64 * groups * (z.Kp / 8);
+    hipLaunchKernelGGL(deform_columns_nk_kernel<E>, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, x, offset, mask, d, n_img, d.C / groups,
+                       z.Kp, groups, total, col);
+    DF_TRY(check_launch());
+    const size_t wtotal = (size_t)c_out * z.Kp;
+    hipLaunchKernelGGL(deform_pad_rows_kernel<E>, dim3(df_blocks(wtotal)), dim3(DF_BLOCK), 0, s, weight, z.K, wp, z.Kp, wtotal);
+    DF_TRY(check_launch());
+    for (int w = 0; w < groups; ++w)
+        DF_TRY(launch_gemm_nt16_nchw(elem_type, wp + (size_t)w * z.cog * z.Kp, z.Kp, col + (size_t)w * z.Kp, groups * z.Kp, z.cog, z.N,
+                                     z.Kp, bias, out, d.P, c_out, w * z.cog, s));
+    return FRCNN_OK;
+}
+
+template <typename E>
+static int deform16_backward_columns(int elem_type, const DeformGeom& d, const Deform16Sizes& z, int c_out, int groups, int n_img,
+                                     const E* weight, const E* dout, float* dcol, char* ws, hipStream_t s)
+{
+    E* wt = reinterpret_cast<E*>(ws);
+    E* gT = reinterpret_cast<E*>(ws + z.wt);
+    const size_t wtotal = (size_t)groups * z.K * z.cogp;
+    hipLaunchKernelGGL(deform_pack_weight_t_kernel<E>, dim3(df_blocks(wtotal)), dim3(DF_BLOCK), 0, s, weight, z.cog, z.cogp, z.K, wtotal, wt);
+    DF_TRY(check_launch());
+    const size_t gtotal = (size_t)z.ld * groups * z.cogp;
+    hipLaunchKernelGGL(deform_pack_grad_t_kernel<E>, dim3(df_blocks(gtotal)), dim3(DF_BLOCK), 0, s, dout, c_out, z.cog, z.cogp, groups, d.P,
+                       d.Pp, gtotal, gT);
+    DF_TRY(check_launch());
+    for (int w = 0; w < groups; ++w)
+        DF_TRY(launch_gemm_nt16(elem_type, wt + (size_t)w * z.K * z.cogp, z.cogp, gT + (size_t)w * z.cogp, groups * z.cogp,
+                                dcol + (size_t)w * z.K * z.ld, z.ld, z.K, z.ld, z.cogp, s));
+    return FRCNN_OK;
+}
+
+template <typename E>
+static int deform16_backward_weight(int elem_type, const DeformGeom& d, const Deform16Sizes& z, int c_out, int groups, int n_img, const E* x,
+                                    const E* offset, const E* mask, const E* dout, float* dweight, int accumulate, char* ws, hipStream_t s)
+{
+    E* col = reinterpret_cast<E*>(ws);
+    E* gt = reinterpret_cast<E*>(ws + z.col);
+    void* part = ws + z.col + z.gt;
+    DF_TRY(deform_launch_columns(d, n_img, x, offset, mask, col, s));
+    DF_TRY(deform_launch_pack_grad(n_img, c_out, d, dout, gt, s));
+    for (int w = 0; w < groups; ++w)
+        DF_TRY(launch_gemm_nt16_split(elem_type, gt + (size_t)w * z.cog * z.ld, z.ld, col + (size_t)w * z.K * z.ld, z.ld,
+                                      dweight + (size_t)w * z.cog * z.K, z.K, z.cog, z.K, z.ld, accumulate, part, z.part, s));
+    return FRCNN_OK;
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
 
-#define DF_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
+// the body of a 16-bit entry point by element-type code
+#define DF_DISPATCH_16(elem_type, E, call)                                                                    \
+    do {                                                                                                      \
+        if ((elem_type) == FRCNN_OPS_F16) { typedef deform_f16 E; return call; }                              \
+        if ((elem_type) == FRCNN_OPS_BF16) { typedef deform_bf16 E; return call; }                            \
+        return FRCNN_EINVAL;                                                                                  \
+    } while (0)
 
 extern "C" {
 
@@ -351,7 +582,7 @@ int frcnn_ops_deform_backward_columns(const frcnn_deform_geom* g, int n_img, con
     float* wp = reinterpret_cast<float*>(ws);
     float* gt = reinterpret_cast<float*>(ws + z.wp);
     const size_t wtotal = (size_t)c_out * z.Kp;
-    hipLaunchKernelGGL(deform_pad_rows_kernel, dim3(df_blocks(wtotal)), dim3(DF_BLOCK), 0, s, d_weight, z.K, wp, z.Kp, wtotal);
+    hipLaunchKernelGGL(deform_pad_rows_kernel<float>, dim3(df_blocks(wtotal)), dim3(DF_BLOCK), 0, s, d_weight, z.K, wp, z.Kp, wtotal);
     DF_TRY(check_launch());
     DF_TRY(deform_launch_pack_grad(n_img, c_out, d, d_dout, gt, s));
     for (int w = 0; w < groups; ++w)
@@ -363,44 +594,19 @@ int frcnn_ops_deform_backward_columns(const frcnn_deform_geom* g, int n_img, con
 int frcnn_ops_deform_backward_offset(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
                                      const float* d_dcol, float* d_doffset, float* d_dmask, void* stream)
 {
-    DeformGeom d; int c_out, groups;
-    if (!deform_geom(g, n_img, d, c_out, groups)) return FRCNN_EINVAL;
-    if (!d_x || !d_offset || !d_dcol || (!d_doffset && !d_dmask)) return FRCNN_EINVAL;
-    const size_t total = (size_t)n_img * d.G * d.kk * d.P;
-    hipLaunchKernelGGL(deform_offset_grad_kernel, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, (hipStream_t)stream, d_x, d_offset, d_mask,
-                       d_dcol, d, n_img, total, d_doffset, d_dmask);
-    return check_launch();
+    return deform_backward_offset_impl<float>(g, n_img, 4, d_x, d_offset, d_mask, d_dcol, d_doffset, d_dmask, stream);
 }
 
 int frcnn_ops_deform_input_plan(const frcnn_deform_geom* g, int n_img, const float* d_offset, const float* d_mask, int64_t* d_keys,
                                 float* d_weights, void* stream)
 {
-    DeformGeom d; int c_out, groups;
-    if (!deform_geom(g, n_img, d, c_out, groups)) return FRCNN_EINVAL;
-    if (!d_offset || !d_keys || !d_weights) return FRCNN_EINVAL;
-    const size_t total = (size_t)n_img * d.G * d.kk * d.P;
-    hipLaunchKernelGGL(deform_plan_kernel, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, (hipStream_t)stream, d_offset, d_mask, d, n_img,
-                       total, reinterpret_cast<long long*>(d_keys), d_weights);
-    return check_launch();
+    return deform_input_plan_impl<float>(g, n_img, 4, d_offset, d_mask, d_keys, d_weights, stream);
 }
 
 int frcnn_ops_deform_backward_input(const frcnn_deform_geom* g, int n_img, const int64_t* d_sorted_keys, const int64_t* d_order,
                                     const float* d_weights, const float* d_dcol, float* d_dx, void* d_ws, size_t ws_bytes, void* stream)
 {
-    DeformGeom d; int c_out, groups;
-    if (!deform_geom(g, n_img, d, c_out, groups)) return FRCNN_EINVAL;
-    if (!d_sorted_keys || !d_order || !d_weights || !d_dcol || !d_dx || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
-    if (ws_bytes < deform_workspace(d, deform_sizes(d, c_out, groups, n_img), n_img, FRCNN_DEFORM_WS_BACKWARD_INPUT)) return FRCNN_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    int* start = static_cast<int*>(d_ws);
-    const int n_cells = n_img * d.G * d.H * d.W, n_entries = n_img * d.G * d.kk * d.P * 4;
-    hipLaunchKernelGGL(deform_segments_kernel, dim3(df_blocks((size_t)n_cells + 1)), dim3(DF_BLOCK), 0, s,
-                       reinterpret_cast<const long long*>(d_sorted_keys), n_entries, n_cells, start);
-    DF_TRY(check_launch());
-    const size_t total = (size_t)n_img * d.C * d.H * d.W;
-    hipLaunchKernelGGL(deform_input_grad_kernel, dim3(df_blocks(total)), dim3(DF_BLOCK), 0, s, start,
-                       reinterpret_cast<const long long*>(d_order), d_weights, d_dcol, d, n_img, total, d_dx);
-    return check_launch();
+    return deform_backward_input_impl<float>(g, n_img, 4, d_sorted_keys, d_order, d_weights, d_dcol, d_dx, d_ws, ws_bytes, stream);
 }
 
 int frcnn_ops_deform_backward_weight(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
@@ -431,6 +637,82 @@ int frcnn_ops_deform_backward_weight(const frcnn_deform_geom* g, int n_img, cons
         DF_TRY(check_launch());
     }
     return FRCNN_OK;
+}
+
+// ---- float16 / bfloat16 (elem_type: FRCNN_OPS_F16 / FRCNN_OPS_BF16) ------------------------------------------------------------------
+static bool deform16_elem(int elem_type) { return elem_type == FRCNN_OPS_F16 || elem_type == FRCNN_OPS_BF16; }
+
+size_t frcnn_ops_deform_workspace_bytes_16(int elem_type, const frcnn_deform_geom* g, int n_img, int stage)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform16_elem(elem_type) || !deform_geom(g, n_img, d, c_out, groups, 8)) return 0;
+    return deform16_workspace(d, deform16_sizes(d, c_out, groups, n_img), n_img, stage);
+}
+
+int frcnn_ops_deform_forward_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                const void* d_mask, const void* d_weight, const void* d_bias, void* d_out, void* d_ws, size_t ws_bytes,
+                                void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform16_elem(elem_type) || !deform_geom(g, n_img, d, c_out, groups, 8)) return FRCNN_EINVAL;
+    const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
+    if (!d_x || !d_offset || !d_weight || !d_out || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
+    if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_FORWARD)) return FRCNN_EINVAL;
+    DF_DISPATCH_16(elem_type, E, deform16_forward<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
+                                                     static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                     static_cast<const E*>(d_weight), static_cast<const E*>(d_bias), static_cast<E*>(d_out),
+                                                     static_cast<char*>(d_ws), (hipStream_t)stream));
+}
+
+int frcnn_ops_deform_backward_columns_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_weight, const void* d_dout,
+                                         float* d_dcol, void* d_ws, size_t ws_bytes, void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform16_elem(elem_type) || !deform_geom(g, n_img, d, c_out, groups, 8)) return FRCNN_EINVAL;
+    const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
+    if (!d_weight || !d_dout || !d_dcol || !aligned16(d_dcol) || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
+    if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_BACKWARD_COLUMNS)) return FRCNN_EINVAL;
+    DF_DISPATCH_16(elem_type, E, deform16_backward_columns<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_weight),
+                                                              static_cast<const E*>(d_dout), d_dcol, static_cast<char*>(d_ws),
+                                                              (hipStream_t)stream));
+}
+
+int frcnn_ops_deform_backward_offset_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                        const void* d_mask, const float* d_dcol, void* d_doffset, void* d_dmask, void* stream)
+{
+    DF_DISPATCH_16(elem_type, E, deform_backward_offset_impl<E>(g, n_img, 8, static_cast<const E*>(d_x), static_cast<const E*>(d_offset),
+                                                                static_cast<const E*>(d_mask), d_dcol, static_cast<E*>(d_doffset),
+                                                                static_cast<E*>(d_dmask), stream));
+}
+
+int frcnn_ops_deform_input_plan_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_offset, const void* d_mask,
+                                   int64_t* d_keys, float* d_weights, void* stream)
+{
+    DF_DISPATCH_16(elem_type, E, deform_input_plan_impl<E>(g, n_img, 8, static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                           d_keys, d_weights, stream));
+}
+
+int frcnn_ops_deform_backward_input_16(int elem_type, const frcnn_deform_geom* g, int n_img, const int64_t* d_sorted_keys,
+                                       const int64_t* d_order, const float* d_weights, const float* d_dcol, void* d_dx, void* d_ws,
+                                       size_t ws_bytes, void* stream)
+{
+    DF_DISPATCH_16(elem_type, E, deform_backward_input_impl<E>(g, n_img, 8, d_sorted_keys, d_order, d_weights, d_dcol,
+                                                               static_cast<E*>(d_dx), d_ws, ws_bytes, stream));
+}
+
+int frcnn_ops_deform_backward_weight_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                        const void* d_mask, const void* d_dout, float* d_dweight, int accumulate, void* d_ws,
+                                        size_t ws_bytes, void* stream)
+{
+    DeformGeom d; int c_out, groups;
+    if (!deform16_elem(elem_type) || !deform_geom(g, n_img, d, c_out, groups, 8)) return FRCNN_EINVAL;
+    const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
+    if (!d_x || !d_offset || !d_dout || !d_dweight || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
+    if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_BACKWARD_WEIGHT)) return FRCNN_EINVAL;
+    DF_DISPATCH_16(elem_type, E, deform16_backward_weight<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
+                                                             static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                             static_cast<const E*>(d_dout), d_dweight, accumulate,
+                                                             static_cast<char*>(d_ws), (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -67,12 +67,27 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       the sum over c of dcol * sample; d_bias is grad.sum((0, 2, 3)).  The backward is deterministic and free of atomics -- the input
       gradient sums, per cell, the sorted plan of the samples that reach it -- so two runs agree bit for bit, which torchvision's own
       GPU backward does not promise; it skips the work of every argument that needs no gradient.  Double backward raises.
-      All tensors are float32 (torchvision's autocast rule casts this operator to float32; a 16-bit or float64 tensor is a TypeError:
-      pass .float()), on the GPU or on `meta`.  Contiguous NCHW is the native layout, a channels_last argument is made contiguous by
-      one copy, gradients come back in each argument's own memory format, the result is contiguous NCHW.  The products run on the
+      All tensors are float32, or all float16, or all bfloat16 (below); any other mix, and float64, is the TypeError that names the
+      first tensor that is not float32 (pass .float()).  Tensors live on the GPU or on `meta`.  Contiguous NCHW is the native layout, a channels_last argument is made contiguous by
+      one copy, gradients come back in each argument's own memory format, the result is contiguous NCHW.  The float32 products run on the
       exact-float32 MFMA kernel of csrc/gemm_tn.hip over chunks of DEFORM_CHUNK_IMAGES images (the bound of the column workspace);
       the forward, d_input, d_offset and d_mask do not depend on the chunking, d_weight sums the chunks in ascending order.  N == 0
       or C_out == 0 return empty tensors (zero gradients).  The 32-bit indices of the kernels bound the sizes (MAX_DEFORM_INDEX).
+      float16 / bfloat16 (T; the frcnn_ops_deform_*_16 kernels, csrc/gemm_nt16.hip).  Columns: input, offset and mask are widened to
+      float32 on read; the sample coordinate, the bilinear value and mask * sample are computed in float32 by the device functions of
+      the float32 kernels (csrc/ops_deform.h); the column value is rounded ONCE to T, to nearest even -- bit for bit the float32
+      operator's column of the widened tensors, rounded.  Forward: the products of two T values are exact in float32 and are summed in
+      float32 accumulators on v_mfma_f32_32x32x16_{f16,bf16}, both operands 16-bit in memory, without a split reduction, so an output
+      does not depend on the chunking; out = round_T(acc + float(bias)) is the one rounding; a float16 result beyond 65504 is inf, as
+      for any half convolution.  Backward: dcol = W^T dout on the same kernel, no split, kept in float32; d_offset, d_mask and d_input
+      are the float32 gathers (T input, offset and mask, float32 dcol, the same order of summation, d_input through the same plan,
+      stable sort and ascending sum), rounded once to T on the store; d_weight samples the columns again to T (the forward's values),
+      multiplies on the same kernel with a deterministic split reduction, adds the chunks of DEFORM_CHUNK_IMAGES images in ascending
+      order in a FLOAT32 buffer and rounds it to T once after the last chunk (never in T); d_bias =
+      grad.sum((0, 2, 3), dtype=float32).to(T).  Deterministic, no atomics; the forward, d_input, d_offset and d_mask do not depend
+      on the chunking.  The result and the gradients have dtype T.  DeformConv2d.forward follows mmcv's AMP rule: when input is 16-bit,
+      offset, mask, weight and bias are cast to input.dtype by differentiable .to calls, so float32 parameters receive float32
+      gradients; a float32 input casts nothing.
   deform_roi_pool(input, rois, offset, output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1)
   DeformRoIPool(output_size, spatial_scale=1.0, sampling_ratio=0, gamma=0.1).forward(input, rois, offset=None)
   DeformRoIPoolPack / ModulatedDeformRoIPoolPack(output_size, output_channels, deform_fc_channels=1024, spatial_scale=1.0,
@@ -973,6 +988,27 @@ def _opt_ptr(t, i0=0):
     return None if t is None else t[i0:].data_ptr()
 
 
+def _deform_call(like):
+    """call(name, *args): frcnn_ops_deform_<name> for float32 tensors, frcnn_ops_deform_<name>_16 with the element-type code first for
+    16-bit ones; the value comes back (a status, checked, or workspace bytes)."""
+    e = _elem(like.dtype)
+    lib = nv.lib()
+
+    def call(name, *args):
+        full = "frcnn_ops_deform_" + name + ("" if e is None else "_16")
+        rc = getattr(lib, full)(*(args if e is None else (e,) + args))
+        if name != "workspace_bytes":
+            nv.check(rc, full)
+        elif rc == 0:
+            raise nv.FrcnnError(-1, full)
+        return rc
+    return call
+
+
+def _deform_buffer(call, like, ref, images, stage):
+    return torch.empty((call("workspace_bytes", ref, images, stage),), dtype=torch.uint8, device=like.device)
+
+
 def _opt_contiguous(t):
     return None if t is None else t.contiguous()
 
@@ -989,12 +1025,11 @@ def _deform_conv2d(input: Tensor, offset: Tensor, weight: Tensor, bias: Optional
         geom = _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
         x, off, wgt, b, m = input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(bias), _opt_contiguous(mask)
         nb = min(n, chunk)
-        ws = _workspace("deform", input, C.byref(geom), nb, nv.DEFORM_WS_FORWARD)
-        lib = nv.lib()
+        call = _deform_call(input)
+        ws = _deform_buffer(call, input, C.byref(geom), nb, nv.DEFORM_WS_FORWARD)
         for i0 in range(0, n, nb):
-            nv.check(lib.frcnn_ops_deform_forward(C.byref(geom), min(nb, n - i0), x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0),
-                                                  wgt.data_ptr(), _opt_ptr(b), out[i0:].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  _stream(input)), "frcnn_ops_deform_forward")
+            call("forward", C.byref(geom), min(nb, n - i0), x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), wgt.data_ptr(),
+                 _opt_ptr(b), out[i0:].data_ptr(), ws.data_ptr(), ws.numel(), _stream(input))
     return out
 
 
@@ -1027,9 +1062,11 @@ def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight:
         geom = _deform_geom(input, offset, weight, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w)
         g, x, off, wgt, m = grad.contiguous(), input.contiguous(), offset.contiguous(), weight.contiguous(), _opt_contiguous(mask)
         new = lambda want, like: torch.empty(like.shape, dtype=like.dtype, device=like.device) if want else None   # noqa: E731
-        dx, doff, dw, dm = new(want_input, x), new(want_offset, off), new(want_weight, wgt), new(want_mask, m)
-        lib, stream, ref = nv.lib(), _stream(grad), C.byref(geom)
-        stage = lambda which: _workspace("deform", grad, ref, min(n, chunk), which)                                 # noqa: E731
+        dx, doff, dm = new(want_input, x), new(want_offset, off), new(want_mask, m)
+        # the 16-bit kernels add the chunks of d_weight in a float32 buffer, rounded once after the last chunk
+        dw = torch.empty(wgt.shape, dtype=torch.float32, device=wgt.device) if want_weight else None
+        call, stream, ref = _deform_call(grad), _stream(grad), C.byref(geom)
+        stage = lambda which: _deform_buffer(call, grad, ref, min(n, chunk), which)                                  # noqa: E731
         want_columns = want_input or want_offset or want_mask
         if want_columns:
             dcol = stage(nv.DEFORM_WS_COLUMNS)
@@ -1041,25 +1078,24 @@ def _deform_conv2d_backward(grad: Tensor, input: Tensor, offset: Tensor, weight:
         samples = geom.offset_groups * kh * kw * offset.shape[2] * offset.shape[3]          # per image
         for i0, k in _chunks(n, chunk):
             if want_columns:
-                nv.check(lib.frcnn_ops_deform_backward_columns(ref, k, wgt.data_ptr(), g[i0:].data_ptr(), dcol.data_ptr(), ws_col.data_ptr(),
-                                                               ws_col.numel(), stream), "frcnn_ops_deform_backward_columns")
+                call("backward_columns", ref, k, wgt.data_ptr(), g[i0:].data_ptr(), dcol.data_ptr(), ws_col.data_ptr(), ws_col.numel(), stream)
             if want_offset or want_mask:
-                nv.check(lib.frcnn_ops_deform_backward_offset(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), dcol.data_ptr(),
-                                                              _opt_ptr(doff, i0), _opt_ptr(dm, i0), stream), "frcnn_ops_deform_backward_offset")
+                call("backward_offset", ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), dcol.data_ptr(), _opt_ptr(doff, i0),
+                     _opt_ptr(dm, i0), stream)
             if want_input:
                 def fill(keys, wts):
-                    nv.check(lib.frcnn_ops_deform_input_plan(ref, k, off[i0:].data_ptr(), _opt_ptr(m, i0), keys, wts, stream),
-                             "frcnn_ops_deform_input_plan")
+                    call("input_plan", ref, k, off[i0:].data_ptr(), _opt_ptr(m, i0), keys, wts, stream)
 
                 def gather(keys, order, wts):
-                    nv.check(lib.frcnn_ops_deform_backward_input(ref, k, keys, order, wts, dcol.data_ptr(), dx[i0:].data_ptr(),
-                                                                 ws_in.data_ptr(), ws_in.numel(), stream), "frcnn_ops_deform_backward_input")
+                    call("backward_input", ref, k, keys, order, wts, dcol.data_ptr(), dx[i0:].data_ptr(), ws_in.data_ptr(), ws_in.numel(),
+                         stream)
                 held = _sorted_gather(fill, gather, k * samples * 4, grad.device)       # noqa: F841 (kept alive)
             if want_weight:
-                nv.check(lib.frcnn_ops_deform_backward_weight(ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), g[i0:].data_ptr(),
-                                                              dw.data_ptr(), int(i0 > 0), ws_w.data_ptr(), ws_w.numel(), stream),
-                         "frcnn_ops_deform_backward_weight")
-        db = g.sum((0, 2, 3)) if want_bias else None
+                call("backward_weight", ref, k, x[i0:].data_ptr(), off[i0:].data_ptr(), _opt_ptr(m, i0), g[i0:].data_ptr(), dw.data_ptr(),
+                     int(i0 > 0), ws_w.data_ptr(), ws_w.numel(), stream)
+        if want_weight:
+            dw = dw.to(grad.dtype)
+        db = g.sum((0, 2, 3), dtype=torch.float32).to(grad.dtype) if want_bias else None
         return [_placeholder(grad) if t is None else _grad_layout(t, t.shape[1], cl) if t.dim() == 4 else t
                 for t, (_, cl) in zip((dx, doff, dw, db, dm), plan)]
 
@@ -2092,7 +2128,8 @@ def ps_roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1
     return _ps_roi_align(input, rois, float(spatial_scale), oh, ow, int(sampling_ratio))
 
 
-_F32_ONLY = "float32 (deform_conv2d computes in float32 only, as under torchvision's autocast rule: pass .float())"
+_F32_ONLY = ("float32 (deform_conv2d takes all-float32 tensors, or all-float16 / all-bfloat16 ones for the 16-bit kernels, and no mix: "
+             "pass .float())")
 
 
 def _check_int(name, v):
@@ -2114,8 +2151,14 @@ def _int_pair(name, v, low):
 def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None):
     """torchvision.ops.deform_conv2d: deformable convolution v1, v2 with a mask; [N, C_out, oh, ow], contiguous."""
     tensors = [("input", input), ("offset", offset), ("weight", weight)] + [(k, t) for k, t in (("bias", bias), ("mask", mask)) if t is not None]
+    if all(isinstance(t, torch.Tensor) and t.dtype == torch.float16 for _, t in tensors):
+        allowed = (torch.float16,)
+    elif all(isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 for _, t in tensors):
+        allowed = (torch.bfloat16,)
+    else:
+        allowed = (torch.float32,)                      # a mix is refused at its first tensor that is not float32
     for name, t in tensors:
-        _check_tensor(name, t, (torch.float32,), _F32_ONLY)
+        _check_tensor(name, t, allowed, _F32_ONLY)
     for name, t in tensors[1:]:
         _check_same_device(input, t, "input", name)
     if input.dim() != 4:
@@ -2155,8 +2198,9 @@ def deform_conv2d(input, offset, weight, bias=None, stride=(1, 1), padding=(0, 0
     if bias is not None and tuple(bias.shape) != (co,):
         raise ValueError("bias must be [C_out] = [%d], got shape %s" % (co, tuple(bias.shape)))
     nb = max(1, min(n, DEFORM_CHUNK_IMAGES))
-    pp = (oh * ow + 3) // 4 * 4
-    largest = max(nb * pp, c * kh * kw, nb * og * h * w, nb * og * kh * kw * oh * ow * 4, h + padding[0] + dilation[0] * (kh - 1) + 1,
+    run = 8 if input.dtype in _HALF else 4               # what the kernels pad a row of the column matrix to
+    pp = (oh * ow + run - 1) // run * run
+    largest = max(nb * pp, c * kh * kw + (8 * groups if input.dtype in _HALF else 0), nb * og * h * w, nb * og * kh * kw * oh * ow * 4, h + padding[0] + dilation[0] * (kh - 1) + 1,
                   w + padding[1] + dilation[1] * (kw - 1) + 1)
     if largest > MAX_DEFORM_INDEX:
         raise ValueError("deform_conv2d is too large for the kernels' 32-bit indices: %d > MAX_DEFORM_INDEX = %d (columns, cells or "
@@ -3290,8 +3334,15 @@ class DeformConv2d(torch.nn.Module):
             torch.nn.init.uniform_(self.bias, -bound, bound)
 
     def forward(self, input, offset, mask=None):
-        return deform_conv2d(input, offset, self.weight, self.bias, stride=self.stride, padding=self.padding, dilation=self.dilation,
-                             mask=mask)
+        weight, bias = self.weight, self.bias
+        if isinstance(input, torch.Tensor) and input.dtype in _HALF:
+            # mmcv's AMP rule: a 16-bit input takes the other tensors to its dtype; the casts are differentiable, so the float32
+            # parameters receive float32 gradients
+            weight = weight.to(input.dtype)
+            bias = None if bias is None else bias.to(input.dtype)
+            offset = offset.to(input.dtype) if isinstance(offset, torch.Tensor) else offset
+            mask = mask.to(input.dtype) if isinstance(mask, torch.Tensor) else mask
+        return deform_conv2d(input, offset, weight, bias, stride=self.stride, padding=self.padding, dilation=self.dilation, mask=mask)
 
     def __repr__(self):
         s = "%s(%s, %s, kernel_size=%s, stride=%s" % (self.__class__.__name__, self.in_channels, self.out_channels, self.kernel_size,

@@ -93,6 +93,8 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_convex_iou, its _tile_rows getter, frcnn_ops_convex_giou and
                                  frcnn_ops_min_area_polygons (the point-set operators of Oriented RepPoints, CFA and SASM: mmcv's convex_iou,
                                  convex_giou and min_area_polygons);
+                                 still 21 (additions only): the frcnn_ops_deform_*_16 forms (deformable convolution on float16 / bfloat16 tensors,
+                                 its products on the 16-bit matrix pipe);
                                  still 21 (no prototype or struct changed): frcnn_detections returns the documented FRCNN_EUNSUPPORTED for images past
                                  the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before) */
 
@@ -584,7 +586,8 @@ int frcnn_ops_ps_roi_align_backward_16(int elem_type, const float* d_rois, int k
                                        float spatial_scale, int sampling_ratio, const void* d_dout, void* d_dx, void* stream);
 
 /* Deformable convolution v1 / v2 (csrc/ops_deform.hip): torchvision.ops.deform_conv2d in both directions, restated from the published
- *   algorithm of torchvision/csrc/ops/cuda/deform_conv2d_kernel.cu (third party, absent here: restated, unpinned).  Float32, plain NCHW;
+ *   algorithm of torchvision/csrc/ops/cuda/deform_conv2d_kernel.cu (third party, absent here: restated, unpinned).  Float32 (the _16
+ *   forms below: float16 / bfloat16), plain NCHW;
  *   every entry point works on one chunk of n_img images (the caller walks the chunks and owns every buffer):
  *     d_x      : [n_img][c_in][height][width]
  *     d_weight : [c_out][c_in / groups][kernel_h][kernel_w]
@@ -635,6 +638,44 @@ int frcnn_ops_deform_backward_input(const frcnn_deform_geom* g, int n_img, const
                                     const float* d_weights, const float* d_dcol, float* d_dx, void* d_ws, size_t ws_bytes, void* stream);
 int frcnn_ops_deform_backward_weight(const frcnn_deform_geom* g, int n_img, const float* d_x, const float* d_offset, const float* d_mask,
                                      const float* d_dout, float* d_dweight, int accumulate, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The same operator on float16 / bfloat16 tensors (elem_type: FRCNN_OPS_F16 / FRCNN_OPS_BF16; T below): every tensor of the float32
+ *   forms above is of type T here, in the same layouts, EXCEPT d_dcol, the plan's d_weights and d_dweight, which stay float32.  The
+ *   validation rules are the float32 forms', plus FRCNN_EINVAL (0 from _workspace_bytes_16) for an unknown elem_type.  Nothing allocates.
+ *   Arithmetic contract:
+ *   columns   input, offset and mask are widened to float32 on read (exact); the sample coordinate, the bilinear value and
+ *             mask * sample are computed in float32 by the device functions of the float32 kernels (csrc/ops_deform.h); the column
+ *             value is rounded ONCE to T, to nearest even: bit for bit the float32 operator's column of the widened tensors, rounded.
+ *   forward   out = round_T(sum_k w col + float(bias)): the products w * col of two T values are exact in float32, the sum runs in
+ *             float32 accumulators on v_mfma_f32_32x32x16_{f16,bf16} (csrc/gemm_nt16.hip) without a split reduction, so an output
+ *             element does not depend on the chunking; the bias is added in float32 and the result rounded once.  A float16 result
+ *             beyond 65504 is inf, as for any half convolution.
+ *   backward  d_dcol = W^T dout on the same kernel, without a split, kept in float32 (the accumulators as they are), in the column
+ *             layout with Pp = P rounded up to a multiple of 8: [c_in * kh * kw][n_img * Pp] floats (.._workspace_bytes_16(..,
+ *             FRCNN_DEFORM_WS_COLUMNS)).  d_doffset, d_dmask and d_dx are the float32 forms' gathers: they read T input, offset and
+ *             mask and the float32 d_dcol, sum in float32 in the same order (d_dx through the same plan, stable sort and ascending
+ *             sum) and round once to T on the store; they do not depend on the chunking.
+ *             frcnn_ops_deform_backward_weight_16: the columns are sampled again to T (the forward's values), dout col^T runs on the
+ *             same kernel with a deterministic split reduction over the chunk's outputs (float32 planes added in ascending order), and
+ *             d_dweight is a FLOAT32 [c_out][c_in / groups][kh][kw] buffer (= or, with accumulate != 0, +=): the caller adds the
+ *             chunks in ascending order in float32 and rounds to T once after the last one; the chunks are never accumulated in T.
+ *   Everything is deterministic and free of atomics. */
+size_t frcnn_ops_deform_workspace_bytes_16(int elem_type, const frcnn_deform_geom* g, int n_img, int stage);
+int frcnn_ops_deform_forward_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                const void* d_mask, const void* d_weight, const void* d_bias, void* d_out, void* d_ws, size_t ws_bytes,
+                                void* stream);
+int frcnn_ops_deform_backward_columns_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_weight, const void* d_dout,
+                                         float* d_dcol, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_deform_backward_offset_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                        const void* d_mask, const float* d_dcol, void* d_doffset, void* d_dmask, void* stream);
+int frcnn_ops_deform_input_plan_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_offset, const void* d_mask,
+                                   int64_t* d_keys, float* d_weights, void* stream);
+int frcnn_ops_deform_backward_input_16(int elem_type, const frcnn_deform_geom* g, int n_img, const int64_t* d_sorted_keys,
+                                       const int64_t* d_order, const float* d_weights, const float* d_dcol, void* d_dx, void* d_ws,
+                                       size_t ws_bytes, void* stream);
+int frcnn_ops_deform_backward_weight_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
+                                        const void* d_mask, const void* d_dout, float* d_dweight, int accumulate, void* d_ws,
+                                        size_t ws_bytes, void* stream);
 
 /* Deformable RoI pooling (DCN v1 / v2; csrc/ops_droi.hip): mmcv's deform_roi_pool in both directions, restated from the published
  *   definition of mmcv/ops/csrc/common/cuda/deform_roi_pool_cuda_kernel.cuh (third party, absent here: restated, unpinned; where the two

@@ -28,7 +28,8 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
   * deform: deformable convolution at a DCN stage (2 x 256 -> 256, 3 x 3, padding 1, 50 x 68 maps), 1 and 4 offset groups, with and
     without a mask, offsets N(0, 2 px): ops.deform_conv2d beside the same operator composed from torch operations on the GPU (the
     restatement of tests/deform_conv_cases.py: floor, index gathers and einsum), forward and forward + backward of all five gradients,
-    in alternating windows.
+    in alternating windows.  The same shapes in float16 and bfloat16: the 16-bit operator (16-bit columns, the products on the
+    16-bit matrix pipe) beside the float32 operator on the widened tensors, forward and forward + backward.
 
   * droi: deformable RoI pooling on a C4 map (2 x 256 x 50 x 68, 512 RoIs, 7 x 7, scale 1 / 16, sampling_ratio 2), with offsets N(0, 0.5)
     and without, float32 and bfloat16: ops.deform_roi_pool beside the same operator composed from torch operations on the GPU (the
@@ -333,6 +334,22 @@ def deform_leg(rng, reps, warmup):
                 r[name] = {"ops.deform_conv2d": round(t_native, 1), "torch composition": round(t_comp, 1),
                            "composition / deform_conv2d": round(t_comp / t_native, 2)}
             res["deform 2 x 256 -> 256, 3 x 3, pad 1, 50 x 68, G %d, %s" % (groups, "mask" if with_mask else "no mask")] = r
+            # float16 / bfloat16: the 16-bit operator beside the float32 operator on the widened tensors (the only way to run the call before)
+            for dtype in (torch.float16, torch.bfloat16):
+                half = [t.to(dtype) if t is not None else None for t in (x, offset, weight, bias, mask)]
+                wide = [t.float() if t is not None else None for t in half]
+                leaves16 = [t.clone().requires_grad_(True) if t is not None else None for t in half]
+                leaves32 = [t.clone().requires_grad_(True) if t is not None else None for t in wide]
+                g16 = g.to(dtype)
+                y16, y32 = native(half).float(), native(wide)
+                r = {"max |16-bit - float32 of the widened tensors| / max |float32|": float((y16 - y32).abs().max() / y32.abs().max())}
+                for name, fns in (("fwd", (lambda: native(half), lambda: native(wide))),
+                                  ("fwd+bwd", (lambda: native(leaves16).backward(g16), lambda: native(leaves32).backward(g16.float())))):
+                    t_half, t_wide = timed_pair(fns[0], fns[1], reps, warmup)
+                    r[name] = {"ops.deform_conv2d %s" % str(dtype).split(".")[-1]: round(t_half, 1),
+                               "ops.deform_conv2d float32 (widened)": round(t_wide, 1), "float32 / 16-bit": round(t_wide / t_half, 2)}
+                res["deform %s 2 x 256 -> 256, 3 x 3, pad 1, 50 x 68, G %d, %s" % (str(dtype).split(".")[-1], groups,
+                                                                                  "mask" if with_mask else "no mask")] = r
     return res
 
 
