@@ -18,7 +18,7 @@
 // The reduction of one output element is sequential inside one wave.  Without a split (splits == 1) the result does not depend on
 // anything but the operands; with one, split z sums r in [z rps, (z + 1) rps) into plane z of a float32 workspace and
 // gemm_nt16_reduce_kernel adds the planes in ascending z: deterministic, no atomics.
-#include "ops_deform.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
@@ -31,11 +31,11 @@ static constexpr int NT_MAX_SPLITS = 64;
 static constexpr int NT_SPLIT_BLOCKS = 512;  // blocks a split product aims at (2 per CU)
 
 template <typename E> struct NtFrag;
-template <> struct NtFrag<deform_f16> {
+template <> struct NtFrag<f16> {
     typedef f16x8_t vec;
     static __device__ __forceinline__ f32x16 mfma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
-template <> struct NtFrag<deform_bf16> {
+template <> struct NtFrag<bf16> {
     typedef bf16x8_t vec;
     static __device__ __forceinline__ f32x16 mfma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
@@ -127,8 +127,8 @@ void gemm_nt16_kernel(const E* __restrict__ A, int lda, const E* __restrict__ B,
                 if (m >= M) continue;
                 if (NCHW) {
                     const int co = st.c_base + m;
-                    const float v = st.bias ? acc[mt][nt][i] + deform_load(static_cast<const E*>(st.bias), co) : acc[mt][nt][i];
-                    deform_store(static_cast<E*>(st.out), ((size_t)b * st.c_total + co) * st.P + p, v);
+                    const float v = st.bias ? acc[mt][nt][i] + Elem<E>::load(static_cast<const E*>(st.bias), co) : acc[mt][nt][i];
+                    round_to(v, static_cast<E*>(st.out)[((size_t)b * st.c_total + co) * st.P + p]);
                 } else {
                     st.c[(size_t)blockIdx.z * st.plane + (size_t)m * st.ldc + n] = acc[mt][nt][i];
                 }
@@ -184,9 +184,7 @@ int launch_gemm_nt16(int elem_type, const void* A, int lda, const void* B, int l
 {
     if (!nt16_operands_ok(A, lda, B, ldb, M, N, R) || !C || ldc < N) return FRCNN_EINVAL;
     NtStore st = {C, ldc, 0, nullptr, nullptr, 0, 0, 0};
-    if (elem_type == FRCNN_OPS_F16) return nt16_launch<deform_f16, false>(A, lda, B, ldb, M, N, R, 1, st, s);
-    if (elem_type == FRCNN_OPS_BF16) return nt16_launch<deform_bf16, false>(A, lda, B, ldb, M, N, R, 1, st, s);
-    return FRCNN_EINVAL;
+    OPS_ELEM_DISPATCH(elem_type, E, nt16_launch<E, false>(A, lda, B, ldb, M, N, R, 1, st, s));
 }
 
 // C (float32, row stride ldc) = or += A B^T through the deterministic split of gemm_nt16_splits; ws: gemm_nt16_workspace_bytes
@@ -198,10 +196,7 @@ int launch_gemm_nt16_split(int elem_type, const void* A, int lda, const void* B,
     const int splits = gemm_nt16_splits(M, N, R);
     const size_t plane = (size_t)M * N;
     NtStore st = {static_cast<float*>(ws), N, plane, nullptr, nullptr, 0, 0, 0};
-    int rc;
-    if (elem_type == FRCNN_OPS_F16) rc = nt16_launch<deform_f16, false>(A, lda, B, ldb, M, N, R, splits, st, s);
-    else if (elem_type == FRCNN_OPS_BF16) rc = nt16_launch<deform_bf16, false>(A, lda, B, ldb, M, N, R, splits, st, s);
-    else return FRCNN_EINVAL;
+    const int rc = [&]() -> int { OPS_ELEM_DISPATCH(elem_type, E, nt16_launch<E, false>(A, lda, B, ldb, M, N, R, splits, st, s)); }();
     if (rc) return rc;
     const size_t blocks = (plane + 255) / 256;
     hipLaunchKernelGGL(gemm_nt16_reduce_kernel, dim3((unsigned)std::min<size_t>(blocks, 16384)), dim3(256), 0, s,
@@ -215,9 +210,7 @@ int launch_gemm_nt16_nchw(int elem_type, const void* A, int lda, const void* B, 
 {
     if (!nt16_operands_ok(A, lda, B, ldb, M, N, R) || !out || P < 1 || N % P != 0 || c_base < 0 || c_base + M > c_total) return FRCNN_EINVAL;
     NtStore st = {nullptr, 0, 0, out, bias, P, c_total, c_base};
-    if (elem_type == FRCNN_OPS_F16) return nt16_launch<deform_f16, true>(A, lda, B, ldb, M, N, R, 1, st, s);
-    if (elem_type == FRCNN_OPS_BF16) return nt16_launch<deform_bf16, true>(A, lda, B, ldb, M, N, R, 1, st, s);
-    return FRCNN_EINVAL;
+    OPS_ELEM_DISPATCH(elem_type, E, nt16_launch<E, true>(A, lda, B, ldb, M, N, R, 1, st, s));
 }
 
 }  // namespace frcnn

@@ -299,11 +299,8 @@ int frcnn_ops_border_align_16(int elem_type, const void* d_x, int n_img, int fh,
 {
     if (c % OPS_HALF_RUN != 0) return FRCNN_EINVAL;
     // the forward always walks runs of OPS_HALF_RUN: only those two kernels are built
-    if (elem_type == FRCNN_OPS_F16)
-        return border_forward_impl<f16_t<OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_boxes, k, pool_size, d_out, d_argmax, stream);
-    if (elem_type == FRCNN_OPS_BF16)
-        return border_forward_impl<bf16_t<OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_boxes, k, pool_size, d_out, d_argmax, stream);
-    return FRCNN_EINVAL;
+    OPS_ELEM_DISPATCH(elem_type, E,
+                      border_forward_impl<run_t<E, OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_boxes, k, pool_size, d_out, d_argmax, stream));
 }
 
 int frcnn_ops_border_align_backward_16(int elem_type, const float* d_boxes, int k, int n_img, int fh, int fw, int c, int pool_size,

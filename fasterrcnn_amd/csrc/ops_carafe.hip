@@ -21,11 +21,11 @@
 // contributions in a fixed order -- low-resolution neighbour (qy, qx) row-major, then sub-pixel (sy, sx) row-major; the mask value of a
 // contribution is loaded once for the run.  Bit-identical from run to run.
 //
-// Element types: templates over the storage type E (float, float16, bfloat16): widened exactly on load, every product and sum in
-// float32 in one shared body (each term one explicit fmaf), rounded once to nearest even on store as Tensor.to() rounds, so
+// Element types: templates over the storage type E (float, float16, bfloat16: ops_elem.h): widened exactly on load, every product and
+// sum in float32 in one shared body (each term one explicit fmaf), rounded once to nearest even on store as Tensor.to() rounds, so
 // op(x_T, m_T) == op(x_T.float(), m_T.float()).to(T) bit for bit, forward and backward.
 // Indices: 64-bit plane bases, 32-bit inside a plane (s h s w < 2^31, checked by the entry points).
-#include "common.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
@@ -37,28 +37,6 @@ static constexpr int CARAFE_RUN = 4;          // channels a d_features thread ow
 static constexpr int CARAFE_TILE_W = 64;      // output pixels along pw: one wave
 static constexpr int CARAFE_TILE_H = 4;       // rows of a block: one per wave
 static constexpr int CARAFE_BLOCK = CARAFE_TILE_W * CARAFE_TILE_H;
-
-struct cf_f16 { _Float16 v; };
-struct cf_bf16 { unsigned short bits; };
-
-// One element in memory as E, in registers as float32 (ops_ps.hip's scalar form, with its roundings).
-template <typename E> struct CfElem;
-template <> struct CfElem<float> {
-    static __device__ __forceinline__ float load(const float* p, size_t i) { return p[i]; }
-    static __device__ __forceinline__ void store(float* p, size_t i, float v) { p[i] = v; }
-};
-template <> struct CfElem<cf_f16> {
-    static __device__ __forceinline__ float load(const cf_f16* p, size_t i) { return (float)p[i].v; }
-    static __device__ __forceinline__ void store(cf_f16* p, size_t i, float v) { p[i].v = (_Float16)v; }
-};
-template <> struct CfElem<cf_bf16> {
-    static __device__ __forceinline__ float load(const cf_bf16* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
-    static __device__ __forceinline__ void store(cf_bf16* p, size_t i, float v)
-    {
-        const unsigned b = __float_as_uint(v);     // c10::BFloat16's rounding: every NaN becomes 0x7FC0
-        p[i].bits = v != v ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-    }
-};
 
 // the cell of a thread in a tile of CARAFE_TILE_H rows of CARAFE_TILE_W cells: blockIdx.x = tile row * tiles_w + tile column
 __device__ __forceinline__ bool carafe_pixel(int out_h, int out_w, int& ph, int& pw)
@@ -110,7 +88,7 @@ template <int K> struct CarafeTile {
             const E* const xr = x + (((size_t)n * C + c0 + ch) * fh + (yin ? y : 0)) * fw;
             for (int tx = lane; tx < tw; tx += 64) {
                 const int xx = qx0 + tx;
-                s_x[(ch * TH + ty) * P + tx] = yin && xx >= 0 && xx < fw ? CfElem<E>::load(xr, (size_t)xx) : 0.f;
+                s_x[(ch * TH + ty) * P + tx] = yin && xx >= 0 && xx < fw ? Elem<E>::load(xr, (size_t)xx) : 0.f;
             }
         }
     }
@@ -131,7 +109,7 @@ void ops_carafe_kernel(const E* __restrict__ x, const E* __restrict__ masks, int
     const E* const mp = masks + ((size_t)n * G + g) * (K * K) * plane + pix;
     float m[K * K];
 #pragma unroll
-    for (int k = 0; k < K * K; ++k) m[k] = t.active ? CfElem<E>::load(mp, (size_t)k * plane) : 0.f;
+    for (int k = 0; k < K * K; ++k) m[k] = t.active ? Elem<E>::load(mp, (size_t)k * plane) : 0.f;
     for (int c0 = c_lo; c0 < c_hi; c0 += CARAFE_STAGE) {
         const int nc = min(CARAFE_STAGE, c_hi - c0);
         __syncthreads();                                 // the previous channels have been read
@@ -145,7 +123,7 @@ void ops_carafe_kernel(const E* __restrict__ x, const E* __restrict__ masks, int
             for (int i = 0; i < K; ++i)
 #pragma unroll
                 for (int j = 0; j < K; ++j) acc = fmaf(w[i * T::P + j], m[i * K + j], acc);
-            CfElem<E>::store(out, ((size_t)n * C + c0 + ch) * plane + pix, acc);
+            Elem<E>::store(out, ((size_t)n * C + c0 + ch) * plane + pix, acc);
         }
     }
 }
@@ -173,7 +151,7 @@ void ops_carafe_backward_masks_kernel(const E* __restrict__ x, const E* __restri
         if (!t.active) continue;
         for (int ch = 0; ch < nc; ++ch) {
             const float* const w = s_x + ch * (T::TH * T::P) + t.base;
-            const float d = CfElem<E>::load(dout, ((size_t)n * C + c0 + ch) * plane + pix);
+            const float d = Elem<E>::load(dout, ((size_t)n * C + c0 + ch) * plane + pix);
 #pragma unroll
             for (int i = 0; i < K; ++i)
 #pragma unroll
@@ -187,7 +165,7 @@ void ops_carafe_backward_masks_kernel(const E* __restrict__ x, const E* __restri
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             const bool ok = ((t.yok >> i) & (t.xok >> j) & 1u) != 0;     // exactly 0 outside the map, whatever the gradient holds
-            CfElem<E>::store(dp, (size_t)(i * K + j) * plane, ok ? acc[i * K + j] : 0.f);
+            Elem<E>::store(dp, (size_t)(i * K + j) * plane, ok ? acc[i * K + j] : 0.f);
         }
 }
 
@@ -226,9 +204,9 @@ void ops_carafe_backward_features_kernel(const E* __restrict__ masks, const E* _
             for (int sy = 0; sy < s; ++sy) {
                 const size_t row = (size_t)(qy * s + sy) * out_w + (size_t)qx * s;
                 for (int sx = 0; sx < s; ++sx) {
-                    const float m = CfElem<E>::load(mt, row + sx);
+                    const float m = Elem<E>::load(mt, row + sx);
 #pragma unroll
-                    for (int u = 0; u < CARAFE_RUN; ++u) acc[u] = fmaf(CfElem<E>::load(dp[u], row + sx), m, acc[u]);
+                    for (int u = 0; u < CARAFE_RUN; ++u) acc[u] = fmaf(Elem<E>::load(dp[u], row + sx), m, acc[u]);
                 }
             }
         }
@@ -236,7 +214,7 @@ void ops_carafe_backward_features_kernel(const E* __restrict__ masks, const E* _
     const size_t cell = (size_t)y * fw + xx;
 #pragma unroll
     for (int u = 0; u < CARAFE_RUN; ++u)
-        if (c0 + u < c_end) CfElem<E>::store(dx, ((size_t)n * C + c0 + u) * fh * fw + cell, acc[u]);
+        if (c0 + u < c_end) Elem<E>::store(dx, ((size_t)n * C + c0 + u) * fh * fw + cell, acc[u]);
 }
 
 // ---- the entry points' bodies, one per element type ---------------------------------------------------------------------------------
@@ -314,14 +292,6 @@ static int carafe_backward_impl(const void* d_features, const void* d_masks, con
 
 using namespace frcnn;
 
-// a 16-bit entry point's body by element-type code
-#define CARAFE_DISPATCH_16(elem_type, impl, ...)                               \
-    do {                                                                       \
-        if ((elem_type) == FRCNN_OPS_F16) return impl<cf_f16>(__VA_ARGS__);    \
-        if ((elem_type) == FRCNN_OPS_BF16) return impl<cf_bf16>(__VA_ARGS__);  \
-        return FRCNN_EINVAL;                                                   \
-    } while (0)
-
 extern "C" {
 
 int frcnn_ops_carafe_max_kernel(void) { return CARAFE_MAX_KERNEL; }
@@ -345,15 +315,16 @@ int frcnn_ops_carafe_backward(const float* d_features, const float* d_masks, con
 int frcnn_ops_carafe_16(int elem_type, const void* d_features, const void* d_masks, int n, int c, int h, int w, int kernel_size,
                         int group_size, int scale_factor, void* d_out, void* stream)
 {
-    CARAFE_DISPATCH_16(elem_type, carafe_impl, d_features, d_masks, n, c, h, w, kernel_size, group_size, scale_factor, d_out, stream);
+    OPS_ELEM_DISPATCH(elem_type, E,
+                      carafe_impl<E>(d_features, d_masks, n, c, h, w, kernel_size, group_size, scale_factor, d_out, stream));
 }
 
 int frcnn_ops_carafe_backward_16(int elem_type, const void* d_features, const void* d_masks, const void* d_dout, int n, int c, int h,
                                  int w, int kernel_size, int group_size, int scale_factor, void* d_dfeatures, void* d_dmasks,
                                  void* stream)
 {
-    CARAFE_DISPATCH_16(elem_type, carafe_backward_impl, d_features, d_masks, d_dout, n, c, h, w, kernel_size, group_size, scale_factor,
-                       d_dfeatures, d_dmasks, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, carafe_backward_impl<E>(d_features, d_masks, d_dout, n, c, h, w, kernel_size, group_size, scale_factor,
+                                                            d_dfeatures, d_dmasks, stream));
 }
 
 }  // extern "C"

@@ -400,12 +400,4 @@ static inline int dc_backward_input(int elem_type, const int64_t* sorted_keys, c
                        dinput, ws, ws_bytes, (hipStream_t)stream);
 }
 
-// a 16-bit entry point's body by element-type code
-#define DCN_DISPATCH_16(elem_type, impl, ...)                                  \
-    do {                                                                       \
-        if ((elem_type) == FRCNN_OPS_F16) return impl<ms_f16>(__VA_ARGS__);    \
-        if ((elem_type) == FRCNN_OPS_BF16) return impl<ms_bf16>(__VA_ARGS__);  \
-        return FRCNN_EINVAL;                                                   \
-    } while (0)
-
 }  // namespace frcnn

@@ -60,7 +60,7 @@ int frcnn_ops_dcnv3_block_items(int gc, int kernel_h, int kernel_w, int elem_typ
     if (gc < 1 || gc > MSDA_MAX_CHANNELS || kernel_h < 1 || kernel_h > DCN_MAX_KERNEL || kernel_w < 1 || kernel_w > DCN_MAX_KERNEL)
         return 0;
     if (elem_type != 0 && elem_type != FRCNN_OPS_F16 && elem_type != FRCNN_OPS_BF16) return 0;
-    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<ms_f16>::RUN;
+    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<f16>::RUN;
     return ms_map(gc, kernel_h * kernel_w, run, gc % run == 0).ipb;
 }
 
@@ -111,8 +111,8 @@ int frcnn_ops_dcnv3_forward_16(int elem_type, const void* d_input, const float* 
                                int g, int gc, int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
                                int dil_w, float offset_scale, void* d_out, void* stream)
 {
-    DCN_DISPATCH_16(elem_type, dcnv3_forward_impl, d_input, d_offset, d_mask, n_img, h, w, g, gc, kernel_h, kernel_w, stride_h, stride_w,
-                      pad_h, pad_w, dil_h, dil_w, offset_scale, d_out, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, dcnv3_forward_impl<E>(d_input, d_offset, d_mask, n_img, h, w, g, gc, kernel_h, kernel_w, stride_h,
+                                                          stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, d_out, stream));
 }
 
 int frcnn_ops_dcnv3_backward_offset_16(int elem_type, const void* d_input, const float* d_offset, const float* d_mask, const void* d_dout,
@@ -120,8 +120,9 @@ int frcnn_ops_dcnv3_backward_offset_16(int elem_type, const void* d_input, const
                                        int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, float* d_doffset, float* d_dmask,
                                        void* stream)
 {
-    DCN_DISPATCH_16(elem_type, dcnv3_backward_offset_impl, d_input, d_offset, d_mask, d_dout, n_img, h, w, g, gc, kernel_h, kernel_w,
-                      stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, d_doffset, d_dmask, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, dcnv3_backward_offset_impl<E>(d_input, d_offset, d_mask, d_dout, n_img, h, w, g, gc, kernel_h, kernel_w,
+                                                                  stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, d_doffset,
+                                                                  d_dmask, stream));
 }
 
 int frcnn_ops_dcnv3_backward_input_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,

@@ -84,7 +84,7 @@ int frcnn_ops_dcnv4_block_items(int gc, int kernel_h, int kernel_w, int remove_c
     const int p = dcnv4_points(kernel_h, kernel_w, remove_center);
     if (p == 0 || gc < 1 || gc > MSDA_MAX_CHANNELS) return 0;
     if (elem_type != 0 && elem_type != FRCNN_OPS_F16 && elem_type != FRCNN_OPS_BF16) return 0;
-    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<ms_f16>::RUN;
+    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<f16>::RUN;
     return ms_map(gc, p, run, gc % run == 0).ipb;
 }
 
@@ -139,8 +139,9 @@ int frcnn_ops_dcnv4_forward_16(int elem_type, const void* d_input, const float* 
                                int kernel_h, int kernel_w, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                float offset_scale, int remove_center, void* d_out, void* stream)
 {
-    DCN_DISPATCH_16(elem_type, dcnv4_forward_impl, d_input, d_offset_mask, n_img, h, w, g, gc, kernel_h, kernel_w, stride_h, stride_w, pad_h,
-                    pad_w, dil_h, dil_w, offset_scale, remove_center, d_out, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, dcnv4_forward_impl<E>(d_input, d_offset_mask, n_img, h, w, g, gc, kernel_h, kernel_w, stride_h,
+                                                          stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, remove_center, d_out,
+                                                          stream));
 }
 
 int frcnn_ops_dcnv4_backward_offset_mask_16(int elem_type, const void* d_input, const float* d_offset_mask, const void* d_dout, int n_img,
@@ -148,8 +149,9 @@ int frcnn_ops_dcnv4_backward_offset_mask_16(int elem_type, const void* d_input, 
                                             int pad_w, int dil_h, int dil_w, float offset_scale, int remove_center, float* d_doffset_mask,
                                             void* stream)
 {
-    DCN_DISPATCH_16(elem_type, dcnv4_backward_offset_mask_impl, d_input, d_offset_mask, d_dout, n_img, h, w, g, gc, kernel_h, kernel_w,
-                    stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, remove_center, d_doffset_mask, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, dcnv4_backward_offset_mask_impl<E>(d_input, d_offset_mask, d_dout, n_img, h, w, g, gc, kernel_h,
+                                                                       kernel_w, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
+                                                                       offset_scale, remove_center, d_doffset_mask, stream));
 }
 
 int frcnn_ops_dcnv4_backward_input_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,

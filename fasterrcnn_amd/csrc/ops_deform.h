@@ -1,36 +1,14 @@
 // ops_deform.h -- the bilinear sample of deformable convolution, stated once for every kernel of ops_deform.hip (torchvision's
 // deform_conv2d_kernel.cu: bilinear_interpolate and get_coordinate_weight, restated, unpinned), over the storage type E of the maps:
-// float, or a 16-bit type that is widened exactly on load, so that the arithmetic is the float32 kernels' whatever E is.
+// float, or a 16-bit type of ops_elem.h that is widened exactly on load, so that the arithmetic is the float32 kernels' whatever E is.
 #pragma once
-#include "common.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
-// Storage types of input, offset, mask and their gradients: float, or the 16-bit ones of the frcnn_ops_deform_*_16 entry points.
-// deform_load widens exactly; deform_store rounds to nearest even once, NaN and infinities as torch's Tensor.to() (float16 by the
-// hardware conversion, bfloat16 by the integer rounding of c10::BFloat16: every NaN becomes 0x7FC0).
-struct deform_f16 { _Float16 v; };
-struct deform_bf16 { unsigned short bits; };
-
-__device__ __forceinline__ float deform_load(const float* p, size_t i) { return p[i]; }
-__device__ __forceinline__ float deform_load(const deform_f16* p, size_t i) { return (float)p[i].v; }
-__device__ __forceinline__ float deform_load(const deform_bf16* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
-
-__device__ __forceinline__ void deform_round(float v, float& e) { e = v; }
-// The empty asm pins v as a float32 VALUE before the conversion.  Without it the compiler folds a preceding float32 multiply or add
-// into the conversion (v_fma_mixlo_f16), which rounds the exact product to float16 directly: where the float32 product is a float16
-// tie that skips the float32 rounding of the contract and lands on the other neighbour (seen on an MI355X: one column in 21384).
-__device__ __forceinline__ void deform_round(float v, deform_f16& e)
-{
-    asm volatile("" : "+v"(v));
-    e.v = (_Float16)v;
-}
-__device__ __forceinline__ void deform_round(float v, deform_bf16& e)
-{
-    const unsigned b = __float_as_uint(v);
-    e.bits = v != v ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-}
-template <typename E> __device__ __forceinline__ void deform_store(E* p, size_t i, float v) { deform_round(v, p[i]); }
+// Elem<E>::store, with the element's address formed before the value is rounded: the order in which ops_deform.hip's kernels compile
+// to the instruction streams they were measured with
+template <typename E> __device__ __forceinline__ void deform_store(E* p, size_t i, float v) { round_to(v, p[i]); }
 
 // sample coordinate of tap i at output index o along one axis: the integer position first, then the float displacement
 __device__ __forceinline__ float deform_coord(int o, int stride, int pad, int i, int dil, float off)
@@ -75,7 +53,7 @@ __device__ __forceinline__ float deform_bilinear(const E* __restrict__ plane, in
     deform_corners(s, H, W, w, cell);
     float v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = cell[k] >= 0 ? deform_load(plane, cell[k]) : 0.f;
+    for (int k = 0; k < 4; ++k) v[k] = cell[k] >= 0 ? Elem<E>::load(plane, cell[k]) : 0.f;
     return ((w[0] * v[0] + w[1] * v[1]) + w[2] * v[2]) + w[3] * v[3];
 }
 
@@ -90,8 +68,8 @@ __device__ __forceinline__ float deform_coordinate_weight(const E* __restrict__ 
     const float yf = floorf(y), xf = floorf(x);
     const int yl = (int)yf, xl = (int)xf, yh = yl + 1, xh = xl + 1;
     const bool vyl = yl >= 0, vyh = yh < H, vxl = xl >= 0, vxh = xh < W;      // yl <= H - 1 and yh >= 0 hold in the accepted range
-    const float v_yx = (vyl && vxl) ? deform_load(plane, yl * W + xl) : 0.f, v_yX = (vyl && vxh) ? deform_load(plane, yl * W + xh) : 0.f;
-    const float v_Yx = (vyh && vxl) ? deform_load(plane, yh * W + xl) : 0.f, v_YX = (vyh && vxh) ? deform_load(plane, yh * W + xh) : 0.f;
+    const float v_yx = (vyl && vxl) ? Elem<E>::load(plane, yl * W + xl) : 0.f, v_yX = (vyl && vxh) ? Elem<E>::load(plane, yl * W + xh) : 0.f;
+    const float v_Yx = (vyh && vxl) ? Elem<E>::load(plane, yh * W + xl) : 0.f, v_YX = (vyh && vxh) ? Elem<E>::load(plane, yh * W + xh) : 0.f;
     const float dx = x - xf, dy = y - yf;
     return y_direction ? dx * (v_YX - v_yX) + (1.0f - dx) * (v_Yx - v_yx) : dy * (v_YX - v_Yx) + (1.0f - dy) * (v_yX - v_yx);
 }

@@ -30,7 +30,7 @@
 //            ascending order by the caller's accumulate flag.
 //
 // float16 / bfloat16 (the frcnn_ops_deform_*_16 entry points): the same kernels, templates over the storage type E of the tensors
-// (ops_deform.h widens on load, rounds once on store; dcol and the plan's weights stay float32), around gemm_nt16.hip's product of
+// (ops_elem.h widens on load, rounds once on store; dcol and the plan's weights stay float32), around gemm_nt16.hip's product of
 // 16-bit operands; see "the 16-bit operator" below for the operand layouts and include/frcnn_hip.h for the arithmetic contract.
 #include "ops_deform.h"
 
@@ -86,9 +86,9 @@ __device__ __forceinline__ void deform_read(const DeformGeom& g, const E* __rest
                                             size_t t, int p, int tap, float& y, float& x, float& m)
 {
     const int i = tap / g.kw, j = tap - i * g.kw, oy = p / g.ow, ox = p - oy * g.ow;
-    y = deform_coord(oy, g.sh, g.ph, i, g.dh, deform_load(offset, (2 * t) * g.P + p));
-    x = deform_coord(ox, g.sw, g.pw, j, g.dw, deform_load(offset, (2 * t + 1) * g.P + p));
-    m = mask ? deform_load(mask, t * g.P + p) : 1.0f;
+    y = deform_coord(oy, g.sh, g.ph, i, g.dh, Elem<E>::load(offset, (2 * t) * g.P + p));
+    x = deform_coord(ox, g.sw, g.pw, j, g.dw, Elem<E>::load(offset, (2 * t + 1) * g.P + p));
+    m = mask ? Elem<E>::load(mask, t * g.P + p) : 1.0f;
 }
 
 // the column value of input channel c, tap `tap`, image b of the chunk, output p: mask * bilinear sample, in float32
@@ -148,7 +148,7 @@ void deform_columns_nk_kernel(const E* __restrict__ x, const E* __restrict__ off
                 const int cl = kl / g.kk;
                 v = deform_column(g, x, offset, mask, b, w * cg + cl, kl - cl * g.kk, p);
             }
-            deform_round(v, r.e[j]);
+            round_to(v, r.e[j]);
         }
         *reinterpret_cast<u32x4*>(col + (size_t)n * groups * Kp + (size_t)run * 8) = r.v;
     }
@@ -527,14 +527,6 @@ static int deform16_backward_weight(int elem_type, const DeformGeom& d, const De
 
 using namespace frcnn;
 
-// the body of a 16-bit entry point by element-type code
-#define DF_DISPATCH_16(elem_type, E, call)                                                                    \
-    do {                                                                                                      \
-        if ((elem_type) == FRCNN_OPS_F16) { typedef deform_f16 E; return call; }                              \
-        if ((elem_type) == FRCNN_OPS_BF16) { typedef deform_bf16 E; return call; }                            \
-        return FRCNN_EINVAL;                                                                                  \
-    } while (0)
-
 extern "C" {
 
 size_t frcnn_ops_deform_workspace_bytes(const frcnn_deform_geom* g, int n_img, int stage)
@@ -658,10 +650,10 @@ int frcnn_ops_deform_forward_16(int elem_type, const frcnn_deform_geom* g, int n
     const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
     if (!d_x || !d_offset || !d_weight || !d_out || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
     if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_FORWARD)) return FRCNN_EINVAL;
-    DF_DISPATCH_16(elem_type, E, deform16_forward<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
-                                                     static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
-                                                     static_cast<const E*>(d_weight), static_cast<const E*>(d_bias), static_cast<E*>(d_out),
-                                                     static_cast<char*>(d_ws), (hipStream_t)stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform16_forward<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
+                                                        static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                        static_cast<const E*>(d_weight), static_cast<const E*>(d_bias), static_cast<E*>(d_out),
+                                                        static_cast<char*>(d_ws), (hipStream_t)stream));
 }
 
 int frcnn_ops_deform_backward_columns_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_weight, const void* d_dout,
@@ -672,32 +664,32 @@ int frcnn_ops_deform_backward_columns_16(int elem_type, const frcnn_deform_geom*
     const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
     if (!d_weight || !d_dout || !d_dcol || !aligned16(d_dcol) || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
     if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_BACKWARD_COLUMNS)) return FRCNN_EINVAL;
-    DF_DISPATCH_16(elem_type, E, deform16_backward_columns<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_weight),
-                                                              static_cast<const E*>(d_dout), d_dcol, static_cast<char*>(d_ws),
-                                                              (hipStream_t)stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform16_backward_columns<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_weight),
+                                                                 static_cast<const E*>(d_dout), d_dcol, static_cast<char*>(d_ws),
+                                                                 (hipStream_t)stream));
 }
 
 int frcnn_ops_deform_backward_offset_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
                                         const void* d_mask, const float* d_dcol, void* d_doffset, void* d_dmask, void* stream)
 {
-    DF_DISPATCH_16(elem_type, E, deform_backward_offset_impl<E>(g, n_img, 8, static_cast<const E*>(d_x), static_cast<const E*>(d_offset),
-                                                                static_cast<const E*>(d_mask), d_dcol, static_cast<E*>(d_doffset),
-                                                                static_cast<E*>(d_dmask), stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform_backward_offset_impl<E>(g, n_img, 8, static_cast<const E*>(d_x), static_cast<const E*>(d_offset),
+                                                                   static_cast<const E*>(d_mask), d_dcol, static_cast<E*>(d_doffset),
+                                                                   static_cast<E*>(d_dmask), stream));
 }
 
 int frcnn_ops_deform_input_plan_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_offset, const void* d_mask,
                                    int64_t* d_keys, float* d_weights, void* stream)
 {
-    DF_DISPATCH_16(elem_type, E, deform_input_plan_impl<E>(g, n_img, 8, static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
-                                                           d_keys, d_weights, stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform_input_plan_impl<E>(g, n_img, 8, static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                              d_keys, d_weights, stream));
 }
 
 int frcnn_ops_deform_backward_input_16(int elem_type, const frcnn_deform_geom* g, int n_img, const int64_t* d_sorted_keys,
                                        const int64_t* d_order, const float* d_weights, const float* d_dcol, void* d_dx, void* d_ws,
                                        size_t ws_bytes, void* stream)
 {
-    DF_DISPATCH_16(elem_type, E, deform_backward_input_impl<E>(g, n_img, 8, d_sorted_keys, d_order, d_weights, d_dcol,
-                                                               static_cast<E*>(d_dx), d_ws, ws_bytes, stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform_backward_input_impl<E>(g, n_img, 8, d_sorted_keys, d_order, d_weights, d_dcol,
+                                                                  static_cast<E*>(d_dx), d_ws, ws_bytes, stream));
 }
 
 int frcnn_ops_deform_backward_weight_16(int elem_type, const frcnn_deform_geom* g, int n_img, const void* d_x, const void* d_offset,
@@ -709,10 +701,10 @@ int frcnn_ops_deform_backward_weight_16(int elem_type, const frcnn_deform_geom* 
     const Deform16Sizes z = deform16_sizes(d, c_out, groups, n_img);
     if (!d_x || !d_offset || !d_dout || !d_dweight || !d_ws || !aligned16(d_ws)) return FRCNN_EINVAL;
     if (ws_bytes < deform16_workspace(d, z, n_img, FRCNN_DEFORM_WS_BACKWARD_WEIGHT)) return FRCNN_EINVAL;
-    DF_DISPATCH_16(elem_type, E, deform16_backward_weight<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
-                                                             static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
-                                                             static_cast<const E*>(d_dout), d_dweight, accumulate,
-                                                             static_cast<char*>(d_ws), (hipStream_t)stream));
+    OPS_ELEM_DISPATCH(elem_type, E, deform16_backward_weight<E>(elem_type, d, z, c_out, groups, n_img, static_cast<const E*>(d_x),
+                                                                static_cast<const E*>(d_offset), static_cast<const E*>(d_mask),
+                                                                static_cast<const E*>(d_dout), d_dweight, accumulate,
+                                                                static_cast<char*>(d_ws), (hipStream_t)stream));
 }
 
 }  // extern "C"

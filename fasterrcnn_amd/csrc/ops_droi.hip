@@ -24,9 +24,10 @@
 // ops.hip narrows its runs to 4; and a wave reads all out_h x out_w windows of every listed RoI, with no cut finer than the RoI's union.
 //
 // Element types: templates over the storage type E of maps, outputs and their gradients (float, float16, bfloat16): widened exactly on
-// load, geometry, weights and sums in float32 in one shared body, rounded once on store with ops.hip's roundings, so that
+// load, geometry, weights and sums in float32 in one shared body, rounded once on store (ops_elem.h), so that
 // op(x_T) == op(x_T.float()).to(T) bit for bit for the output and d_x.
 #include "ops_geom.h"
+#include "ops_elem.h"
 #include <climits>
 #include <cstdint>
 
@@ -41,57 +42,6 @@ static_assert(DROI_LIST >= 256, "a culling step of 256 RoIs must fit an empty li
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
-
-struct droi_f16 { _Float16 v; };
-struct droi_bf16 { unsigned short bits; };
-
-// DRun<E, N>: N consecutive channels of one pixel, in memory as E, in registers as float32: ops.hip's Run<E> with its roundings (float16
-// by the hardware conversion, bfloat16 by c10::BFloat16's integer rounding, every NaN 0x7FC0).  DWide<E>::V is the run of 16 bytes.
-template <typename E> struct DWide { static constexpr int V = 8; };
-template <> struct DWide<float> { static constexpr int V = 4; };
-template <typename E, int N> struct DRun;
-template <> struct DRun<float, 4> {
-    static constexpr int V = 4;
-    typedef f32x4 vec;
-    static __device__ __forceinline__ vec load(const float* p, size_t i) { return reinterpret_cast<const vec*>(p)[i]; }
-    static __device__ __forceinline__ void store(float* p, size_t i, vec v) { reinterpret_cast<vec*>(p)[i] = v; }
-};
-template <int N> struct DRun<droi_f16, N> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef _Float16 raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const droi_f16* p, size_t i)
-    {
-        return __builtin_convertvector(reinterpret_cast<const raw*>(p)[i], vec);
-    }
-    static __device__ __forceinline__ void store(droi_f16* p, size_t i, vec v)
-    {
-        reinterpret_cast<raw*>(p)[i] = __builtin_convertvector(v, raw);
-    }
-};
-template <int N> struct DRun<droi_bf16, N> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef unsigned short raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const droi_bf16* p, size_t i)
-    {
-        const raw u = reinterpret_cast<const raw*>(p)[i];
-        vec v;
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = __uint_as_float((unsigned)u[j] << 16);
-        return v;
-    }
-    static __device__ __forceinline__ void store(droi_bf16* p, size_t i, vec v)
-    {
-        raw u;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const unsigned b = __float_as_uint(v[j]);
-            u[j] = v[j] != v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-        }
-        reinterpret_cast<raw*>(p)[i] = u;
-    }
-};
 
 // ---- geometry ------------------------------------------------------------------------------------------------------------------------
 // the aligned RoIAlign plan of a RoI with the sizes that scale its offsets
@@ -149,7 +99,7 @@ void ops_droi_forward_kernel(const E* __restrict__ x, int n_img, int fh, int fw,
                              const float* __restrict__ offset, int out_h, int out_w, float scale, int sampling_ratio, float gamma,
                              E* __restrict__ out)
 {
-    typedef DRun<E, DWide<E>::V> R;
+    typedef ElemRun<E, ELEM_WIDE_RUN<E>> R;
     typedef typename R::vec vec;
     const int r = blockIdx.x, ph = blockIdx.y, C4 = C / R::V, bins = out_h * out_w;
     const float* roi = rois + (size_t)r * 5;
@@ -202,7 +152,7 @@ void ops_droi_offset_grad_kernel(const E* __restrict__ x, int n_img, int fh, int
                                  const float* __restrict__ offset, int k, int out_h, int out_w, float scale, int sampling_ratio,
                                  float gamma, const E* __restrict__ dout, float* __restrict__ doffset)
 {
-    typedef DRun<E, 4> R;                  // runs of 4 for every element type: the lanes' partial sums are those of the float32 kernel
+    typedef ElemRun<E, 4> R;               // runs of 4 for every element type: the lanes' partial sums are those of the float32 kernel
     typedef typename R::vec vec;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C4 = C / R::V, bins = out_h * out_w;
@@ -345,7 +295,7 @@ void ops_droi_input_grad_kernel(const float* __restrict__ rois, int k, int n_img
                                 int sampling_ratio, const i32x4* __restrict__ win, const int* __restrict__ rec,
                                 const f32x2* __restrict__ start, const E* __restrict__ dout, E* __restrict__ dx)
 {
-    typedef DRun<E, DWide<E>::V> R;
+    typedef ElemRun<E, ELEM_WIDE_RUN<E>> R;
     __shared__ int s_list[DROI_LIST];
     __shared__ int s_cnt[4];
     __shared__ int s_n;
@@ -418,7 +368,7 @@ template <typename E>
 static int droi_forward_impl(const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, const float* d_offset, int k,
                              int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma, void* d_out, void* stream)
 {
-    if (!droi_args_ok(n_img, fh, fw, c, k, out_h, out_w, sampling_ratio, DWide<E>::V)) return FRCNN_EINVAL;
+    if (!droi_args_ok(n_img, fh, fw, c, k, out_h, out_w, sampling_ratio, ELEM_WIDE_RUN<E>)) return FRCNN_EINVAL;
     if (k == 0) return FRCNN_OK;
     if (!d_x || !d_rois || !d_out) return FRCNN_EINVAL;
     hipLaunchKernelGGL(ops_droi_forward_kernel<E>, dim3(k, out_h), dim3(256), 0, (hipStream_t)stream, static_cast<const E*>(d_x), n_img,
@@ -431,7 +381,7 @@ static int droi_backward_impl(const void* d_x, const float* d_rois, const float*
                               int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma, const void* d_dout, void* d_dx,
                               float* d_doffset, void* d_ws, size_t ws_bytes, void* stream)
 {
-    if (!droi_args_ok(n_img, fh, fw, c, k, out_h, out_w, sampling_ratio, DWide<E>::V)) return FRCNN_EINVAL;
+    if (!droi_args_ok(n_img, fh, fw, c, k, out_h, out_w, sampling_ratio, ELEM_WIDE_RUN<E>)) return FRCNN_EINVAL;
     if (!d_dx && !d_doffset) return FRCNN_EINVAL;
     if (d_doffset && !d_offset) return FRCNN_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
@@ -457,9 +407,10 @@ static int droi_backward_impl(const void* d_x, const float* d_rois, const float*
                            sampling_ratio, gamma, win, rec, start);
         const int rc = check_launch();
         if (rc) return rc;
-        hipLaunchKernelGGL(ops_droi_input_grad_kernel<E>, dim3(cdiv(fw, DROI_TILE), cdiv(fh, DROI_TILE), n_img * cdiv(c / DWide<E>::V, 64)),
-                           dim3(256), 0, s, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, win, rec, start,
-                           static_cast<const E*>(d_dout), static_cast<E*>(d_dx));
+        hipLaunchKernelGGL(ops_droi_input_grad_kernel<E>,
+                           dim3(cdiv(fw, DROI_TILE), cdiv(fh, DROI_TILE), n_img * cdiv(c / ELEM_WIDE_RUN<E>, 64)), dim3(256), 0, s, d_rois, k,
+                           n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, win, rec, start, static_cast<const E*>(d_dout),
+                           static_cast<E*>(d_dx));
         return check_launch();
     }
     return FRCNN_OK;
@@ -468,14 +419,6 @@ static int droi_backward_impl(const void* d_x, const float* d_rois, const float*
 }  // namespace frcnn
 
 using namespace frcnn;
-
-// a 16-bit entry point's body by element-type code
-#define DROI_DISPATCH_16(elem_type, impl, ...)                                   \
-    do {                                                                         \
-        if ((elem_type) == FRCNN_OPS_F16) return impl<droi_f16>(__VA_ARGS__);    \
-        if ((elem_type) == FRCNN_OPS_BF16) return impl<droi_bf16>(__VA_ARGS__);  \
-        return FRCNN_EINVAL;                                                     \
-    } while (0)
 
 extern "C" {
 
@@ -507,8 +450,8 @@ int frcnn_ops_deform_roi_pool_16(int elem_type, const void* d_x, int n_img, int 
                                  const float* d_offset, int k, int out_h, int out_w, float spatial_scale, int sampling_ratio, float gamma,
                                  void* d_out, void* stream)
 {
-    DROI_DISPATCH_16(elem_type, droi_forward_impl, d_x, n_img, fh, fw, c, d_rois, d_offset, k, out_h, out_w, spatial_scale, sampling_ratio,
-                     gamma, d_out, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, droi_forward_impl<E>(d_x, n_img, fh, fw, c, d_rois, d_offset, k, out_h, out_w, spatial_scale,
+                                                         sampling_ratio, gamma, d_out, stream));
 }
 
 int frcnn_ops_deform_roi_pool_backward_16(int elem_type, const void* d_x, const float* d_rois, const float* d_offset, int k, int n_img,
@@ -516,8 +459,8 @@ int frcnn_ops_deform_roi_pool_backward_16(int elem_type, const void* d_x, const 
                                           float gamma, const void* d_dout, void* d_dx, float* d_doffset, void* d_ws, size_t ws_bytes,
                                           void* stream)
 {
-    DROI_DISPATCH_16(elem_type, droi_backward_impl, d_x, d_rois, d_offset, k, n_img, fh, fw, c, out_h, out_w, spatial_scale,
-                     sampling_ratio, gamma, d_dout, d_dx, d_doffset, d_ws, ws_bytes, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, droi_backward_impl<E>(d_x, d_rois, d_offset, k, n_img, fh, fw, c, out_h, out_w, spatial_scale,
+                                                          sampling_ratio, gamma, d_dout, d_dx, d_doffset, d_ws, ws_bytes, stream));
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // ops_msda.h -- what the channels-last deformable samplers share (ops_msda.hip: multi-scale deformable attention; ops_dcn.h: DCNv3 and
-// DCNv4):
-// the element types and their 16-byte runs, the lanes-along-channels mapping, and the sorted-plan gather of the value / input gradient.
+// DCNv4): the 16-byte runs of the element types (ops_elem.h), the lanes-along-channels mapping, and the sorted-plan gather of the
+// value / input gradient.
 #pragma once
-#include "common.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
@@ -15,15 +15,9 @@ static constexpr long long MSDA_MAX_SIDE = 1 << 24;      // H_l, W_l: exact in f
 static constexpr long long MSDA_MAX_INDEX = (long long)INT32_MAX - 1024;   // plan entries and cells of one call
 static constexpr int MSDA_MAX_BLOCKS = 16384;            // of the one-thread-per-element kernels: grid-stride beyond
 
-struct ms_f16 { _Float16 v; };
-struct ms_bf16 { unsigned short bits; };
-
 template <int R> struct MsVec { float v[R]; };
 
-template <typename E> struct MsElem;
-template <> struct MsElem<float> { static constexpr int RUN = 4; };
-template <> struct MsElem<ms_f16> { static constexpr int RUN = 8; };
-template <> struct MsElem<ms_bf16> { static constexpr int RUN = 8; };
+template <typename E> struct MsElem { static constexpr int RUN = ELEM_WIDE_RUN<E>; };
 
 // R consecutive channels from p (16-byte aligned when R > 1), widened exactly
 template <typename E, int R> __device__ __forceinline__ MsVec<R> ms_load(const E* p)
@@ -48,20 +42,12 @@ template <typename E, int R> __device__ __forceinline__ MsVec<R> ms_load(const E
             u[0] = *reinterpret_cast<const unsigned short*>(p);
         }
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-            if constexpr (__is_same(E, ms_f16)) {
-                _Float16 h;
-                __builtin_memcpy(&h, &u[j], 2);
-                r.v[j] = (float)h;
-            } else {
-                r.v[j] = __uint_as_float((unsigned)u[j] << 16);
-            }
-        }
+        for (int j = 0; j < R; ++j) r.v[j] = widen(__builtin_bit_cast(E, u[j]));
     }
     return r;
 }
 
-// one rounding to nearest even, NaN as Tensor.to(): float16 by the hardware conversion, bfloat16 by c10::BFloat16's integer rounding
+// rounded once (ops_elem.h)
 template <typename E, int R> __device__ __forceinline__ void ms_store(E* p, const MsVec<R>& a)
 {
     if constexpr (sizeof(E) == 4) {
@@ -74,15 +60,7 @@ template <typename E, int R> __device__ __forceinline__ void ms_store(E* p, cons
         typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
         unsigned short u[R];
 #pragma unroll
-        for (int j = 0; j < R; ++j) {
-            if constexpr (__is_same(E, ms_f16)) {
-                const _Float16 h = (_Float16)a.v[j];
-                __builtin_memcpy(&u[j], &h, 2);
-            } else {
-                const unsigned b = __float_as_uint(a.v[j]);
-                u[j] = a.v[j] != a.v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-            }
-        }
+        for (int j = 0; j < R; ++j) u[j] = __builtin_bit_cast(unsigned short, narrow<E>(a.v[j]));
         if constexpr (R == 8) {
             u16x8 t;
 #pragma unroll

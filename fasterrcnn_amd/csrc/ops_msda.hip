@@ -492,11 +492,8 @@ int msda_gather(int elem_type, const int64_t* sorted_keys, const int64_t* order,
     if (n_cells < 1 || n_entries < 1 || samples4 < 4 || d < 1 || d > MSDA_MAX_CHANNELS) return FRCNN_EINVAL;
     if (elem_type == 0)
         return msda_gather_impl<float>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
-    if (elem_type == FRCNN_OPS_F16)
-        return msda_gather_impl<ms_f16>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
-    if (elem_type == FRCNN_OPS_BF16)
-        return msda_gather_impl<ms_bf16>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream);
-    return FRCNN_EINVAL;
+    OPS_ELEM_DISPATCH(elem_type, E,
+                      msda_gather_impl<E>(sorted_keys, order, wts, dout, n_cells, n_entries, samples4, d, dvalue, ws, ws_bytes, stream));
 }
 
 static int msda_backward_value(int elem_type, const int64_t* sorted_keys, const int64_t* order, const float* wts, const void* dout,
@@ -513,14 +510,6 @@ static int msda_backward_value(int elem_type, const int64_t* sorted_keys, const 
 
 using namespace frcnn;
 
-// a 16-bit entry point's body by element-type code
-#define MSDA_DISPATCH_16(elem_type, impl, ...)                                 \
-    do {                                                                       \
-        if ((elem_type) == FRCNN_OPS_F16) return impl<ms_f16>(__VA_ARGS__);    \
-        if ((elem_type) == FRCNN_OPS_BF16) return impl<ms_bf16>(__VA_ARGS__);  \
-        return FRCNN_EINVAL;                                                   \
-    } while (0)
-
 extern "C" {
 
 int frcnn_ops_msda_max_levels(void) { return MSDA_MAX_LEVELS; }
@@ -531,7 +520,7 @@ int frcnn_ops_msda_block_items(int d, int levels, int points, int elem_type)
 {
     if (d < 1 || d > MSDA_MAX_CHANNELS || levels < 1 || levels > MSDA_MAX_LEVELS || points < 1 || points > MSDA_MAX_POINTS) return 0;
     if (elem_type != 0 && elem_type != FRCNN_OPS_F16 && elem_type != FRCNN_OPS_BF16) return 0;
-    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<ms_f16>::RUN;
+    const int run = elem_type == 0 ? MsElem<float>::RUN : MsElem<f16>::RUN;
     return ms_map(d, levels * points, run, d % run == 0).ipb;
 }
 
@@ -581,16 +570,16 @@ int frcnn_ops_msda_forward_16(int elem_type, const void* d_value, const int64_t*
                               const float* d_attn, int n_img, int s, int m, int d, int q, int levels, int points, void* d_out,
                               void* stream)
 {
-    MSDA_DISPATCH_16(elem_type, msda_forward_impl, d_value, d_shapes, d_starts, d_loc, d_attn, n_img, s, m, d, q, levels, points, d_out,
-                     stream);
+    OPS_ELEM_DISPATCH(elem_type, E, msda_forward_impl<E>(d_value, d_shapes, d_starts, d_loc, d_attn, n_img, s, m, d, q, levels, points,
+                                                         d_out, stream));
 }
 
 int frcnn_ops_msda_backward_loc_16(int elem_type, const void* d_value, const int64_t* d_shapes, const int64_t* d_starts,
                                    const float* d_loc, const float* d_attn, const void* d_dout, int n_img, int s, int m, int d, int q,
                                    int levels, int points, float* d_dloc, float* d_dattn, void* stream)
 {
-    MSDA_DISPATCH_16(elem_type, msda_backward_loc_impl, d_value, d_shapes, d_starts, d_loc, d_attn, d_dout, n_img, s, m, d, q, levels,
-                     points, d_dloc, d_dattn, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, msda_backward_loc_impl<E>(d_value, d_shapes, d_starts, d_loc, d_attn, d_dout, n_img, s, m, d, q,
+                                                              levels, points, d_dloc, d_dattn, stream));
 }
 
 int frcnn_ops_msda_backward_value_16(int elem_type, const int64_t* d_sorted_keys, const int64_t* d_order, const float* d_weights,

@@ -316,8 +316,7 @@ void ops_prroi_roi_reduce_kernel(const f32x4* __restrict__ part, int k, int bins
 // ---- the entry points' bodies, one per element type ---------------------------------------------------------------------------------
 // the element type walked in runs of 4 channels
 template <typename E> struct PrNarrow { typedef E type; };
-template <int N> struct PrNarrow<f16_t<N>> { typedef f16_t<4> type; };
-template <int N> struct PrNarrow<bf16_t<N>> { typedef bf16_t<4> type; };
+template <typename E, int N> struct PrNarrow<run_t<E, N>> { typedef run_t<E, 4> type; };
 
 // roi_align's limits (roi_args_ok), the gather grid's tile rows and the 32-bit (RoI, bin) indices
 static bool prroi_args_ok(int n_img, int fh, int fw, int c, int k, int out_h, int out_w, int v)
@@ -409,11 +408,8 @@ int frcnn_ops_prroi_pool_16(int elem_type, const void* d_x, int n_img, int fh, i
 {
     if (c % OPS_HALF_RUN != 0) return FRCNN_EINVAL;
     // the forward always walks runs of OPS_HALF_RUN: only those two kernels are built
-    if (elem_type == FRCNN_OPS_F16)
-        return prroi_forward_impl<f16_t<OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, stream);
-    if (elem_type == FRCNN_OPS_BF16)
-        return prroi_forward_impl<bf16_t<OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, stream);
-    return FRCNN_EINVAL;
+    OPS_ELEM_DISPATCH(elem_type, E, prroi_forward_impl<run_t<E, OPS_HALF_RUN>>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale,
+                                                                               d_out, stream));
 }
 
 int frcnn_ops_prroi_pool_backward_16(int elem_type, const void* d_x, const float* d_rois, int k, int n_img, int fh, int fw, int c,

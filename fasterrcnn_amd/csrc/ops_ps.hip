@@ -16,38 +16,17 @@
 // tests its cell against the listed windows -- a broadcast LDS read and four compares for the many bins that miss it -- and adds what
 // the few that hold it send, in ascending RoI order: bit-identical from run to run.  The sum stays in a register until it is stored once.
 //
-// Element types: templates over the storage type E of maps, outputs and gradients (float, float16, bfloat16); widened exactly on load,
-// geometry and sums in float32 in one shared body, rounded once to nearest even on store as Tensor.to() rounds, so that
-// op(x_T) == op(x_T.float()).to(T) bit for bit.  One element per lane: no constraint on C beyond C % (out_h out_w) == 0.
+// Element types: templates over the storage type E of maps, outputs and gradients (float, float16, bfloat16: ops_elem.h); widened
+// exactly on load, geometry and sums in float32 in one shared body, rounded once to nearest even on store as Tensor.to() rounds, so
+// that op(x_T) == op(x_T.float()).to(T) bit for bit.  One element per lane: no constraint on C beyond C % (out_h out_w) == 0.
 #include "ops_geom.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
 static constexpr int PS_MAX_OUT = 64;        // out_h, out_w <= 64
 static constexpr int PS_MAX_SAMPLING = 16;   // sampling_ratio <= 16
 static constexpr int PS_BLOCK = 256;
-
-struct ps_f16 { _Float16 v; };
-struct ps_bf16 { unsigned short bits; };
-
-// One element in memory as E, in registers as float32 (the scalar form of ops.hip's Run<E>, with its roundings).
-template <typename E> struct Elem;
-template <> struct Elem<float> {
-    static __device__ __forceinline__ float load(const float* p, size_t i) { return p[i]; }
-    static __device__ __forceinline__ void store(float* p, size_t i, float v) { p[i] = v; }
-};
-template <> struct Elem<ps_f16> {
-    static __device__ __forceinline__ float load(const ps_f16* p, size_t i) { return (float)p[i].v; }
-    static __device__ __forceinline__ void store(ps_f16* p, size_t i, float v) { p[i].v = (_Float16)v; }
-};
-template <> struct Elem<ps_bf16> {
-    static __device__ __forceinline__ float load(const ps_bf16* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
-    static __device__ __forceinline__ void store(ps_bf16* p, size_t i, float v)
-    {
-        const unsigned b = __float_as_uint(v);     // c10::BFloat16's rounding: every NaN becomes 0x7FC0
-        p[i].bits = v != v ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-    }
-};
 
 // ---- geometry ------------------------------------------------------------------------------------------------------------------------
 // ps_roi_align's plan: roi_align's aligned plan with torchvision's count = grid_h * grid_w for this operator, which has no lower bound
@@ -334,14 +313,6 @@ static int ps_roi_align_backward_impl(const float* d_rois, int k, int n_img, int
 
 using namespace frcnn;
 
-// a 16-bit entry point's body by element-type code
-#define PS_DISPATCH_16(elem_type, impl, ...)                                   \
-    do {                                                                       \
-        if ((elem_type) == FRCNN_OPS_F16) return impl<ps_f16>(__VA_ARGS__);    \
-        if ((elem_type) == FRCNN_OPS_BF16) return impl<ps_bf16>(__VA_ARGS__);  \
-        return FRCNN_EINVAL;                                                   \
-    } while (0)
-
 extern "C" {
 
 int frcnn_ops_ps_roi_pool(const float* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h, int out_w,
@@ -371,27 +342,28 @@ int frcnn_ops_ps_roi_align_backward(const float* d_rois, int k, int n_img, int f
 int frcnn_ops_ps_roi_pool_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
                              int out_w, float spatial_scale, void* d_out, void* stream)
 {
-    PS_DISPATCH_16(elem_type, ps_roi_pool_impl, d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, ps_roi_pool_impl<E>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, d_out, stream));
 }
 
 int frcnn_ops_ps_roi_pool_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
                                       float spatial_scale, const void* d_dout, void* d_dx, void* stream)
 {
-    PS_DISPATCH_16(elem_type, ps_roi_pool_backward_impl, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_dout, d_dx, stream);
+    OPS_ELEM_DISPATCH(elem_type, E,
+                      ps_roi_pool_backward_impl<E>(d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, d_dout, d_dx, stream));
 }
 
 int frcnn_ops_ps_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
                               int out_w, float spatial_scale, int sampling_ratio, void* d_out, void* stream)
 {
-    PS_DISPATCH_16(elem_type, ps_roi_align_impl, d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, sampling_ratio, d_out,
-                   stream);
+    OPS_ELEM_DISPATCH(elem_type, E, ps_roi_align_impl<E>(d_x, n_img, fh, fw, c, d_rois, k, out_h, out_w, spatial_scale, sampling_ratio,
+                                                         d_out, stream));
 }
 
 int frcnn_ops_ps_roi_align_backward_16(int elem_type, const float* d_rois, int k, int n_img, int fh, int fw, int c, int out_h, int out_w,
                                        float spatial_scale, int sampling_ratio, const void* d_dout, void* d_dx, void* stream)
 {
-    PS_DISPATCH_16(elem_type, ps_roi_align_backward_impl, d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio, d_dout,
-                   d_dx, stream);
+    OPS_ELEM_DISPATCH(elem_type, E, ps_roi_align_backward_impl<E>(d_rois, k, n_img, fh, fw, c, out_h, out_w, spatial_scale, sampling_ratio,
+                                                                  d_dout, d_dx, stream));
 }
 
 }  // extern "C"

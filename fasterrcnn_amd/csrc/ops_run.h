@@ -1,8 +1,9 @@
-// ops_run.h -- what the RoI and NMS kernels of fasterrcnn_amd.ops share across files (ops.hip, ops_rot.hip): the limits, the storage
-// types Run<E> of maps and gradients, the ordered culling of the backward gathers, the entry points' argument checks and 16-bit
-// dispatch, and the launcher of the greedy NMS pass.
+// ops_run.h -- what the RoI and NMS kernels of fasterrcnn_amd.ops share across files (ops.hip, ops_rot.hip): the limits, the runs
+// Run<E> of maps and gradients (ops_elem.h's), the ordered culling of the backward gathers, the entry points' argument checks and
+// 16-bit dispatch, and the launcher of the greedy NMS pass.
 #pragma once
 #include "ops_geom.h"
+#include "ops_elem.h"
 
 namespace frcnn {
 
@@ -17,67 +18,18 @@ static constexpr int OPS_NMS_MAX_WORDS = 8192;   // removed-bits of one segment 
 static constexpr int OPS_MS_MAX_LEVELS = 8;  // multi-scale RoIAlign: feature maps per call
 
 // ---- storage types --------------------------------------------------------------------------------------------------------------
-// 16-bit elements carry the width N of a lane's run in their type, so that one tensor can be walked in runs of 8 or of 4 channels
-template <int N> struct f16_t { _Float16 v; };
-template <int N> struct bf16_t { unsigned short bits; };
+// A 16-bit element carries the width N of a lane's run in its type, so that one tensor can be walked in runs of 8 or of 4 channels
+template <typename E, int N> struct run_t : E {};
 
 // 16-bit channels per lane.  8 = 16 B per load and store, as a float quad: measured faster than 4 in every forward kernel and in the
 // backward kernels once C / 8 fills a wave (C >= 512).  Below that a backward block, whose lanes are the channel runs of one cell,
 // would idle half of each wave: there the gather walks the same tensors in runs of 4 (C = 256: 7 % faster forward + backward).
 static constexpr int OPS_HALF_RUN = 8, OPS_HALF_RUN_NARROW = 4;
 
-// Run<E>: V consecutive channels of one pixel, in memory as E, in registers as float32 (vec).  load widens exactly; store rounds to
-// nearest even once, NaN and infinities as torch's Tensor.to(): float16 by the hardware conversion (v_cvt_f16_f32), bfloat16 by the
-// integer rounding of c10::BFloat16 (every NaN becomes 0x7FC0 there, which the packed hardware conversion would not give).
+// Run<E>: V consecutive channels of one pixel, in memory as E, in registers as float32 (vec): ops_elem.h's run and its roundings
 template <typename E> struct Run;
-template <> struct Run<float> {
-    static constexpr int V = 4;
-    typedef f32x4 vec;
-    typedef int ivec __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ vec load(const float* p, size_t i) { return reinterpret_cast<const vec*>(p)[i]; }
-    static __device__ __forceinline__ void store(float* p, size_t i, vec v) { reinterpret_cast<vec*>(p)[i] = v; }
-    static __device__ __forceinline__ float at(const float* p, size_t i) { return p[i]; }      // one element, widened
-};
-template <int N> struct Run<f16_t<N>> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef int ivec __attribute__((ext_vector_type(N)));
-    typedef _Float16 raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const f16_t<N>* p, size_t i)
-    {
-        return __builtin_convertvector(reinterpret_cast<const raw*>(p)[i], vec);
-    }
-    static __device__ __forceinline__ void store(f16_t<N>* p, size_t i, vec v)
-    {
-        reinterpret_cast<raw*>(p)[i] = __builtin_convertvector(v, raw);
-    }
-    static __device__ __forceinline__ float at(const f16_t<N>* p, size_t i) { return (float)p[i].v; }
-};
-template <int N> struct Run<bf16_t<N>> {
-    static constexpr int V = N;
-    typedef float vec __attribute__((ext_vector_type(N)));
-    typedef int ivec __attribute__((ext_vector_type(N)));
-    typedef unsigned short raw __attribute__((ext_vector_type(N)));
-    static __device__ __forceinline__ vec load(const bf16_t<N>* p, size_t i)
-    {
-        const raw u = reinterpret_cast<const raw*>(p)[i];
-        vec v;
-#pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = __uint_as_float((unsigned)u[j] << 16);
-        return v;
-    }
-    static __device__ __forceinline__ void store(bf16_t<N>* p, size_t i, vec v)
-    {
-        raw u;
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const unsigned b = __float_as_uint(v[j]);
-            u[j] = v[j] != v[j] ? (unsigned short)0x7FC0 : (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-        }
-        reinterpret_cast<raw*>(p)[i] = u;
-    }
-    static __device__ __forceinline__ float at(const bf16_t<N>* p, size_t i) { return __uint_as_float((unsigned)p[i].bits << 16); }
-};
+template <> struct Run<float> : ElemRun<float, 4> {};
+template <typename E, int N> struct Run<run_t<E, N>> : ElemRun<E, N> {};
 
 template <typename E> __device__ __forceinline__ void zero_row(E* orow, int n)
 {
@@ -129,13 +81,10 @@ int launch_ops_nms_reduce(const u64* mask, const int64_t* order, const int64_t* 
 }  // namespace frcnn
 
 // A 16-bit entry point's body by element-type code, in runs of `run` channels; c must hold whole runs of OPS_HALF_RUN either way.
-#define OPS_DISPATCH_16(elem_type, c, run, impl, ...)                                        \
-    do {                                                                                     \
-        if ((c) % OPS_HALF_RUN != 0) return FRCNN_EINVAL;                                    \
-        const bool wide = (run) == OPS_HALF_RUN;                                             \
-        if ((elem_type) == FRCNN_OPS_F16)                                                    \
-            return wide ? impl<f16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<f16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__);   \
-        if ((elem_type) == FRCNN_OPS_BF16)                                                   \
-            return wide ? impl<bf16_t<OPS_HALF_RUN>>(__VA_ARGS__) : impl<bf16_t<OPS_HALF_RUN_NARROW>>(__VA_ARGS__); \
-        return FRCNN_EINVAL;                                                                 \
+#define OPS_DISPATCH_16(elem_type, c, run, impl, ...)                                                                         \
+    do {                                                                                                                      \
+        if ((c) % OPS_HALF_RUN != 0) return FRCNN_EINVAL;                                                                     \
+        const bool wide = (run) == OPS_HALF_RUN;                                                                              \
+        OPS_ELEM_DISPATCH(elem_type, E_, wide ? impl<run_t<E_, OPS_HALF_RUN>>(__VA_ARGS__)                                    \
+                                              : impl<run_t<E_, OPS_HALF_RUN_NARROW>>(__VA_ARGS__));                           \
     } while (0)

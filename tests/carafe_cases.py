@@ -15,6 +15,7 @@ d_features on (|grad|, |m|) with n = k k s s.  Where S is 0 (a tap outside the m
 is O(1) and lands orders of magnitude outside.  The bound assumes no underflow: the one case with denormal inputs draws masks and
 gradients from powers of two >= 1, so every product is exact and only additions round (an addition never underflows inexactly)."""
 import functools
+from fractions import Fraction
 
 import torch
 import torch.nn.functional as F
@@ -177,3 +178,63 @@ def reference(name):
     out = carafe_ref(x, m, k, G, s)
     dx, dm = gradients(carafe_ref, x, m, grad, k, G, s)
     return (out, dx, dm), bounds(x, m, grad, k, G, s)
+
+
+# ---- float16 ties of the forward ------------------------------------------------------------------------------------------------------
+# The contract rounds twice: the float32 sum, then once to float16.  A conversion fused with the last multiply-add (v_fma_mixlo_f16)
+# rounds the exact value of acc + x m once instead, and the two part ways where the float32 sum is a float16 midpoint.  One image, one
+# channel, one group, s = 1 and a k x k map: output pixel (r, r) sees map cell (i, j) at tap (i, j), and the kernel adds the taps in
+# row-major order, (k - 1, k - 1) last (ops_carafe_kernel: acc = fmaf(w[i P + j], m[i k + j], acc), i outer, j inner).  Taps 0 and 1
+# make acc a float16 midpoint that float32 holds exactly; the last tap adds a quarter of a float32 ulp, 2**-12 * 2**-13 = 2**-25, on
+# either side; every other tap is 0 * 0.  k = 1 has no such case: the product of two float16 values has 22 significant bits at the most
+# and is exact in float32, so both roundings see the same value.  d_features and d_masks are not built: neither kernel's device code
+# held a fused conversion.
+# name: ((x, mask) of tap 0, of tap 1, of the last tap, the float16 result)
+TIES = {
+    "down": ((1.0, 1.0), (2.0 ** -11, 1.0), (2.0 ** -12, 2.0 ** -13), 1.0),                   # 1 + 2**-11 (+ 2**-25): even is 1
+    "down-negative": ((1.0, -1.0), (2.0 ** -11, -1.0), (2.0 ** -12, -(2.0 ** -13)), -1.0),
+    "up": ((1.0, 1.0), (3 * 2.0 ** -11, 1.0), (2.0 ** -12, -(2.0 ** -13)), 1.0 + 2.0 ** -9),   # 1 + 3 2**-11 (- 2**-25): even is 1 + 2**-9
+}
+TIE_KERNELS = (3, 5, 7)
+
+
+def round_exact(v, bits, emin):
+    """The Fraction v rounded to the nearest binary floating-point value of `bits` significant bits and least normal exponent emin,
+    ties to even, as a Fraction (no overflow: the values here are near 1)."""
+    if v == 0:
+        return v
+    e = emin
+    while abs(v) >= Fraction(2) ** (e + 1):
+        e += 1
+    while e > emin and abs(v) < Fraction(2) ** e:
+        e -= 1
+    ulp = Fraction(2) ** (e - bits + 1)
+    q = v / ulp
+    n = q.numerator // q.denominator                                         # floor
+    rest = q - n
+    if rest > Fraction(1, 2) or (rest == Fraction(1, 2) and n % 2 == 1):
+        n += 1
+    return n * ulp
+
+
+@functools.lru_cache(maxsize=None)
+def tie_case(name, k):
+    """(features, masks, want) of a tie: float16 CPU tensors [1, 1, k, k] and [1, k k, k, k] (every pixel has the same masks) and the
+    float16 value of output pixel (r, r).  Checked here in exact arithmetic: the kernel's float32 chain followed by one rounding gives
+    `want`, the rounding of the exact last step gives the other neighbour.  Cached: do not modify."""
+    first, second, last, want = TIES[name]
+    taps = {0: first, 1: second, k * k - 1: last}
+    x = torch.zeros((1, 1, k, k), dtype=torch.float16)
+    m = torch.zeros((1, k * k, k, k), dtype=torch.float16)
+    for t, (xv, mv) in taps.items():
+        x[0, 0, t // k, t % k], m[0, t] = xv, mv
+        assert float(x[0, 0, t // k, t % k]) == xv and float(m[0, t, 0, 0]) == mv, "the inputs are float16 values"
+    acc = fused = Fraction(0)
+    for t in range(k * k):
+        xv, mv = taps.get(t, (0.0, 0.0))
+        fused = round_exact(acc + Fraction(xv) * Fraction(mv), 11, -14)        # the exact fmaf rounded straight to float16
+        acc = round_exact(acc + Fraction(xv) * Fraction(mv), 24, -126)         # fmaf: one float32 rounding
+    two_step = round_exact(acc, 11, -14)
+    assert two_step == Fraction(want) and fused != two_step, (name, k, float(two_step), float(fused))
+    assert abs(fused - two_step) == Fraction(2) ** -10, "the other float16 neighbour of the midpoint"
+    return x, m, want

@@ -137,6 +137,22 @@ def test_16_bit_tensors_equal_the_float32_operator_rounded_once(name, dtype):
     assert float(got[0].float().abs().max()) > 0.1
 
 
+@pytest.mark.parametrize("k", K.TIE_KERNELS)
+@pytest.mark.parametrize("name", list(K.TIES))
+def test_float16_forward_rounds_the_float32_sum_at_a_tie(name, k):
+    """tests/carafe_cases.py: the float32 sum of pixel (r, r) is a float16 midpoint and the exact sum lies a quarter of a float32 ulp
+    off it.  Rounding the float32 sum gives the even neighbour, `want`; a conversion fused with the last multiply-add gives the other
+    one (a library with that fusion returned 1 + 2**-10 for down and up and -(1 + 2**-10) for down-negative, at every k)."""
+    x, m, want = K.tie_case(name, k)
+    r = (k - 1) // 2
+    got = ops.carafe(x.to(DEV), m.to(DEV), k, 1, 1)
+    rounded = ops.carafe(x.float().to(DEV), m.float().to(DEV), k, 1, 1).to(torch.float16)
+    values = "pixel (r, r) %r, float32 operator rounded %r, want %r" % (float(got[0, 0, r, r]), float(rounded[0, 0, r, r]), want)
+    assert got.dtype == torch.float16 and got.shape == (1, 1, k, k)
+    assert torch.equal(got, rounded), values
+    assert float(got[0, 0, r, r]) == want, values
+
+
 # ---- 4. layouts and empty inputs ---------------------------------------------------------------------------------------------------------------
 def test_layouts_give_the_same_bits_and_gradients_keep_their_format():
     for name in ("x-channels-last", "m-channels-last"):
