@@ -77,6 +77,8 @@ SYMBOLS = (
     "frcnn_ops_roi_align_rotated_backward", "frcnn_ops_roi_align_rotated_16", "frcnn_ops_roi_align_rotated_backward_16",
     "frcnn_ops_diff_iou_rotated", "frcnn_ops_diff_iou_rotated_backward",
     "frcnn_ops_convex_iou_tile_rows", "frcnn_ops_convex_iou", "frcnn_ops_convex_giou", "frcnn_ops_min_area_polygons",
+    "frcnn_ops_box_iou_quadri_tile_rows", "frcnn_ops_points_in_polygons_tile_rows", "frcnn_ops_quadri_max_rows", "frcnn_ops_quadri_max_columns",
+    "frcnn_ops_box_iou_quadri", "frcnn_ops_nms_quadri", "frcnn_ops_points_in_polygons",
     "frcnn_ops_soft_nms_block_threads", "frcnn_ops_soft_nms_lds_boxes", "frcnn_ops_soft_nms_max_boxes", "frcnn_ops_soft_nms_workspace_bytes",
     "frcnn_ops_soft_nms",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
@@ -353,6 +355,14 @@ _SIGNATURES = {
     "frcnn_ops_convex_iou": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp]),
     "frcnn_ops_convex_giou": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frcnn_ops_min_area_polygons": (C.c_int, [_vp, _i, _vp, _vp]),
+    # the quadrilateral operators (csrc/ops_quadri.hip): frcnn_ops_box_iou_rotated's and frcnn_ops_nms_rotated's arguments on rows of 8 floats
+    "frcnn_ops_box_iou_quadri_tile_rows": (C.c_int, []),
+    "frcnn_ops_points_in_polygons_tile_rows": (C.c_int, []),
+    "frcnn_ops_quadri_max_rows": (C.c_int, []),
+    "frcnn_ops_quadri_max_columns": (C.c_int, []),
+    "frcnn_ops_box_iou_quadri": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "frcnn_ops_nms_quadri": (C.c_int, [_vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "frcnn_ops_points_in_polygons": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp]),
     # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
     "frcnn_ops_soft_nms_block_threads": (C.c_int, []),
     "frcnn_ops_soft_nms_lds_boxes": (C.c_int, []),

@@ -1,4 +1,4 @@
-// ops_run.h -- what the RoI and NMS kernels of fasterrcnn_amd.ops share across files (ops.hip, ops_rot.hip): the limits, the runs
+// ops_run.h -- what the RoI and NMS kernels of fasterrcnn_amd.ops share across files (ops.hip, ops_rot.hip, ops_quadri.hip): the limits, the runs
 // Run<E> of maps and gradients (ops_elem.h's), the ordered culling of the backward gathers, the entry points' argument checks and
 // 16-bit dispatch, and the launcher of the greedy NMS pass.
 #pragma once
@@ -73,7 +73,7 @@ static inline bool roi_args_ok(int n_img, int fh, int fw, int c, int k, int out_
 }
 
 // the run of a backward gather over c channels: the wide one when its runs fill the 64 lanes that share a cell
-static int backward_run(int c) { return c / OPS_HALF_RUN >= 64 ? OPS_HALF_RUN : OPS_HALF_RUN_NARROW; }
+static inline int backward_run(int c) { return c / OPS_HALF_RUN >= 64 ? OPS_HALF_RUN : OPS_HALF_RUN_NARROW; }
 
 // ops.hip: ops_nms_reduce_kernel on a mask of 64 x 64 bit tiles (ops_nms_mask_kernel's layout; nw = ceil(n / 64) words per row)
 int launch_ops_nms_reduce(const u64* mask, const int64_t* order, const int64_t* cats, int n, int nw, uint8_t* keep, hipStream_t s);

@@ -18,6 +18,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import rotated_feature_align, RotatedFeatureAlign, rotated_feature_align_pytorch
     from fasterrcnn_amd.ops import convex_iou, convex_giou, min_area_polygons
     from fasterrcnn_amd.ops import convex_iou_pytorch, convex_giou_pytorch, min_area_polygons_pytorch
+    from fasterrcnn_amd.ops import box_iou_quadri, nms_quadri, points_in_polygons, box_iou_quadri_pytorch, points_in_polygons_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -406,6 +407,34 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       forms are the same contract from torch operations (hull edges by the all-pairs left-of test, areas by the boundary sum over the
       clipped edge pieces), on any device, float32 or float64, convex_giou_pytorch's gradient from autograd; they serve point sets in
       GENERAL POSITION only: no duplicate points, no three collinear hull points, no coincident edges.
+  box_iou_quadri(bboxes1, bboxes2, mode="iou", aligned=False) -> float32 [N, M], or [N] when aligned
+  nms_quadri(dets, scores, iou_threshold, labels=None) -> (dets [K, 9], keep int64 [K])
+  points_in_polygons(points, polygons) -> float32 [N, M]
+  box_iou_quadri_pytorch(bboxes1, bboxes2, mode="iou", aligned=False), points_in_polygons_pytorch(points, polygons)
+      The quadrilateral operators of the heads that predict four free corners and of the point-set assigners (csrc/ops_quadri.hip, on
+      the device functions of convex_iou; mmcv has operators of these names and signatures, the contract is include/frcnn_hip.h's).
+      Everything is float32.  A quadrilateral is a row (x1, y1, ..., x4, y4): four vertices in ANY order and either winding, and it
+      stands for Q, the convex hull of its vertices under convex_iou's hull rules, so permuting the four vertices changes no bit of any
+      result.  A non-convex or self-crossing row therefore counts as its hull: the one deliberate deviation from mmcv, whose kernels walk
+      the vertices in the order given; for a convex quadrilateral given in order, which is every use in mmrotate, the two agree.  A row
+      with a non-finite coordinate is dead, and so is a quadrilateral whose hull area is below 1e-14 (CONVEX_MIN_AREA).
+      box_iou_quadri: A1, A2 the hull areas, I the area of hull 1 clipped against hull 2's half-planes (Sutherland-Hodgman, a vertex on
+      the line inside) on coordinates relative to hull 2's smallest vertex, clamped at 0; mode "iou" is I / (A1 + A2 - I), "iof" is I /
+      A1; exactly 0 for a dead row or a denominator below 1e-14, and without a clip when the bounding boxes are apart; a live
+      quadrilateral against its own bits gives exactly 1 in both modes; aligned=True needs N == M and gives the matrix's diagonal bit
+      for bit.  In mode "iou" the result has the bits of convex_iou(s, bboxes2), s[i] being bboxes1[i]'s four vertices followed by five
+      copies of the first.  A workgroup forms each hull of its QUADRI_IOU_TILE_ROWS x 64 tile once.  nms_quadri: nms_rotated on
+      quadrilaterals -- the same ordering (stable descending scores, NaN scores last), labels, bit mask and greedy pass; sorted
+      quadrilateral j goes iff a kept quadrilateral i before it, of the same label, has box_iou_quadri(i, j) > float32(iou_threshold);
+      dets is cat(dets[keep], scores[keep, None]).  N <= MAX_NMS_BOXES.  points_in_polygons: 1.0 when point i [N, 2] lies in the CLOSED
+      hull Q_j of polygon j [M, 8] -- for every hull edge a -> b, (b_x - a_x) (p_y - a_y) >= (b_y - a_y) (p_x - a_x) on coordinates
+      relative to Q_j's smallest vertex, the two rounded products compared --, else 0.0; 0.0 for a dead polygon and a non-finite point.
+      A point on an edge or a vertex is inside (mmcv's crossing-number loop is half-open on the boundary instead).  A workgroup owns
+      POINTS_IN_POLYGONS_TILE_ROWS points x 64 polygons.  None is differentiable (inputs are detached; mmcv has no autograd either).
+      Empty inputs give empty outputs without a launch; rows <= MAX_QUADRI_ROWS, columns of a matrix <= MAX_QUADRI_COLUMNS.  Other
+      dtypes are a TypeError, CPU tensors, other shapes and differing devices a ValueError.  The _pytorch forms are the same contract
+      from torch operations (convex_iou_pytorch's hull list and boundary sum), on any device, float32 or float64, for quadrilaterals in
+      GENERAL POSITION only: no duplicate vertices, no three collinear vertices, no coincident edges, no point on an edge's line.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -439,7 +468,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "dcnv3", "DCNv3Function", "dcnv3_core_pytorch", "DCNv3", "dcnv4", "DCNv4Function", "dcnv4_core_pytorch", "DCNv4",
            "border_align", "BorderAlign", "border_align_pytorch", "riroi_align_rotated", "RiRoIAlignRotated",
            "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch",
-           "convex_iou", "convex_giou", "min_area_polygons", "convex_iou_pytorch", "convex_giou_pytorch", "min_area_polygons_pytorch"]
+           "convex_iou", "convex_giou", "min_area_polygons", "convex_iou_pytorch", "convex_giou_pytorch", "min_area_polygons_pytorch",
+           "box_iou_quadri", "nms_quadri", "points_in_polygons", "box_iou_quadri_pytorch", "points_in_polygons_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -454,6 +484,10 @@ MAX_CONVEX_ROWS = 2 ** 31 - 1 - 1024      # point sets of one call (CVX_MAX_ROWS
 CONVEX_IOU_TILE_ROWS = 32                 # rows of convex_iou's tile (CVX_TILE_ROWS of csrc/ops_convex.hip); its columns: 64
 CONVEX_MIN_AREA = 1e-14                   # below it a polygon, a union or an enclosing hull is dead (CVX_MIN_AREA)
 CONVEX_RECT_TIE = 1 - 2.0 ** -18          # min_area_polygons: a later edge wins only with an area below this times the best (CVX_RECT_TIE)
+MAX_QUADRI_ROWS = 2 ** 31 - 1 - 1024      # quadrilaterals or points of one call (frcnn_ops_quadri_max_rows: the grids' ceilings are formed in int)
+MAX_QUADRI_COLUMNS = 65535 * 64           # columns of box_iou_quadri's and points_in_polygons' matrix (frcnn_ops_quadri_max_columns)
+QUADRI_IOU_TILE_ROWS = 32                 # rows of box_iou_quadri's tile (QUAD_TILE_ROWS of csrc/ops_quadri.hip); its columns: 64
+POINTS_IN_POLYGONS_TILE_ROWS = 256        # points of points_in_polygons' tile (QUAD_POINT_ROWS of csrc/ops_quadri.hip); its columns: 64
 MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
                                           # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
                                           # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
@@ -1375,9 +1409,9 @@ def _score_order(scores):
     return order[torch.sort(nan[order].to(torch.uint8), stable=True).indices]
 
 
-def _nms(boxes, scores, idxs, iou_threshold, rotated=False):
-    """The kept indices of greedy NMS, within each category of idxs when given: the sorting and merging around frcnn_ops_nms, or around
-    frcnn_ops_nms_rotated on boxes in the kernels' (clockwise) convention."""
+def _nms(boxes, scores, idxs, iou_threshold, rotated=False, quadri=False):
+    """The kept indices of greedy NMS, within each category of idxs when given: the sorting and merging around frcnn_ops_nms, around
+    frcnn_ops_nms_rotated on boxes in the kernels' (clockwise) convention, or around frcnn_ops_nms_quadri on rows of 8 floats."""
     n = boxes.shape[0]
     if n == 0:
         return torch.empty((0,), dtype=torch.int64, device=boxes.device)
@@ -1395,6 +1429,8 @@ def _nms(boxes, scores, idxs, iou_threshold, rotated=False):
                 _stream(boxes))
         if rotated:
             nv.check(lib.frcnn_ops_nms_rotated(b.data_ptr(), *tail), "frcnn_ops_nms_rotated")
+        elif quadri:
+            nv.check(lib.frcnn_ops_nms_quadri(b.data_ptr(), *tail), "frcnn_ops_nms_quadri")
         else:
             nv.check(lib.frcnn_ops_nms(b.data_ptr(), int(b.dtype == torch.float64), *tail), "frcnn_ops_nms")
         kept = order[keep.bool()]
@@ -2530,21 +2566,27 @@ def diff_iou_rotated_2d_pytorch(box1, box2):
     return torch.where(valid, iou, zero).view(box1.shape[:-1])
 
 
+def _nms_scores_labels(op, name, boxes, scores, labels):
+    """The checks nms_rotated and nms_quadri share once their boxes (`name`) are checked: float32 scores [N], at most MAX_NMS_BOXES
+    boxes, integer labels [N] or None, one device."""
+    _check_tensor("scores", scores, (torch.float32,), "float32")
+    _check_same_device(boxes, scores, name, "scores")
+    if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
+        raise ValueError("scores must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(scores.shape)))
+    if boxes.shape[0] > MAX_NMS_BOXES:
+        raise ValueError("%s takes at most %d boxes, got %d" % (op, MAX_NMS_BOXES, boxes.shape[0]))
+    if labels is not None:
+        _check_tensor("labels", labels, (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8), "an integer tensor")
+        _check_same_device(boxes, labels, name, "labels")
+        if labels.dim() != 1 or labels.shape[0] != boxes.shape[0]:
+            raise ValueError("labels must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(labels.shape)))
+
+
 def nms_rotated(boxes, scores, iou_threshold, labels=None, clockwise=True):
     """mmcv.ops.nms_rotated: greedy NMS on box_iou_rotated, within each label when labels are given.  Returns (dets [K, 6] =
     cat(boxes[keep], scores[keep, None]), keep int64 [K]), by descending score, ties by ascending index."""
     b = _rotated_boxes("boxes", boxes, clockwise)
-    _check_tensor("scores", scores, (torch.float32,), "float32")
-    _check_same_device(boxes, scores, "boxes", "scores")
-    if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:
-        raise ValueError("scores must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(scores.shape)))
-    if boxes.shape[0] > MAX_NMS_BOXES:
-        raise ValueError("nms_rotated takes at most %d boxes, got %d" % (MAX_NMS_BOXES, boxes.shape[0]))
-    if labels is not None:
-        _check_tensor("labels", labels, (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8), "an integer tensor")
-        _check_same_device(boxes, labels, "boxes", "labels")
-        if labels.dim() != 1 or labels.shape[0] != boxes.shape[0]:
-            raise ValueError("labels must be [N] with N = %d, got shape %s" % (boxes.shape[0], tuple(labels.shape)))
+    _nms_scores_labels("nms_rotated", "boxes", boxes, scores, labels)
     keep = _nms_rotated_op(b.detach(), scores.detach(), labels, float(iou_threshold))
     return torch.cat([boxes[keep], scores[keep, None]], dim=1), keep
 
@@ -4068,3 +4110,165 @@ def min_area_polygons_pytorch(pointsets):
         c0, c1 = a + u0 * ub, a + u1 * ub
         out = torch.stack([c0, c1, c1 + v1 * left, c0 + v1 * left], 1) + origin
         return torch.where(ok[:, None], out.reshape(n, 8), torch.zeros_like(pointsets[:, :8]))
+
+
+# ---- quadrilateral operators: box_iou_quadri, nms_quadri, points_in_polygons (csrc/ops_quadri.hip) ------------------------------------
+@torch.library.custom_op("frcnn::box_iou_quadri", mutates_args=())
+def _box_iou_quadri(bboxes1: Tensor, bboxes2: Tensor, mode: int, aligned: bool) -> Tensor:
+    n, m = bboxes1.shape[0], bboxes2.shape[0]
+    out = torch.empty((n,) if aligned else (n, m), dtype=torch.float32, device=bboxes1.device)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(bboxes1.device):
+        a, b = bboxes1.contiguous(), bboxes2.contiguous()
+        nv.check(nv.lib().frcnn_ops_box_iou_quadri(a.data_ptr(), n, b.data_ptr(), m, mode, int(aligned), out.data_ptr(), _stream(bboxes1)),
+                 "frcnn_ops_box_iou_quadri")
+    return out
+
+
+@_box_iou_quadri.register_fake
+def _(bboxes1, bboxes2, mode, aligned):
+    n, m = bboxes1.shape[0], bboxes2.shape[0]
+    return bboxes1.new_empty((n,) if aligned else (n, m), dtype=torch.float32)
+
+
+@torch.library.custom_op("frcnn::nms_quadri", mutates_args=())
+def _nms_quadri_op(dets: Tensor, scores: Tensor, labels: Optional[Tensor], iou_threshold: float) -> Tensor:
+    """The kept indices."""
+    return _nms(dets, scores, labels, iou_threshold, quadri=True)
+
+
+@_nms_quadri_op.register_fake
+def _(dets, scores, labels, iou_threshold):
+    return _nms_fake_result(dets)
+
+
+@torch.library.custom_op("frcnn::points_in_polygons", mutates_args=())
+def _points_in_polygons(points: Tensor, polygons: Tensor) -> Tensor:
+    n, m = points.shape[0], polygons.shape[0]
+    out = points.new_empty((n, m))
+    if n == 0 or m == 0:
+        return out
+    with torch.cuda.device(points.device):
+        a, b = points.contiguous(), polygons.contiguous()
+        nv.check(nv.lib().frcnn_ops_points_in_polygons(a.data_ptr(), n, b.data_ptr(), m, out.data_ptr(), _stream(points)),
+                 "frcnn_ops_points_in_polygons")
+    return out
+
+
+@_points_in_polygons.register_fake
+def _(points, polygons):
+    return points.new_empty((points.shape[0], polygons.shape[0]))
+
+
+_QUADRI_ROW, _POINT_ROW = "(x1, y1, ..., x4, y4)", "(x, y)"
+
+
+def _quadri_input(name, t, width, row, fallback=None):
+    _check_tensor(name, t, (torch.float32,), "float32 (the quadrilateral operators are float32 only: pass .float())", fallback)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError("%s must be [N, %d] %s, got shape %s" % (name, width, row, tuple(t.shape)))
+    if t.shape[0] > MAX_QUADRI_ROWS:
+        raise ValueError("%s holds at most MAX_QUADRI_ROWS = %d rows, got %d" % (name, MAX_QUADRI_ROWS, t.shape[0]))
+
+
+def _quadri_mode(mode, bboxes1, bboxes2, aligned):
+    if mode not in ("iou", "iof"):
+        raise ValueError("mode must be 'iou' or 'iof', got %r" % (mode,))
+    if aligned and bboxes1.shape[0] != bboxes2.shape[0]:
+        raise ValueError("aligned=True needs bboxes1 and bboxes2 of one length, got %d and %d" % (bboxes1.shape[0], bboxes2.shape[0]))
+
+
+def box_iou_quadri(bboxes1, bboxes2, mode="iou", aligned=False):
+    """mmcv.ops.box_iou_quadri: the IoU (or, mode="iof", the intersection over the first one's area) of quadrilaterals [N, 8] and [M, 8]
+    (x1, y1, ..., x4, y4): float32 [N, M], or [N] when aligned.  A row stands for the convex hull of its four vertices, in any order
+    (the module docstring states the contract).  No autograd."""
+    _quadri_input("bboxes1", bboxes1, 8, _QUADRI_ROW, "box_iou_quadri_pytorch")
+    _quadri_input("bboxes2", bboxes2, 8, _QUADRI_ROW, "box_iou_quadri_pytorch")
+    _quadri_mode(mode, bboxes1, bboxes2, aligned)
+    _check_same_device(bboxes1, bboxes2, "bboxes1", "bboxes2")
+    if not aligned and bboxes2.shape[0] > MAX_QUADRI_COLUMNS:
+        raise ValueError("bboxes2 holds at most MAX_QUADRI_COLUMNS = %d rows, got %d" % (MAX_QUADRI_COLUMNS, bboxes2.shape[0]))
+    return _box_iou_quadri(bboxes1.detach(), bboxes2.detach(), int(mode == "iof"), bool(aligned))
+
+
+def nms_quadri(dets, scores, iou_threshold, labels=None):
+    """mmcv.ops.nms_quadri: greedy NMS on box_iou_quadri, within each label when labels are given.  dets [N, 8] quadrilaterals, scores
+    [N].  Returns (dets [K, 9] = cat(dets[keep], scores[keep, None]), keep int64 [K]), by descending score, ties by ascending index,
+    NaN scores last (nms_rotated's rules)."""
+    _quadri_input("dets", dets, 8, _QUADRI_ROW)
+    _nms_scores_labels("nms_quadri", "dets", dets, scores, labels)
+    keep = _nms_quadri_op(dets.detach(), scores.detach(), labels, float(iou_threshold))
+    return torch.cat([dets[keep], scores[keep, None]], dim=1), keep
+
+
+def points_in_polygons(points, polygons):
+    """mmcv.ops.points_in_polygons: float32 [N, M], 1.0 where point i of points [N, 2] lies in the closed convex hull of polygon j of
+    polygons [M, 8] (x1, y1, ..., x4, y4; vertices in any order), else 0.0 (the module docstring states the contract).  No autograd."""
+    _quadri_input("points", points, 2, _POINT_ROW, "points_in_polygons_pytorch")
+    _quadri_input("polygons", polygons, 8, _QUADRI_ROW, "points_in_polygons_pytorch")
+    _check_same_device(points, polygons, "points", "polygons")
+    if polygons.shape[0] > MAX_QUADRI_COLUMNS:
+        raise ValueError("polygons holds at most MAX_QUADRI_COLUMNS = %d rows, got %d" % (MAX_QUADRI_COLUMNS, polygons.shape[0]))
+    return _points_in_polygons(points.detach(), polygons.detach())
+
+
+def _quadri_hulls(quads):
+    """quads [n, 8] -> (the hull lists [n, 4, 2] of _convex_hull_list, their areas on coordinates relative to the smallest vertex, the
+    mask of the live rows)."""
+    ok = _convex_finite(quads)
+    hull = _convex_hull_list(torch.where(ok[:, None], quads, torch.zeros_like(quads)).view(-1, 4, 2))
+    area = _convex_list_area(hull - hull[:, :1])
+    return hull, area, ok & (area >= CONVEX_MIN_AREA)
+
+
+def box_iou_quadri_pytorch(bboxes1, bboxes2, mode="iou", aligned=False):
+    """box_iou_quadri from torch operations, on any device, float32 or float64 -> [N, M], or [N] when aligned: convex_iou_pytorch's
+    hull list and boundary sum, so it serves quadrilaterals in GENERAL POSITION only: no duplicate vertices, no three collinear
+    vertices, no edge of one on an edge of the other.  Not fast: rows go through in chunks."""
+    _convex_pytorch_input("bboxes1", bboxes1, 8, _QUADRI_ROW)
+    _convex_pytorch_input("bboxes2", bboxes2, 8, _QUADRI_ROW)
+    _quadri_mode(mode, bboxes1, bboxes2, aligned)
+    n, m = bboxes1.shape[0], bboxes2.shape[0]
+    out = bboxes1.new_zeros((n,) if aligned else (n, m))
+    if out.numel() == 0:
+        return out
+    with torch.no_grad():
+        q, aq, okq = _quadri_hulls(bboxes2.detach().to(bboxes1.dtype))
+        origin = q[:, :1]
+        q = q - origin
+        for i0 in range(0, n, 1024):
+            p, ap, okp = _quadri_hulls(bboxes1[i0:i0 + 1024].detach())
+            if aligned:
+                chunk = slice(i0, i0 + 1024)
+                inter, a1, a2, ok = _convex_inter(p - origin[chunk], q[chunk]), ap, aq[chunk], okp & okq[chunk]
+            else:
+                inter, a1, a2, ok = _convex_inter(p[:, None] - origin[None], q[None]), ap[:, None], aq[None], okp[:, None] & okq[None]
+            den = a1.expand_as(inter) if mode == "iof" else a1 + a2 - inter
+            ok = ok & (den >= CONVEX_MIN_AREA)
+            out[i0:i0 + 1024] = torch.where(ok, inter / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+    return out
+
+
+def points_in_polygons_pytorch(points, polygons):
+    """points_in_polygons from torch operations, on any device, float32 or float64 -> [N, M]: the hull list of convex_iou_pytorch and
+    the closed left-of test of every hull edge, so it serves polygons in GENERAL POSITION only: no duplicate vertices, no three
+    collinear vertices."""
+    _convex_pytorch_input("points", points, 2, _POINT_ROW)
+    _convex_pytorch_input("polygons", polygons, 8, _QUADRI_ROW)
+    n, m = points.shape[0], polygons.shape[0]
+    out = points.new_zeros((n, m))
+    if n == 0 or m == 0:
+        return out
+    with torch.no_grad():
+        q, _, okq = _quadri_hulls(polygons.detach().to(points.dtype))
+        origin = q[:, 0]
+        a = q - origin[:, None]                                                        # [m, 4, 2]; the repeated start: an edge of length zero
+        e = torch.roll(a, -1, 1) - a
+        for i0 in range(0, n, 4096):
+            pts = points[i0:i0 + 4096].detach()
+            okp = _convex_finite(pts)
+            d = torch.where(okp[:, None], pts, torch.zeros_like(pts))[:, None, None, :] - origin[None, :, None, :] - a[None]     # [n, m, 4, 2]
+            inside = (e[None, ..., 0] * d[..., 1] >= e[None, ..., 1] * d[..., 0]).all(-1)
+            out[i0:i0 + 4096] = (inside & okp[:, None] & okq[None]).to(out.dtype)
+    return out

@@ -96,7 +96,10 @@ extern "C" {
                                  still 21 (additions only): the frcnn_ops_deform_*_16 forms (deformable convolution on float16 / bfloat16 tensors,
                                  its products on the 16-bit matrix pipe);
                                  still 21 (no prototype or struct changed): frcnn_detections returns the documented FRCNN_EUNSUPPORTED for images past
-                                 the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before) */
+                                 the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before);
+                                 still 21 (additions only): frcnn_ops_box_iou_quadri, frcnn_ops_nms_quadri, frcnn_ops_points_in_polygons and the
+                                 frcnn_ops_box_iou_quadri_tile_rows / frcnn_ops_points_in_polygons_tile_rows / frcnn_ops_quadri_max_rows /
+                                 _max_columns getters (the quadrilateral operators: mmcv's box_iou_quadri, nms_quadri and points_in_polygons) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -1021,6 +1024,51 @@ int frcnn_ops_convex_iou_tile_rows(void);
 int frcnn_ops_convex_iou(const float* d_pointsets, int n, const float* d_polygons, int k, float* d_out, void* stream);
 int frcnn_ops_convex_giou(const float* d_pointsets, const float* d_polygons, int n, float* d_giou, float* d_grad, void* stream);
 int frcnn_ops_min_area_polygons(const float* d_pointsets, int n, float* d_out, void* stream);
+
+/* box_iou_quadri, nms_quadri and points_in_polygons, the quadrilateral operators of the heads that predict four free corners and of the
+ *   point-set assigners (csrc/ops_quadri.hip, on the device functions of csrc/ops_convex.h).  mmcv has operators of these names (third
+ *   party, absent here); this text is the contract and holds where mmcv's kernels deviate from it.  Everything is float32.
+ * The quadrilateral.  A row of 8 floats (x1, y1, ..., x4, y4): four vertices in ANY order and either winding.  It stands for Q, the
+ *   convex hull of its four vertices under the hull rules stated above for convex_iou: strictly convex vertices, counter-clockwise from
+ *   the smallest (x, y); of equal points the smallest index; a turn decided by comparing the two rounded products of its cross product,
+ *   formed relative to the quadrilateral's own smallest point.  Permuting the four vertices changes no bit of any result.  A non-convex
+ *   or self-crossing row therefore counts as its hull: THE ONE DELIBERATE DEVIATION from mmcv, whose kernels walk the vertices in the
+ *   order given.  For a convex quadrilateral given in order -- every use in mmrotate -- the two definitions agree.
+ * Dead rows.  A row with a coordinate that is not finite is dead; so is a quadrilateral whose hull area is below 1e-14.
+ * frcnn_ops_box_iou_quadri: A1, A2 are the hull areas (the fan from the first hull vertex, on coordinates relative to the row's own
+ *   smallest point); I is the area of hull 1 clipped against hull 2's half-planes (Sutherland-Hodgman, a vertex on the line counts as
+ *   inside, at most 8 vertices), formed on coordinates relative to hull 2's smallest vertex and clamped at 0 from below.
+ *   mode 0: I / (A1 + A2 - I);  mode 1 (iof): I / A1.  A pair is exactly 0 when either row is dead or the denominator is below 1e-14; a
+ *   pair whose axis-aligned bounding boxes are apart is 0 without a clip.  A live quadrilateral against its own bits gives exactly 1 in
+ *   both modes.  aligned == 0: d_out[n][m]; one launch, a workgroup owns frcnn_ops_box_iou_quadri_tile_rows() rows x 64 columns and
+ *   forms the hull of each of its rows and columns once, in LDS.  aligned != 0 needs n == m and writes d_out[n], one lane per pair,
+ *   bit-identical to the matrix's diagonal.  Consequence of the shared arithmetic: in mode 0, for a live row a[i],
+ *   box_iou_quadri(a, b)[i][j] has the bits of convex_iou(s, b)[i][j], where s[i] is a[i]'s four vertices followed by five copies of
+ *   its first vertex.
+ * frcnn_ops_nms_quadri: frcnn_ops_nms_rotated on rows of 8 floats -- the same arguments, the same workspace
+ *   (frcnn_ops_nms_workspace_bytes(n)), the same 64 x 64 bit tiles, tile skipping and greedy pass.  Sorted quadrilateral j goes iff a
+ *   kept quadrilateral i before it, of the same category, has IoU(i, j) > iou_threshold; that IoU has the value and the argument order
+ *   of frcnn_ops_box_iou_quadri mode 0 (quads1 = i, quads2 = j), from the same device function.
+ * frcnn_ops_points_in_polygons: d_points[n][2], d_polygons[m][8], d_out[n][m].  d_out[i][j] = 1.0f when point i lies in the CLOSED hull
+ *   Q_j: for every hull edge a -> b, (b_x - a_x) (p_y - a_y) >= (b_y - a_y) (p_x - a_x), every difference formed on coordinates
+ *   relative to Q_j's smallest vertex and the two rounded products compared; otherwise 0.0f.  0.0f for a dead polygon and for a point
+ *   with a coordinate that is not finite.  A point on an edge or on a vertex is inside, as a vertex on the line is in the clip; mmcv's
+ *   crossing-number loop is half-open on the boundary instead.  One launch; a workgroup owns
+ *   frcnn_ops_points_in_polygons_tile_rows() points x 64 polygons and forms each polygon's hull once.
+ * No vertex list lives in scratch memory (LDS columns, one per lane); no atomics; every output element is written once; two runs agree
+ *   bit for bit.  Arguments are validated before the GPU is touched (FRCNN_EINVAL): negative counts, more than
+ *   frcnn_ops_quadri_max_rows() rows (2^31 - 1 - 1024: the grids' ceilings are formed in int), more than
+ *   frcnn_ops_quadri_max_columns() (65535 * 64) columns of a matrix, mode outside {0, 1}, aligned with n != m, more boxes than
+ *   frcnn_ops_nms takes, a workspace that is too small, NULL pointers with non-zero counts.  n == 0 (or m == 0) returns FRCNN_OK
+ *   without a launch. */
+int frcnn_ops_box_iou_quadri_tile_rows(void);
+int frcnn_ops_points_in_polygons_tile_rows(void);
+int frcnn_ops_quadri_max_rows(void);
+int frcnn_ops_quadri_max_columns(void);
+int frcnn_ops_box_iou_quadri(const float* d_quads1, int n, const float* d_quads2, int m, int mode, int aligned, float* d_out, void* stream);
+int frcnn_ops_nms_quadri(const float* d_quads, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
+                         uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
+int frcnn_ops_points_in_polygons(const float* d_points, int n, const float* d_polygons, int m, float* d_out, void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

@@ -98,6 +98,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     pairs, forward and forward + backward (the loss), and ops.min_area_polygons of the 20000 sets, each beside its _pytorch
     composition on the same GPU, in alternating windows.  Informational: no speed bound is set.
 
+  * quadri: the quadrilateral operators on a 1024 x 1024 image, float32: ops.box_iou_quadri of 20000 quadrilaterals against 64 (the
+    assigner: half of them lie around one of the 64, half anywhere), ops.nms_quadri of 4096 clustered quadrilaterals at threshold 0.1
+    with and without 15 labels, and ops.points_in_polygons of 20000 points against 64 polygons, each beside its _pytorch composition on
+    the same GPU (for NMS: ops.box_iou_quadri_pytorch's matrix, then a greedy pass on the host).  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only quadri          # just the quadrilateral leg
     python tools/ops_bench.py --only convex          # just the point-set leg
     python tools/ops_bench.py --only rfa             # just the rotated_feature_align leg
     python tools/ops_bench.py --only riroi           # just the RiRoIAlignRotated leg
@@ -709,6 +715,78 @@ def convex_leg(rng, reps, warmup):
     return {"convex float32 (microseconds)": res}
 
 
+def quadri_leg(rng, reps, warmup):
+    import time
+    n, k, boxes, n_labels, thr = 20000, 64, 4096, 15, 0.1
+
+    def rot(a):
+        return np.stack([np.stack([np.cos(a), -np.sin(a)], -1), np.stack([np.sin(a), np.cos(a)], -1)], -2)
+
+    def quads(c, wh, a):
+        corners = (np.array([[-.5, -.5], [.5, -.5], [.5, .5], [-.5, .5]])[None] + rng.uniform(-0.15, 0.15, (c.shape[0], 4, 2))) * wh[:, None]
+        return (np.einsum("nij,nkj->nki", rot(a), corners) + c[:, None]).reshape(-1, 8)
+
+    to = lambda v: torch.from_numpy(v.astype(np.float32)).to(DEV)     # noqa: E731
+    c, wh, a = rng.uniform(0, 1024, (k, 2)), np.exp(rng.uniform(np.log(16), np.log(256), (k, 2))), rng.uniform(-np.pi / 2, np.pi / 2, k)
+    gts = to(quads(c, wh, a))
+    pick = np.arange(n) % k
+    around = (np.arange(n) % 2 == 0)[:, None]
+    cs = np.where(around, c[pick] + rng.uniform(-0.3, 0.3, (n, 2)) * wh[pick], rng.uniform(0, 1024, (n, 2)))
+    rows = to(quads(cs, wh[pick] * np.exp(rng.uniform(-0.3, 0.3, (n, 1))), a[pick] + rng.uniform(-0.3, 0.3, n)))
+    points = to(np.where(around, c[pick] + np.einsum("nij,nj->ni", rot(a[pick]), rng.uniform(-0.8, 0.8, (n, 2)) * wh[pick]),
+                         rng.uniform(0, 1024, (n, 2))))
+    groups = boxes // 8                                                        # clusters of eight around one base quadrilateral
+    gc, gwh, ga = rng.uniform(0, 1024, (groups, 2)), np.exp(rng.uniform(np.log(16), np.log(128), (groups, 2))), rng.uniform(-np.pi / 2, np.pi / 2, groups)
+    g = np.arange(boxes) % groups
+    dets = to(quads(gc[g] + rng.uniform(-0.3, 0.3, (boxes, 2)) * gwh[g], gwh[g] * np.exp(rng.uniform(-0.3, 0.3, (boxes, 1))),
+                    ga[g] + rng.uniform(-0.3, 0.3, boxes)))
+    scores = to(rng.uniform(0.02, 1.0, boxes))
+    labels = torch.from_numpy(rng.randint(0, n_labels, boxes)).to(DEV)
+
+    def composed_nms(lab):
+        """The IoU matrix of the composition, then the greedy pass on the host; the kept indices."""
+        order = torch.sort(scores, descending=True, stable=True).indices
+        d = dets[order]
+        over = ops.box_iou_quadri_pytorch(d, d) > thr
+        if lab is not None:
+            over &= lab[order][:, None] == lab[order][None, :]
+        over = over.cpu().numpy()
+        gone = np.zeros(boxes, dtype=bool)
+        kept = []
+        for i in range(boxes):
+            if not gone[i]:
+                kept.append(i)
+                gone[i + 1:] |= over[i, i + 1:]
+        return order[torch.tensor(kept, device=DEV)]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    iou, iou_c = ops.box_iou_quadri(rows, gts), ops.box_iou_quadri_pytorch(rows, gts)
+    hit, hit_c = ops.points_in_polygons(points, gts), ops.points_in_polygons_pytorch(points, gts)
+    res = {"max |box_iou_quadri - composition|": float((iou - iou_c).abs().max()), "share of pairs with IoU > 0": float((iou > 0).float().mean()),
+           "points_in_polygons: pairs that differ from the composition": int((hit != hit_c).sum()), "share of pairs inside": float(hit.mean())}
+    for name, native, comp in (
+            ("box_iou_quadri %d x %d" % (n, k), lambda: ops.box_iou_quadri(rows, gts), lambda: ops.box_iou_quadri_pytorch(rows, gts)),
+            ("points_in_polygons %d x %d" % (n, k), lambda: ops.points_in_polygons(points, gts), lambda: ops.points_in_polygons_pytorch(points, gts))):
+        t_native, t_comp = timed_pair(native, comp, reps, warmup)
+        res[name] = {"ops": round(t_native, 1), "_pytorch composition": round(t_comp, 1), "composition / ops": round(t_comp / t_native, 2)}
+    for name, lab in (("nms_quadri %d, thr %s" % (boxes, thr), None), ("nms_quadri %d, thr %s, %d labels" % (boxes, thr, n_labels), labels)):
+        keep = ops.nms_quadri(dets, scores, thr, lab)[1]
+        keep_c = composed_nms(lab)
+        t_native = timed(lambda: ops.nms_quadri(dets, scores, thr, lab), reps, warmup)
+        t_comp = float(np.median([wall(lambda: composed_nms(lab)) for _ in range(3)]))
+        res[name] = {"kept": int(keep.numel()), "kept by the composition": int(keep_c.numel()),
+                     "kept by both": int(np.intersect1d(keep.cpu().numpy(), keep_c.cpu().numpy()).size),
+                     "ops": round(t_native, 1), "matrix composition + host greedy pass": round(t_comp, 1),
+                     "composition / ops": round(t_comp / t_native, 2)}
+    return {"quadri float32 (microseconds)": res}
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -792,7 +870,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -849,6 +927,9 @@ def main():
         return
     if a.only == "convex":
         print(json.dumps(convex_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "quadri":
+        print(json.dumps(quadri_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -924,6 +1005,7 @@ def main():
     res.update(riroi_leg(rng, 5, 2))
     res.update(rfa_leg(rng, 5, 2))
     res.update(convex_leg(rng, 5, 2))
+    res.update(quadri_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
