@@ -79,6 +79,8 @@ SYMBOLS = (
     "frcnn_ops_convex_iou_tile_rows", "frcnn_ops_convex_iou", "frcnn_ops_convex_giou", "frcnn_ops_min_area_polygons",
     "frcnn_ops_box_iou_quadri_tile_rows", "frcnn_ops_points_in_polygons_tile_rows", "frcnn_ops_quadri_max_rows", "frcnn_ops_quadri_max_columns",
     "frcnn_ops_box_iou_quadri", "frcnn_ops_nms_quadri", "frcnn_ops_points_in_polygons",
+    "frcnn_ops_masked_conv2d_tile_pixels", "frcnn_ops_masked_conv2d_tile_channels", "frcnn_ops_masked_conv2d_k_chunk",
+    "frcnn_ops_masked_conv2d_max_index", "frcnn_ops_masked_conv2d_workspace_bytes", "frcnn_ops_masked_conv2d",
     "frcnn_ops_soft_nms_block_threads", "frcnn_ops_soft_nms_lds_boxes", "frcnn_ops_soft_nms_max_boxes", "frcnn_ops_soft_nms_workspace_bytes",
     "frcnn_ops_soft_nms",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
@@ -170,6 +172,7 @@ MAX_PRE_NMS = 16384         # frcnn_ctx pre_cap (csrc/api.hip): one-block radix 
 # FRCNN_DEFORM_WS_*: the stage whose workspace frcnn_ops_deform_workspace_bytes sizes (DEFORM_WS_COLUMNS: the column matrix itself)
 DEFORM_WS_FORWARD, DEFORM_WS_BACKWARD_COLUMNS, DEFORM_WS_BACKWARD_INPUT, DEFORM_WS_BACKWARD_WEIGHT, DEFORM_WS_COLUMNS = range(5)
 OPS_F16, OPS_BF16 = 1, 2     # FRCNN_OPS_F16 / FRCNN_OPS_BF16: element type of the frcnn_ops_*_16 entry points
+OPS_F32 = 0                  # FRCNN_OPS_F32: float32 where one entry point serves all three element types (frcnn_ops_masked_conv2d)
 MATH_F32 = 0      # exact f32 MFMA
 MATH_F32_WINOGRAD = 2   # exact f32 MFMA; 3x3 layers with uses_winograd(cin, cout) as Winograd F(2x2,3x3) in float32
 MATH_MODES = {"f32": MATH_F32, "f32_winograd": MATH_F32_WINOGRAD}     # (1 was the direct f32x6 convolution of round 2: removed, ABI 13)
@@ -363,6 +366,14 @@ _SIGNATURES = {
     "frcnn_ops_box_iou_quadri": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "frcnn_ops_nms_quadri": (C.c_int, [_vp, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "frcnn_ops_points_in_polygons": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp]),
+    # masked_conv2d (csrc/ops_mconv.hip): elem_type, input, its 4 strides (a host int64 array), n, c_in, h, w, weight, bias, c_out, kh, kw,
+    # pad_h, pad_w, the uint8 mask, output, its 4 strides, workspace, its bytes, stream
+    "frcnn_ops_masked_conv2d_tile_pixels": (C.c_int, []),
+    "frcnn_ops_masked_conv2d_tile_channels": (C.c_int, []),
+    "frcnn_ops_masked_conv2d_k_chunk": (C.c_int, []),
+    "frcnn_ops_masked_conv2d_max_index": (C.c_int, []),
+    "frcnn_ops_masked_conv2d_workspace_bytes": (_sz, [_i, _i, _i]),
+    "frcnn_ops_masked_conv2d": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
     "frcnn_ops_soft_nms_block_threads": (C.c_int, []),
     "frcnn_ops_soft_nms_lds_boxes": (C.c_int, []),

@@ -19,6 +19,7 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import convex_iou, convex_giou, min_area_polygons
     from fasterrcnn_amd.ops import convex_iou_pytorch, convex_giou_pytorch, min_area_polygons_pytorch
     from fasterrcnn_amd.ops import box_iou_quadri, nms_quadri, points_in_polygons, box_iou_quadri_pytorch, points_in_polygons_pytorch
+    from fasterrcnn_amd.ops import masked_conv2d, MaskedConv2d, masked_conv2d_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -435,6 +436,31 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       dtypes are a TypeError, CPU tensors, other shapes and differing devices a ValueError.  The _pytorch forms are the same contract
       from torch operations (convex_iou_pytorch's hull list and boundary sum), on any device, float32 or float64, for quadrilaterals in
       GENERAL POSITION only: no duplicate vertices, no three collinear vertices, no coincident edges, no point on an edge's line.
+  masked_conv2d(features, mask, weight, bias, padding=0, stride=1) -> [N, C_out, oh, ow]
+  MaskedConv2d(in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True).forward(input, mask=None)
+  masked_conv2d_pytorch(features, mask, weight, bias, padding=0, stride=1)
+      The sparse convolution of Guided Anchoring's heads (GA-RPN, GA-Faster R-CNN, GA-RetinaNet evaluate conv_cls and conv_reg only
+      where the location map passed its threshold; csrc/ops_mconv.hip; mmcv has operators of these names and signatures, the contract
+      is include/frcnn_hip.h's).  features [N, C_in, H, W], weight [C_out, C_in, kh, kw] and bias [C_out] (or None: a zero bias) are
+      all float32, all float16 or all bfloat16; every mix is a TypeError.  padding is an int or a pair, stride must be 1 (mmcv's rule;
+      else ValueError).  mask [N, oh, ow] lies on the OUTPUT grid oh = H + 2 pad_h - kh + 1, ow = W + 2 pad_w - kw + 1, in any real
+      dtype or bool; a pixel is active iff mask > 0, so NaN is inactive.  At an active pixel out[b, co, y, x] = bias[co] + sum over (c,
+      i, j) of weight[co, c, i, j] features[b, c, y - pad_h + i, x - pad_w + j], taps outside the map counting as zero; everywhere
+      else out is +0.0, without the bias.  The sum runs in float32 in ascending (c, i, j) -- on the exact-float32 matrix instruction,
+      or for 16-bit tensors on the 16-bit one with float32 accumulators, bias added in float32, one rounding on the store -- in an
+      order that depends on (C_in, kh, kw) alone: an active pixel's bits do not depend on the rest of the mask, on N, or on the memory
+      format.  The output has the features' dtype and memory format; NCHW-contiguous and channels_last maps are read in place, any
+      other layout is made contiguous first.  A compaction kernel lists the active pixels on the device and a fused gather-and-
+      multiply kernel works through tiles of MASKED_CONV_TILE_PIXELS listed pixels x MASKED_CONV_TILE_CHANNELS channels in chunks of
+      MASKED_CONV_K_CHUNK reduction indices; its grid holds the worst case and surplus blocks return at once, so the active count
+      never reaches the host: no host synchronisation anywhere in the call.  Deviations from mmcv, all deliberate: N >= 1 (mmcv
+      asserts 1), the mask on the output grid (mmcv asserts the map's size and scatters out of bounds when they differ), bias=None
+      allowed, MaskedConv2d.forward with a mask and dilation != 1 or groups != 1 a ValueError (mmcv ignores the dilation).  Inference
+      only, like mmcv (whose backward returns None for every input): no autograd formula is registered, so a backward through the op
+      raises torch's not-implemented error.  MaskedConv2d is an nn.Conv2d -- parameters weight and bias, so mmdet checkpoints load
+      strict --; without a mask it is nn.Conv2d.forward and trains.  Sizes up to MAX_MASKED_CONV_INDEX (N oh ow, C_out C_in kh kw and
+      each tensor's elements).  masked_conv2d_pytorch keeps the same contract from torch operations (mmcv's nonzero / gather / addmm /
+      scatter composition, one image at a time, which synchronises on a GPU), on any device, float64 too.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -469,7 +495,8 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "border_align", "BorderAlign", "border_align_pytorch", "riroi_align_rotated", "RiRoIAlignRotated",
            "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch",
            "convex_iou", "convex_giou", "min_area_polygons", "convex_iou_pytorch", "convex_giou_pytorch", "min_area_polygons_pytorch",
-           "box_iou_quadri", "nms_quadri", "points_in_polygons", "box_iou_quadri_pytorch", "points_in_polygons_pytorch"]
+           "box_iou_quadri", "nms_quadri", "points_in_polygons", "box_iou_quadri_pytorch", "points_in_polygons_pytorch",
+           "masked_conv2d", "MaskedConv2d", "masked_conv2d_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -488,6 +515,10 @@ MAX_QUADRI_ROWS = 2 ** 31 - 1 - 1024      # quadrilaterals or points of one call
 MAX_QUADRI_COLUMNS = 65535 * 64           # columns of box_iou_quadri's and points_in_polygons' matrix (frcnn_ops_quadri_max_columns)
 QUADRI_IOU_TILE_ROWS = 32                 # rows of box_iou_quadri's tile (QUAD_TILE_ROWS of csrc/ops_quadri.hip); its columns: 64
 POINTS_IN_POLYGONS_TILE_ROWS = 256        # points of points_in_polygons' tile (QUAD_POINT_ROWS of csrc/ops_quadri.hip); its columns: 64
+MASKED_CONV_TILE_PIXELS = 64              # listed pixels of masked_conv2d's tile (frcnn_ops_masked_conv2d_tile_pixels(): MC_T of csrc/ops_mconv.hip)
+MASKED_CONV_TILE_CHANNELS = 64            # output channels of that tile (frcnn_ops_masked_conv2d_tile_channels())
+MASKED_CONV_K_CHUNK = 32                  # reduction indices (c, i, j) of one of its LDS stages (frcnn_ops_masked_conv2d_k_chunk())
+MAX_MASKED_CONV_INDEX = 2 ** 31 - 1 - 1024    # what its 32-bit indices hold: N oh ow, C_out C_in kh kw, a tensor's elements (frcnn_ops_masked_conv2d_max_index())
 MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
                                           # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
                                           # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
@@ -4272,3 +4303,135 @@ def points_in_polygons_pytorch(points, polygons):
             inside = (e[None, ..., 0] * d[..., 1] >= e[None, ..., 1] * d[..., 0]).all(-1)
             out[i0:i0 + 4096] = (inside & okp[:, None] & okq[None]).to(out.dtype)
     return out
+
+
+# ---- masked_conv2d / MaskedConv2d: the sparse convolution of Guided Anchoring's heads (csrc/ops_mconv.hip) ----------------------------
+@torch.library.custom_op("frcnn::masked_conv2d", mutates_args=())
+def _masked_conv2d(input: Tensor, mask: Tensor, weight: Tensor, bias: Optional[Tensor], pad_h: int, pad_w: int) -> Tensor:
+    """mask: uint8 [N, oh, ow], active where not 0.  No autograd formula is registered: a backward through the op raises."""
+    n, c, h, w = input.shape
+    co, _, kh, kw = weight.shape
+    oh, ow = h + 2 * pad_h - kh + 1, w + 2 * pad_w - kw + 1
+    channels_last = _input_is_channels_last(input)
+    out = _grad_empty((n, co, oh, ow), input, channels_last)
+    if out.numel() == 0:
+        return out
+    with torch.cuda.device(input.device):
+        x = input if channels_last else input.contiguous()        # both formats are read in place through their strides
+        wt, m = weight.contiguous(), mask.contiguous()
+        b = None if bias is None else bias.contiguous()
+        ws = _workspace("masked_conv2d", input, n, oh, ow)
+        e = _elem(input.dtype)
+        nv.check(nv.lib().frcnn_ops_masked_conv2d(nv.OPS_F32 if e is None else e, x.data_ptr(), (C.c_int64 * 4)(*x.stride()), n, c, h, w,
+                                                  wt.data_ptr(), None if b is None else b.data_ptr(), co, kh, kw, pad_h, pad_w,
+                                                  m.data_ptr(), out.data_ptr(), (C.c_int64 * 4)(*out.stride()), ws.data_ptr(), ws.numel(),
+                                                  _stream(input)), "frcnn_ops_masked_conv2d")
+    return out
+
+
+@_masked_conv2d.register_fake
+def _(input, mask, weight, bias, pad_h, pad_w):
+    n, _, h, w = input.shape
+    co, _, kh, kw = weight.shape
+    return _grad_empty((n, co, h + 2 * pad_h - kh + 1, w + 2 * pad_w - kw + 1), input, _input_is_channels_last(input))
+
+
+_MCONV_WHAT = ("float32, float16 or bfloat16, the same for features, weight and bias (masked_conv2d takes no mix: cast the other tensors "
+               "to the features' dtype)")
+
+
+def _masked_conv2d_input(features, mask, weight, bias, padding, stride, dtypes, what, device_check):
+    """The checks masked_conv2d and masked_conv2d_pytorch share; returns (pad_h, pad_w, oh, ow)."""
+    tensors = [("features", features), ("weight", weight)] + ([("bias", bias)] if bias is not None else [])
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    allowed = (features.dtype,) if features.dtype in dtypes else dtypes[:1]      # a mix is refused at its first tensor of another dtype
+    for name, t in tensors:
+        if t.dtype not in allowed or t.dtype not in dtypes:
+            raise TypeError("%s must be %s, got %s%s" % (name, what, t.dtype, "" if name == "features" else " beside features of %s" % features.dtype))
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("mask must be a torch.Tensor, got %s" % type(mask).__name__)
+    if mask.dtype.is_complex:
+        raise TypeError("mask must have a real dtype or bool, got %s" % mask.dtype)
+    if device_check:
+        for name, t in tensors + [("mask", mask)]:
+            _check_tensor(name, t, (t.dtype,), "", "masked_conv2d_pytorch")
+    for name, t in tensors[1:] + [("mask", mask)]:
+        _check_same_device(features, t, "features", name)
+    pad = _int_pair("padding", padding, 0)
+    if _int_pair("stride", stride, 1) != (1, 1):
+        raise ValueError("masked_conv2d supports stride 1 only (mmcv's rule), got %r" % (stride,))
+    if features.dim() != 4:
+        raise ValueError("features must be [N, C_in, H, W], got shape %s" % (tuple(features.shape),))
+    if weight.dim() != 4:
+        raise ValueError("weight must be [C_out, C_in, kh, kw], got shape %s" % (tuple(weight.shape),))
+    n, c, h, w = features.shape
+    co, cw, kh, kw = weight.shape
+    if min(c, h, w, co, kh, kw) < 1:
+        raise ValueError("features and weight must not be empty beyond N, got features %s, weight %s" % (tuple(features.shape), tuple(weight.shape)))
+    if cw != c:
+        raise ValueError("weight must be [C_out, C_in, kh, kw] with C_in = %d (no groups), got shape %s" % (c, tuple(weight.shape)))
+    if bias is not None and tuple(bias.shape) != (co,):
+        raise ValueError("bias must be [C_out] = [%d], got shape %s" % (co, tuple(bias.shape)))
+    oh, ow = h + 2 * pad[0] - kh + 1, w + 2 * pad[1] - kw + 1
+    if oh < 1 or ow < 1:
+        raise ValueError("the output would be empty: (%d, %d) for features %s, kernel (%d, %d), padding %s" % (oh, ow, tuple(features.shape), kh, kw, pad))
+    if tuple(mask.shape) != (n, oh, ow):
+        raise ValueError("mask must lie on the output grid [N, oh, ow] = [%d, %d, %d], got shape %s" % (n, oh, ow, tuple(mask.shape)))
+    return pad[0], pad[1], oh, ow
+
+
+def masked_conv2d(features, mask, weight, bias, padding=0, stride=1):
+    """mmcv.ops.masked_conv2d: the stride-1 convolution of features [N, C_in, H, W] with weight [C_out, C_in, kh, kw] and bias [C_out] (or
+    None) at the pixels where mask [N, oh, ow] > 0, +0.0 (no bias) everywhere else -> [N, C_out, oh, ow] in the features' dtype and
+    memory format.  Inference only: a backward through it raises."""
+    ph, pw, oh, ow = _masked_conv2d_input(features, mask, weight, bias, padding, stride, _MAP_DTYPES, _MCONV_WHAT, True)
+    n, c, h, w = features.shape
+    co, _, kh, kw = weight.shape
+    largest = max(n * oh * ow, co * c * kh * kw, n * c * h * w, n * co * oh * ow, h + ph + kh, w + pw + kw)
+    if largest > MAX_MASKED_CONV_INDEX:
+        raise ValueError("masked_conv2d is too large for the kernels' 32-bit indices: %d > MAX_MASKED_CONV_INDEX = %d (output pixels, "
+                         "weights or a tensor's elements)" % (largest, MAX_MASKED_CONV_INDEX))
+    return _masked_conv2d(features, (mask > 0).view(torch.uint8), weight, bias, ph, pw)
+
+
+def masked_conv2d_pytorch(features, mask, weight, bias, padding=0, stride=1):
+    """masked_conv2d from torch operations, on any device, float64 too: mmcv's composition, one image at a time -- nonzero (a host
+    synchronisation on a GPU), the active pixels' taps gathered from the zero-padded map into a column matrix, addmm, scatter.  16-bit
+    tensors multiply in float32 and round once."""
+    dtypes = _MAP_DTYPES + (torch.float64,)
+    ph, pw, oh, ow = _masked_conv2d_input(features, mask, weight, bias, padding, stride, dtypes, _MCONV_WHAT[:-1] + "; float64 too)", False)
+    n, c = features.shape[:2]
+    co, _, kh, kw = weight.shape
+    math_dtype = torch.float32 if features.dtype in _HALF else features.dtype
+    out = _grad_empty((n, co, oh, ow), features, _input_is_channels_last(features)).zero_()
+    with torch.no_grad():
+        wt = weight.detach().to(math_dtype).reshape(co, c * kh * kw)
+        b = wt.new_zeros((co,)) if bias is None else bias.detach().to(math_dtype)
+        padded = torch.nn.functional.pad(features.detach().to(math_dtype), (pw, pw, ph, ph))
+        for i in range(n):
+            y, x = torch.nonzero(mask[i] > 0, as_tuple=True)
+            if y.numel() == 0:
+                continue
+            cols = torch.stack([padded[i][:, y + di, x + dj] for di in range(kh) for dj in range(kw)], dim=1)       # [C_in, kh kw, active]
+            out[i][:, y, x] = torch.addmm(b[:, None], wt, cols.reshape(c * kh * kw, -1)).to(out.dtype)
+    return out
+
+
+class MaskedConv2d(torch.nn.Conv2d):
+    """mmcv.ops.MaskedConv2d: an nn.Conv2d (same constructor, same parameters weight and bias, so a Conv2d or mmdet state dict loads
+    strict) whose forward takes an optional mask.  Without one it is nn.Conv2d.forward and trains as usual; with one it is
+    masked_conv2d(input, mask, weight, bias, padding), inference only.  A mask with a dilation or groups other than 1 is a ValueError
+    (mmcv silently ignores the dilation), as is a stride other than 1."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias)
+
+    def forward(self, input, mask=None):
+        if mask is None:
+            return super().forward(input)
+        if tuple(self.dilation) != (1, 1) or self.groups != 1:
+            raise ValueError("MaskedConv2d with a mask supports dilation 1 and groups 1 only, got dilation %s, groups %d"
+                             % (tuple(self.dilation), self.groups))
+        return masked_conv2d(input, mask, self.weight, self.bias, self.padding, self.stride)

@@ -99,7 +99,10 @@ extern "C" {
                                  the limit stated with it (sides of about 3000 px at the 0.3 threshold; it accepted them without a proof before);
                                  still 21 (additions only): frcnn_ops_box_iou_quadri, frcnn_ops_nms_quadri, frcnn_ops_points_in_polygons and the
                                  frcnn_ops_box_iou_quadri_tile_rows / frcnn_ops_points_in_polygons_tile_rows / frcnn_ops_quadri_max_rows /
-                                 _max_columns getters (the quadrilateral operators: mmcv's box_iou_quadri, nms_quadri and points_in_polygons) */
+                                 _max_columns getters (the quadrilateral operators: mmcv's box_iou_quadri, nms_quadri and points_in_polygons);
+                                 still 21 (additions only): frcnn_ops_masked_conv2d, frcnn_ops_masked_conv2d_workspace_bytes, the
+                                 frcnn_ops_masked_conv2d_tile_pixels / _tile_channels / _k_chunk / _max_index getters and FRCNN_OPS_F32 (the sparse
+                                 convolution of Guided Anchoring's heads: mmcv's masked_conv2d) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -535,6 +538,7 @@ int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, co
  *   entry points; an unknown elem_type is FRCNN_EINVAL.  The multi-scale workspace is frcnn_ops_ms_roi_align_workspace_bytes's. */
 #define FRCNN_OPS_F16  1   /* IEEE binary16 (torch.float16) */
 #define FRCNN_OPS_BF16 2   /* bfloat16 (torch.bfloat16) */
+#define FRCNN_OPS_F32  0   /* float32: only where one entry point serves all three element types (frcnn_ops_masked_conv2d) */
 int frcnn_ops_half_run(void);
 int frcnn_ops_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
                            int out_w, float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream);
@@ -1069,6 +1073,47 @@ int frcnn_ops_box_iou_quadri(const float* d_quads1, int n, const float* d_quads2
 int frcnn_ops_nms_quadri(const float* d_quads, const int64_t* d_order, const int64_t* d_categories, int n, float iou_threshold,
                          uint8_t* d_keep, void* d_ws, size_t ws_bytes, void* stream);
 int frcnn_ops_points_in_polygons(const float* d_points, int n, const float* d_polygons, int m, float* d_out, void* stream);
+
+/* masked_conv2d, the sparse convolution of Guided Anchoring's heads (GA-RPN, GA-Faster R-CNN, GA-RetinaNet; csrc/ops_mconv.hip): a
+ *   stride-1 convolution evaluated only at the output pixels a mask marks.  mmcv has an operator of this name (third party, absent here:
+ *   its published algorithm restated, unpinned; where the two differ this text holds).  Inference only: there is no backward.
+ * Tensors.  T is float32, float16 or bfloat16 (elem_type FRCNN_OPS_F32 / _F16 / _BF16), one type for every tensor of a call.
+ *   d_input  [n_img, c_in, h, w] elements of T read IN PLACE through in_stride[4], the element strides of (b, c, y, x): an NCHW-contiguous
+ *            and a channels_last map are both legal, as is any other non-negative stride set whose extent stays below the index limit.
+ *   d_weight [c_out, c_in, kh, kw] contiguous; d_bias [c_out] contiguous, or NULL for a zero bias.
+ *   d_mask   [n_img, oh, ow] uint8, contiguous, on the OUTPUT grid oh = h + 2 pad_h - kh + 1, ow = w + 2 pad_w - kw + 1; a pixel is active
+ *            iff its byte is not 0 (the caller forms it as mask > 0, so a NaN is inactive).
+ *   d_out    [n_img, c_out, oh, ow] written through out_stride[4]; every element is written by this call.
+ * Values.  At an active pixel
+ *     out[b, co, y, x] = T(bias[co] + sum over (c, i, j) of weight[co, c, i, j] * input[b, c, y - pad_h + i, x - pad_w + j]),
+ *   taps outside the map counting as zero; at every other pixel out is +0.0 (no bias there: mmcv's new_zeros).  The sum runs in float32
+ *   in ascending r = (c kh + i) kw + j: for float32 an fma chain on v_mfma_f32_32x32x2_f32, for the 16-bit types exact products on
+ *   v_mfma_f32_32x32x16_{f16,bf16} with float32 accumulators; the bias is widened and added last, in float32, and the store rounds once
+ *   to nearest even.  The order depends on (c_in, kh, kw) alone: not on the pixel's place in the list or the tile, n_img, the strides or
+ *   the rest of the mask, so an active pixel's bits are those it has under the all-ones mask, an n_img-image call equals n_img calls, the
+ *   two memory formats agree, and two runs agree.
+ * Deliberate deviations from mmcv: n_img >= 1 (mmcv asserts 1); the mask lives on the output grid (mmcv asserts the map's size and
+ *   scatters out of bounds when the padding makes the output smaller); a NULL bias is a zero bias (mmcv fails); no host synchronisation
+ *   (mmcv finds the active pixels with nonzero); the Python module refuses a dilation or groups other than 1 (mmcv ignores the dilation).
+ * Kernels.  A compaction pass over the mask appends each active pixel's index b oh ow + p (int32) to a list in the workspace behind its
+ *   count, and writes the zeros of each inactive pixel, once.  The list's order is not fixed (integer atomics on the count); no output
+ *   bit depends on it.  The product is an implicit GEMM over tiles of frcnn_ops_masked_conv2d_tile_pixels() listed pixels by
+ *   frcnn_ops_masked_conv2d_tile_channels() output channels, staged through LDS in chunks of frcnn_ops_masked_conv2d_k_chunk() reduction
+ *   indices; its grid is sized for the worst case and a block whose tile starts at or past the device-side count returns at once.  Taps
+ *   outside the map are zeros formed in registers; no address outside a tensor is formed.  No atomics on floating-point data.
+ * Limits.  Indices are 32-bit.  FRCNN_EINVAL before the GPU is touched: an unknown elem_type, sizes < 1, a negative padding, an empty
+ *   output grid, n_img oh ow, c_in kh kw, c_out c_in kh kw or a tensor's extent (1 + the largest element offset its strides reach) above
+ *   frcnn_ops_masked_conv2d_max_index() = 2^31 - 1 - 1024, a negative stride, c_out above 65535 channel tiles, NULL pointers (d_bias
+ *   excepted), a workspace smaller than frcnn_ops_masked_conv2d_workspace_bytes(n_img, oh, ow) (0 for sizes it refuses) or not 4-byte
+ *   aligned.  in_stride and out_stride are HOST arrays, read before the call returns. */
+int frcnn_ops_masked_conv2d_tile_pixels(void);
+int frcnn_ops_masked_conv2d_tile_channels(void);
+int frcnn_ops_masked_conv2d_k_chunk(void);
+int frcnn_ops_masked_conv2d_max_index(void);
+size_t frcnn_ops_masked_conv2d_workspace_bytes(int n_img, int oh, int ow);
+int frcnn_ops_masked_conv2d(int elem_type, const void* d_input, const int64_t* in_stride, int n_img, int c_in, int h, int w,
+                            const void* d_weight, const void* d_bias, int c_out, int kh, int kw, int pad_h, int pad_w,
+                            const uint8_t* d_mask, void* d_out, const int64_t* out_stride, void* d_ws, size_t ws_bytes, void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

@@ -103,6 +103,12 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     with and without 15 labels, and ops.points_in_polygons of 20000 points against 64 polygons, each beside its _pytorch composition on
     the same GPU (for NMS: ops.box_iou_quadri_pytorch's matrix, then a greedy pass on the host).  Informational: no speed bound is set.
 
+  * mconv: ops.masked_conv2d at GA-RetinaNet's two head shapes (256 -> 80 and 256 -> 4, 1 x 1) and one 3 x 3, 256 -> 256 shape, on a
+    100 x 152 map, one image, at 5 %, 25 % and 100 % active pixels, in float32 and bfloat16, NCHW and channels_last, beside what a head
+    does without the operator (dense F.conv2d, then * mask) and beside ops.masked_conv2d_pytorch on the same GPU (mmcv's composition,
+    its nonzero synchronisation included), in alternating windows.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only mconv           # just the masked-convolution leg
     python tools/ops_bench.py --only quadri          # just the quadrilateral leg
     python tools/ops_bench.py --only convex          # just the point-set leg
     python tools/ops_bench.py --only rfa             # just the rotated_feature_align leg
@@ -787,6 +793,30 @@ def quadri_leg(rng, reps, warmup):
     return {"quadri float32 (microseconds)": res}
 
 
+def mconv_leg(rng, reps, warmup):
+    import torch.nn.functional as F
+    h, w, c = 100, 152, 256
+    res = {}
+    for dtype in (torch.float32, torch.bfloat16):
+        x = torch.from_numpy(rng.randn(1, c, h, w).astype(np.float32)).to(DEV).to(dtype)
+        x_cl = x.contiguous(memory_format=torch.channels_last)
+        for co, k in ((80, 1), (4, 1), (256, 3)):
+            wt = (torch.from_numpy(rng.randn(co, c, k, k).astype(np.float32)) / (c * k * k) ** 0.5).to(DEV).to(dtype)
+            b = torch.from_numpy(rng.randn(co).astype(np.float32)).to(DEV).to(dtype)
+            for share in (0.05, 0.25, 1.0):
+                mask = torch.from_numpy((rng.rand(1, h, w) < share).astype(np.float32)).to(DEV)
+                mask_t = mask[:, None].to(dtype)
+                fns = [lambda: ops.masked_conv2d(x, mask, wt, b, k // 2), lambda: ops.masked_conv2d(x_cl, mask, wt, b, k // 2),
+                       lambda: F.conv2d(x, wt, b, padding=k // 2) * mask_t, lambda: ops.masked_conv2d_pytorch(x, mask, wt, b, k // 2)]
+                dense, native = fns[2]().float(), fns[0]().float()
+                t = timed_group(fns, reps, warmup)
+                res["%s %d -> %d, %d x %d, %g %% active" % (str(dtype).split(".")[-1], c, co, k, k, 100 * share)] = {
+                    "active pixels": int(mask.sum()), "max |ops - dense conv2d * mask|": float((native - dense).abs().max()),
+                    "ops": round(t[0], 1), "ops channels_last": round(t[1], 1), "dense conv2d * mask": round(t[2], 1),
+                    "_pytorch composition": round(t[3], 1), "dense / ops": round(t[2] / t[0], 2), "composition / ops": round(t[3] / t[0], 2)}
+    return {"masked_conv2d, 1 x 256 x 100 x 152 (microseconds)": res}
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -870,7 +900,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri", "mconv"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -930,6 +960,9 @@ def main():
         return
     if a.only == "quadri":
         print(json.dumps(quadri_leg(rng, 5, 2), indent=1))
+        return
+    if a.only == "mconv":
+        print(json.dumps(mconv_leg(rng, 50, 5), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -1006,6 +1039,7 @@ def main():
     res.update(rfa_leg(rng, 5, 2))
     res.update(convex_leg(rng, 5, 2))
     res.update(quadri_leg(rng, 5, 2))
+    res.update(mconv_leg(rng, 50, 5))
     print(json.dumps(res, indent=1))
 
 
