@@ -20,6 +20,8 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import convex_iou_pytorch, convex_giou_pytorch, min_area_polygons_pytorch
     from fasterrcnn_amd.ops import box_iou_quadri, nms_quadri, points_in_polygons, box_iou_quadri_pytorch, points_in_polygons_pytorch
     from fasterrcnn_amd.ops import masked_conv2d, MaskedConv2d, masked_conv2d_pytorch
+    from fasterrcnn_amd.ops import paste_masks_in_image, paste_masks_aligned, masks_to_boxes
+    from fasterrcnn_amd.ops import paste_masks_in_image_pytorch, paste_masks_aligned_pytorch, masks_to_boxes_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -461,6 +463,43 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       strict --; without a mask it is nn.Conv2d.forward and trains.  Sizes up to MAX_MASKED_CONV_INDEX (N oh ow, C_out C_in kh kw and
       each tensor's elements).  masked_conv2d_pytorch keeps the same contract from torch operations (mmcv's nonzero / gather / addmm /
       scatter composition, one image at a time, which synchronises on a GPU), on any device, float64 too.
+  paste_masks_in_image(masks, boxes, img_shape, padding=1) -> [K, 1, H, W]            paste_masks_in_image_pytorch(...)
+  paste_masks_aligned(masks, boxes, image_shape, threshold=0.5) -> bool / uint8 [K, H, W]    paste_masks_aligned_pytorch(...)
+  masks_to_boxes(masks) -> float32 [N, 4]                                                 masks_to_boxes_pytorch(masks)
+      The last step of a Mask R-CNN's mask head and the box of a mask (csrc/ops_mask.hip; the contracts are include/frcnn_hip.h's,
+      restated from torchvision and detectron2 / mmdetection, unpinned).  No autograd (upstream's paste is never differentiated): a
+      mask or box tensor that requires grad is accepted and the result does not.  Nothing synchronises with the host, every output
+      element is written by the one launch (no memset in front of it), two runs agree bit for bit.
+      paste_masks_in_image is torchvision's roi_heads.paste_masks_in_image without its Python loop (4 host reads and ~6 launches per
+      mask): masks [K, 1, M, M] float32 / float16 / bfloat16, square (else ValueError), M <= MAX_PASTE_MASK_SIDE; boxes [K, 4] float32
+      (x1, y1, x2, y2); img_shape (H, W); padding an int in [0, MAX_PASTE_PADDING].  With M' = M + 2 padding and s = float32(M' / M)
+      (the division in double), per box IN FLOAT32 AND IN THIS ORDER, no fused multiply-add: w_half = (x2 - x1) * 0.5, x_c =
+      (x2 + x1) * 0.5, w_half = w_half * s, X0 = trunc(x_c - w_half), X1 = trunc(x_c + w_half), likewise in y; trunc is toward zero and
+      saturates to [-PASTE_CORNER, PASTE_CORNER].  bw = max(X1 - X0 + 1, 1), bh likewise.  Pixel (y, x) is non-zero only if X0 <= x <
+      X0 + bw, X0 <= X1, Y0 <= y < Y0 + bh, Y0 <= Y1; there r = float32(M') / float32(bw), sx = max(r * (dx + 0.5) - 0.5, 0) with dx =
+      x - X0, ix = min((int)sx, M' - 1), ix1 = ix + (ix < M' - 1), lx = sx - ix, likewise y, and value = (1 - ly) * ((1 - lx) * P[iy][ix]
+      + lx * P[iy][ix1]) + ly * ((1 - lx) * P[iy1][ix] + lx * P[iy1][ix1]), P the mask padded by `padding` zeros (never materialised).
+      float32 arithmetic on widened masks, one rounding on the store: op(x_T) == op(x_T.float()).to(T) bit for bit.  Deviations
+      (torchvision raises or is undefined there): a non-finite coordinate, an inverted integer box or a box wholly outside the image
+      give an all-zero image; corners saturate; a huge box costs nothing extra; K == 0 gives an empty [0, 1, H, W].
+      paste_masks_aligned is detectron2's paste_masks_in_image / mmdet's _do_paste_mask plus its threshold, without the K x H x W x 2
+      grid, the float image and the 1 GB chunking: masks [K, Mh, Mw] or [K, 1, Mh, Mw] (rectangular allowed, each side <=
+      MAX_PASTE_MASK_SIDE), boxes [K, 4] float32 (x0, y0, x1, y1), threshold a float.  Sample coordinates in pixels, float32, in this
+      order: sx = ((x + 0.5) - x0) / (x1 - x0) * Mw - 0.5, sy likewise with Mh; value is the blend above on floor / floor + 1 of the
+      unpadded mask with a corner outside it counting 0 (grid_sample(align_corners=False, padding_mode="zeros")), never rounded to a
+      16-bit type.  threshold >= 0: torch.bool, value >= float32(threshold); threshold < 0: torch.uint8, trunc(value * 255) saturated
+      to [0, 255], NaN giving 0.  Deviations: a row with a non-finite coordinate, x1 <= x0 or y1 <= y0 gives all False / 0 (upstream
+      flips or smears such a mask); decisions may differ from upstream's within the float32 error of the threshold.
+      masks_to_boxes is torchvision.ops.masks_to_boxes without its loop (a torch.where and a host read per mask): masks [N, H, W]
+      bool, uint8, float32, float16 or bfloat16 with any strides (made contiguous by one copy); (x_min, y_min, x_max, y_max) over the
+      pixels != 0, maxima inclusive; NaN counts as non-zero, -0.0 as zero; an all-zero mask gives (0, 0, 0, 0), detectron2's convention
+      (torchvision raises there); N == 0 gives [0, 4].  H W of one image up to MAX_MASK_PLANE; K H W may exceed 2^31.
+      The _pytorch twins state the same contracts, deviations included, from torch operations on any device, float64 masks too (then
+      the arithmetic after the float32 integer box is float64).
+      Measured on an MI355X (tools/ops_bench.py --only mask; K = 100, M = 28, 800 x 1333; MASK_BENCH below):
+      paste_masks_in_image float32 82 us (38 x its twin, 96 x torchvision's loop; 5.2 TB/s written), float16 58 us;
+      paste_masks_aligned bool 68 us, uint8 60 us (28-36 x the grid_sample composition; 1.6-1.8 TB/s: the evaluation inside the boxes
+      bounds the byte forms, not the store); masks_to_boxes bool 28 us (15 x its twin), float32 74 us (5.8 TB/s read).
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -496,7 +535,9 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "riroi_align_rotated_pytorch", "rotated_feature_align", "RotatedFeatureAlign", "rotated_feature_align_pytorch",
            "convex_iou", "convex_giou", "min_area_polygons", "convex_iou_pytorch", "convex_giou_pytorch", "min_area_polygons_pytorch",
            "box_iou_quadri", "nms_quadri", "points_in_polygons", "box_iou_quadri_pytorch", "points_in_polygons_pytorch",
-           "masked_conv2d", "MaskedConv2d", "masked_conv2d_pytorch"]
+           "masked_conv2d", "MaskedConv2d", "masked_conv2d_pytorch",
+           "paste_masks_in_image", "paste_masks_aligned", "masks_to_boxes",
+           "paste_masks_in_image_pytorch", "paste_masks_aligned_pytorch", "masks_to_boxes_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -519,6 +560,10 @@ MASKED_CONV_TILE_PIXELS = 64              # listed pixels of masked_conv2d's til
 MASKED_CONV_TILE_CHANNELS = 64            # output channels of that tile (frcnn_ops_masked_conv2d_tile_channels())
 MASKED_CONV_K_CHUNK = 32                  # reduction indices (c, i, j) of one of its LDS stages (frcnn_ops_masked_conv2d_k_chunk())
 MAX_MASKED_CONV_INDEX = 2 ** 31 - 1 - 1024    # what its 32-bit indices hold: N oh ow, C_out C_in kh kw, a tensor's elements (frcnn_ops_masked_conv2d_max_index())
+MAX_PASTE_MASK_SIDE = 112                 # M, Mh, Mw of the paste operators: the mask lies in LDS as float32 (frcnn_ops_paste_masks_max_side())
+MAX_PASTE_PADDING = 65536                 # paste_masks_in_image's padding (frcnn_ops_paste_masks_max_padding())
+PASTE_CORNER = 2 ** 29                    # its integer corners saturate to [-2^29, 2^29] (frcnn_ops_paste_masks_max_corner())
+MAX_MASK_PLANE = 2 ** 31 - 1 - 1024       # H W of one image of the mask operators (frcnn_ops_mask_max_plane()); K H W is 64-bit
 MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
                                           # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
                                           # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
@@ -4435,3 +4480,293 @@ class MaskedConv2d(torch.nn.Conv2d):
             raise ValueError("MaskedConv2d with a mask supports dilation 1 and groups 1 only, got dilation %s, groups %d"
                              % (tuple(self.dilation), self.groups))
         return masked_conv2d(input, mask, self.weight, self.bias, self.padding, self.stride)
+
+
+# ---- paste_masks_in_image / paste_masks_aligned / masks_to_boxes: a Mask R-CNN's last step (csrc/ops_mask.hip) ------------------------
+# One run on an MI355X (tools/ops_bench.py --only mask; K = 100, M = 28, 800 x 1333, boxes of 30 to 400 px a side): microseconds of the
+# operator, of its _pytorch twin and of upstream's composition (torchvision's loop restated; grid_sample in one chunk and the threshold),
+# and the operator's rate over the bytes it writes (masks_to_boxes: reads).  No form is slower than its twin.  The float32 paste runs
+# at 0.65 of the 8 TB/s HBM peak.  The byte forms do not reach the store's rate: with 16 pixels a lane they took 116 / 123 us (the few
+# lanes of a wave that a box covers evaluated 16 pixels each), so a lane stores 4 pixels there; the evaluation inside the boxes remains.
+MASK_BENCH = {
+    "paste_masks_in_image float32, padding 1": {"ops": 81.8, "twin": 3091.9, "upstream": 7871.0, "TB/s": 5.22},
+    "paste_masks_in_image float16, padding 1": {"ops": 58.1, "twin": 3203.2, "upstream": 7887.7, "TB/s": 3.67},
+    "paste_masks_aligned bool, threshold 0.5": {"ops": 67.7, "twin": 3038.8, "upstream": 1869.4, "TB/s": 1.58},
+    "paste_masks_aligned uint8": {"ops": 60.1, "twin": 3890.7, "upstream": 2148.8, "TB/s": 1.78},
+    "masks_to_boxes bool": {"ops": 27.8, "twin": 411.3, "TB/s": 3.84},
+    "masks_to_boxes float32": {"ops": 73.5, "twin": 343.0, "TB/s": 5.81},
+}
+
+
+def _mask_elem(dtype):
+    e = _elem(dtype)
+    return nv.OPS_F32 if e is None else e
+
+
+@torch.library.custom_op("frcnn::paste_masks_in_image", mutates_args=())
+def _paste_masks_in_image(masks: Tensor, boxes: Tensor, h: int, w: int, padding: int) -> Tensor:
+    k, m = masks.shape[0], masks.shape[2]
+    out = torch.empty((k, 1, h, w), dtype=masks.dtype, device=masks.device)
+    if k == 0:
+        return out
+    with torch.cuda.device(masks.device):
+        mk, bx = masks.contiguous(), boxes.contiguous()
+        nv.check(nv.lib().frcnn_ops_paste_masks_in_image(_mask_elem(masks.dtype), mk.data_ptr(), bx.data_ptr(), k, m, padding, h, w,
+                                                         out.data_ptr(), _stream(masks)), "frcnn_ops_paste_masks_in_image")
+    return out
+
+
+@_paste_masks_in_image.register_fake
+def _(masks, boxes, h, w, padding):
+    return torch.empty((masks.shape[0], 1, h, w), dtype=masks.dtype, device=masks.device)
+
+
+@torch.library.custom_op("frcnn::paste_masks_aligned", mutates_args=())
+def _paste_masks_aligned(masks: Tensor, boxes: Tensor, h: int, w: int, threshold: float, as_uint8: bool) -> Tensor:
+    """masks [K, Mh, Mw]; bytes [K, H, W] as torch.uint8 (the public function views the comparison's bytes as bool)."""
+    k, mh, mw = masks.shape
+    out = torch.empty((k, h, w), dtype=torch.uint8, device=masks.device)
+    if k == 0:
+        return out
+    with torch.cuda.device(masks.device):
+        mk, bx = masks.contiguous(), boxes.contiguous()
+        nv.check(nv.lib().frcnn_ops_paste_masks_aligned(_mask_elem(masks.dtype), mk.data_ptr(), bx.data_ptr(), k, mh, mw, h, w, threshold,
+                                                        int(as_uint8), out.data_ptr(), _stream(masks)), "frcnn_ops_paste_masks_aligned")
+    return out
+
+
+@_paste_masks_aligned.register_fake
+def _(masks, boxes, h, w, threshold, as_uint8):
+    return torch.empty((masks.shape[0], h, w), dtype=torch.uint8, device=masks.device)
+
+
+@torch.library.custom_op("frcnn::masks_to_boxes", mutates_args=())
+def _masks_to_boxes(masks: Tensor) -> Tensor:
+    """masks [N, H, W] of 1-, 2- or 4-byte elements (bool as uint8)."""
+    n, h, w = masks.shape
+    out = torch.empty((n, 4), dtype=torch.float32, device=masks.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(masks.device):
+        mk = masks.contiguous()
+        ws = _workspace("masks_to_boxes", masks, n, h, w, mk.element_size())
+        nv.check(nv.lib().frcnn_ops_masks_to_boxes(mk.element_size(), mk.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _stream(masks)), "frcnn_ops_masks_to_boxes")
+    return out
+
+
+@_masks_to_boxes.register_fake
+def _(masks):
+    return torch.empty((masks.shape[0], 4), dtype=torch.float32, device=masks.device)
+
+
+_MASKS_TO_BOXES_DTYPES = (torch.bool, torch.uint8) + _MAP_DTYPES
+_MASKS_TO_BOXES_WHAT = "bool, uint8, float32, float16 or bfloat16"
+
+
+def _image_shape(name, shape):
+    if not (isinstance(shape, (tuple, list, torch.Size)) and len(shape) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in shape)):
+        raise TypeError("%s must be a pair of ints (H, W), got %r" % (name, shape))
+    h, w = shape
+    if h < 1 or w < 1:
+        raise ValueError("%s must be at least (1, 1), got (%d, %d)" % (name, h, w))
+    if h * w > MAX_MASK_PLANE:
+        raise ValueError("%s (%d, %d) has more than MAX_MASK_PLANE = %d pixels (indices inside one image are 32-bit)" % (name, h, w, MAX_MASK_PLANE))
+    return h, w
+
+
+def _paste_input(masks, boxes, shape, shape_name, float64, fallback):
+    """The checks the paste operators and their twins share (fallback: the twin's name for a GPU operator, None for the twin itself);
+    returns (H, W)."""
+    dtypes = _MAP_DTYPES + ((torch.float64,) if float64 else ())
+    what = _MAP_WHAT + (" (or float64)" if float64 else "")
+    if fallback is None:
+        for name, t, d, wh in (("masks", masks, dtypes, what), ("boxes", boxes, (torch.float32,), "float32")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+            if t.dtype not in d:
+                raise TypeError("%s must be %s, got %s" % (name, wh, t.dtype))
+    else:
+        _check_tensor("masks", masks, dtypes, what, fallback)
+        _check_tensor("boxes", boxes, (torch.float32,), "float32", fallback)
+    _check_same_device(masks, boxes, "masks", "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be [K, 4], got shape %s" % (tuple(boxes.shape),))
+    return _image_shape(shape_name, shape)
+
+
+def _paste_in_image_input(masks, boxes, img_shape, padding, float64, fallback):
+    h, w = _paste_input(masks, boxes, img_shape, "img_shape", float64, fallback)
+    if masks.dim() != 4 or masks.shape[1] != 1:
+        raise ValueError("masks must be [K, 1, M, M], got shape %s" % (tuple(masks.shape),))
+    if masks.shape[2] != masks.shape[3]:
+        raise ValueError("masks must be square, [K, 1, M, M] (paste_masks_aligned takes rectangular ones), got shape %s" % (tuple(masks.shape),))
+    if masks.shape[0] != boxes.shape[0]:
+        raise ValueError("masks and boxes must have the same K, got %d masks and %d boxes" % (masks.shape[0], boxes.shape[0]))
+    if not isinstance(padding, int) or isinstance(padding, bool):
+        raise TypeError("padding must be an int, got %r" % (padding,))
+    if not 0 <= padding <= MAX_PASTE_PADDING:
+        raise ValueError("padding must lie in [0, %d], got %d" % (MAX_PASTE_PADDING, padding))
+    if not 1 <= masks.shape[2] <= MAX_PASTE_MASK_SIDE:
+        raise ValueError("masks must be M x M with 1 <= M <= MAX_PASTE_MASK_SIDE = %d, got M = %d" % (MAX_PASTE_MASK_SIDE, masks.shape[2]))
+    return h, w
+
+
+def _paste_aligned_input(masks, boxes, image_shape, threshold, float64, fallback):
+    """Returns (H, W, masks as [K, Mh, Mw], float32(threshold), as_uint8)."""
+    h, w = _paste_input(masks, boxes, image_shape, "image_shape", float64, fallback)
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3:
+        raise ValueError("masks must be [K, Mh, Mw] or [K, 1, Mh, Mw], got shape %s" % (tuple(masks.shape),))
+    if masks.shape[0] != boxes.shape[0]:
+        raise ValueError("masks and boxes must have the same K, got %d masks and %d boxes" % (masks.shape[0], boxes.shape[0]))
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise TypeError("threshold must be a float, got %r" % (threshold,))
+    if not (1 <= masks.shape[1] <= MAX_PASTE_MASK_SIDE and 1 <= masks.shape[2] <= MAX_PASTE_MASK_SIDE):
+        raise ValueError("masks must be Mh x Mw with 1 <= Mh, Mw <= MAX_PASTE_MASK_SIDE = %d, got %d x %d"
+                         % (MAX_PASTE_MASK_SIDE, masks.shape[1], masks.shape[2]))
+    return h, w, masks, C.c_float(threshold).value, threshold < 0
+
+
+def paste_masks_in_image(masks, boxes, img_shape, padding=1):
+    """torchvision's roi_heads.paste_masks_in_image in one launch: masks [K, 1, M, M] (float32 / float16 / bfloat16) padded by `padding`
+    zeros and resized bilinearly into the integer boxes of boxes [K, 4] float32 -> [K, 1, H, W] in the masks' dtype, zero elsewhere.
+    No autograd (upstream's paste is never differentiated); no host synchronisation."""
+    h, w = _paste_in_image_input(masks, boxes, img_shape, padding, False, "paste_masks_in_image_pytorch")
+    return _paste_masks_in_image(masks.detach(), boxes.detach(), h, w, padding)
+
+
+def paste_masks_aligned(masks, boxes, image_shape, threshold=0.5):
+    """detectron2's paste_masks_in_image / mmdet's _do_paste_mask and its threshold in one launch: masks [K, Mh, Mw] or [K, 1, Mh, Mw]
+    sampled bilinearly (zero padding) at every pixel centre of boxes [K, 4] float32 -> [K, H, W], torch.bool (value >= threshold) for
+    threshold >= 0, else torch.uint8 (trunc(255 value), saturated).  No autograd; no host synchronisation."""
+    h, w, mk, thr, as_uint8 = _paste_aligned_input(masks, boxes, image_shape, threshold, False, "paste_masks_aligned_pytorch")
+    out = _paste_masks_aligned(mk.detach(), boxes.detach(), h, w, thr, as_uint8)
+    return out if as_uint8 else out.view(torch.bool)
+
+
+def _masks_to_boxes_input(masks, fallback):
+    dtypes = _MASKS_TO_BOXES_DTYPES + ((torch.float64,) if fallback is None else ())
+    what = _MASKS_TO_BOXES_WHAT + (" (or float64)" if fallback is None else "")
+    if fallback is None:
+        if not isinstance(masks, torch.Tensor):
+            raise TypeError("masks must be a torch.Tensor, got %s" % type(masks).__name__)
+        if masks.dtype not in dtypes:
+            raise TypeError("masks must be %s, got %s" % (what, masks.dtype))
+    else:
+        _check_tensor("masks", masks, dtypes, what, fallback)
+    if masks.dim() != 3:
+        raise ValueError("masks must be [N, H, W], got shape %s" % (tuple(masks.shape),))
+    _image_shape("the masks' (H, W)", tuple(masks.shape[1:]))
+
+
+def masks_to_boxes(masks):
+    """torchvision.ops.masks_to_boxes without its loop: masks [N, H, W] (bool, uint8, float32, float16, bfloat16) -> float32 [N, 4],
+    (x_min, y_min, x_max, y_max) over the pixels != 0, maxima inclusive; an all-zero mask gives (0, 0, 0, 0) (detectron2's convention;
+    torchvision raises).  No autograd; no host synchronisation."""
+    _masks_to_boxes_input(masks, "masks_to_boxes_pytorch")
+    m = masks.detach().contiguous()
+    return _masks_to_boxes(m.view(torch.uint8) if m.dtype == torch.bool else m)
+
+
+def _mask_blend(p, iy, iy1, ly, ix, ix1, lx):
+    """(1 - ly) ((1 - lx) p[iy][ix] + lx p[iy][ix1]) + ly ((1 - lx) p[iy1][ix] + lx p[iy1][ix1]) for p [K, A, B], row terms [K, H] and
+    column terms [K, W] -> [K, H, W]."""
+    k, h, w = p.shape[0], iy.shape[1], ix.shape[1]
+    rows0 = p.gather(1, iy[:, :, None].expand(k, h, p.shape[2]))
+    rows1 = p.gather(1, iy1[:, :, None].expand(k, h, p.shape[2]))
+    cx, cx1, lx, ly = ix[:, None, :].expand(k, h, w), ix1[:, None, :].expand(k, h, w), lx[:, None, :], ly[:, :, None]
+    top = (1 - lx) * rows0.gather(2, cx) + lx * rows0.gather(2, cx1)
+    bot = (1 - lx) * rows1.gather(2, cx) + lx * rows1.gather(2, cx1)
+    return (1 - ly) * top + ly * bot
+
+
+def _paste_integer_boxes(boxes, m, padding):
+    """The integer boxes of paste_masks_in_image's contract, from float32 torch operations, each rounded on its own: (X0, Y0, X1, Y1)
+    int64 [K] each, saturated to [-PASTE_CORNER, PASTE_CORNER] (a NaN row: 0; such rows are dead anyway)."""
+    b = boxes.detach().to(torch.float32)
+    s = torch.tensor((m + 2 * padding) / m, dtype=torch.float32, device=b.device)
+
+    def corners(lo, hi):
+        half = (hi - lo) * 0.5
+        c = (hi + lo) * 0.5
+        half = half * s
+        return [torch.nan_to_num(v, nan=0.0).clamp(-PASTE_CORNER, PASTE_CORNER).to(torch.int64) for v in (c - half, c + half)]
+    (x0, x1), (y0, y1) = corners(b[:, 0], b[:, 2]), corners(b[:, 1], b[:, 3])
+    return x0, y0, x1, y1
+
+
+def paste_masks_in_image_pytorch(masks, boxes, img_shape, padding=1):
+    """paste_masks_in_image's contract, deviations included, from torch operations: any device, float64 masks too (the integer boxes are
+    the float32 sequence's either way; everything after them is then float64).  16-bit masks compute in float32 and round once."""
+    h, w = _paste_in_image_input(masks, boxes, img_shape, padding, True, None)
+    k, m = masks.shape[0], masks.shape[2]
+    mp = m + 2 * padding
+    math = torch.float64 if masks.dtype == torch.float64 else torch.float32
+    dev = masks.device
+    with torch.no_grad():
+        if k == 0:
+            return masks.new_zeros((0, 1, h, w))
+        x0, y0, x1, y1 = _paste_integer_boxes(boxes, m, padding)
+        alive = torch.isfinite(boxes.detach()).all(1) & (x0 <= x1) & (y0 <= y1)
+        p = torch.nn.functional.pad(masks.detach()[:, 0].to(math), (padding,) * 4)
+
+        def axis(n, origin, size):
+            d = torch.arange(n, device=dev)[None, :] - origin[:, None]
+            r = torch.full((k,), float(mp), dtype=math, device=dev) / size.to(math)
+            sc = (r[:, None] * (d.to(math) + 0.5) - 0.5).clamp(min=0)
+            i0 = sc.to(torch.int64).clamp(max=mp - 1)
+            return (d >= 0) & (d < size[:, None]), i0, i0 + (i0 < mp - 1).to(torch.int64), sc - i0.to(math)
+        in_x, ix, ix1, lx = axis(w, x0, (x1 - x0 + 1).clamp(min=1))
+        in_y, iy, iy1, ly = axis(h, y0, (y1 - y0 + 1).clamp(min=1))
+        value = _mask_blend(p, iy, iy1, ly, ix, ix1, lx)
+        keep = alive[:, None, None] & in_y[:, :, None] & in_x[:, None, :]
+        return torch.where(keep, value, value.new_zeros(())).to(masks.dtype)[:, None]
+
+
+def paste_masks_aligned_pytorch(masks, boxes, image_shape, threshold=0.5):
+    """paste_masks_aligned's contract, deviations included, from torch operations: any device, float64 masks too (then the sample
+    coordinates and the blend are float64 on the float32 boxes, compared with float32(threshold))."""
+    h, w, mk, thr, as_uint8 = _paste_aligned_input(masks, boxes, image_shape, threshold, True, None)
+    k, mh, mw = mk.shape
+    math = torch.float64 if mk.dtype == torch.float64 else torch.float32
+    dev = mk.device
+    with torch.no_grad():
+        if k == 0:
+            return torch.zeros((0, h, w), dtype=torch.uint8 if as_uint8 else torch.bool, device=dev)
+        b = boxes.detach()
+        alive = torch.isfinite(b).all(1) & (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+        b = b.to(math)
+        p = torch.nn.functional.pad(mk.detach().to(math), (1, 1, 1, 1))              # the zero padding: index i + 1 holds mask[i]
+
+        def axis(n, c0, c1, m):
+            c = torch.arange(n, dtype=math, device=dev) + 0.5
+            sc = (c[None, :] - c0[:, None]) / (c1 - c0)[:, None] * m - 0.5
+            ok = alive[:, None] & (sc > -1) & (sc < m)
+            f = torch.where(ok, sc.floor(), sc.new_zeros(()))
+            i0 = f.to(torch.int64) + 1
+            return ok, i0, i0 + 1, torch.where(ok, sc - f, sc.new_zeros(()))
+        ok_x, ix, ix1, lx = axis(w, b[:, 0], b[:, 2], mw)
+        ok_y, iy, iy1, ly = axis(h, b[:, 1], b[:, 3], mh)
+        value = _mask_blend(p, iy, iy1, ly, ix, ix1, lx)
+        value = torch.where(ok_y[:, :, None] & ok_x[:, None, :], value, value.new_zeros(()))
+        live = alive[:, None, None]
+        if as_uint8:
+            q = value * 255
+            q = torch.where(q >= 255, q.new_full((), 255.0), torch.where(q > 0, q.trunc(), q.new_zeros(())))
+            return q.to(torch.uint8) * live.to(torch.uint8)
+        return (value >= torch.tensor(thr, dtype=torch.float32, device=dev).to(math)) & live
+
+
+def masks_to_boxes_pytorch(masks):
+    """masks_to_boxes' contract from torch operations: any device, float64 masks too."""
+    _masks_to_boxes_input(masks, None)
+    n, h, w = masks.shape
+    with torch.no_grad():
+        nz = masks.detach() != 0                                                      # NaN != 0, -0.0 == 0
+        cols, rows = nz.any(1), nz.any(2)
+        xs, ys = torch.arange(w, device=masks.device)[None, :], torch.arange(h, device=masks.device)[None, :]
+        out = torch.stack([torch.where(cols, xs, w).amin(1), torch.where(rows, ys, h).amin(1),
+                           torch.where(cols, xs, -1).amax(1), torch.where(rows, ys, -1).amax(1)], dim=1).to(torch.float32)
+        return torch.where(cols.any(1)[:, None], out, out.new_zeros(()))

@@ -102,7 +102,11 @@ extern "C" {
                                  _max_columns getters (the quadrilateral operators: mmcv's box_iou_quadri, nms_quadri and points_in_polygons);
                                  still 21 (additions only): frcnn_ops_masked_conv2d, frcnn_ops_masked_conv2d_workspace_bytes, the
                                  frcnn_ops_masked_conv2d_tile_pixels / _tile_channels / _k_chunk / _max_index getters and FRCNN_OPS_F32 (the sparse
-                                 convolution of Guided Anchoring's heads: mmcv's masked_conv2d) */
+                                 convolution of Guided Anchoring's heads: mmcv's masked_conv2d);
+                                 still 21 (additions only): frcnn_ops_paste_masks_in_image, frcnn_ops_paste_masks_aligned, frcnn_ops_masks_to_boxes,
+                                 frcnn_ops_masks_to_boxes_workspace_bytes and the frcnn_ops_paste_masks_max_side / _max_padding / _max_corner and
+                                 frcnn_ops_mask_max_plane getters (a Mask R-CNN's last step: torchvision's and detectron2's paste_masks_in_image,
+                                 torchvision's masks_to_boxes) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -538,7 +542,7 @@ int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, co
  *   entry points; an unknown elem_type is FRCNN_EINVAL.  The multi-scale workspace is frcnn_ops_ms_roi_align_workspace_bytes's. */
 #define FRCNN_OPS_F16  1   /* IEEE binary16 (torch.float16) */
 #define FRCNN_OPS_BF16 2   /* bfloat16 (torch.bfloat16) */
-#define FRCNN_OPS_F32  0   /* float32: only where one entry point serves all three element types (frcnn_ops_masked_conv2d) */
+#define FRCNN_OPS_F32  0   /* float32: only where one entry point serves all three element types (frcnn_ops_masked_conv2d, frcnn_ops_paste_masks_*) */
 int frcnn_ops_half_run(void);
 int frcnn_ops_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
                            int out_w, float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream);
@@ -1114,6 +1118,70 @@ size_t frcnn_ops_masked_conv2d_workspace_bytes(int n_img, int oh, int ow);
 int frcnn_ops_masked_conv2d(int elem_type, const void* d_input, const int64_t* in_stride, int n_img, int c_in, int h, int w,
                             const void* d_weight, const void* d_bias, int c_out, int kh, int kw, int pad_h, int pad_w,
                             const uint8_t* d_mask, void* d_out, const int64_t* out_stride, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The mask operators of a Mask R-CNN's last step (csrc/ops_mask.hip).  torchvision and detectron2 / mmdetection are third parties, absent
+ *   here: their published algorithms restated, unpinned; where they differ from this text, this text holds.  No autograd (upstream's
+ *   paste is never differentiated).  Nothing synchronises with the host; every output element is written by the call's own launches, no
+ *   memset precedes them, no atomics: two runs agree bit for bit.
+ *
+ * frcnn_ops_paste_masks_in_image: torchvision's roi_heads.paste_masks_in_image (expand_masks, expand_boxes, .to(int64),
+ *   paste_mask_in_image) without its loop over the masks and its four host reads per mask.
+ *   d_masks [k, m, m] elements of T (elem_type FRCNN_OPS_F32 / _F16 / _BF16), contiguous; d_boxes [k, 4] float32 (x1, y1, x2, y2);
+ *   d_out [k, h, w] elements of T, contiguous.  With M' = m + 2 padding and s = float32((double)M' / (double)m):
+ *   The integer box, in float32, every operation rounded on its own (NO contraction into fused multiply-adds: a fused
+ *   x_c - w_half * s changes the integer for real boxes), in this order:
+ *       w_half = (x2 - x1) * 0.5    h_half = (y2 - y1) * 0.5    x_c = (x2 + x1) * 0.5    y_c = (y2 + y1) * 0.5
+ *       w_half = w_half * s         h_half = h_half * s
+ *       X0 = trunc(x_c - w_half)    X1 = trunc(x_c + w_half)    Y0 = trunc(y_c - h_half)    Y1 = trunc(y_c + h_half)
+ *   trunc rounds toward zero (torch's .to(int64)) and SATURATES to [-C, C], C = frcnn_ops_paste_masks_max_corner() = 2^29.
+ *   The target size: bw = max(X1 - X0 + 1, 1), bh = max(Y1 - Y0 + 1, 1).
+ *   Pixel (y, x) of image i is non-zero only if X0 <= x < X0 + bw, X0 <= X1, Y0 <= y < Y0 + bh and Y0 <= Y1.  There, with dx = x - X0,
+ *       r = float32(M') / float32(bw)    sx = max(r * (float32(dx) + 0.5) - 0.5, 0)
+ *       ix = min((int)sx, M' - 1)        ix1 = ix + (ix < M' - 1)        lx = sx - ix
+ *   likewise (iy, iy1, ly) from dy = y - Y0 and bh, and
+ *       value = (1 - ly) * ((1 - lx) * P[iy][ix] + lx * P[iy][ix1]) + ly * ((1 - lx) * P[iy1][ix] + lx * P[iy1][ix1])
+ *   where P is the mask padded by `padding` zeros on each side (never materialised) -- F.interpolate(bilinear, align_corners=False)
+ *   to (bh, bw).  Masks are widened exactly, the arithmetic is float32 without contraction, and the store rounds once (ops_elem.h):
+ *   op(x_T) == op(x_T.float()).to(T) bit for bit.  Everywhere else the pixel is +0.0.
+ *   Stated deviations (torchvision raises or is undefined there): a row with a non-finite coordinate, an inverted integer box or a box
+ *   wholly outside the image gives an all-zero image; integer corners saturate as above; a huge box costs nothing extra (only pixels of
+ *   the image are evaluated); k == 0 is legal and launches nothing.
+ *
+ * frcnn_ops_paste_masks_aligned: detectron2's paste_masks_in_image / mmdetection's _do_paste_mask followed by the threshold.
+ *   d_masks [k, mh, mw] elements of T, contiguous; d_boxes [k, 4] float32 (x0, y0, x1, y1); d_out [k, h, w] bytes.  The sample
+ *   coordinates of pixel (y, x) are formed in pixels, in float32 and in this order (no normalised round trip):
+ *       sx = ((float32(x) + 0.5) - x0) / (x1 - x0) * float32(mw) - 0.5        sy = ((float32(y) + 0.5) - y0) / (y1 - y0) * float32(mh) - 0.5
+ *   and value is the blend above with ix = floor(sx), ix1 = ix + 1, lx = sx - ix (likewise y) on the UNPADDED mask, a corner outside
+ *   it counting 0 (grid_sample(align_corners=False, padding_mode="zeros")); a sample with sx outside (-1, mw) or sy outside (-1, mh)
+ *   is 0.  float32 on widened masks, never rounded to a 16-bit type.  The byte is value >= threshold (as_uint8 == 0; 0 or 1), or
+ *   trunc(value * 255) saturated to [0, 255] with NaN giving 0 (as_uint8 != 0).
+ *   Stated deviations: a row with a non-finite coordinate, x1 <= x0 or y1 <= y0 gives all 0 bytes, whatever the threshold (upstream
+ *   flips or smears such a mask); decisions may differ from upstream's on values within the float32 error of the threshold.
+ *
+ * frcnn_ops_masks_to_boxes: torchvision.ops.masks_to_boxes.  d_masks [n, h, w] elements of elem_bytes = 1 (bool, uint8), 2 (float16,
+ *   bfloat16) or 4 (float32) bytes, contiguous; d_out [n, 4] float32 (x_min, y_min, x_max, y_max) over the pixels != 0, maxima inclusive.
+ *   A float is non-zero iff any bit but its sign is set: -0.0 is zero, every NaN is not.  A mask without such a pixel gives
+ *   (0, 0, 0, 0) -- detectron2's convention for empty masks; torchvision raises there.  Two stages: integer extrema of bands of
+ *   every mask into the workspace (every entry written, no initial value needed), then one wave per mask combines them.
+ *
+ * Limits, FRCNN_EINVAL before the GPU is touched: an unknown elem_type / elem_bytes; m, mh or mw outside [1,
+ *   frcnn_ops_paste_masks_max_side()] (the mask is staged in LDS as float32; 112); padding outside [0,
+ *   frcnn_ops_paste_masks_max_padding()]; h or w < 1 or h w above frcnn_ops_mask_max_plane() = 2^31 - 1 - 1024 (indices inside one image
+ *   are 32-bit; the offset of an image is 64-bit, so k h w may exceed 2^31); k or n < 0; with k, n > 0 a NULL pointer, an output not
+ *   aligned to its element, a workspace smaller than frcnn_ops_masks_to_boxes_workspace_bytes(n, h, w, elem_bytes) (0 for arguments it
+ *   refuses) or not 16-byte aligned.  Inputs and outputs need no other alignment: heads and tails of an image around the aligned
+ *   vectors are handled element by element. */
+int frcnn_ops_paste_masks_max_side(void);
+int frcnn_ops_paste_masks_max_padding(void);
+int frcnn_ops_paste_masks_max_corner(void);
+int frcnn_ops_mask_max_plane(void);
+int frcnn_ops_paste_masks_in_image(int elem_type, const void* d_masks, const float* d_boxes, int k, int m, int padding, int h, int w,
+                                   void* d_out, void* stream);
+int frcnn_ops_paste_masks_aligned(int elem_type, const void* d_masks, const float* d_boxes, int k, int mh, int mw, int h, int w,
+                                  float threshold, int as_uint8, uint8_t* d_out, void* stream);
+size_t frcnn_ops_masks_to_boxes_workspace_bytes(int n, int h, int w, int elem_bytes);
+int frcnn_ops_masks_to_boxes(int elem_bytes, const void* d_masks, int n, int h, int w, float* d_out, void* d_ws, size_t ws_bytes,
+                             void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

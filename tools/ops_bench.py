@@ -108,6 +108,14 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     does without the operator (dense F.conv2d, then * mask) and beside ops.masked_conv2d_pytorch on the same GPU (mmcv's composition,
     its nonzero synchronisation included), in alternating windows.  Informational: no speed bound is set.
 
+  * mask: the mask operators of a Mask R-CNN's last step at K = 100 masks of 28 x 28 on an 800 x 1333 image (boxes of 30 to 400 pixels a
+    side, some over the image's sides): ops.paste_masks_in_image (padding 1; float32 and float16) beside its _pytorch twin and beside
+    torchvision's loop restated (per mask four host reads, F.interpolate, zeros and a slice copy); ops.paste_masks_aligned (bool at 0.5,
+    uint8) beside its twin and beside the grid_sample composition of detectron2 / mmdetection in one chunk; ops.masks_to_boxes on the
+    pasted bool masks beside its twin.  Each operator's row also holds the bytes it writes (reads, for masks_to_boxes), the rate, and
+    that rate as a share of the 8 TB/s HBM peak.  Informational: no speed bound is set.
+
+    python tools/ops_bench.py --only mask            # just the mask leg
     python tools/ops_bench.py --only mconv           # just the masked-convolution leg
     python tools/ops_bench.py --only quadri          # just the quadrilateral leg
     python tools/ops_bench.py --only convex          # just the point-set leg
@@ -817,6 +825,75 @@ def mconv_leg(rng, reps, warmup):
     return {"masked_conv2d, 1 x 256 x 100 x 152 (microseconds)": res}
 
 
+def mask_leg(rng, reps, warmup):
+    import torch.nn.functional as F
+    k, m, h, w = 100, 28, 800, 1333
+    cx, cy = rng.uniform(0, w, k), rng.uniform(0, h, k)
+    bw, bh = rng.uniform(30, 400, k), rng.uniform(30, 400, k)
+    boxes = torch.from_numpy(np.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], 1).astype(np.float32)).to(DEV)
+    masks = torch.from_numpy(rng.uniform(0, 1, (k, 1, m, m)).astype(np.float32)).to(DEV)
+
+    def tv_loop(masks, boxes, pad=1):
+        """torchvision's paste_masks_in_image restated: expand_masks / expand_boxes, then its loop"""
+        scale = (m + 2 * pad) / m
+        mk = F.pad(masks, (pad,) * 4)
+        w_half, h_half = (boxes[:, 2] - boxes[:, 0]) * 0.5 * scale, (boxes[:, 3] - boxes[:, 1]) * 0.5 * scale
+        x_c, y_c = (boxes[:, 2] + boxes[:, 0]) * 0.5, (boxes[:, 3] + boxes[:, 1]) * 0.5
+        ib = torch.stack([x_c - w_half, y_c - h_half, x_c + w_half, y_c + h_half], 1).to(torch.int64)
+        res = []
+        for mask, box in zip(mk, ib):
+            x0, y0, x1, y1 = (int(v) for v in box)                                     # four host reads
+            bw_, bh_ = max(x1 - x0 + 1, 1), max(y1 - y0 + 1, 1)
+            mask = F.interpolate(mask.expand((1, 1, -1, -1)), size=(bh_, bw_), mode="bilinear", align_corners=False)[0][0]
+            im = torch.zeros((h, w), dtype=mask.dtype, device=mask.device)
+            xa, xb, ya, yb = max(x0, 0), min(x1 + 1, w), max(y0, 0), min(y1 + 1, h)
+            im[ya:yb, xa:xb] = mask[(ya - y0):(yb - y0), (xa - x0):(xb - x0)]
+            res.append(im)
+        return torch.stack(res, 0)[:, None]
+
+    def grid_sample_paste(masks, boxes, thr):
+        """detectron2's _do_paste_mask (one chunk, no skip_empty) and its threshold"""
+        x0, y0, x1, y1 = torch.split(boxes, 1, dim=1)
+        ys = (torch.arange(0, h, device=DEV, dtype=torch.float32) + 0.5 - y0) / (y1 - y0) * 2 - 1
+        xs = (torch.arange(0, w, device=DEV, dtype=torch.float32) + 0.5 - x0) / (x1 - x0) * 2 - 1
+        grid = torch.stack([xs[:, None, :].expand(k, h, w), ys[:, :, None].expand(k, h, w)], dim=3)
+        img = F.grid_sample(masks, grid, align_corners=False)[:, 0]
+        return img >= thr if thr >= 0 else (img * 255).to(torch.uint8)
+
+    res = {}
+
+    def row(name, fns, labels, nbytes):
+        t = timed_group(fns, reps, warmup)
+        r = {lab: round(v, 1) for lab, v in zip(labels, t)}
+        for lab, v in zip(labels[1:], t[1:]):
+            r["%s / ops" % lab] = round(v / t[0], 1)
+        r["bytes"] = nbytes
+        r["ops TB/s"] = round(nbytes / t[0] / 1e6, 3)
+        r["share of the 8 TB/s peak"] = round(nbytes / t[0] / 1e6 / 8.0, 3)
+        res[name] = r
+
+    half = masks.half()
+    row("paste_masks_in_image float32, padding 1", [lambda: ops.paste_masks_in_image(masks, boxes, (h, w), 1),
+        lambda: ops.paste_masks_in_image_pytorch(masks, boxes, (h, w), 1), lambda: tv_loop(masks, boxes)],
+        ["ops", "_pytorch twin", "torchvision's loop"], k * h * w * 4)
+    row("paste_masks_in_image float16, padding 1", [lambda: ops.paste_masks_in_image(half, boxes, (h, w), 1),
+        lambda: ops.paste_masks_in_image_pytorch(half, boxes, (h, w), 1), lambda: tv_loop(half, boxes)],
+        ["ops", "_pytorch twin", "torchvision's loop"], k * h * w * 2)
+    for name, thr in (("bool, threshold 0.5", 0.5), ("uint8", -1.0)):
+        row("paste_masks_aligned " + name, [lambda: ops.paste_masks_aligned(masks, boxes, (h, w), thr),
+            lambda: ops.paste_masks_aligned_pytorch(masks, boxes, (h, w), thr), lambda: grid_sample_paste(masks, boxes, thr)],
+            ["ops", "_pytorch twin", "grid_sample composition"], k * h * w)
+    pasted = ops.paste_masks_aligned(masks, boxes, (h, w), 0.5)
+    row("masks_to_boxes bool", [lambda: ops.masks_to_boxes(pasted), lambda: ops.masks_to_boxes_pytorch(pasted)], ["ops", "_pytorch twin"], k * h * w)
+    pasted32 = pasted.float()
+    row("masks_to_boxes float32", [lambda: ops.masks_to_boxes(pasted32), lambda: ops.masks_to_boxes_pytorch(pasted32)], ["ops", "_pytorch twin"],
+        k * h * w * 4)
+    a, b = ops.paste_masks_in_image(masks, boxes, (h, w), 1), tv_loop(masks, boxes)
+    res["max |ops - torchvision's loop| (float32)"] = float((a - b).abs().max())
+    res["pixels where ops.paste_masks_aligned(0.5) differs from the grid_sample composition"] = int((pasted != grid_sample_paste(masks, boxes, 0.5)).sum())
+    return {"mask operators, K = 100, M = 28, 800 x 1333 (microseconds)": res}
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -900,7 +977,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri", "mconv"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri", "mconv", "mask"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -963,6 +1040,9 @@ def main():
         return
     if a.only == "mconv":
         print(json.dumps(mconv_leg(rng, 50, 5), indent=1))
+        return
+    if a.only == "mask":
+        print(json.dumps(mask_leg(rng, 10, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -1040,6 +1120,7 @@ def main():
     res.update(convex_leg(rng, 5, 2))
     res.update(quadri_leg(rng, 5, 2))
     res.update(mconv_leg(rng, 50, 5))
+    res.update(mask_leg(rng, 10, 2))
     print(json.dumps(res, indent=1))
 
 
