@@ -83,6 +83,7 @@ SYMBOLS = (
     "frcnn_ops_masked_conv2d_max_index", "frcnn_ops_masked_conv2d_workspace_bytes", "frcnn_ops_masked_conv2d",
     "frcnn_ops_paste_masks_max_side", "frcnn_ops_paste_masks_max_padding", "frcnn_ops_paste_masks_max_corner", "frcnn_ops_mask_max_plane",
     "frcnn_ops_paste_masks_in_image", "frcnn_ops_paste_masks_aligned", "frcnn_ops_masks_to_boxes_workspace_bytes", "frcnn_ops_masks_to_boxes",
+    "frcnn_ops_keypoint_max_map_side", "frcnn_ops_keypoint_max_roi_side", "frcnn_ops_keypoint_block_threads", "frcnn_ops_heatmaps_to_keypoints",
     "frcnn_ops_soft_nms_block_threads", "frcnn_ops_soft_nms_lds_boxes", "frcnn_ops_soft_nms_max_boxes", "frcnn_ops_soft_nms_workspace_bytes",
     "frcnn_ops_soft_nms",
     "frcnn_ops_carafe_max_kernel", "frcnn_ops_carafe_channel_chunk", "frcnn_ops_carafe_tile_width", "frcnn_ops_carafe_tile_height",
@@ -174,7 +175,7 @@ MAX_PRE_NMS = 16384         # frcnn_ctx pre_cap (csrc/api.hip): one-block radix 
 # FRCNN_DEFORM_WS_*: the stage whose workspace frcnn_ops_deform_workspace_bytes sizes (DEFORM_WS_COLUMNS: the column matrix itself)
 DEFORM_WS_FORWARD, DEFORM_WS_BACKWARD_COLUMNS, DEFORM_WS_BACKWARD_INPUT, DEFORM_WS_BACKWARD_WEIGHT, DEFORM_WS_COLUMNS = range(5)
 OPS_F16, OPS_BF16 = 1, 2     # FRCNN_OPS_F16 / FRCNN_OPS_BF16: element type of the frcnn_ops_*_16 entry points
-OPS_F32 = 0                  # FRCNN_OPS_F32: float32 where one entry point serves all three element types (frcnn_ops_masked_conv2d, frcnn_ops_paste_masks_*)
+OPS_F32 = 0                  # FRCNN_OPS_F32: float32 where one entry point serves all three element types (frcnn_ops_masked_conv2d, frcnn_ops_paste_masks_*, frcnn_ops_heatmaps_to_keypoints)
 MATH_F32 = 0      # exact f32 MFMA
 MATH_F32_WINOGRAD = 2   # exact f32 MFMA; 3x3 layers with uses_winograd(cin, cout) as Winograd F(2x2,3x3) in float32
 MATH_MODES = {"f32": MATH_F32, "f32_winograd": MATH_F32_WINOGRAD}     # (1 was the direct f32x6 convolution of round 2: removed, ABI 13)
@@ -387,6 +388,11 @@ _SIGNATURES = {
     "frcnn_ops_paste_masks_aligned": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     "frcnn_ops_masks_to_boxes_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "frcnn_ops_masks_to_boxes": (C.c_int, [_i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    # the keypoint operator (csrc/ops_keypoint.hip): elem_type, maps, rois, r, k, mh, mw, out, stream
+    "frcnn_ops_keypoint_max_map_side": (C.c_int, []),
+    "frcnn_ops_keypoint_max_roi_side": (C.c_int, []),
+    "frcnn_ops_keypoint_block_threads": (C.c_int, []),
+    "frcnn_ops_heatmaps_to_keypoints": (C.c_int, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     # Soft-NMS (csrc/ops_softnms.hip): boxes, scores, order, categories, n, threshold, sigma, min_score, method, offset, then the outputs
     "frcnn_ops_soft_nms_block_threads": (C.c_int, []),
     "frcnn_ops_soft_nms_lds_boxes": (C.c_int, []),

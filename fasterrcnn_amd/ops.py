@@ -22,6 +22,8 @@ torchvision.ops-style operators on the project's HIP kernels (csrc/ops.hip), as 
     from fasterrcnn_amd.ops import masked_conv2d, MaskedConv2d, masked_conv2d_pytorch
     from fasterrcnn_amd.ops import paste_masks_in_image, paste_masks_aligned, masks_to_boxes
     from fasterrcnn_amd.ops import paste_masks_in_image_pytorch, paste_masks_aligned_pytorch, masks_to_boxes_pytorch
+    from fasterrcnn_amd.ops import heatmaps_to_keypoints, heatmaps_to_keypoints_scored, keypointrcnn_inference, keypoints_to_heatmap
+    from fasterrcnn_amd.ops import heatmaps_to_keypoints_pytorch, heatmaps_to_keypoints_scored_pytorch
 
 Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them):
   nms(boxes, scores, iou_threshold) -> int64[K]     boxes (x1, y1, x2, y2) float32 or float64; visited in a stable descending sort of
@@ -500,6 +502,34 @@ Signatures and semantics are torchvision's (oracle/frcnn_oracle.py restates them
       paste_masks_in_image float32 82 us (38 x its twin, 96 x torchvision's loop; 5.2 TB/s written), float16 58 us;
       paste_masks_aligned bool 68 us, uint8 60 us (28-36 x the grid_sample composition; 1.6-1.8 TB/s: the evaluation inside the boxes
       bounds the byte forms, not the store); masks_to_boxes bool 28 us (15 x its twin), float32 74 us (5.8 TB/s read).
+  heatmaps_to_keypoints(maps, rois) -> (xy_preds [R, K, 3], end_scores [R, K])             heatmaps_to_keypoints_pytorch(maps, rois)
+  heatmaps_to_keypoints_scored(maps, rois) -> [R, K, 4] = (x, y, logit, prob)               heatmaps_to_keypoints_scored_pytorch(maps, rois)
+  keypointrcnn_inference(x, boxes) -> (list of xy_preds, list of end_scores)
+  keypoints_to_heatmap(keypoints, rois, heatmap_size) -> (heatmaps int64 [R, K], valid int64 [R, K])
+      The last step of a Keypoint R-CNN's keypoint head (csrc/ops_keypoint.hip; the contract is include/frcnn_hip.h's, restated from
+      torchvision's roi_heads and detectron2's structures/keypoints, unpinned).  Upstream loops over the detections: two host reads, a
+      [K, ceil(h), ceil(w)] float image from F.interpolate(bicubic), an argmax and a gather per detection.  Here one launch does all
+      of them, a block per (RoI, keypoint) with the map in LDS; the image never exists, nothing synchronises with the host, two runs
+      agree bit for bit.  No autograd: a tensor that requires grad is accepted and the result does not.
+      maps [R, K, Mh, Mw] float32 / float16 / bfloat16 (a 16-bit map gives, bit for bit, the result of maps.float()), each side <=
+      MAX_KEYPOINT_MAP_SIDE; rois [R, 4] (x1, y1, x2, y2) of any float dtype, converted to float32.  Per RoI w = max(x2 - x1, 1), h
+      likewise, W = ceil(w), H = ceil(h); the logit image is torch's upsample_bicubic2d(align_corners=False) of the map to [H, W]
+      (A = -0.75, the source coordinate scale * (d + 0.5) - 0.5 not clamped, tap indices clamped), in float32 in the header's stated
+      order without fused multiply-adds, rows combined first.  The maximum's (xi, yi) -- ties to the smallest yi * W + xi, a NaN above
+      every number and the first NaN winning -- gives x = (xi + 0.5) * (w / W) + x1, y likewise, logit = the maximum, prob = 1 /
+      sum(exp(map - logit)) (detectron2's score).  Defined where upstream is not: a constant map gives (xi, yi) = (0, 0) and its own
+      value as the logit (an all -inf map among them: logit -inf, prob NaN); a RoI with a non-finite coordinate or with W or H above
+      MAX_KEYPOINT_ROI_SIDE is refused: four NaNs per keypoint (torchvision's shape: NaN, NaN, 1 and a NaN score), no work; R == 0
+      or K == 0 launch nothing.  heatmaps_to_keypoints is torchvision's signature and return, heatmaps_to_keypoints_scored
+      detectron2's; keypointrcnn_inference is torchvision's wrapper over per-image box lists: one launch for all images, then the
+      split.  CPU tensors and float64 maps are served by the _pytorch twins: the per-RoI loop upstream runs (F.interpolate, argmax,
+      gather; two host reads per RoI) with the defined cases carried, float64 maps computed and returned in float64.
+      keypoints_to_heatmap is torchvision's training-target encoder (keypoints [R, K, 3] = (x, y, visibility) -> the flat index
+      y * S + x of each keypoint's cell in its RoI's S x S heatmap and whether it is valid): a handful of elementwise torch operations
+      that never read the host, so it is plain torch on any device and has no kernel.
+      Measured on an MI355X (tools/ops_bench.py --only keypoint; KEYPOINT_BENCH below): R = 100 detections of an
+      800 x 1333 image, K = 17, 56 x 56 maps: 292 us, 56 x the twin's loop (16.3 ms), float16 maps the same; R = 4 image-sized boxes:
+      927 us, 1.6 x the loop.
 
 Mixed precision.  For T in {float16, bfloat16} the RoI operators run natively on 16-bit maps (the frcnn_ops_*_16 kernels), with
 torchvision's autocast definition as the contract, bit for bit:
@@ -537,7 +567,9 @@ __all__ = ["nms", "batched_nms", "roi_pool", "roi_align", "RoIPool", "RoIAlign",
            "box_iou_quadri", "nms_quadri", "points_in_polygons", "box_iou_quadri_pytorch", "points_in_polygons_pytorch",
            "masked_conv2d", "MaskedConv2d", "masked_conv2d_pytorch",
            "paste_masks_in_image", "paste_masks_aligned", "masks_to_boxes",
-           "paste_masks_in_image_pytorch", "paste_masks_aligned_pytorch", "masks_to_boxes_pytorch"]
+           "paste_masks_in_image_pytorch", "paste_masks_aligned_pytorch", "masks_to_boxes_pytorch",
+           "heatmaps_to_keypoints", "heatmaps_to_keypoints_scored", "keypointrcnn_inference", "keypoints_to_heatmap",
+           "heatmaps_to_keypoints_pytorch", "heatmaps_to_keypoints_scored_pytorch"]
 
 _CL = torch.channels_last
 MAX_OUTPUT = 64
@@ -564,6 +596,9 @@ MAX_PASTE_MASK_SIDE = 112                 # M, Mh, Mw of the paste operators: th
 MAX_PASTE_PADDING = 65536                 # paste_masks_in_image's padding (frcnn_ops_paste_masks_max_padding())
 PASTE_CORNER = 2 ** 29                    # its integer corners saturate to [-2^29, 2^29] (frcnn_ops_paste_masks_max_corner())
 MAX_MASK_PLANE = 2 ** 31 - 1 - 1024       # H W of one image of the mask operators (frcnn_ops_mask_max_plane()); K H W is 64-bit
+MAX_KEYPOINT_MAP_SIDE = 112               # Mh, Mw of heatmaps_to_keypoints: the map lies in LDS as float32 (frcnn_ops_keypoint_max_map_side())
+MAX_KEYPOINT_ROI_SIDE = 4096              # ceil(w), ceil(h) of one of its RoIs: one block walks the resized image (frcnn_ops_keypoint_max_roi_side())
+KEYPOINT_BLOCK_THREADS = 256              # its block: 4 waves, an output row each per pass, 64 pixels a step (frcnn_ops_keypoint_block_threads())
 MAX_SOFT_NMS_BOXES = 65536                # soft_nms: one label may hold every box, and one workgroup then runs N dependent picks.  Measured on
                                           # an MI355X at N = 65536 in one problem (clustered boxes, thr 0.3): 43 ms linear and 48 ms gaussian at
                                           # min_score 0.05 (1503 / 1104 picks), 7 ms naive; 2.06 s in the worst case, min_score = 0, where all
@@ -4770,3 +4805,154 @@ def masks_to_boxes_pytorch(masks):
         out = torch.stack([torch.where(cols, xs, w).amin(1), torch.where(rows, ys, h).amin(1),
                            torch.where(cols, xs, -1).amax(1), torch.where(rows, ys, -1).amax(1)], dim=1).to(torch.float32)
         return torch.where(cols.any(1)[:, None], out, out.new_zeros(()))
+
+
+# ---- heatmaps_to_keypoints / keypointrcnn_inference / keypoints_to_heatmap: a Keypoint R-CNN's last step (csrc/ops_keypoint.hip) -------
+# One run on an MI355X (tools/ops_bench.py --only keypoint; K = 17, 56 x 56 maps, boxes of an 800 x 1333 image): microseconds of the
+# operator and of its _pytorch twin (upstream's loop) on the same device, and the operator's rate over the pixels of the resized images.
+# The image-sized case is what a single block per (RoI, keypoint) costs when only 68 blocks exist: still ahead of the loop, so a large
+# box is not split over several blocks.
+KEYPOINT_BENCH = {
+    "R = 100 detections, float32 maps": {"ops": 291.6, "twin": 16265.0, "Gpixel/s": 254.4},
+    "R = 100 detections, float16 maps": {"ops": 291.3, "twin": 16160.1, "Gpixel/s": 254.7},
+    "R = 4 image-sized boxes, float32 maps": {"ops": 927.4, "twin": 1466.3, "Gpixel/s": 60.7},
+}
+
+
+@torch.library.custom_op("frcnn::heatmaps_to_keypoints", mutates_args=())
+def _heatmaps_to_keypoints(maps: Tensor, rois: Tensor) -> Tensor:
+    """maps [R, K, Mh, Mw], rois [R, 4] float32 -> float32 [R, K, 4] = (x, y, logit, prob)."""
+    r, k, mh, mw = maps.shape
+    out = torch.empty((r, k, 4), dtype=torch.float32, device=maps.device)
+    if r == 0 or k == 0:
+        return out
+    with torch.cuda.device(maps.device):
+        mp, bx = maps.contiguous(), rois.contiguous()
+        nv.check(nv.lib().frcnn_ops_heatmaps_to_keypoints(_mask_elem(maps.dtype), mp.data_ptr(), bx.data_ptr(), r, k, mh, mw, out.data_ptr(),
+                                                          _stream(maps)), "frcnn_ops_heatmaps_to_keypoints")
+    return out
+
+
+@_heatmaps_to_keypoints.register_fake
+def _(maps, rois):
+    return torch.empty((maps.shape[0], maps.shape[1], 4), dtype=torch.float32, device=maps.device)
+
+
+_KEYPOINT_BOX_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64)
+
+
+def _keypoint_input(maps, rois):
+    """The checks heatmaps_to_keypoints and its twin share; returns rois as float32."""
+    for name, t, d, what in (("maps", maps, _MAP_DTYPES + (torch.float64,), _MAP_WHAT + " (or float64: the _pytorch twin)"),
+                             ("rois", rois, _KEYPOINT_BOX_DTYPES, "a float dtype")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.dtype not in d:
+            raise TypeError("%s must be %s, got %s" % (name, what, t.dtype))
+    _check_same_device(maps, rois, "maps", "rois")
+    if maps.dim() != 4:
+        raise ValueError("maps must be [R, K, Mh, Mw], got shape %s" % (tuple(maps.shape),))
+    if rois.dim() != 2 or rois.shape[1] != 4:
+        raise ValueError("rois must be [R, 4], got shape %s" % (tuple(rois.shape),))
+    if maps.shape[0] != rois.shape[0]:
+        raise ValueError("maps and rois must have the same R, got %d maps and %d rois" % (maps.shape[0], rois.shape[0]))
+    if not (1 <= maps.shape[2] <= MAX_KEYPOINT_MAP_SIDE and 1 <= maps.shape[3] <= MAX_KEYPOINT_MAP_SIDE):
+        raise ValueError("maps must be Mh x Mw with 1 <= Mh, Mw <= MAX_KEYPOINT_MAP_SIDE = %d, got %d x %d"
+                         % (MAX_KEYPOINT_MAP_SIDE, maps.shape[2], maps.shape[3]))
+    return rois.detach().to(torch.float32)
+
+
+def _keypoints_torchvision(scored):
+    """(x, y, logit, prob) [R, K, 4] as torchvision returns it: (x, y, 1) [R, K, 3] and the logits [R, K]."""
+    return torch.cat([scored[..., :2], torch.ones_like(scored[..., :1])], dim=2), scored[..., 2]
+
+
+def heatmaps_to_keypoints_scored(maps, rois):
+    """detectron2's heatmaps_to_keypoints in one launch: maps [R, K, Mh, Mw] (float32 / float16 / bfloat16), rois [R, 4] -> float32
+    [R, K, 4] = (x, y, logit, prob) of the maximum of each map resized bicubically to its RoI.  No autograd; no host synchronisation.
+    CPU tensors and float64 maps are served by heatmaps_to_keypoints_scored_pytorch."""
+    boxes = _keypoint_input(maps, rois)
+    if maps.device.type == "cpu" or maps.dtype == torch.float64:
+        return heatmaps_to_keypoints_scored_pytorch(maps, rois)
+    return _heatmaps_to_keypoints(maps.detach(), boxes)
+
+
+def heatmaps_to_keypoints(maps, rois):
+    """torchvision's roi_heads.heatmaps_to_keypoints in one launch: (xy_preds [R, K, 3] = (x, y, 1), end_scores [R, K] = the logits)."""
+    return _keypoints_torchvision(heatmaps_to_keypoints_scored(maps, rois))
+
+
+def keypointrcnn_inference(x, boxes):
+    """torchvision's roi_heads.keypointrcnn_inference: x [sum of R_i, K, Mh, Mw], boxes a list of [R_i, 4] per image -> (list of xy_preds
+    [R_i, K, 3], list of end_scores [R_i, K]).  One launch for all images, then the split."""
+    if not isinstance(boxes, (list, tuple)) or not all(isinstance(b, torch.Tensor) for b in boxes):
+        raise TypeError("boxes must be a list of Tensor[R_i, 4], one per image, got %s" % type(boxes).__name__)
+    if len(boxes) == 0:
+        return [], []
+    per_image = [b.shape[0] for b in boxes]
+    xy, scores = heatmaps_to_keypoints(x, torch.cat(list(boxes), dim=0))
+    return list(xy.split(per_image, dim=0)), list(scores.split(per_image, dim=0))
+
+
+def heatmaps_to_keypoints_scored_pytorch(maps, rois):
+    """heatmaps_to_keypoints_scored's contract, defined cases included, as the per-RoI loop upstream runs (two host reads, F.interpolate
+    (bicubic), argmax and a gather per RoI): any device, float64 maps too (computed and returned in float64; else float32)."""
+    boxes = _keypoint_input(maps, rois)
+    r, k = maps.shape[:2]
+    math = torch.float64 if maps.dtype == torch.float64 else torch.float32
+    with torch.no_grad():
+        out = torch.full((r, k, 4), float("nan"), dtype=math, device=maps.device)
+        if r == 0 or k == 0:
+            return out
+        flat = maps.detach().to(math).reshape(r, k, -1)
+        first = flat[:, :, 0]
+        constant = (flat == first[:, :, None]).all(2)
+        w, h = (boxes[:, 2] - boxes[:, 0]).clamp(min=1), (boxes[:, 3] - boxes[:, 1]).clamp(min=1)
+        wc, hc = w.ceil(), h.ceil()
+        ok = torch.isfinite(boxes).all(1) & (wc <= MAX_KEYPOINT_ROI_SIDE) & (hc <= MAX_KEYPOINT_ROI_SIDE)
+        sizes = torch.stack([torch.where(ok, wc, wc.new_zeros(())), torch.where(ok, hc, hc.new_zeros(()))], 1).tolist()
+        for i, (wi, hi) in enumerate(sizes):
+            if wi == 0:                                                          # refused: four NaNs
+                continue
+            wi, hi = int(wi), int(hi)
+            image = torch.nn.functional.interpolate(flat[i].reshape((k, 1) + tuple(maps.shape[2:])), size=(hi, wi), mode="bicubic",
+                                                    align_corners=False).reshape(k, -1)
+            pos = torch.where(constant[i], 0, image.argmax(1))                   # NaN is the largest, the first of equals wins
+            v = torch.where(constant[i], first[i], image.gather(1, pos[:, None])[:, 0])
+            xi, yi = pos % wi, pos // wi
+            out[i, :, 0] = (xi.to(torch.float32) + 0.5) * (w[i] / wc[i]) + boxes[i, 0]
+            out[i, :, 1] = (yi.to(torch.float32) + 0.5) * (h[i] / hc[i]) + boxes[i, 1]
+            out[i, :, 2] = v
+            out[i, :, 3] = 1 / (flat[i] - v[:, None]).exp().sum(1)
+        return out
+
+
+def heatmaps_to_keypoints_pytorch(maps, rois):
+    """heatmaps_to_keypoints_scored_pytorch in torchvision's shape: (xy_preds [R, K, 3], end_scores [R, K])."""
+    return _keypoints_torchvision(heatmaps_to_keypoints_scored_pytorch(maps, rois))
+
+
+def keypoints_to_heatmap(keypoints, rois, heatmap_size):
+    """torchvision's roi_heads.keypoints_to_heatmap, the training-target encoder: keypoints [R, K, 3] = (x, y, visibility), rois [R, 4],
+    heatmap_size S -> (heatmaps int64 [R, K]: y * S + x of the keypoint's cell in its RoI's S x S map, 0 where not valid; valid int64
+    [R, K]: inside the map and visibility > 0).  A keypoint exactly on the RoI's right or bottom edge belongs to the last cell.
+    Plain torch operations on any device: a handful of elementwise operations that read nothing back to the host, so there is no
+    kernel to write (the loss over it is F.cross_entropy)."""
+    for name, t in (("keypoints", keypoints), ("rois", rois)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if keypoints.dim() != 3 or keypoints.shape[2] != 3:
+        raise ValueError("keypoints must be [R, K, 3], got shape %s" % (tuple(keypoints.shape),))
+    if rois.dim() != 2 or rois.shape[1] != 4 or rois.shape[0] != keypoints.shape[0]:
+        raise ValueError("rois must be [R, 4] with the keypoints' R = %d, got shape %s" % (keypoints.shape[0], tuple(rois.shape)))
+    if not isinstance(heatmap_size, int) or isinstance(heatmap_size, bool) or heatmap_size < 1:
+        raise ValueError("heatmap_size must be a positive int, got %r" % (heatmap_size,))
+    s = heatmap_size
+    x, y = keypoints[..., 0], keypoints[..., 1]
+    on_right, on_bottom = x == rois[:, 2, None], y == rois[:, 3, None]
+    size = rois.new_full((), s)                                                  # S / extent as one division (int / Tensor is reciprocal * S)
+    x = ((x - rois[:, 0, None]) * (size / (rois[:, 2] - rois[:, 0]))[:, None]).floor().long()
+    y = ((y - rois[:, 1, None]) * (size / (rois[:, 3] - rois[:, 1]))[:, None]).floor().long()
+    x, y = torch.where(on_right, s - 1, x), torch.where(on_bottom, s - 1, y)
+    valid = ((x >= 0) & (y >= 0) & (x < s) & (y < s) & (keypoints[..., 2] > 0)).long()
+    return (y * s + x) * valid, valid

@@ -106,7 +106,10 @@ extern "C" {
                                  still 21 (additions only): frcnn_ops_paste_masks_in_image, frcnn_ops_paste_masks_aligned, frcnn_ops_masks_to_boxes,
                                  frcnn_ops_masks_to_boxes_workspace_bytes and the frcnn_ops_paste_masks_max_side / _max_padding / _max_corner and
                                  frcnn_ops_mask_max_plane getters (a Mask R-CNN's last step: torchvision's and detectron2's paste_masks_in_image,
-                                 torchvision's masks_to_boxes) */
+                                 torchvision's masks_to_boxes);
+                                 still 21 (additions only): frcnn_ops_heatmaps_to_keypoints and the frcnn_ops_keypoint_max_map_side /
+                                 _max_roi_side / _block_threads getters (a Keypoint R-CNN's last step: torchvision's and detectron2's
+                                 heatmaps_to_keypoints) */
 
 /* flags for frcnn_conv3x3_nhwc / frcnn_linear */
 #define FRCNN_RELU   1u
@@ -542,7 +545,8 @@ int frcnn_ops_nms(const void* d_boxes, int boxes_f64, const int64_t* d_order, co
  *   entry points; an unknown elem_type is FRCNN_EINVAL.  The multi-scale workspace is frcnn_ops_ms_roi_align_workspace_bytes's. */
 #define FRCNN_OPS_F16  1   /* IEEE binary16 (torch.float16) */
 #define FRCNN_OPS_BF16 2   /* bfloat16 (torch.bfloat16) */
-#define FRCNN_OPS_F32  0   /* float32: only where one entry point serves all three element types (frcnn_ops_masked_conv2d, frcnn_ops_paste_masks_*) */
+#define FRCNN_OPS_F32  0   /* float32: only where one entry point serves all three element types (frcnn_ops_masked_conv2d, frcnn_ops_paste_masks_*,
+                              frcnn_ops_heatmaps_to_keypoints) */
 int frcnn_ops_half_run(void);
 int frcnn_ops_roi_align_16(int elem_type, const void* d_x, int n_img, int fh, int fw, int c, const float* d_rois, int k, int out_h,
                            int out_w, float spatial_scale, int sampling_ratio, int aligned, void* d_out, void* stream);
@@ -1182,6 +1186,60 @@ int frcnn_ops_paste_masks_aligned(int elem_type, const void* d_masks, const floa
 size_t frcnn_ops_masks_to_boxes_workspace_bytes(int n, int h, int w, int elem_bytes);
 int frcnn_ops_masks_to_boxes(int elem_bytes, const void* d_masks, int n, int h, int w, float* d_out, void* d_ws, size_t ws_bytes,
                              void* stream);
+
+/* The keypoint operator of a Keypoint R-CNN's last step (csrc/ops_keypoint.hip): torchvision's roi_heads.heatmaps_to_keypoints and
+ *   detectron2's structures.keypoints.heatmaps_to_keypoints without their loop over the detections, its two host reads and its
+ *   [k, H, W] float image per detection.  Third parties, absent here: their published algorithm restated, unpinned; where they differ
+ *   from this text, this text holds.  No autograd.  One launch, a block per (RoI, keypoint); nothing synchronises with the host, no
+ *   workspace, no memset, no atomics; every output element is written once; two runs agree bit for bit.
+ *
+ * frcnn_ops_heatmaps_to_keypoints: d_maps [r, k, mh, mw] elements of T (elem_type FRCNN_OPS_F32 / _F16 / _BF16), contiguous, widened
+ *   exactly once on the way into LDS (ops_elem.h), so that op(x_T) == op(x_T.float()) bit for bit; d_rois [r, 4] float32
+ *   (x1, y1, x2, y2); d_out [r, k, 4] float32 (x, y, logit, prob).
+ *   Per RoI, in float32:  w = max(x2 - x1, 1)   h = max(y2 - y1, 1)   W = ceil(w)   H = ceil(h).
+ *   The logit image of keypoint j is the bicubic resize of map j to [H, W], torch's upsample_bicubic2d(align_corners=False): Keys'
+ *   kernel with A = -0.75, the source coordinate not clamped, the four taps per axis on indices clamped to the map.  Its arithmetic is
+ *   float32, every operation rounded on its own (NO contraction into fused multiply-adds), in THIS order (it need not be torch's:
+ *   torch's CPU and CUDA kernels do not agree with each other either).  For output coordinate d of an axis of n source and N output
+ *   pixels (n = mw, N = W for x; n = mh, N = H for y):
+ *       scale = float32(n) / float32(N)        src = scale * (float32(d) + 0.5) - 0.5        f = floor(src)        t = src - f
+ *       i_j = min(max(f - 1 + j, 0), n - 1),  j = 0 .. 3
+ *       u0 = t + 1                  c_0 = ((-0.75 * u0 + 3.75) * u0 - 6) * u0 + 3
+ *                                   c_1 = ((1.25 * t - 2.25) * t) * t + 1
+ *       u2 = 1 - t                  c_2 = ((1.25 * u2 - 2.25) * u2) * u2 + 1
+ *       u3 = u2 + 1                 c_3 = ((-0.75 * u3 + 3.75) * u3 - 6) * u3 + 3
+ *   The rows are combined first, then the columns, each sum from the left:
+ *       v[y][c] = ((cy_0 * M[iy_0][c] + cy_1 * M[iy_1][c]) + cy_2 * M[iy_2][c]) + cy_3 * M[iy_3][c]          for every column c of the map
+ *       image[y][x] = ((cx_0 * v[y][ix_0] + cx_1 * v[y][ix_1]) + cx_2 * v[y][ix_2]) + cx_3 * v[y][ix_3]
+ *   The answer is the image's maximum under a total order on (value, index = y * W + x): a NaN is larger than every number, then the
+ *   larger value (+0.0 and -0.0 are equal), then the smaller index -- so ties go to the smallest y * W + x and the first NaN wins
+ *   (torch's argmax rule), whatever the order of the reduction.  With the maximum v at (xi, yi), in float32 and in this order:
+ *       x = (float32(xi) + 0.5) * (w / float32(W)) + x1        y = (float32(yi) + 0.5) * (h / float32(H)) + y1        logit = v
+ *       prob = 1 / sum over the mh x mw map of exp(M - v)      (detectron2's roi_map_scores at the maximum)
+ *   The sum's order is fixed (per lane, a butterfly, the waves in order) but not part of the contract; prob is accurate to the
+ *   float32 error of its terms, not bit-exact against another implementation.
+ *   Defined where upstream leaves it open:
+ *     - A constant map (every element compares equal to the first; +0.0 == -0.0) IS its resized image, whose float32 evaluation would
+ *       otherwise differ in the last bits from pixel to pixel: (xi, yi) = (0, 0), logit = the first element, prob by the formula
+ *       (1 / (mh mw) for a finite constant).
+ *     - A NaN in the map spreads to the pixels whose taps touch it; the first such pixel wins, logit and prob are NaN.
+ *     - An all -inf map is a constant map: (0, 0), logit = -inf, and prob is NaN (exp(-inf - -inf)); so is an all +inf map.  A map that
+ *       mixes -inf with numbers resizes to NaNs around each -inf (0 * inf, inf - inf in the taps) and falls under the NaN rule.
+ *     - A RoI is REFUSED when a coordinate is not finite or when W or H exceeds frcnn_ops_keypoint_max_roi_side() = 4096 (one block
+ *       walks the whole image: at most 2^24 pixels, 2^16 a lane, about ten milliseconds; x2 - x1 overflowing to +inf is refused by
+ *       the same comparison).  A refused RoI gives four NaNs for each of its keypoints and costs no work: its blocks return before
+ *       they read the map.
+ *     - w or h under 1, an inverted box included, is clamped to 1 as upstream clamps it.
+ *     - r == 0 or k == 0 is legal and launches nothing.
+ * Limits, FRCNN_EINVAL before the GPU is touched: an unknown elem_type; mh or mw outside [1, frcnn_ops_keypoint_max_map_side()] (the map
+ *   is staged in LDS as float32; 112); r or k < 0; r k above 2^31 - 1; with r k > 0 a NULL pointer.
+ *   frcnn_ops_keypoint_block_threads() = 256: a block's waves of 64 lanes take one output row each per pass and 64 pixels of it per
+ *   step (what the tests size their seams by). */
+int frcnn_ops_keypoint_max_map_side(void);
+int frcnn_ops_keypoint_max_roi_side(void);
+int frcnn_ops_keypoint_block_threads(void);
+int frcnn_ops_heatmaps_to_keypoints(int elem_type, const void* d_maps, const float* d_rois, int r, int k, int mh, int mw, float* d_out,
+                                    void* stream);
 
 /* Soft-NMS (Bodla et al., 2017), per label (csrc/ops_softnms.hip): mmcv's soft_nms, which exists on the CPU only, restated from its
  *   published loop (third party, absent here: restated, unpinned; where the two differ this text holds).

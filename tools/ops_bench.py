@@ -115,6 +115,14 @@ input, and at an FPN-like shape.  Device events around `--reps` calls after `--w
     pasted bool masks beside its twin.  Each operator's row also holds the bytes it writes (reads, for masks_to_boxes), the rate, and
     that rate as a share of the 8 TB/s HBM peak.  Informational: no speed bound is set.
 
+  * keypoint: the last step of a Keypoint R-CNN at R = 100 detections of an 800 x 1333 image (boxes of 30 to 400 pixels a side), K = 17
+    keypoints, 56 x 56 maps: ops.heatmaps_to_keypoints_scored (float32 and float16 maps) beside its _pytorch twin on the same device,
+    which is upstream's loop (two host reads, F.interpolate(bicubic), argmax and a gather per detection); and one case of R = 4
+    image-sized boxes, where a block walks a million pixels: the case that says whether a large box should be split over several
+    blocks.  Each row also holds the pixels of the resized images and the operator's rate over them.  Informational: no speed bound
+    is set.
+
+    python tools/ops_bench.py --only keypoint        # just the keypoint leg
     python tools/ops_bench.py --only mask            # just the mask leg
     python tools/ops_bench.py --only mconv           # just the masked-convolution leg
     python tools/ops_bench.py --only quadri          # just the quadrilateral leg
@@ -894,6 +902,35 @@ def mask_leg(rng, reps, warmup):
     return {"mask operators, K = 100, M = 28, 800 x 1333 (microseconds)": res}
 
 
+def keypoint_leg(rng, reps, warmup):
+    k, m, h, w = 17, 56, 800, 1333
+    res = {}
+
+    def row(name, boxes, dtype):
+        r = len(boxes)
+        maps = (torch.from_numpy(rng.standard_normal((r, k, m, m)).astype(np.float32)) * 3).to(DEV).to(dtype)
+        rois = torch.from_numpy(boxes.astype(np.float32)).to(DEV)
+        t = timed_group([lambda: ops.heatmaps_to_keypoints_scored(maps, rois), lambda: ops.heatmaps_to_keypoints_scored_pytorch(maps, rois)],
+                        reps, warmup)
+        size = (rois[:, 2:] - rois[:, :2]).clamp(min=1).ceil().double()
+        pixels = int((size[:, 0] * size[:, 1]).sum()) * k
+        a, b = ops.heatmaps_to_keypoints_scored(maps, rois), ops.heatmaps_to_keypoints_scored_pytorch(maps, rois)
+        res[name] = {"ops": round(t[0], 1), "_pytorch twin (upstream's loop)": round(t[1], 1), "twin / ops": round(t[1] / t[0], 1),
+                     "pixels of the resized images": pixels, "ops Gpixel/s": round(pixels / t[0] / 1e3, 2),
+                     "pairs whose position differs from the twin's": int(((a[..., :2] != b[..., :2]).any(2)).sum()),
+                     "max |logit - twin's|": float((a[..., 2] - b[..., 2]).abs().max())}
+
+    r = 100
+    cx, cy = rng.uniform(0, w, r), rng.uniform(0, h, r)
+    bw, bh = rng.uniform(30, 400, r), rng.uniform(30, 400, r)
+    detections = np.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], 1)
+    row("R = 100 detections, float32 maps", detections, torch.float32)
+    row("R = 100 detections, float16 maps", detections, torch.float16)
+    image_sized = np.array([[0, 0, w, h], [10.5, 20.25, w - 30, h - 7.5], [0, 0, w, h / 2], [w / 3, 0, w, h]])
+    row("R = 4 image-sized boxes, float32 maps", image_sized, torch.float32)
+    return {"heatmaps_to_keypoints, K = 17, 56 x 56 maps, 800 x 1333 (microseconds)": res}
+
+
 def diffiou_leg(rng, reps, warmup):
     n = 1 << 20
     u = lambda lo, hi, *shape: torch.from_numpy(rng.uniform(lo, hi, (n,) + shape).astype(np.float32))     # noqa: E731
@@ -977,7 +1014,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri", "mconv", "mask"], default=None)
+    ap.add_argument("--only", choices=["multiscale", "half", "ps", "deform", "droi", "rot", "carafe", "msda", "prroi", "dcnv3", "dcnv4", "diffiou", "softnms", "border", "riroi", "rfa", "convex", "quadri", "mconv", "mask", "keypoint"], default=None)
     a = ap.parse_args()
     nv.require_gpu()
     lib = nv.lib()
@@ -1043,6 +1080,9 @@ def main():
         return
     if a.only == "mask":
         print(json.dumps(mask_leg(rng, 10, 2), indent=1))
+        return
+    if a.only == "keypoint":
+        print(json.dumps(keypoint_leg(rng, 5, 2), indent=1))
         return
     c, fh, fw = 512, 37, 62
     x = torch.relu(torch.randn((1, c, fh, fw), device=DEV))
@@ -1121,6 +1161,7 @@ def main():
     res.update(quadri_leg(rng, 5, 2))
     res.update(mconv_leg(rng, 50, 5))
     res.update(mask_leg(rng, 10, 2))
+    res.update(keypoint_leg(rng, 5, 2))
     print(json.dumps(res, indent=1))
 
 
